@@ -23,6 +23,7 @@ Launch:  python bench.py                      (N=1)
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
                 --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
          python bench.py --gpus N             (spawns the line above itself)
+         python bench.py ... --dump-outputs DIR   (also writes what the timed steps leave, DIR/<name>.npy, for output comparisons)
 Rank 0 prints ONE JSON line.
 """
 import argparse
@@ -59,6 +60,34 @@ def algorithmic_model(cal, ds, summary_dims):
     return bytes_, flops
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(tr, flags, out_dir, normal_equations):
+    """--dump-outputs: the timed steps (oicc_run_lm_iterations) take LM steps without accepting them, so what they leave a caller
+    is the parameter state (spline knots, T_i_c, gravity) and, in every step, the Jacobian + assembly pass at it: cost, gradient
+    and J^T J.  The pass is read back through Evaluate on one rank only (on sharded ranks it would be a collective).  An array that
+    does not fit the budget is replaced by a fixed, seeded sample of its entries (<name>_sample + <name>_sample_index)."""
+    so3, r3 = tr.GetKnots()
+    arrays = dict(so3_knots=so3, r3_knots=r3, T_i_c=tr.GetT_i_c(), gravity=tr.GetGravity())
+    if normal_equations:
+        cost, H, g = tr.Evaluate(flags)
+        arrays.update(cost=np.array([cost]), gradient=g, jtj=H)
+    os.makedirs(out_dir, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for name in sorted(arrays, key=lambda k: arrays[k].size):      # largest last: only it is ever sampled
+        a = np.ascontiguousarray(arrays[name], dtype=np.float64)
+        if a.nbytes > left:
+            n = max(1, left // 16)
+            idx = np.sort(np.random.default_rng(20241115).choice(a.size, size=min(n, a.size), replace=False))
+            np.save(os.path.join(out_dir, name + "_sample.npy"), a.ravel()[idx])
+            np.save(os.path.join(out_dir, name + "_sample_index.npy"), idx.astype(np.float64))
+            left -= 16 * len(idx)
+        else:
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+            left -= a.nbytes
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -66,6 +95,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the C5-size single-GPU Jacobian-pass measurement")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they leave for a caller as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -223,6 +254,8 @@ def main():
     dt = float(tmax[0])
     ms_per_step = 1e3 * dt / args.steps
     value = n_blocks * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, flags, args.dump_outputs, normal_equations=not use_dist)
 
     # N > 1: the all-reduce of the packed system, timed by HIP events on the library's stream (a collective: every rank runs it)
     allreduce_ms, allreduce_bytes = None, None

@@ -1,25 +1,24 @@
-"""Worker of test_two_processes_on_one_gpu_reduce_through_the_hook: rank r of WORLD_SIZE processes, ALL on GPU 0, holds the
-r-th time shard of a problem and runs oicc_optimize with an all-reduce hook that stages through host memory and gloo
-(RCCL refuses two ranks on one device; the hook is the product path under test, the transport is not).
-usage: python mp_shard_worker.py <cfg> <flags> <iterations> <bounds_line_search> <out.json> [inner_iterations] [owner_computes]   (RANK / WORLD_SIZE / MASTER_* from the env)
+"""Worker of test_two_processes_on_one_gpu_reduce_through_the_hook: ranks of WORLD_SIZE, ALL on GPU 0, each holding its time shard of
+a problem and running oicc_optimize with an all-reduce hook that stages through host memory and gloo (RCCL refuses two ranks on
+one device; the hook is the product path under test, the transport is not).  One process hosts the ranks listed in RANKS (default:
+RANK), each in a thread of its own with its own problem, stream and gloo group: more ranks than GPU processes the machine allows.
+usage: python mp_shard_worker.py <cfg> <flags> <iterations> <bounds_line_search> <out.json> [inner_iterations] [owner_computes]   (RANK(S) / WORLD_SIZE / MASTER_* from the env;
+{rank} in <out.json> is replaced by the rank)
 owner_computes = 1: the round-4 exchange (oicc_set_shard): halo rows to their owners, gather of the owned band ranges, all-reduce of
 the arrow corner only -- through the transport hooks (oicc_set_exchange: gloo send / recv / broadcast staged through host memory).
 With inner_iterations = 1 every rank also builds the WHOLE problem on the device and hands it to its shard as the source of the
 inner-iteration sweeps (oicc_set_inner_iteration_source): the reference's solver configuration on time-sharded ranks."""
-import ctypes, json, os, sys
+import ctypes, datetime, json, os, sys, threading, traceback
 import numpy as np
 import torch
 import torch.distributed as dist
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from openimucameracalibrator_amd import synthetic, estimator as E
+from openimucameracalibrator_amd import _lib, synthetic, estimator as E
 
 
-def main():
-    cfg, flags, iters, ls, out = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), sys.argv[5]
-    inner = int(sys.argv[6]) if len(sys.argv) > 6 else 0
-    owner = int(sys.argv[7]) if len(sys.argv) > 7 else 0
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+def run_rank(rank, world, cfg, flags, iters, ls, out, inner, owner):
+    store = dist.TCPStore(os.environ["MASTER_ADDR"], int(os.environ["MASTER_PORT"]), is_master=False, timeout=datetime.timedelta(seconds=300))
+    pg = dist.ProcessGroupGloo(dist.PrefixStore("shards", store), rank, world, datetime.timedelta(seconds=300))
     hip = ctypes.CDLL("libamdhip64.so")
     hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
     hip.hipStreamSynchronize.argtypes = [ctypes.c_void_p]
@@ -29,7 +28,7 @@ def main():
         assert hip.hipStreamSynchronize(strm) == 0
         buf = torch.empty(count, dtype=torch.float64)
         assert hip.hipMemcpy(buf.data_ptr(), ptr, count * 8, 2) == 0      # device -> host
-        dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+        pg.allreduce([buf]).wait()                                          # (SUM)
         assert hip.hipMemcpy(ptr, buf.data_ptr(), count * 8, 1) == 0      # host -> device
         calls["n"] += 1; calls["doubles"] += count; calls["max"] = max(calls["max"], count)
 
@@ -42,14 +41,15 @@ def main():
             if sc: assert hip.hipMemcpy(sb.data_ptr(), sp, sc * 8, 2) == 0
             for turn in (0, 1):
                 if (turn == 0) == (rank < peer):
-                    if sc: dist.send(sb[:sc], dst=peer)
-                elif rc: dist.recv(rb[:rc], src=peer)
+                    if sc: pg.send([sb[:sc]], peer, 0).wait()
+                elif rc: pg.recv([rb[:rc]], peer, 0).wait()
             if rc: assert hip.hipMemcpy(rp, rb.data_ptr(), rc * 8, 1) == 0
             xch["sendrecv"] += 1; xch["doubles"] += sc + rc
         else:            # `peer` holds sc doubles at sp; everybody receives them in place
             b = torch.empty(sc, dtype=torch.float64)
             if rank == peer: assert hip.hipMemcpy(b.data_ptr(), sp, sc * 8, 2) == 0
-            dist.broadcast(b, src=peer)
+            o = dist.BroadcastOptions(); o.rootRank = peer
+            pg.broadcast([b], o).wait()
             if rank != peer: assert hip.hipMemcpy(rp, b.data_ptr(), sc * 8, 1) == 0
             xch["broadcast"] += 1; xch["doubles"] += sc if rank != peer else 0; xch["max_broadcast"] = max(xch["max_broadcast"], sc)
 
@@ -75,9 +75,32 @@ def main():
     assert tr._b.lib.oicc_debug_dist_solve_info(tr._h, info) == 0
     res = dict(rejected=int(s["num_unsuccessful_steps"]), dist_solves=int(info[0]), dist_first_block=int(info[1]), dist_blocks=int(info[2]), dist_ranks=int(info[3]), band_row_doubles=int(s["half_bandwidth"]) + 1 + int(s["arrow_dim"]) + 1, band_dim=int(s["band_dim"]), rank=rank, blocks=cal.num_blocks, iterations=[dict(cost=i["cost"], ok=i["step_is_successful"], gmax=i["gradient_max_norm"]) for i in it],
                final_cost=s["final_cost"], inner_sweeps=s["inner_sweeps"], inner_lm_iterations=s["inner_lm_iterations"], T_i_c=[float(v) for v in tr.GetT_i_c()], hook_calls=calls["n"], hook_doubles=calls["doubles"], hook_max_doubles=calls["max"], P=int(s["num_parameters_tangent"]), exchange=xch)
-    json.dump(res, open(out, "w"))
-    dist.barrier()
-    dist.destroy_process_group()
+    json.dump(res, open(out.format(rank=rank), "w"))
+    pg.barrier().wait()
+
+
+def main():
+    cfg, flags, iters, ls, out = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), sys.argv[5]
+    inner = int(sys.argv[6]) if len(sys.argv) > 6 else 0
+    owner = int(sys.argv[7]) if len(sys.argv) > 7 else 0
+    world = int(os.environ["WORLD_SIZE"])
+    ranks = [int(r) for r in os.environ.get("RANKS", os.environ.get("RANK", "0")).split(",")]
+    # the process that hosts rank 0 serves the rendezvous store; it lives until every rank of this process is done
+    master = dist.TCPStore(os.environ["MASTER_ADDR"], int(os.environ["MASTER_PORT"]), is_master=True, wait_for_workers=False) if 0 in ranks else None
+    _lib.load()     # (bound once, before the rank threads)
+    failed = []
+
+    def body(rank):
+        try:
+            run_rank(rank, world, cfg, flags, iters, ls, out, inner, owner)
+        except BaseException:
+            traceback.print_exc(); failed.append(rank)
+    threads = [threading.Thread(target=body, args=(r,)) for r in ranks]
+    for t in threads: t.start()
+    for t in threads: t.join()
+    del master
+    if failed:
+        raise SystemExit("ranks %s failed" % failed)
 
 
 if __name__ == "__main__":

@@ -17,6 +17,8 @@ import oracle_backend
 from openimucameracalibrator_amd import synthetic, estimator as E, _abi, _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the reference's class interfaces, recorded from its headers by tests/golden/make_reference_facts.py
+REF_FACTS = os.path.join(ROOT, "tests", "golden", "reference_facts.json")
 
 
 def header_functions():
@@ -174,42 +176,36 @@ def test_remaining_calibrator_methods(cpu):
     cal.trajectory_.SetGravity(ds.gravity_init)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/include/OpenCameraCalibrator/core"), reason="reads the reference headers: only where the tree is mounted")
 def test_mirrors_carry_every_defined_method_of_the_reference_classes():
     """Same names as the reference's interface for this path: every public method of SplineTrajectoryEstimator<6> and
     ImuCameraCalibrator that the reference DEFINES exists in the Python mirror and in the C++ facade.  Declared-only or
     Theia-typed leftovers are listed (spline_trajectory_estimator.h:48,59,66-73,87-90,99,146-148: no definition, or unused
     inverse-depth / GPS experiments)."""
-    core = "/root/reference/include/OpenCameraCalibrator/core/"
+    import json
+    facts = json.load(open(REF_FACTS))
     py = open(os.path.join(ROOT, "openimucameracalibrator_amd", "estimator.py")).read()
     cpp = open(os.path.join(ROOT, "openimucameracalibrator_amd", "csrc", "host", "estimator.hpp")).read()
     py_names = set(re.findall(r"def ([A-Z][A-Za-z0-9_]+)\(", py)); cpp_names = set(re.findall(r"\b([A-Z][A-Za-z0-9_]+)\s*\(", cpp))
     not_defined_or_unused = {"AddGPSMeasurement", "AddGSInvCameraMeasurement", "AddRSInvCameraMeasurement", "InitSpline", "InitScenePoints",
                              "SetTelemetryData", "ConvertInvDepthPointsToHom", "ConvertToTheiaRecon"}
-    hdr = open(core + "spline_trajectory_estimator.h").read()
-    pub = hdr[hdr.index("public:"):hdr.index("private:")]
-    names = set(re.findall(r"\b([A-Z][A-Za-z0-9_]+)\s*\(", pub)) - {"SplineTrajectoryEstimator", "EIGEN_MAKE_ALIGNED_OPERATOR_NEW"}
+    names = set(facts["spline_trajectory_estimator_public"])     # (public section of spline_trajectory_estimator.h, constructor excluded)
     need = names - not_defined_or_unused
     assert len(need) >= 30
     assert need <= py_names, sorted(need - py_names)
     assert need <= cpp_names, sorted(need - cpp_names)
-    hdr = open(core + "imu_camera_calibrator.h").read()
-    names = set(re.findall(r"\b([A-Z][A-Za-z0-9_]+)\s*\(", hdr[hdr.index("class ImuCameraCalibrator"):])) - {"ImuCameraCalibrator"}
+    names = set(facts["imu_camera_calibrator_names"])
     private_helper = {"InitializeGravity"}          # private in the reference; part of BatchInitSpline here
     assert names - private_helper <= py_names, sorted(names - private_helper - py_names)
     assert names - private_helper <= cpp_names, sorted(names - private_helper - cpp_names)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/include/OpenCameraCalibrator/core"), reason="reads the reference headers: only where the tree is mounted")
 def test_calibrator_pose_estimator_and_rotation_mirrors_carry_the_reference_names():
-    core = "/root/reference/include/OpenCameraCalibrator/core/"
+    import json
     pkg = os.path.join(ROOT, "openimucameracalibrator_amd")
+    facts = json.load(open(REF_FACTS))["public_methods"]     # (public methods of each class, constructor excluded)
 
     def public_methods(header, cls):
-        h = open(core + header).read()
-        body = h[h.index("class " + cls):]
-        body = body[body.index("public:"):body.index("private:")]
-        return set(re.findall(r"\b([A-Z][A-Za-z0-9_]+)\s*\(", body)) - {cls, "EIGEN_MAKE_ALIGNED_OPERATOR_NEW"}
+        return set(facts[cls])
     cc = open(os.path.join(pkg, "camera_calibrator.py")).read()
     names = set(re.findall(r"def ([A-Z][A-Za-z0-9_]+)\(", cc))
     assert public_methods("camera_calibrator.h", "CameraCalibrator") - {"WriteCalibration"} <= names      # declared, never defined

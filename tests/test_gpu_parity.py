@@ -965,13 +965,16 @@ def test_distributed_cyclic_reduction_through_rejected_steps(tmp_path, monkeypat
 def test_more_ranks_than_blocks_fall_back_to_the_gathered_band(tmp_path):
     """Degenerate sharding: C1 (five 64-column blocks) on EIGHT time shards -- the cuts, rounded to block boundaries, leave ranks that
     own no block, so the distributed solve does not apply: every rank gathers the band (owned ranges of zero rows included) and solves
-    the whole system, and the eight processes still take the steps of one."""
+    the whole system, and the eight ranks still take the steps of one."""
     parts, whole = _sharded_processes_take_the_steps_of_one("C1", FLAGS1, 0, 0, 1, tmp_path, 8)
     assert all(p_["dist_ranks"] == 0 and p_["dist_solves"] == 0 for p_ in parts)
 
 
+MAX_WORKER_PROCESSES = 4     # (with this test process: no more than five processes have the GPU open at once)
+
+
 def _sharded_processes_take_the_steps_of_one(cfg, flags, ls, inner, owner, tmp_path, nproc, iters=6):
-    """Rank r of `nproc` PROCESSES holds the r-th time shard (remote measurements declared) and runs `oicc_optimize` with the
+    """Rank r of `nproc` ranks holds the r-th time shard (remote measurements declared) and runs `oicc_optimize` with the
     all-reduce hook (`oicc_set_allreduce`): packed normal equations after every Jacobian pass, the candidate cost (accumulated in
     LmState) after every cost pass, slopes of the bounds line search.  RCCL refuses two ranks on one device, so the hook stages
     through host memory and gloo -- the product side of the hook is what is tested.  Both ranks must take the same steps as ONE
@@ -979,16 +982,21 @@ def _sharded_processes_take_the_steps_of_one(cfg, flags, ls, inner, owner, tmp_p
     owner = 1 (round 4): the owner-computes exchange instead of the all-reduce of the whole buffer -- every band row has one owning
     rank; the ranks send the partial rows they hold of the other's range (oicc_set_exchange: send / receive), gather the owned
     ranges (broadcast per owner) and all-reduce only the arrow corner, the arrow gradient and the cost: the whole buffer is never
-    summed, the steps are those of ONE process."""
+    summed, the steps are those of ONE process.
+    Every rank runs in a process of its own up to MAX_WORKER_PROCESSES ranks; with more, each worker process hosts several ranks, one
+    thread, problem, stream and gloo group per rank (tests/mp_shard_worker.py)."""
     import os, subprocess, sys as _sys, json as _json, socket
     worker = os.path.join(os.path.dirname(os.path.abspath(__file__)), "mp_shard_worker.py")
     sock = socket.socket(); sock.bind(("127.0.0.1", 0)); port = sock.getsockname()[1]; sock.close()
 
     def run(world):
-        procs, outs = [], []
-        for r in range(world):
-            env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port + world), LOCAL_RANK="0")
-            out = str(tmp_path / ("w%d_r%d.json" % (world, r))); outs.append(out)
+        # at most MAX_WORKER_PROCESSES processes hold the GPU besides this one: more ranks share a process (a thread per rank)
+        nprocs = min(world, MAX_WORKER_PROCESSES)
+        procs, outs = [], [str(tmp_path / ("w%d_r%d.json" % (world, r))) for r in range(world)]
+        for k in range(nprocs):
+            ranks = ",".join(str(r) for r in range(world) if r % nprocs == k)
+            env = dict(os.environ, RANKS=ranks, WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port + world), LOCAL_RANK="0")
+            out = str(tmp_path / ("w%d_r{rank}.json" % world))
             procs.append(subprocess.Popen([_sys.executable, worker, cfg, str(int(flags)), str(iters), str(ls), out, str(inner), str(owner)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
         for p_ in procs:
             o, _ = p_.communicate(timeout=400)

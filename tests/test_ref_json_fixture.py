@@ -1,6 +1,7 @@
 """File formats pinned by the REFERENCE's own JSON library: tests/golden/ref_corners.* were written by
 oracle/_ref/ref_json_tool (= include/OpenCameraCalibrator/utils/json.h of the reference, nlohmann::json 3.7.0, built from
-the reference tree by `make -C oracle ref`; tests/golden/make_ubjson_golden.py).  The corner file is the input of the
+the reference tree by `make -C oracle ref`; tests/golden/make_ubjson_golden.py), tests/golden/ref_json_cases.json holds what the
+same tool made of the documents below (tests/golden/make_reference_facts.py).  The corner file is the input of the
 whole chain (src/io/read_scene.cc:25-41), so its reader must agree with the reference's serializer byte for byte."""
 import json
 import os
@@ -14,7 +15,7 @@ from openimucameracalibrator_amd import io_files, planar_init, camera_calibrator
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 G = os.path.join(ROOT, "tests", "golden")
 CSRC = os.path.join(ROOT, "openimucameracalibrator_amd", "csrc")
-TOOL = os.path.join(ROOT, "oracle", "_ref", "ref_json_tool")
+CASES = os.path.join(G, "ref_json_cases.json")
 
 
 def _sorted(o):
@@ -62,16 +63,15 @@ def test_cpp_reader_parses_the_reference_bytes():
         assert np.abs(got[:3] - C).max() < 1e-7 and np.abs(got[3:] - CC.rotation_to_angle_axis(R)).max() < 1e-7
 
 
-@pytest.mark.skipif(not os.path.exists(TOOL), reason="oracle/_ref/ref_json_tool is only built where /root/reference is mounted")
-def test_reference_library_reads_what_this_repository_writes(tmp_path):
-    """live: files of io_files.ubjson_encode (synthetic corner files of the tests) through the reference's from_ubjson."""
+def test_reference_library_reads_what_this_repository_writes():
+    """files of io_files.ubjson_encode (synthetic corner files of the tests) through the reference's from_ubjson: the encoder still
+    writes the bytes the reference read, and what it read is the scene."""
     ds = CC.make_calibration_dataset("pinhole", num_views=4, corners_per_view=12, seed=5)
     import test_ba_applications as T
     sc = T.scene_of(ds)
-    a, b = str(tmp_path / "mine.uson"), str(tmp_path / "back.json")
-    open(a, "wb").write(io_files.ubjson_encode(sc))
-    subprocess.check_call([TOOL, "from_ubjson", a, b])
-    assert json.load(open(b)) == json.loads(json.dumps(sc))
+    case = json.load(open(CASES))["scene"]
+    assert io_files.ubjson_encode(sc) == bytes.fromhex(case["encoder_ubjson"])
+    assert case["reference_reads"] == json.loads(json.dumps(sc))
 
 
 def test_cpp_reader_and_writer_reproduce_the_reference_dump(tmp_path):
@@ -103,35 +103,30 @@ def _documents():
     return st.recursive(leaves, lambda c: st.one_of(st.lists(c, max_size=5), st.dictionaries(st.one_of(keys, texts), c, max_size=5)), max_leaves=25)
 
 
-@pytest.mark.skipif(not os.path.exists(TOOL), reason="oracle/_ref/ref_json_tool is only built where /root/reference is mounted")
 def test_random_documents_against_the_reference_serializer(tmp_path):
-    """property test with the reference library as the judge: for random documents the encoder's bytes equal
-    nlohmann::json::to_ubjson's, the Python and C++ decoders read the reference's bytes, from_ubjson reads the encoder's."""
-    from hypothesis import given, settings, HealthCheck
+    """property test with the reference library as the judge: for random documents (the 150 derandomized examples of
+    _documents(), recorded with the reference's answers) the encoder's bytes equal nlohmann::json::to_ubjson's, the Python and
+    C++ decoders read the reference's bytes, from_ubjson reads the encoder's."""
     a, b, c = str(tmp_path / "d.json"), str(tmp_path / "d.uson"), str(tmp_path / "back.json")
     exe = str(tmp_path / "json_roundtrip")
     subprocess.check_call(["g++", "-O1", "-std=c++17", os.path.join(CSRC, "host", "json_roundtrip.cpp"), "-o", exe])
-
-    @settings(max_examples=150, derandomize=True, deadline=None, suppress_health_check=list(HealthCheck))
-    @given(_documents())
-    def run(doc):
-        doc = {"doc": doc}
-        json.dump(doc, open(a, "w"))
-        subprocess.check_call([TOOL, "to_ubjson", a, b])
-        raw = open(b, "rb").read()
+    cases = json.load(open(CASES))["documents"]
+    assert len(cases) == 150
+    for case in cases:
+        doc = json.loads(case["json"])
+        open(a, "w").write(case["json"])
+        raw = bytes.fromhex(case["reference_ubjson"])                 # to_ubjson of the JSON text
+        open(b, "wb").write(raw)
         assert io_files.ubjson_encode(_sorted(doc)) == raw
         assert io_files.ubjson_decode(raw) == doc
         subprocess.check_call([exe, b, c, "2"])                      # the C++ reader (host/json_min.hpp) on the reference's bytes
         assert json.load(open(c)) == doc
         subprocess.check_call([exe, a, c, "0"])                      # ... and its text parser on the JSON text
         assert json.load(open(c)) == doc
-        open(b, "wb").write(io_files.ubjson_encode(doc))
-        subprocess.check_call([TOOL, "from_ubjson", b, c])
-        assert json.load(open(c)) == doc
-    run()
+        assert io_files.ubjson_encode(doc) == bytes.fromhex(case["encoder_ubjson"])   # the bytes from_ubjson was given ...
+        assert case["reference_reads_encoder"] == doc                                 # ... and what it read
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src/io"), reason="reads the reference sources: only where the tree is mounted")
 def test_every_json_key_of_the_reference_io_layer_is_known_to_the_host_code():
     """Drop-in at the file level: every JSON key the reference's readers / writers of this path use (string literals in
     json["..."] accesses of src/io/*.cc, the three applications' mains and the calibrator / pose estimator sources) appears in
@@ -139,15 +134,7 @@ def test_every_json_key_of_the_reference_io_layer_is_known_to_the_host_code():
     (vendor format) and two board-description fields only the board extractor writes."""
     import glob
     import re
-    ref = glob.glob("/root/reference/src/io/*.cc") + ["/root/reference/applications/continuous_time_imu_to_camera_calibration.cc",
-                                                       "/root/reference/applications/estimate_imu_to_camera_rotation.cc",
-                                                       "/root/reference/applications/calibrate_camera.cc",
-                                                       "/root/reference/applications/estimate_camera_poses_from_checkerboard.cc",
-                                                       "/root/reference/src/core/board_extractor.cc", "/root/reference/src/core/camera_calibrator.cc",
-                                                       "/root/reference/src/core/pose_estimator.cc"]
-    keys = set()
-    for f in ref:
-        keys |= set(re.findall(r'\[\s*"([A-Za-z0-9_ /]+)"\s*\]', open(f).read()))
+    keys = set(json.load(open(os.path.join(G, "reference_facts.json")))["io_json_keys"])    # (recorded by tests/golden/make_reference_facts.py)
     mine = ""
     for f in glob.glob(os.path.join(CSRC, "host", "*")) + glob.glob(os.path.join(ROOT, "openimucameracalibrator_amd", "*.py")):
         mine += open(f).read()

@@ -2,7 +2,7 @@
 
 * not gpu: the numpy oracle (oracle/sew_oracle.py) against golden outputs of the REFERENCE module
   (tests/golden/sew_golden.json, produced by tests/golden/make_sew_golden.py importing
-  /root/reference/python/sew.py) -- this oracle is pinned by the reference itself;
+  the reference's python/sew.py) -- this oracle is pinned by the reference itself;
 * gpu: the HIP path (hipFFT + spectral reduction kernels behind oicc_sew_knot_spacing_and_variance)
   against the same goldens and against the oracle.
 Tolerances: knot spacing 1e-9 relative (Brent's xtol is 2e-12), variance 1e-9 relative.
@@ -104,44 +104,17 @@ def test_hip_large_series_linearity_property():
     assert close(d1, d2, 1e-9) and close(9.0 * v1, v2, 1e-9) and 0.01 <= d1 <= 0.3
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/python/sew.py"), reason="live comparison: only where the reference tree is mounted")
 def test_oracle_matches_the_reference_module_on_many_random_signals():
     """beyond the seven committed goldens: 60 seeded signals (random walk + oscillations + noise; odd and even lengths;
-    one or three axes; several quality targets and spacing ranges) through the reference's python/sew.py and through
-    oracle/sew_oracle.py, live."""
-    import subprocess
-    import sys as _sys
-    # the reference module is imported in a child interpreter that never writes bytecode into the read-only tree
-    code = r'''
-import sys, json, numpy as np
-sys.dont_write_bytecode = True
-sys.path.insert(0, "/root/reference/python")
-import sew
-out = []
-for seed in range(60):
-    rng = np.random.default_rng(1000 + seed)
-    n = int(rng.integers(400, 3000)); axes = 1 if seed % 5 == 0 else 3
-    rate = float(rng.choice([100.0, 200.0, 400.0]))
-    t = np.arange(n) / rate
-    sig = np.cumsum(rng.standard_normal((axes, n)), axis=1) * rng.uniform(0.002, 0.05) + rng.uniform(0.0, 0.3) * rng.standard_normal((axes, n))
-    for k in range(3):
-        sig += rng.uniform(0.1, 1.0) * np.sin(2 * np.pi * rng.uniform(0.2, 15.0) * t + rng.uniform(0, 6.28))
-    q = float(rng.choice([0.9, 0.96, 0.99, 0.999])); lo = float(rng.choice([0.005, 0.01, 0.02])); hi = float(rng.choice([0.1, 0.15, 0.4]))
-    dt, var = sew.knot_spacing_and_variance(sig, t, q, min_dt=lo, max_dt=hi)
-    out.append(dict(seed=seed, dt=float(dt), var=float(var)))
-print(json.dumps(out))
-'''
-    ref = json.loads(subprocess.check_output([_sys.executable, "-c", code], env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1")).decode().splitlines()[-1])
+    one or three axes; several quality targets and spacing ranges) through the reference's python/sew.py (its answers recorded
+    in tests/golden/reference_facts.json by tests/golden/make_reference_facts.py) and through oracle/sew_oracle.py."""
+    sys.path.insert(0, os.path.join(HERE, "golden"))
+    from make_reference_facts import sew_signal
+    ref = json.load(open(os.path.join(HERE, "golden", "reference_facts.json")))["sew_random_signals"]
+    assert [r["seed"] for r in ref] == list(range(60))
     for r in ref:
         seed = r["seed"]
-        rng = np.random.default_rng(1000 + seed)
-        n = int(rng.integers(400, 3000)); axes = 1 if seed % 5 == 0 else 3
-        rate = float(rng.choice([100.0, 200.0, 400.0]))
-        t = np.arange(n) / rate
-        sig = np.cumsum(rng.standard_normal((axes, n)), axis=1) * rng.uniform(0.002, 0.05) + rng.uniform(0.0, 0.3) * rng.standard_normal((axes, n))
-        for k in range(3):
-            sig += rng.uniform(0.1, 1.0) * np.sin(2 * np.pi * rng.uniform(0.2, 15.0) * t + rng.uniform(0, 6.28))
-        q = float(rng.choice([0.9, 0.96, 0.99, 0.999])); lo = float(rng.choice([0.005, 0.01, 0.02])); hi = float(rng.choice([0.1, 0.15, 0.4]))
+        sig, t, q, lo, hi = sew_signal(seed)
         dt, var = sew_oracle.knot_spacing_and_variance(sig, t, q, min_dt=lo, max_dt=hi)
         assert abs(dt - r["dt"]) <= 1e-9 * r["dt"], (seed, dt, r["dt"])
         assert abs(var - r["var"]) <= 1e-8 * abs(r["var"]) + 1e-300, (seed, var, r["var"])
@@ -157,34 +130,17 @@ class _OracleSewBackend:
         return 0
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/python/get_sew_for_dataset.py"), reason="live comparison: only where the reference tree is mounted")
 def test_twin_application_writes_what_the_reference_script_writes(tmp_path):
-    """python -m openimucameracalibrator_amd.sew is the twin of python/get_sew_for_dataset.py: the REFERENCE SCRIPT ITSELF is run
-    on a telemetry file (child interpreter, bytecode writing off; its unused imports cv2 / matplotlib, absent here, are
-    stubbed) and its output JSON is compared with the twin's (host logic of the twin + numpy oracle instead of the device)."""
-    import subprocess
-    import sys as _sys
-    from openimucameracalibrator_amd import synthetic, io_files, sew as twin
-    ds = synthetic.make_config("C1", camera="gopro9_division")
-    files = io_files.write_dataset_files(ds, str(tmp_path))
-    tel = json.load(open(files["telemetry_json"]))
-    tel["camera_fps"] = 59.94                                   # read_generic_json requires the key (telemetry_converter.py:237)
-    json.dump(tel, open(files["telemetry_json"], "w"))
-    out_ref = str(tmp_path / "sew_ref.json")
-    code = r'''
-import sys, types
-sys.dont_write_bytecode = True
-for name in ("cv2", "matplotlib", "matplotlib.pyplot", "natsort"):
-    sys.modules[name] = types.ModuleType(name)
-sys.modules["matplotlib"].pyplot = sys.modules["matplotlib.pyplot"]
-sys.path.insert(0, "/root/reference/python")
-sys.argv = ["get_sew_for_dataset.py", "--input_json_path", sys.argv[1], "--output_path", sys.argv[2]]
-import get_sew_for_dataset
-get_sew_for_dataset.main()
-'''
-    subprocess.check_call([_sys.executable, "-c", code, files["telemetry_json"], out_ref], env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"),
-                          stdout=subprocess.DEVNULL)
-    ref = json.load(open(out_ref))
+    """python -m openimucameracalibrator_amd.sew is the twin of python/get_sew_for_dataset.py: the REFERENCE SCRIPT ITSELF was run
+    on this telemetry file (tests/golden/make_reference_facts.py; its unused imports cv2 / matplotlib stubbed) and its output JSON
+    is compared with the twin's (host logic of the twin + numpy oracle instead of the device)."""
+    sys.path.insert(0, os.path.join(HERE, "golden"))
+    from make_reference_facts import sew_case_c1, telemetry_digest
+    from openimucameracalibrator_amd import sew as twin
+    _, tel = sew_case_c1(str(tmp_path))
+    golden = json.load(open(os.path.join(HERE, "golden", "reference_facts.json")))["sew_for_dataset_C1"]
+    assert telemetry_digest(tel) == golden["telemetry_sha256"]        # the input the reference script was run on
+    ref = golden["output"]
     mine = twin.spline_weighting_for_telemetry(tel, backend=_OracleSewBackend())
     assert set(mine) == set(ref) == {"so3", "r3", "camera_fps"} and mine["camera_fps"] == ref["camera_fps"] == 59.94
     for k in ("so3", "r3"):
