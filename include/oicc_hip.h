@@ -317,7 +317,8 @@ int oicc_time_allreduce(oicc_problem* p, int32_t flags, int32_t repeats, double*
  * cyclic reduction: step (2) above shrinks to two doubles per row (diagonal and gradient: what every rank needs of ALL rows), every
  * rank reduces the blocks of ITS range down to the range's first block, ONE all-gather moves the ranks' separator blocks (0.11 MB each),
  * every rank solves the N-block top system and back-substitutes its own range, ONE all-gather moves the step -- the same bits on
- * every rank, so the candidate is not broadcast any more (only the step's scalars are).  The band rows never leave their owner.  The choice is part of what the ranks agree on in (b); where the geometry is not the cyclic reduction's (half
+ * every rank, so the candidate is not broadcast any more (only the step's scalars are).  The band rows never leave their owner.  The choice is part of what the ranks agree on in (b) (options distributed_solve, solver_algorithm and bcr_max_border
+ * are in the hash; ranks that differ in one fall back together to the all-reduce of the whole buffer); where the geometry is not the cyclic reduction's (half
  * bandwidth > 64, more than 63 arrow columns) or a rank would own no block, all ranks gather the band and solve the whole system as
  * before.  Both gathers go through the same transport as (a): ncclAllGather, or OICC_XCHG_BROADCAST per owner on the hook. */
 enum { OICC_XCHG_SENDRECV = 0, OICC_XCHG_BROADCAST = 1 };
@@ -353,7 +354,10 @@ int oicc_get_tangent_layout(oicc_problem* p, int32_t flags, int32_t* num_tangent
  * point order.  offsets: one entry per point of oicc_set_scene_points. */
 int oicc_get_scene_point_offsets(oicc_problem* p, int32_t flags, int32_t* offsets);
 /* One residual + Jacobian + normal-equation pass at the current parameters.
- * cost = 0.5*sum r^2.  H_dense (P*P row-major, symmetric) and g (P) optional. */
+ * cost = 0.5*sum r^2.  H_dense (P*P row-major, symmetric) and g (P) optional.
+ * Time-sharded problems (oicc_set_shard with a reduction installed): a collective that returns the WHOLE problem's cost, J^T J and
+ * gradient on every rank -- the band is gathered for this call even where the ranks agreed on the distributed solve, which never
+ * gathers it.  The same holds for oicc_evaluate_cost and oicc_evaluate_entries. */
 int oicc_evaluate(oicc_problem* p, int32_t flags, double* cost, double* H_dense,
                   double* g, int32_t P_capacity);
 /* Cost-only pass (what LM runs for a candidate point). */

@@ -83,13 +83,27 @@ bool owner_exchange_ready(const oicc_problem* p) {   // this rank alone: can it 
 // collective statement) sums [ready, 1, h, h^2] through the installed reduction, h = a hash of the cuts and of every pair's row
 // count as THIS rank derived them: the exchange is used only if every rank is ready and all hashes are equal (n sum h^2 == (sum h)^2,
 // exact in doubles for 20-bit hashes); otherwise every rank falls back to the all-reduce of the whole packed buffer.
+// The same agreement decides the distributed solve (dist_solve_usable): the options it depends on are mixed into h, and its
+// workspaces are allocated BEFORE the sum, their success part of `ready` -- no rank-local outcome can send one rank into the
+// solve's all-gathers while another gathers the band.
+static bool dist_solve_prepare(oicc_problem* p, bool* applies);
+static uint32_t hash_mix(uint32_t h, double v) {   // (splitmix64 finaliser over the hash and an option's bits)
+  uint64_t b; std::memcpy(&b, &v, sizeof(b));
+  uint64_t z = ((uint64_t(h) << 32) ^ b) + 0x9e3779b97f4a7c15ull;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull; z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return uint32_t(z ^ (z >> 31));
+}
 int owner_exchange_agree(oicc_problem* p, hipStream_t st, bool* use) {
   *use = false;
   if (p->shard_n <= 1 || p->reduce == nullptr) return OICC_OK;
   oicc_problem::OwnerPlan& op = p->owner;
   if (op.agreed_gen == p->layout_gen) { *use = op.agreed; return OICC_OK; }
-  const double h = double(op.valid ? ((op.hash ^ (p->opt["distributed_solve"] != 0.0 ? 0x5bd1eu : 0u)) & 0xfffffu) : 0u);   // (the choice of solve is part of what the ranks must agree on)
-  double v[4] = {owner_exchange_ready(p) ? 1.0 : 0.0, 1.0, h, h * h};
+  bool dist_applies = false;
+  const bool dist_ok = dist_solve_prepare(p, &dist_applies);
+  uint32_t hm = op.hash;
+  for (const char* name : {"distributed_solve", "solver_algorithm", "bcr_max_border"}) hm = hash_mix(hm, p->opt[name]);   // (the choice of solve is part of what the ranks must agree on)
+  const double h = double(op.valid ? (hm & 0xfffffu) : 0u);
+  double v[4] = {owner_exchange_ready(p) && dist_ok ? 1.0 : 0.0, 1.0, h, h * h};
   if (!p->d_xagree.resize(4)) { p->err = "hipMalloc exchange agreement"; return OICC_ERR_HIP; }
   HIPCK(p, hipMemcpyAsync(p->d_xagree.p, v, sizeof(v), hipMemcpyHostToDevice, st));
   if (p->reduce(p->reduce_user, p->d_xagree.p, 4, st) != 0) { p->err = "allreduce callback failed"; return OICC_ERR_STATE; }
@@ -97,6 +111,7 @@ int owner_exchange_agree(oicc_problem* p, hipStream_t st, bool* use) {
   HIPCK(p, hipStreamSynchronize(st));
   op.agreed = v[0] == v[1] && v[1] == double(p->shard_n) && v[1] * v[3] == v[2] * v[2];
   op.agreed_gen = p->layout_gen;
+  p->dist.usable = op.agreed && dist_applies; p->dist.gen = p->layout_gen;
   if (!op.agreed && p->opt["verbose"] != 0.0) std::printf("[oicc] rank %d: owner-computes exchange not agreed on by all ranks (ready %g of %g, shard size %d): all-reduce of the packed buffer\n", p->shard_rank, v[0], v[1], p->shard_n);
   *use = op.agreed;
   return OICC_OK;
@@ -140,23 +155,23 @@ static int shard_allgather(oicc_problem* p, double* slots, int64_t piece, hipStr
 }
 
 // ---- distributed linear solve (round 6): see kernels_bcr.hip, "Distributed block cyclic reduction" ----
-// Usable when the ranks agreed on the exchange (same cuts everywhere), the geometry is the cyclic reduction's, and every rank owns
-// at least one 64-column block: all of it derived from agreed data, so every rank answers alike.
-bool dist_solve_usable(oicc_problem* p) {
+// Applies when the geometry is the cyclic reduction's and every rank owns at least one 64-column block -- derived from the cuts and
+// options, all of them in the agreement hash, so every rank that agreed answers alike.  The workspaces are allocated here, before
+// the agreement (returns false when an allocation failed; *applies: the solve applies to this layout).
+static bool dist_solve_prepare(oicc_problem* p, bool* applies) {
+  *applies = false;
   oicc_problem::DistSolve& ds = p->dist;
   const oicc_problem::OwnerPlan& op = p->owner;
-  if (ds.gen == p->layout_gen) return ds.usable;
-  ds.gen = p->layout_gen; ds.usable = false;
   const TangentLayout& tl = p->tl;
   const int n = p->shard_n;
-  if (n < 2 || n > 64 || !op.valid || !op.agreed || op.agreed_gen != p->layout_gen || p->opt["distributed_solve"] == 0.0) return false;
+  if (n < 2 || n > 64 || !op.valid || p->opt["distributed_solve"] == 0.0) return true;
   const int algo = int(p->opt["solver_algorithm"]);
-  if (!bcr_applicable(tl) || tl.a + 1 > int(p->opt["bcr_max_border"]) || (algo != 0 && algo != 4)) return false;
+  if (!bcr_applicable(tl) || tl.a + 1 > int(p->opt["bcr_max_border"]) || (algo != 0 && algo != 4)) return true;
   const int nblk = (tl.Pb + 63) / 64;
   ds.b0.assign(size_t(n) + 1, 0);
   for (int k = 0; k <= n; ++k) ds.b0[size_t(k)] = k == n ? nblk : op.cut[size_t(k)] / 64;
   int max_loc = 0;
-  for (int k = 0; k < n; ++k) { const int c = ds.b0[size_t(k) + 1] - ds.b0[size_t(k)]; if (c < 1 || (k > 0 && op.cut[size_t(k)] % 64 != 0)) return false; max_loc = std::max(max_loc, c); }
+  for (int k = 0; k < n; ++k) { const int c = ds.b0[size_t(k) + 1] - ds.b0[size_t(k)]; if (c < 1 || (k > 0 && op.cut[size_t(k)] % 64 != 0)) return true; max_loc = std::max(max_loc, c); }
   BcrDist& d = ds.d;
   d.nranks = n; d.rank = p->shard_rank; d.b0 = ds.b0[size_t(d.rank)]; d.n_loc = ds.b0[size_t(d.rank) + 1] - d.b0; d.max_loc = max_loc;
   d.ws_doubles = bcr_dist_workspace_doubles(tl, d.n_loc, n);
@@ -164,8 +179,13 @@ bool dist_solve_usable(oicc_problem* p) {
   if (!ds.ws.resize(size_t(d.ws_doubles)) || !ds.msg.resize(size_t(d.msg_piece) * size_t(n)) || !ds.xg.resize(size_t(d.x_piece) * size_t(n)) || !ds.d_b0.upload(ds.b0, p->stream)) return false;
   if (hipStreamSynchronize(p->stream) != hipSuccess) return false;   // (b0 may be reassigned)
   d.ws = ds.ws.p; d.msg = ds.msg.p; d.xg = ds.xg.p; d.d_b0 = ds.d_b0.p;
-  ds.usable = true;
+  *applies = true;
   return true;
+}
+// Usable once the ranks agreed on the exchange of the CURRENT layout and the solve applied to it (owner_exchange_agree); before that
+// agreement the answer is no, and nothing is cached -- a call that runs ahead of the agreement cannot fix the decision.
+bool dist_solve_usable(const oicc_problem* p) {
+  return p->dist.usable && p->dist.gen == p->layout_gen && p->owner.agreed_gen == p->layout_gen && p->owner.agreed;
 }
 int dist_solve(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb_in, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st) {
   oicc_problem::DistSolve& ds = p->dist;
@@ -226,8 +246,8 @@ int owner_exchange(oicc_problem* p, const NormalEq& ne, hipStream_t st, int64_t*
   //     a + 2 strided pieces of a range as separate broadcasts: 88 collectives per pass at N = 8, a = 9, thousands under POINTS).
   //     Slot k of the gather buffer belongs to rank k; native: one in-place ncclAllGather of equal (padded) slots, or one broadcast
   //     per owner where that entry point is missing; hook transport: one broadcast per owner.
-  double* slots = p->d_xgather.p;
-  if (dist_solve_usable(p)) {
+  double* slots = p->d_xgather.p;   // (sized for the packed rows of the largest owned range on every rank: the gathered band fits)
+  if (!p->full_system && dist_solve_usable(p)) {
     // distributed solve (round 6): the band rows stay where they are -- the owner eliminates them; every rank still needs the
     // diagonal (Jacobi scaling, Levenberg-Marquardt diagonal) and the gradient of ALL rows: two doubles per row
     const int64_t piece2 = int64_t(std::max(op.max_owned, 1)) * 2;
@@ -364,7 +384,7 @@ int oicc_debug_dist_solve_emulated(oicc_problem* p, int32_t flags, int32_t nrank
 // debug read-out (outside include/oicc_hip.h; tests, bench.py): out4 = [distributed solves run so far, this rank's first block, its block count, ranks]
 int oicc_debug_dist_solve_info(const oicc_problem* p, int64_t out4[4]) {
   if (!p || !out4) return OICC_ERR_INVALID_ARG;
-  out4[0] = p->dist.solves; out4[1] = p->dist.d.b0; out4[2] = p->dist.d.n_loc; out4[3] = p->dist.usable ? p->dist.d.nranks : 0;
+  out4[0] = p->dist.solves; out4[1] = p->dist.d.b0; out4[2] = p->dist.d.n_loc; out4[3] = dist_solve_usable(p) ? p->dist.d.nranks : 0;
   return OICC_OK;
 }
 
@@ -390,6 +410,11 @@ int oicc_time_exchange(oicc_problem* p, int32_t flags, int32_t repeats, double* 
   if (!owner_exchange_ready(p)) { p->err = "owner-computes exchange not set up (oicc_set_shard, remote measurements with their owners, a transport)"; return OICC_ERR_STATE; }
   if (repeats < 0) return OICC_OK;                                               // (a local question: is the exchange set up? nothing is sent)
   hipStream_t st = p->stream;
+  // the agreement of the layout first (a collective, as the exchange is): the exchange timed is the one the solve runs -- with the
+  // distributed solve's branch where the ranks agreed on it -- and a call ahead of every pass fixes no decision before it
+  bool use = false;
+  rc = owner_exchange_agree(p, st, &use); if (rc) return rc;
+  if (!use) { p->err = "owner-computes exchange not agreed on by all ranks"; return OICC_ERR_STATE; }
   HIPCK(p, hipMemsetAsync(p->d_ne2.p, 0, p->ne.total * sizeof(double), st));   // (the second buffer: the current system stays intact)
   EventPair ev; HIPCK(p, hipEventCreate(&ev.a)); HIPCK(p, hipEventCreate(&ev.b)); hipEvent_t e0 = ev.a, e1 = ev.b;
   int64_t moved = 0;

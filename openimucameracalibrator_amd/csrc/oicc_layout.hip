@@ -181,7 +181,7 @@ void build_owner_plan(oicc_problem* p) {
     int c = lo[k] < nk ? (std::min(lo[k], prev_hi) + std::max(lo[k], prev_hi)) / 2 : prev_hi;   // middle of the overlap (or of the gap)
     c = std::min(c, nk);
     // Round 6: a cut lies on a multiple of 64 ROWS (possibly inside a knot's three rows) -- the blocks of the cyclic reduction
-    // (kernels_bcr.hip) are 64 columns, and a rank eliminates the blocks of its own range (distributed solve, oicc_dist_solve.hip)
+    // (kernels_bcr.hip) are 64 columns, and a rank eliminates the blocks of its own range (distributed solve, oicc_exchange.hip)
     int32_t row = int32_t((int64_t(3) * c + 32) / 64) * 64;
     row = std::min<int32_t>(std::max<int32_t>(row, op.cut[k - 1]), int32_t((L.Pb / 64) * 64));
     op.cut[k] = row;
@@ -360,12 +360,11 @@ int prepare(oicc_problem* p, int flags) {
   // pageable arrays: 3 ms of staged copies that block the caller) and allocates the buffers; joined before the tile tables travel.
   // (Measured and not kept: the measurement copies on a second thread + stream instead -- 11 ms there against 3.2 ms here: the staged
   // copies of one thread and the allocations of the other serialise inside the runtime.)
-  std::thread tiles_thread; int tiles_rc = OICC_OK; bool tiles_started = false;
+  std::thread tiles_thread; int tiles_rc = OICC_OK;
   struct Join { std::thread& t; ~Join() { if (t.joinable()) t.join(); } } join{tiles_thread};   // (no exit leaves the thread running)
   if (!current) {
     layout_scalars(p);
     int n_cu = 256; (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, p->device); p->n_cu = n_cu < 1 ? 256 : n_cu;
-    tiles_started = true;
     if (p->corner_view.size() + p->acc.size() + p->gyr.size() >= 100000 && p->opt["debug_sync"] == 0.0 && p->opt["setup_threads"] != 0.0) tiles_thread = std::thread([p, &tiles_rc]() { tiles_rc = build_tiles_host(p); });
     else tiles_rc = build_tiles_host(p);
   }
@@ -375,7 +374,6 @@ int prepare(oicc_problem* p, int flags) {
   const double t2 = now_s();
   if (current) return OICC_OK;
   rc = make_layout_device(p, flags, &tiles_thread, &tiles_rc);
-  (void)tiles_started;
   if (timing) std::printf("[oicc] prepare: runs of samples + host layout %.3f ms, measurements %.3f ms, parameters %.3f ms, buffers + tiles %.3f ms\n", 1e3 * (t0 - t00), 1e3 * (t1 - t0), 1e3 * (t2 - t1), 1e3 * (now_s() - t2));
   return rc;
 }

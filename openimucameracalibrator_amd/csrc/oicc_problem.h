@@ -136,9 +136,11 @@ struct oicc_problem {
                      int64_t agreed_gen = -1; bool agreed = false;   // all ranks agreed (once per layout, through the installed reduction) that every one of them can run the exchange on the same cuts
                      uint32_t hash = 0; } owner;
   DevBuf<int32_t> d_xrows, d_xcut; DevBuf<double> d_xsend, d_xrecv, d_xgather, d_xagree;
+  bool full_system = false;   // the exchange of a Jacobian pass leaves the WHOLE system on every rank (oicc_evaluate*, the solver profile): no distributed-solve branch
   // distributed linear solve (round 6; kernels_bcr.hip launch_bcr_dist_*, oicc_exchange.hip dist_solve): every rank reduces the 64-column
   // blocks of its own range, the ranks' separators are gathered and solved by all, the step is gathered -- the band never travels
-  struct DistSolve { bool usable = false; int64_t gen = -1; BcrDist d; std::vector<int32_t> b0; DevBuf<int32_t> d_b0; DevBuf<double> ws, msg, xg; double ms_forward = 0, ms_gather = 0, ms_middle = 0, ms_gather_x = 0; int64_t solves = 0;
+  // usable: decided together with the exchange agreement of layout `gen` (owner_exchange_agree) -- never before it
+  struct DistSolve { bool usable = false; int64_t gen = -1; BcrDist d; std::vector<int32_t> b0; DevBuf<int32_t> d_b0; DevBuf<double> ws, msg, xg; int64_t solves = 0;
                      bool last_step_gathered = false;   // the last solve left the SAME step, bit for bit, on every rank (the gathered pieces): its retraction needs no broadcast of the candidate
                    } dist;
   bool has_ld_block = false, has_tic_block = false, has_acc = false, has_gyr = false;
@@ -312,7 +314,7 @@ int shard_broadcast_begin(oicc_problem* p);                                     
 int shard_broadcast(oicc_problem* p, double* ptr, int64_t count, int root, hipStream_t st);      // native RCCL (one group) or the transport hook
 int shard_broadcast_end(oicc_problem* p);
 int owner_exchange(oicc_problem* p, const NormalEq& ne, hipStream_t st, int64_t* bytes_moved = nullptr);
-bool dist_solve_usable(oicc_problem* p);   // (after the exchange is agreed on: derived from what all ranks agreed on, so every rank answers alike)
+bool dist_solve_usable(const oicc_problem* p);   // (decided by the exchange agreement of the current layout: every rank answers alike; false before it)
 int dist_solve(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st);
 int lm_solve_any(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st);   // the distributed solve on agreed shards, else launch_lm_solve
 }  // namespace oicc

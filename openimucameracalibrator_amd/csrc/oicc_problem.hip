@@ -419,9 +419,17 @@ int oicc_get_scene_point_offsets(oicc_problem* p, int32_t flags, int32_t* offset
   return OICC_OK;
 }
 
+// A Jacobian pass whose exchange leaves the WHOLE system on every rank of a time-sharded problem: the gathered band, even where the
+// ranks agreed on the distributed solve (whose pass leaves the foreign rows' band and arrow entries as this rank's partial sums).
+static int eval_pass_full_system(oicc_problem* p) {
+  p->full_system = true;
+  const int rc = eval_pass(p, p->d_x.p, true);
+  p->full_system = false;
+  return rc;
+}
 int oicc_evaluate(oicc_problem* p, int32_t flags, double* cost, double* H, double* g, int32_t Pcap) {
   int rc = prepare(p, flags); if (rc) return rc;
-  rc = eval_pass(p, p->d_x.p, true); if (rc) return rc;
+  rc = eval_pass_full_system(p); if (rc) return rc;
   std::vector<double> h(p->ne.total);
   HIPCK(p, hipMemcpyAsync(h.data(), p->ne.base, h.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
   HIPCK(p, hipStreamSynchronize(p->stream));
@@ -441,7 +449,7 @@ int oicc_evaluate(oicc_problem* p, int32_t flags, double* cost, double* H, doubl
 int oicc_evaluate_entries(oicc_problem* p, int32_t flags, int64_t n, const int32_t* rows, const int32_t* cols, double* values) {
   ARG(p, n >= 0 && (n == 0 || (rows && cols && values)), "entries");
   int rc = prepare(p, flags); if (rc) return rc;
-  rc = eval_pass(p, p->d_x.p, true); if (rc) return rc;
+  rc = eval_pass_full_system(p); if (rc) return rc;
   std::vector<double> h(p->ne.total);
   HIPCK(p, hipMemcpyAsync(h.data(), p->ne.base, h.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
   HIPCK(p, hipStreamSynchronize(p->stream));
@@ -1009,7 +1017,7 @@ double oicc_debug_ls_next_step_size(const double init[3], const double* prev, in
 int oicc_debug_solver_profile(oicc_problem* p, int32_t flags, long long out[12]) {
   int rc = prepare(p, flags); if (rc) return rc;
   hipStream_t st = p->stream;
-  rc = eval_pass(p, p->d_x.p, true); if (rc) return rc;
+  rc = eval_pass_full_system(p); if (rc) return rc;   // (time shards: every rank profiles the solve of the whole system)
   const TangentLayout& tl = p->tl;
   DevBuf<long long> d; if (!d.resize(12)) return OICC_ERR_HIP;
   SolveBuffers sb = solve_buffers(p, d.p);

@@ -7,7 +7,14 @@ usage: python mp_shard_worker.py <cfg> <flags> <iterations> <bounds_line_search>
 owner_computes = 1: the round-4 exchange (oicc_set_shard): halo rows to their owners, gather of the owned band ranges, all-reduce of
 the arrow corner only -- through the transport hooks (oicc_set_exchange: gloo send / recv / broadcast staged through host memory).
 With inner_iterations = 1 every rank also builds the WHOLE problem on the device and hands it to its shard as the source of the
-inner-iteration sweeps (oicc_set_inner_iteration_source): the reference's solver configuration on time-sharded ranks."""
+inner-iteration sweeps (oicc_set_inner_iteration_source): the reference's solver configuration on time-sharded ranks.
+OICC_TEST_SEQUENCE: the public calls every rank makes, in this order (default: optimize), comma-separated --
+  optimize[:iterations]  time_exchange  time_linear_solve  evaluate  evaluate_cost  evaluate_entries  solver_profile
+  set_option:<name>:<value>
+evaluate_entries reads the (2, n) int32 array [rows; cols] of OICC_TEST_ENTRIES (.npy).  Each call's results (npz next to <out.json>)
+and oicc_debug_dist_solve_info behind it are listed under "steps"; the top-level fields are those of the LAST optimize (its
+dist_solves: the distributed solves it ran).  time_exchange is a collective of sharded ranks: skipped on one process.
+OICC_TEST_RANK_OPTIONS="<rank>:<name>:<value>;...": options set on that rank only (ranks whose options differ)."""
 import ctypes, datetime, json, os, sys, threading, traceback
 import numpy as np
 import torch
@@ -61,6 +68,9 @@ def run_rank(rank, world, cfg, flags, iters, ls, out, inner, owner):
     if os.environ.get("OICC_TEST_DISTRIBUTED_SOLVE") is not None: tr.SetOption("distributed_solve", int(os.environ["OICC_TEST_DISTRIBUTED_SOLVE"]))
     shared_launch = os.environ.get("OICC_TEST_SHARED_LAUNCH_SLOTS")     # (tests: the shared blocks of the sweeps as a sequence of launches at any size)
     if shared_launch is not None: tr.SetOption("inner_shared_launch_slots", int(shared_launch))
+    for item in filter(None, os.environ.get("OICC_TEST_RANK_OPTIONS", "").split(";")):
+        r_, name, value = item.split(":")
+        if int(r_) == rank and world > 1: tr.SetOption(name, float(value))
     if world > 1:
         tr.SetAllReduce(allreduce)
         if owner: tr.SetExchange(exchange)
@@ -68,12 +78,51 @@ def run_rank(rank, world, cfg, flags, iters, ls, out, inner, owner):
             whole = E.ImuCameraCalibrator().BatchInitSpline(ds)
             # (the plan of the sweeps belongs to the source problem; oicc_optimize forwards the shard's plan options to it: round 6)
             tr.SetInnerIterationSource(whole.trajectory_)
-    s = tr.Optimize(iters, flags)
-    it = tr.GetIterations()
-    info = (ctypes.c_int64 * 4)()
     tr._b.lib.oicc_debug_dist_solve_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64)]
-    assert tr._b.lib.oicc_debug_dist_solve_info(tr._h, info) == 0
-    res = dict(rejected=int(s["num_unsuccessful_steps"]), dist_solves=int(info[0]), dist_first_block=int(info[1]), dist_blocks=int(info[2]), dist_ranks=int(info[3]), band_row_doubles=int(s["half_bandwidth"]) + 1 + int(s["arrow_dim"]) + 1, band_dim=int(s["band_dim"]), rank=rank, blocks=cal.num_blocks, iterations=[dict(cost=i["cost"], ok=i["step_is_successful"], gmax=i["gradient_max_norm"]) for i in it],
+
+    def dist_info():
+        info = (ctypes.c_int64 * 4)()
+        assert tr._b.lib.oicc_debug_dist_solve_info(tr._h, info) == 0
+        return [int(v) for v in info]
+    steps, s, solves_of_last = [], None, 0
+    for k, call in enumerate(os.environ.get("OICC_TEST_SEQUENCE", "optimize").split(",")):
+        op, *args = call.split(":")
+        before, arrays, step = dist_info(), None, dict(op=call)
+        if op == "optimize":
+            s = tr.Optimize(int(args[0]) if args else iters, flags)
+            step.update(final_cost=s["final_cost"], iterations=len(tr.GetIterations()))
+        elif op == "time_exchange":
+            if world == 1: step["skipped"] = True
+            else: tr.TimeExchange(flags, repeats=1)
+        elif op == "time_linear_solve":
+            tr.TimeLinearSolve(flags, repeats=1)
+        elif op == "evaluate":
+            c, H, g = tr.Evaluate(flags)
+            arrays = dict(cost=c, H=H, g=g)
+        elif op == "evaluate_cost":
+            step["cost"] = tr.EvaluateCost(flags)
+        elif op == "evaluate_entries":
+            rc_ = np.load(os.environ["OICC_TEST_ENTRIES"])
+            arrays = dict(values=tr.EvaluateEntries(flags, rc_[0], rc_[1]))
+        elif op == "solver_profile":
+            fn = tr._b.lib.oicc_debug_solver_profile
+            fn.restype = ctypes.c_int; fn.argtypes = [ctypes.c_void_p, ctypes.c_int32, ctypes.POINTER(ctypes.c_longlong)]
+            cycles = (ctypes.c_longlong * 12)()
+            step["rc"] = int(fn(tr._h, flags, cycles)); step["cycles"] = [int(v) for v in cycles]
+        elif op == "set_option":
+            tr.SetOption(args[0], float(args[1]))
+        else:
+            raise ValueError("unknown call in OICC_TEST_SEQUENCE: " + call)
+        step["info"] = dist_info()
+        if op == "optimize": solves_of_last = step["info"][0] - before[0]
+        if arrays is not None:
+            step["file"] = out.format(rank=rank) + ".%d.npz" % k
+            np.savez(step["file"], **arrays)
+        steps.append(step)
+    assert s is not None, "OICC_TEST_SEQUENCE without an optimize"
+    it = tr.GetIterations()
+    info = dist_info()
+    res = dict(rejected=int(s["num_unsuccessful_steps"]), dist_solves=solves_of_last, dist_first_block=int(info[1]), dist_blocks=int(info[2]), dist_ranks=int(info[3]), steps=steps, band_row_doubles=int(s["half_bandwidth"]) + 1 + int(s["arrow_dim"]) + 1, band_dim=int(s["band_dim"]), rank=rank, blocks=cal.num_blocks, iterations=[dict(cost=i["cost"], ok=i["step_is_successful"], gmax=i["gradient_max_norm"]) for i in it],
                final_cost=s["final_cost"], inner_sweeps=s["inner_sweeps"], inner_lm_iterations=s["inner_lm_iterations"], T_i_c=[float(v) for v in tr.GetT_i_c()], hook_calls=calls["n"], hook_doubles=calls["doubles"], hook_max_doubles=calls["max"], P=int(s["num_parameters_tangent"]), exchange=xch)
     json.dump(res, open(out.format(rank=rank), "w"))
     pg.barrier().wait()
