@@ -23,6 +23,7 @@
 #include <unordered_map>
 #include "oicc_device.h"
 #include "lm_decide.h"
+#include "lm_launch.h"
 
 namespace oicc {
 
@@ -856,10 +857,12 @@ int64_t bcr_workspace_doubles(const TangentLayout& tl) {
 
 // ---- the launch sequence in pieces (shared by the one-GPU solve and the distributed one) ----
 struct BcrLevels { int strides[40]; int npivs[40]; int nlev = 0; int64_t off_end = 0; };   // off_end: index of the coupling table behind the last level (distributed: the final coupling (block 0, ghost))
+// build + the inversions of level 0 in one launch (while the level-0 pivots fit on the chip at once)
+static bool bcr_fused_build(int n, const long long* prof) { return n >= 2 && n <= 512 && prof == nullptr; }
 // the damped system in block form (+ the inversions of level 0 in the same launch when they fit the chip at once); returns whether level 0 is inverted
 static bool bcr_launch_build(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb, int reuse_diagonal, double min_diag, double max_diag, BcrArgs A, hipStream_t st) {
   const int n = A.n;
-  const bool fused_build = n >= 2 && n <= 512 && A.prof == nullptr;    // build + the inversions of level 0 in one launch (while the level-0 pivots fit on the chip at once)
+  const bool fused_build = bcr_fused_build(n, A.prof);
   const int64_t work = (int64_t)(n + A.ghost) * 4096;
   A.s = 1; A.offS_in = 0; A.offS_out = 0;
   if (fused_build) {
@@ -916,11 +919,16 @@ static void bcr_launch_last_and_back(BcrArgs A, const BcrLevels& L, hipStream_t 
   }
 }
 
+// the route of one cyclic-reduction solve (lm_solve_route): fused or separate build, or kRouteNone where it does not apply
+int bcr_route(const TangentLayout& tl, const SolveBuffers& sb) {
+  if (!bcr_applicable(tl) || tl.a + 1 > sb.bcr_max_border || sb.ws == nullptr || sb.ws_doubles < bcr_workspace_doubles(tl)) return kRouteNone;
+  if (sb.algo != 0 && sb.algo != 4) return kRouteNone;   // (algorithms 2 and 3 -- the factor-based levels of rounds 1-2 and their parallel form -- left the library in round 4)
+  return bcr_fused_build(bcr_blocks(tl.Pb), sb.prof) ? kRouteBcrFused : kRouteBcrUnfused;
+}
 // build + factor + solve; the solution lands in sb.step_s.  Returns 0, or -1 if not applicable.
 int launch_bcr_solve(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb, int reuse_diagonal,
                      double min_diag, double max_diag, hipStream_t st) {
-  if (!bcr_applicable(tl) || tl.a + 1 > sb.bcr_max_border || sb.ws == nullptr || sb.ws_doubles < bcr_workspace_doubles(tl)) return -1;
-  if (sb.algo != 0 && sb.algo != 4) return -1;   // (algorithms 2 and 3 -- the factor-based levels of rounds 1-2 and their parallel form -- left the library in round 4)
+  if (bcr_route(tl, sb) == kRouteNone) return -1;
   const int n = bcr_blocks(tl.Pb), a1 = tl.a + 1;
   BcrArgs A{};
   bcr_carve(A, sb.ws, n, a1);

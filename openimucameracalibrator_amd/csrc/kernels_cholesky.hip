@@ -25,6 +25,7 @@
 //          half bandwidth 2hb-1); (3) p workgroups back-substitute concurrently.
 #include <hip/hip_runtime.h>
 #include "oicc_device.h"
+#include "lm_launch.h"
 
 namespace oicc {
 
@@ -557,11 +558,16 @@ static bool sweep_geometry_ok(int m, int br) {
   return PW * br <= kCholThreads;
 }
 
+// the partition sweep (window 64) and the reduced system's sweep (window 128) fit LDS and the wave geometry
+static bool partition_geometry_ok(int hb, int a) {
+  if (hb + PW > 64 || 2 * hb - 1 + PW > 128) return false;
+  if (lds_bytes(64, hb + a + 1, hb + PW) > 160 * 1024 - 64 || lds_bytes(128, a + 1, 2 * hb - 1 + PW) > 160 * 1024 - 64) return false;
+  return sweep_geometry_ok(hb + PW, hb + a + 1) && sweep_geometry_ok(2 * hb - 1 + PW, a + 1);
+}
+
 // number of time partitions for (Pb, hb): minimise  interior_panels + 1.6 * reduced_panels
 int choose_partitions(int Pb, int hb, int a) {
-  if (Pb < 8 * (hb + 8) || hb + PW > 64 || 2 * hb - 1 + PW > 128) return 1;
-  if (lds_bytes(64, hb + a + 1, hb + PW) > 160 * 1024 - 64 || lds_bytes(128, a + 1, 2 * hb - 1 + PW) > 160 * 1024 - 64) return 1;
-  if (!sweep_geometry_ok(hb + PW, hb + a + 1) || !sweep_geometry_ok(2 * hb - 1 + PW, a + 1)) return 1;
+  if (Pb < 8 * (hb + 8) || !partition_geometry_ok(hb, a)) return 1;
   int best = 1; double best_cost = Pb / 8.0;
   for (int p = 2; p <= 192; ++p) {
     const int L = (((Pb - (p - 1) * hb) / p) / PW) * PW;
@@ -592,26 +598,36 @@ static void launch_sweep(const CholArgs& A, int grid, int br, hipStream_t st) {
 
 void launch_band_arrow_cholesky_global(const TangentLayout& tl, const SolveBuffers& sb, hipStream_t st);   // kernels_band_global.hip
 
-int launch_band_arrow_cholesky(const TangentLayout& tl, const SolveBuffers& sb, hipStream_t st) {
+// the route of the band solvers: the LDS sweep (window 64 or 128), its time partitions, or the global-memory fallback
+LmRoute band_arrow_route(const TangentLayout& tl, const SolveBuffers& sb) {
   const int ar = tl.a + 1;
   const int m = tl.hb + PW;
-  if (m > 128) { launch_band_arrow_cholesky_global(tl, sb, st); return 0; }   // any geometry: global-memory fallback
+  if (m > 128) return LmRoute{kRouteGlobal, 1};   // any geometry: global-memory fallback
   const int mcap = m <= 64 ? 64 : 128;
-  CholArgs A{};
-  A.sys = CholSys{sb.Mb, sb.Mt, sb.Mc, tl.Pb, tl.W, tl.hb, tl.a};
-  A.sol = sb.step_s; A.fail = &sb.st->chol_failed; A.prof = sb.prof; A.p = 1; A.L = 0; A.Msep = nullptr;
   int p = sb.force_p > 0 ? sb.force_p : choose_partitions(tl.Pb, tl.hb, tl.a);
-  if (p > 1 && choose_partitions(tl.Pb, tl.hb, tl.a) <= 1 && tl.Pb >= 8 * (tl.hb + 8)) p = 1;   // forced p: geometry must still fit
+  // forced p: geometry must still fit (also on a band shorter than the heuristic considers)
+  if (p > 1 && ((choose_partitions(tl.Pb, tl.hb, tl.a) <= 1 && tl.Pb >= 8 * (tl.hb + 8)) || !partition_geometry_ok(tl.hb, tl.a))) p = 1;
   if (sb.ws == nullptr || sb.ws_doubles < solve_workspace_doubles(tl)) p = 1;
   if (p > 1) {
     const int L = (((tl.Pb - (p - 1) * tl.hb) / p) / PW) * PW;
-    if (L < tl.hb + PW) p = 1; else A.L = L;
+    if (L < tl.hb + PW) p = 1;
   }
-  if (p <= 1) {
-    if (lds_bytes(mcap, ar, m) > 160 * 1024 - 64 || !sweep_geometry_ok(m, ar)) { launch_band_arrow_cholesky_global(tl, sb, st); return 0; }
-    if (mcap == 64) launch_sweep<64, 0>(A, 1, ar, st); else launch_sweep<128, 0>(A, 1, ar, st);
-    return 0;
-  }
+  if (p > 1) return LmRoute{kRoutePartitioned, p};
+  if (lds_bytes(mcap, ar, m) > 160 * 1024 - 64 || !sweep_geometry_ok(m, ar)) return LmRoute{kRouteGlobal, 1};
+  return LmRoute{mcap == 64 ? kRouteSweep64 : kRouteSweep128, 1};
+}
+
+int launch_band_arrow_cholesky(const TangentLayout& tl, const SolveBuffers& sb, hipStream_t st) {
+  const int ar = tl.a + 1;
+  const LmRoute r = band_arrow_route(tl, sb);
+  if (r.route == kRouteGlobal) { launch_band_arrow_cholesky_global(tl, sb, st); return 0; }
+  CholArgs A{};
+  A.sys = CholSys{sb.Mb, sb.Mt, sb.Mc, tl.Pb, tl.W, tl.hb, tl.a};
+  A.sol = sb.step_s; A.fail = &sb.st->chol_failed; A.prof = sb.prof; A.p = 1; A.L = 0; A.Msep = nullptr;
+  if (r.route == kRouteSweep64) { launch_sweep<64, 0>(A, 1, ar, st); return 0; }
+  if (r.route == kRouteSweep128) { launch_sweep<128, 0>(A, 1, ar, st); return 0; }
+  const int p = r.p;
+  A.L = (((tl.Pb - (p - 1) * tl.hb) / p) / PW) * PW;
   // workspace carve: Msep | reduced band | reduced arrow rows | reduced corner | reduced solution
   A.p = p;
   const int Pbr = (p - 1) * tl.hb, hbr = 2 * tl.hb - 1, Wr = hbr + 1;

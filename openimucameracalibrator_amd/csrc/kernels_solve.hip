@@ -325,8 +325,8 @@ __global__ void lm_step_slope_kernel(const double* g, const double* step_s, cons
 }
 
 // ---- launchers ----------------------------------------------------------------
-// Residual of the damped, scaled system the solvers just solved, straight from the packed normal equations (none of the
-// solvers' own data): r = (S H S + D^2 / radius) delta_s + S g.  Band rows: one thread per row (lower band by columns:
+// Residual of the damped, scaled system the solvers just solved: H and g straight from the packed normal equations, the scale and
+// D2 as the solve's build left them: r = (S H S + D2) delta_s + S g.  Band rows: one thread per row (lower band by columns:
 // band[j*W + k] = H(j + k, j)); each also adds its share of the arrow rows' sums to acc[2 + q].  out: acc[0] = sum r^2,
 // acc[1] = sum rhs^2 (band rows here, arrow rows by lm_solve_residual_arrow_kernel).
 __global__ void lm_solve_residual_band_kernel(NormalEq ne, TangentLayout tl, SolveBuffers sb, double* acc) {

@@ -17,6 +17,12 @@ void launch_lm_gradmax(const NormalEq& ne, int P, LmState* s, hipStream_t st);
 void launch_lm_build(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb, int reuse_diagonal, double min_diag,
                      double max_diag, hipStream_t st);
 int launch_band_arrow_cholesky(const TangentLayout& tl, const SolveBuffers& sb, hipStream_t st);
+// Which solver one damped solve runs (the route codes of oicc_debug_lm_step, oicc_exchange.hip).  p: time partitions of the sweep.
+enum LmRouteCode { kRouteNone = -1, kRouteBcrFused = 0, kRouteBcrUnfused = 1, kRouteSweep64 = 2, kRouteSweep128 = 3, kRoutePartitioned = 4,
+                   kRouteGlobal = 5, kRouteDistributed = 6 };
+struct LmRoute { int route; int p; };
+LmRoute band_arrow_route(const TangentLayout& tl, const SolveBuffers& sb);   // kernels_cholesky.hip: sweep / partitioned / global
+int bcr_route(const TangentLayout& tl, const SolveBuffers& sb);              // kernels_bcr.hip: kRouteBcrFused / kRouteBcrUnfused, or kRouteNone
 void launch_lm_solve_residual(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb, double* acc, hipStream_t st);
 int64_t bcr_workspace_doubles(const TangentLayout& tl);
 int launch_bcr_solve(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb, int reuse_diagonal, double min_diag,
@@ -28,13 +34,20 @@ int64_t bcr_dist_msg_doubles(const TangentLayout& tl);
 int launch_bcr_dist_forward(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb, int reuse_diagonal, double min_diag, double max_diag, const BcrDist& d, hipStream_t st);
 int launch_bcr_dist_middle(const TangentLayout& tl, const SolveBuffers& sb, const BcrDist& d, hipStream_t st);
 void launch_bcr_dist_finish(const TangentLayout& tl, const SolveBuffers& sb, const BcrDist& d, hipStream_t st);
-// damped system + factorisation + solve (solution in sb.step_s): block cyclic reduction when the
-// geometry allows (hb <= 64, arrow <= 63 columns), else the time-partitioned band sweep
+// the one route decision of a single-device solve: block cyclic reduction when the geometry allows (hb <= 64, arrow <= 63 columns),
+// else the band sweep / its time partitions / the global-memory fallback
+static inline LmRoute lm_solve_route(const TangentLayout& tl, const SolveBuffers& sb) {
+  if (sb.algo != 1) { const int r = bcr_route(tl, sb); if (r != kRouteNone) return LmRoute{r, 1}; }
+  if (sb.algo >= 2 && tl.Pb > 0) return LmRoute{kRouteNone, 0};
+  return band_arrow_route(tl, sb);
+}
+// damped system + factorisation + solve (solution in sb.step_s) on the route above
 static inline int launch_lm_solve(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb_in, double radius, int reuse_diagonal,
                                   double min_diag, double max_diag, hipStream_t st) {
   SolveBuffers sb = sb_in; sb.radius = radius;
-  if (sb.algo != 1 && launch_bcr_solve(ne, tl, sb, reuse_diagonal, min_diag, max_diag, st) == 0) return 0;
-  if (sb.algo >= 2 && tl.Pb > 0) return -1;
+  const LmRoute r = lm_solve_route(tl, sb);
+  if (r.route == kRouteNone) return -1;
+  if (r.route == kRouteBcrFused || r.route == kRouteBcrUnfused) return launch_bcr_solve(ne, tl, sb, reuse_diagonal, min_diag, max_diag, st);
   launch_lm_build(ne, tl, sb, reuse_diagonal, min_diag, max_diag, st);
   return launch_band_arrow_cholesky(tl, sb, st);
 }

@@ -292,6 +292,56 @@ int owner_exchange(oicc_problem* p, const NormalEq& ne, hipStream_t st, int64_t*
 }  // namespace oicc
 
 namespace { struct EventPair { hipEvent_t a = nullptr, b = nullptr; ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } }; }   // (destroyed on every exit of the timing entry points)
+namespace oicc {
+// The emulated distributed cyclic reduction (oicc_debug_dist_solve_emulated, oicc_debug_lm_step): applicable to nranks ranks?
+static bool dist_emulated_applies(const oicc_problem* p, int nranks) {
+  const TangentLayout& tl = p->tl;
+  const int nblk = (tl.Pb + 63) / 64;
+  return nranks >= 2 && nranks <= 64 && nranks <= nblk && bcr_applicable(tl) && tl.a + 1 <= int(p->opt.at("bcr_max_border"));
+}
+// Runs it on `sb` (scale and LmState set by the caller; the solution lands in sb.step_s): every rank's forward part in turn (into its
+// slot of the gather buffer: the "all-gather" is a no-op in one address space), then every rank's top system + local back
+// substitution, then the step.  Block ranges: equal split of the blocks.  ms != nullptr: each rank's part runs reps + 1 times (the
+// first is the warm-up), ms[2 r] / ms[2 r + 1] = ms of rank r's forward part / top system + back substitution; else once.
+static int dist_solve_emulated(oicc_problem* p, const SolveBuffers& sb, int nranks, int reuse_diagonal, int reps, double* ms) {
+  hipStream_t st = p->stream;
+  const TangentLayout& tl = p->tl;
+  const int nblk = (tl.Pb + 63) / 64;
+  std::vector<int32_t> b0(size_t(nranks) + 1); int max_loc = 0;
+  for (int k = 0; k <= nranks; ++k) b0[size_t(k)] = int32_t(int64_t(nblk) * k / nranks);
+  for (int k = 0; k < nranks; ++k) max_loc = std::max(max_loc, int(b0[size_t(k) + 1] - b0[size_t(k)]));
+  DevBuf<int32_t> d_b0; DevBuf<double> msg, xg; std::vector<DevBuf<double>> ws(static_cast<size_t>(nranks));
+  const int64_t msg_piece = (bcr_dist_msg_doubles(tl) + 7) / 8 * 8, x_piece = (int64_t(max_loc) * 64 + tl.a + 7) / 8 * 8;
+  if (!d_b0.upload(b0, st) || !msg.resize(size_t(msg_piece) * size_t(nranks)) || !xg.resize(size_t(x_piece) * size_t(nranks))) { p->err = "hipMalloc distributed solve"; return OICC_ERR_HIP; }
+  std::vector<BcrDist> ds(static_cast<size_t>(nranks));
+  for (int k = 0; k < nranks; ++k) {
+    BcrDist& d = ds[size_t(k)];
+    d.nranks = nranks; d.rank = k; d.b0 = b0[size_t(k)]; d.n_loc = b0[size_t(k) + 1] - d.b0; d.max_loc = max_loc; d.d_b0 = d_b0.p;
+    d.ws_doubles = bcr_dist_workspace_doubles(tl, d.n_loc, nranks);
+    if (!ws[size_t(k)].resize(size_t(d.ws_doubles))) { p->err = "hipMalloc distributed solve"; return OICC_ERR_HIP; }
+    d.ws = ws[size_t(k)].p; d.msg = msg.p; d.msg_piece = msg_piece; d.xg = xg.p; d.x_piece = x_piece;
+  }
+  EventPair ev;
+  if (ms) { HIPCK(p, hipEventCreate(&ev.a)); HIPCK(p, hipEventCreate(&ev.b)); }
+  const double min_diag = p->opt["min_lm_diagonal"], max_diag = p->opt["max_lm_diagonal"];
+  const int runs = ms ? reps + 1 : 1;
+  for (int phase = 0; phase < 2; ++phase)
+    for (int k = 0; k < nranks; ++k) {
+      for (int it = 0; it < runs; ++it) {     // (every run leaves the same results)
+        if (ms && it == 1) HIPCK(p, hipEventRecord(ev.a, st));
+        const int r2 = phase == 0 ? launch_bcr_dist_forward(p->ne, tl, sb, reuse_diagonal, min_diag, max_diag, ds[size_t(k)], st) : launch_bcr_dist_middle(tl, sb, ds[size_t(k)], st);
+        if (r2 != 0) { p->err = "distributed solve: geometry / workspace"; return OICC_ERR_STATE; }
+      }
+      if (!ms) continue;
+      HIPCK(p, hipEventRecord(ev.b, st)); HIPCK(p, hipEventSynchronize(ev.b));
+      float t = 0; (void)hipEventElapsedTime(&t, ev.a, ev.b);
+      ms[2 * k + phase] = double(t) / reps;
+    }
+  launch_bcr_dist_finish(tl, sb, ds[0], st);
+  HIPCK(p, hipStreamSynchronize(st));   // (the workspaces are freed on return)
+  return OICC_OK;
+}
+}  // namespace oicc
 extern "C" {
 
 int oicc_rccl_get_unique_id(uint8_t id[128]) {
@@ -338,40 +388,11 @@ int oicc_debug_dist_solve_emulated(oicc_problem* p, int32_t flags, int32_t nrank
   auto saved = p->reduce; p->reduce = nullptr;
   rc = eval_pass(p, p->d_x.p, true); p->reduce = saved; if (rc) return rc;
   const TangentLayout& tl = p->tl;
-  const int nblk = (tl.Pb + 63) / 64;
-  ARG(p, out != nullptr && nranks >= 2 && nranks <= 64 && nranks <= nblk && bcr_applicable(tl) && tl.a + 1 <= int(p->opt["bcr_max_border"]), "distributed solve: ranks / geometry");
+  ARG(p, out != nullptr && dist_emulated_applies(p, nranks), "distributed solve: ranks / geometry");
   SolveBuffers sb = solve_buffers(p); sb.radius = radius;
   launch_lm_scale(p->ne, tl, sb.scale, p->opt["jacobi_scaling"] != 0, st);
   HIPCK(p, hipMemsetAsync(p->d_state.p, 0, sizeof(LmState), st));
-  std::vector<int32_t> b0(size_t(nranks) + 1); int max_loc = 0;
-  for (int k = 0; k <= nranks; ++k) b0[size_t(k)] = int32_t(int64_t(nblk) * k / nranks);
-  for (int k = 0; k < nranks; ++k) max_loc = std::max(max_loc, int(b0[size_t(k) + 1] - b0[size_t(k)]));
-  DevBuf<int32_t> d_b0; DevBuf<double> msg, xg; std::vector<DevBuf<double>> ws(static_cast<size_t>(nranks));
-  const int64_t msg_piece = (bcr_dist_msg_doubles(tl) + 7) / 8 * 8, x_piece = (int64_t(max_loc) * 64 + tl.a + 7) / 8 * 8;
-  if (!d_b0.upload(b0, st) || !msg.resize(size_t(msg_piece) * size_t(nranks)) || !xg.resize(size_t(x_piece) * size_t(nranks))) { p->err = "hipMalloc distributed solve"; return OICC_ERR_HIP; }
-  std::vector<BcrDist> ds(static_cast<size_t>(nranks));
-  for (int k = 0; k < nranks; ++k) {
-    BcrDist& d = ds[size_t(k)];
-    d.nranks = nranks; d.rank = k; d.b0 = b0[size_t(k)]; d.n_loc = b0[size_t(k) + 1] - d.b0; d.max_loc = max_loc; d.d_b0 = d_b0.p;
-    d.ws_doubles = bcr_dist_workspace_doubles(tl, d.n_loc, nranks);
-    if (!ws[size_t(k)].resize(size_t(d.ws_doubles))) { p->err = "hipMalloc distributed solve"; return OICC_ERR_HIP; }
-    d.ws = ws[size_t(k)].p; d.msg = msg.p; d.msg_piece = msg_piece; d.xg = xg.p; d.x_piece = x_piece;
-  }
-  EventPair ev; HIPCK(p, hipEventCreate(&ev.a)); HIPCK(p, hipEventCreate(&ev.b));
-  const double min_diag = p->opt["min_lm_diagonal"], max_diag = p->opt["max_lm_diagonal"];
-  const int reps = std::max<int>(repeats, 1);
-  for (int phase = 0; phase < 2; ++phase)
-    for (int k = 0; k < nranks; ++k) {
-      for (int it = 0; it < reps + 1; ++it) {     // (the first run is the warm-up; every run leaves the same results)
-        if (it == 1) HIPCK(p, hipEventRecord(ev.a, st));
-        const int r2 = phase == 0 ? launch_bcr_dist_forward(p->ne, tl, sb, 0, min_diag, max_diag, ds[size_t(k)], st) : launch_bcr_dist_middle(tl, sb, ds[size_t(k)], st);
-        if (r2 != 0) { p->err = "distributed solve: geometry / workspace"; return OICC_ERR_STATE; }
-      }
-      HIPCK(p, hipEventRecord(ev.b, st)); HIPCK(p, hipEventSynchronize(ev.b));
-      float ms = 0; (void)hipEventElapsedTime(&ms, ev.a, ev.b);
-      out[2 + 2 * k + phase] = double(ms) / reps;
-    }
-  launch_bcr_dist_finish(tl, sb, ds[0], st);
+  rc = dist_solve_emulated(p, sb, nranks, 0, std::max<int>(repeats, 1), out + 2); if (rc) return rc;
   DevBuf<double> acc; if (!acc.resize(2 + size_t(tl.a))) return OICC_ERR_HIP;
   launch_lm_solve_residual(p->ne, tl, sb, acc.p, st);
   double h[2] = {0, 0}; LmState hs;
@@ -379,6 +400,49 @@ int oicc_debug_dist_solve_emulated(oicc_problem* p, int32_t flags, int32_t nrank
   HIPCK(p, hipMemcpyAsync(&hs, p->d_state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
   HIPCK(p, hipStreamSynchronize(st));
   out[0] = h[1] > 0.0 ? std::sqrt(h[0] / h[1]) : std::sqrt(h[0]); out[1] = double(hs.chol_failed);
+  return OICC_OK;
+}
+// Debug read-out (outside include/oicc_hip.h; tests): ONE damped solve of the system at the current point, as oicc_solve_residual runs
+// it, and everything a host reference needs to redo it.  nranks = 0: the route the options select (lm_solve_route); nranks >= 2: the
+// emulated distributed cyclic reduction of that many ranks.  reuse_diagonal = 1: the clamped diagonal of the previous call (a
+// rejected step: same Jacobian, another radius).  geom = [Pb, hb, a, n = ceil(Pb / 64), route code (lm_launch.h: LmRouteCode), time
+// partitions, W, P].  Copied out: the packed normal equations the solve read -- band [Pb][W], arrow rows [a][Pb], corner [a][a],
+// gradient [P] -- and scale, diag, D2, step_s [P], the failure flag.  band = NULL: geom only (no pass, no solve).
+int oicc_debug_lm_step(oicc_problem* p, int32_t flags, double radius, int32_t reuse_diagonal, int32_t nranks, int64_t geom[8], double* band,
+                       double* Et, double* C, double* g, double* scale, double* diag, double* D2, double* step_s, int32_t* chol_failed) {
+  int rc = prepare(p, flags); if (rc) return rc;
+  const bool solve = band != nullptr;   // band = NULL: geom only (no pass, no solve)
+  ARG(p, geom != nullptr && (!solve || (Et != nullptr && C != nullptr && g != nullptr && scale != nullptr && diag != nullptr && D2 != nullptr &&
+      step_s != nullptr && chol_failed != nullptr)) && radius > 0.0 && (nranks == 0 || nranks >= 2), "debug_lm_step: arguments");
+  const TangentLayout& tl = p->tl;
+  ARG(p, tl.P > 0, "debug_lm_step: no parameters");
+  ARG(p, nranks == 0 || dist_emulated_applies(p, nranks), "debug_lm_step: distributed ranks / geometry");
+  SolveBuffers sb = solve_buffers(p); sb.radius = radius;
+  const LmRoute route = nranks == 0 ? lm_solve_route(tl, sb) : LmRoute{kRouteDistributed, 1};
+  const int64_t P = tl.P, Pb = tl.Pb, a = tl.a;
+  geom[0] = Pb; geom[1] = tl.hb; geom[2] = a; geom[3] = (Pb + 63) / 64; geom[4] = route.route; geom[5] = route.p; geom[6] = tl.W; geom[7] = P;
+  if (!solve) return OICC_OK;
+  ARG(p, route.route != kRouteNone, "debug_lm_step: solver geometry unsupported");
+  hipStream_t st = p->stream;
+  auto saved = p->reduce; p->reduce = nullptr;
+  rc = eval_pass(p, p->d_x.p, true); p->reduce = saved; if (rc) return rc;
+  launch_lm_scale(p->ne, tl, sb.scale, p->opt["jacobi_scaling"] != 0, st);
+  HIPCK(p, hipMemsetAsync(p->d_state.p, 0, sizeof(LmState), st));
+  if (p->opt["debug_poison_lds"] != 0.0) launch_lds_poison(st);
+  const double min_diag = p->opt["min_lm_diagonal"], max_diag = p->opt["max_lm_diagonal"];
+  if (nranks == 0) {
+    if (launch_lm_solve(p->ne, tl, sb, radius, reuse_diagonal ? 1 : 0, min_diag, max_diag, st) != 0) { p->err = "solver geometry unsupported"; return OICC_ERR_UNSUPPORTED; }
+  } else {
+    rc = dist_solve_emulated(p, sb, nranks, reuse_diagonal ? 1 : 0, 0, nullptr); if (rc) return rc;
+  }
+  HIPCK(p, hipGetLastError());
+  auto d2h = [&](double* dst, const double* src, int64_t count) { return count <= 0 ? hipSuccess : hipMemcpyAsync(dst, src, size_t(count) * sizeof(double), hipMemcpyDeviceToHost, st); };
+  HIPCK(p, d2h(band, p->ne.band(), Pb * tl.W)); HIPCK(p, d2h(Et, p->ne.Et(), a * Pb)); HIPCK(p, d2h(C, p->ne.C(), a * a)); HIPCK(p, d2h(g, p->ne.g(), P));
+  HIPCK(p, d2h(scale, sb.scale, P)); HIPCK(p, d2h(diag, sb.diag, P)); HIPCK(p, d2h(D2, sb.D2, P)); HIPCK(p, d2h(step_s, sb.step_s, P));
+  LmState hs;
+  HIPCK(p, hipMemcpyAsync(&hs, p->d_state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+  HIPCK(p, hipStreamSynchronize(st));
+  *chol_failed = hs.chol_failed;
   return OICC_OK;
 }
 // debug read-out (outside include/oicc_hip.h; tests, bench.py): out4 = [distributed solves run so far, this rank's first block, its block count, ranks]

@@ -380,6 +380,31 @@ class SplineTrajectoryEstimator:
         self._ck(fn(self._h, flags, nranks, float(radius), repeats, _dp(out)))
         return float(out[0]), bool(out[1]), out[2::2].copy(), out[3::2].copy()
 
+    ROUTES = ("bcr_fused", "bcr_unfused", "sweep64", "sweep128", "partitioned", "global", "distributed")
+
+    def DebugLmStep(self, flags, radius=1e4, reuse_diagonal=0, nranks=0, solve=True):
+        """Debug read-out (device library only): one damped LM solve at the current point on the route the options select (nranks = 0)
+        or on the emulated distributed cyclic reduction of `nranks` ranks; reuse_diagonal = 1 keeps the clamped diagonal of the
+        previous call.  Returns the geometry (Pb, hb, a, n, route, p), the packed normal equations the solve read (band [Pb, W], Et
+        [a, Pb], C [a, a], g [P]) and scale, diag, D2, step_s, chol_failed.  solve=False: the geometry and route only."""
+        fn = self._b.lib.oicc_debug_lm_step
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_void_p, C.c_int32, C.c_double, C.c_int32, C.c_int32, C.POINTER(C.c_int64)] + [_abi.c_dp] * 8 + [C.POINTER(C.c_int32)]
+        geom = (C.c_int64 * 8)()
+        args = (self._h, int(flags), float(radius), int(reuse_diagonal), int(nranks), geom)
+        self._ck(fn(*args, *([None] * 8), None))     # (the geometry first: it sizes the arrays)
+        if solve:
+            Pb, a, W, P = int(geom[0]), int(geom[2]), int(geom[6]), int(geom[7])
+            arr = dict(band=np.zeros((Pb, W)), Et=np.zeros((a, Pb)), C=np.zeros((a, a)), g=np.zeros(P), scale=np.zeros(P), diag=np.zeros(P),
+                       D2=np.zeros(P), step_s=np.zeros(P))
+            failed = C.c_int32(0)
+            self._ck(fn(*args, *(_dp(arr[k]) for k in ("band", "Et", "C", "g", "scale", "diag", "D2", "step_s")), C.byref(failed)))
+        out = dict(Pb=int(geom[0]), hb=int(geom[1]), a=int(geom[2]), n=int(geom[3]), route=self.ROUTES[int(geom[4])] if geom[4] >= 0 else None,
+                   p=int(geom[5]), W=int(geom[6]), P=int(geom[7]))
+        if solve:
+            out.update(arr); out["chol_failed"] = bool(failed.value)
+        return out
+
     def TimeExchange(self, flags, repeats=10):
         """(ms per owner-computes exchange of the packed normal equations, bytes this rank moved); a collective: every rank calls it."""
         ms = C.c_double(0.0); nb = C.c_int64(0)

@@ -335,8 +335,9 @@ def test_block_cyclic_reduction_deep_tree_c4():
 @pytest.mark.parametrize("cfg", ["C2", "C4", "C5"])
 def test_linear_solvers_leave_a_small_residual_at_full_size(cfg):
     """A size-independent check of the linear solvers, at the full size of BASELINE's configurations (C5: 90 k band columns, 1406
-    blocks, 11 reduction levels): one damped solve, then ||M d - rhs|| / ||rhs|| from the packed normal equations themselves (no
-    solver data).  The Cholesky-based solvers (band sweep, factor-based cyclic reduction) are backward stable: ~5e-16.  The cyclic
+    blocks, 11 reduction levels): one damped solve, then ||M d - rhs|| / ||rhs|| with H and g from the packed normal equations but
+    the scale and the damping D2 the route's own build wrote -- so a wrong damping term in a build passes here; the damping and the
+    step against a host-built M: tests/test_gpu_linear_solve_reference.py.  The Cholesky-based solvers (band sweep, factor-based cyclic reduction) are backward stable: ~5e-16.  The cyclic
     reduction through the explicit inverses of the pivot blocks (the automatic choice) and the parallel cyclic reduction pay a
     factor of 10-150, still 1e-14 -- five orders below the tolerance of the LM iterate comparisons."""
     ds = synthetic.make_config(cfg)
@@ -352,7 +353,7 @@ def test_linear_solvers_leave_a_small_residual_at_full_size(cfg):
 def test_distributed_cyclic_reduction_leaves_a_small_residual_at_full_size(cfg, ranks):
     """The distributed cyclic reduction (round 6) as ONE process runs it for N ranks on the unsharded problem (oicc_debug_dist_solve_
     emulated: every rank's forward part into its slot, every rank's top system + back substitution, the gathered step): the step
-    against the packed normal equations themselves, ||M d - rhs|| / ||rhs|| < 1e-12 like the one-GPU cyclic reduction (undamped: within 100 x of it) -- block ranges
+    against the packed normal equations (with the scale and D2 the ranks' builds wrote), ||M d - rhs|| / ||rhs|| < 1e-12 like the one-GPU cyclic reduction (undamped: within 100 x of it) -- block ranges
     of unequal length (7 ranks on 1407 blocks), one block per rank (29 ranks on C2's 29 blocks: no local level at all), ranges whose
     active block counts are odd at some level (the coupling to the ghost block carried on), 64 ranks (six levels of the top system);
     with Ceres' initial radius and (almost) undamped."""
