@@ -461,6 +461,50 @@ int oicc_estimate_imu_to_camera_rotation(int32_t device_ordinal, int64_t n_vis, 
                                          int32_t estimate_gyro_bias, double q_imu_to_cam_xyzw[4], double* time_offset_imu_to_cam,
                                          double gyro_bias[3], double* alignment_error, int32_t* iterations);
 
+/* ---- IMU noise characterisation: Allan variance and noise-model fit ------------------------------------------
+ * applications/fit_allan_variance.cc + core::AllanVarianceFitter (src/core/allan_variance_fitter.cc:12-128): a still
+ * IMU's six channels, the overlapping Allan variance of each at ~num_clusters log-spaced cluster sizes, and the fit of
+ * sigma2(tau) = Q^2/tau^2 + N^2/tau + B^2 + K^2 tau + R^2 tau^2 that gives white noise and bias instability. */
+enum { OICC_ALLAN_GYRO = 0, OICC_ALLAN_ACC = 1, OICC_ALLAN_REPORT_SIZE = 6 };
+/* AllanGyr::initStrides + getLogSpace (src/allanvariance/allan_gyr.cc:141-196), operation for operation: maxStride = the
+ * largest power of two <= n/2 (shift loop), getLogSpace(0, float(log10(maxStride))), a float exponent
+ * 1.0f/(num_clusters-1), cumulative double products, ceil, consecutive duplicates dropped.  factors has room for
+ * num_clusters entries.  Host only: needs no device.  OICC_ERR_INVALID_ARG for n < 8 or num_clusters < 2. */
+int oicc_allan_factors(int64_t n, int32_t num_clusters, int32_t* factors, int32_t* num_factors);
+/* AllanGyr / AllanAcc ::calc + getVariance + getTimes (allan_gyr.cc:39-125, allan_acc.cc), all channels in one call:
+ *   samples [channels][n] raw values, sample i of every channel at t_s[i] (strictly increasing, seconds);
+ *   scale[c]  per-sample unit factor applied before the sum: 57.3*3600 for pushRadPerSec (:20-23), 1 for pushMPerSec2
+ * Host, sequential as the reference: avgDt = sum(t[i]-t[i-1])/(n-1) (:205-214), *freq = 1/avgDt, *period = avgDt,
+ * mean[c] = sum(samples*scale)/n (getAvgValue), factors / *num_factors as oicc_allan_factors, taus[f] = period*factors[f].
+ * Device: scale and prefix scan to theta[k] = sum_{i<=k} w[i] / freq (:130-139; the channel mean is subtracted first,
+ * which the second difference cancels), then for every channel and factor m
+ *   sigma2[c][f] = sum_{k<n-2m} (theta[k+2m] - 2 theta[k+m] + theta[k])^2 / (2 (period m)^2 (n-2m))   (:104-125)
+ * summed in fp64 without atomics (bitwise-repeatable).  Deviation: where n - 2m <= 0 (the last factor can be maxStride+1)
+ * sigma2 is NaN; the reference gives 0/0 or -0.0 there.  sigma2 has room for channels*num_clusters entries, row stride
+ * *num_factors.  device_ms (may be NULL): device time of the scan, variance and reduction launches.
+ * OICC_ERR_INVALID_ARG for n < 8 or times that do not increase; OICC_ERR_NO_DEVICE without a usable HIP device. */
+int oicc_allan_variance(int32_t device_ordinal, int32_t channels, int64_t n, const double* samples, const double* t_s,
+                        const double* scale, int32_t num_clusters, int32_t* num_factors, int32_t* factors, double* taus,
+                        double* sigma2, double* freq, double* period, double* mean, double* device_ms);
+/* FitAllanGyr (kind OICC_ALLAN_GYRO, src/allanvariance/fitallan_gyr.cc:7-60) / FitAllanAcc (OICC_ALLAN_ACC,
+ * fitallan_acc.cc:7-57), one axis.  Points with sigma2 not finite and positive are left out (see oicc_allan_variance);
+ * the accelerometer then applies checkData (fitallan_acc.cc:120-139: for tau < 1 a point above the running maximum,
+ * which starts at 0, is dropped and raises the maximum).  Start value |C|, C = (F^T F)^-1 F^T sqrt(sigma2) with
+ * F = sqrt(tau)^(-2..2) (initValue :62-101; init_C, may be NULL, gets the signed C the reference prints).  Solve: the
+ * residual log10(model) - log10(sigma2) per point (fitallan_*.h), Ceres 2.1 trust region with trust_region_strategy_type
+ * DOGLEG and default Solver::Options, restated.  Outputs: params_QNBKR as the solver leaves them (signs included),
+ * report (unit = 57.3*3600 for the gyroscope, 1 for the accelerometer; findMinNum / findMinIndex start at 1000.0):
+ *   [0] min_i sqrt(model(tau_i)) / unit        getBiasInstability (:104-106)
+ *   [1] tau_i of that minimum                  taus[findMinIndex(...)] (:53-54)
+ *   [2] sqrt(freq) sqrt(model(1)) / unit       getWhiteNoise (:108-110)
+ *   [3] |B| / 0.6642824703 / unit              getB() / (57.3*3600) (:51-52)
+ *   [4] sqrt(freq) |N| / 57.3                  sqrt(freq) * getN() * 60 / 57.3 (:56-57)
+ *   [5] final cost 0.5 sum r_i^2
+ * num_used: points in the fit; iterations: trust-region iterations.  Host only: needs no device.
+ * OICC_ERR_INVALID_ARG for a bad kind or fewer than 5 usable points. */
+int oicc_allan_fit(int32_t kind, int64_t num, const double* taus, const double* sigma2, double freq, double params_QNBKR[5],
+                   double init_C[5], double report[6], int32_t* num_used, int32_t* iterations);
+
 /* ---- View bundle adjustment: camera intrinsics calibration and per-view pose refinement ------
  * What the reference does through TheiaSfM's bundle adjuster [EXT] in
  *   CameraCalibrator::RunCalibration      src/core/camera_calibrator.cc:131-219  (theia::BundleAdjustViews, three stages)

@@ -178,3 +178,26 @@ class Bound:
             fn.argtypes = args
             setattr(self, name, fn)
         self.device = device
+
+
+# IMU noise characterisation (oicc_allan_* in include/oicc_hip.h): name -> (restype, argtypes).  A table of its own:
+# SIGNATURES is also bound against the CPU checker, which has no counterpart of these entries.
+ALLAN_SIGNATURES = {
+    "factors": (C.c_int, [C.c_int64, C.c_int32, c_i32p, c_i32p]),
+    "variance": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, c_dp, c_dp, c_dp, C.c_int32, c_i32p, c_i32p, c_dp,
+                           c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "fit": (C.c_int, [C.c_int32, C.c_int64, c_dp, c_dp, C.c_double, c_dp, c_dp, c_dp, c_i32p, c_i32p]),
+}
+
+
+class BoundAllan:
+    """Bound oicc_allan_* entry points of one library + prefix (``oicc_allan_`` for liboicc_hip.so)."""
+
+    def __init__(self, lib, prefix):
+        self.lib = lib
+        self.prefix = prefix
+        for name, (res, args) in ALLAN_SIGNATURES.items():
+            fn = getattr(lib, prefix + name)  # AttributeError = missing symbol: fail loudly
+            fn.restype = res
+            fn.argtypes = args
+            setattr(self, name, fn)

@@ -7,12 +7,13 @@ fails when no HIP device is usable.
 import ctypes
 import os
 
-from ._abi import Bound, BoundBa
+from ._abi import Bound, BoundAllan, BoundBa
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OICC_DEV_LIB") or os.path.join(_HERE, "csrc", "liboicc_hip.so")   # OICC_DEV_LIB: another BUILD of the same library (developer A/B timing, scripts/build_variant.sh)
 _bound = None
 _bound_ba = None
+_bound_allan = None
 
 
 def load():
@@ -33,3 +34,11 @@ def load_ba():
     if _bound_ba is None:
         _bound_ba = BoundBa(load().lib, "oicc_ba_")
     return _bound_ba
+
+
+def load_allan():
+    """oicc_allan_* entry points (Allan variance and noise-model fit) of the same library."""
+    global _bound_allan
+    if _bound_allan is None:
+        _bound_allan = BoundAllan(load().lib, "oicc_allan_")
+    return _bound_allan

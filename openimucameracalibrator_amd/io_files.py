@@ -227,3 +227,16 @@ def parse_reference_flags(parser, argv=None):
             i += 1
         i += 1
     return args
+
+
+def write_telemetry_json(path, timestamps_ns, accelerometer, gyroscope, img_timestamps_ns=()):
+    """The telemetry JSON src/io/read_telemetry.cc:29-68 reads: accelerometer[[3]], gyroscope[[3]], timestamps_ns[]
+    (all the same length), img_timestamps_ns[]."""
+    t = np.asarray(timestamps_ns, dtype=np.int64).ravel()
+    a = np.asarray(accelerometer, dtype=np.float64).reshape(-1, 3)
+    g = np.asarray(gyroscope, dtype=np.float64).reshape(-1, 3)
+    if not (len(t) == len(a) == len(g)):
+        raise ValueError("telemetry arrays differ in length")
+    with open(path, "w") as f:
+        json.dump(dict(accelerometer=a.tolist(), gyroscope=g.tolist(), timestamps_ns=t.tolist(),
+                       img_timestamps_ns=[int(x) for x in img_timestamps_ns]), f)

@@ -365,3 +365,27 @@ CONFIGS = {
 def make_config(name, **overrides):
     kw = dict(CONFIGS[name]); kw.update(overrides)
     return make_dataset(name=name, **kw)
+
+
+# ----------------------------------------------------------------- stationary IMU (Allan variance input)
+def make_stationary_imu(duration=7200.0, rate=200.0, gyro_white=2e-3, accel_white=2e-2, gyro_rrw=2e-5, accel_rrw=3e-4,
+                        gyro_bias=(1e-3, -2e-3, 5e-4), accel_bias=(0.02, -0.01, 0.03), gravity=(0.0, 0.0, 9.811104), seed=SEED):
+    """A still IMU with known noise, the input of fit_allan_variance (docs/imu_noise_parameters.md of the reference).
+    Per axis: constant bias + rate random walk (increments K sqrt(dt) N(0,1), K in units/s/sqrt(s)) + white noise of
+    density D (units/sqrt(Hz): sample std D sqrt(rate)).  Gyroscope in rad/s, accelerometer in m/s^2 (gravity added).
+    Its Allan variance is sigma2(tau) = D^2/tau + K^2 tau/3.  Returns the telemetry dict (timestamps_ns, accelerometer,
+    gyroscope as arrays) and the truth."""
+    rng = np.random.RandomState(seed)
+    n = int(round(duration * rate))
+    dt = 1.0 / rate
+    t_ns = np.round(np.arange(n) * (1e9 / rate)).astype(np.int64)
+
+    def axes(white, rrw, bias):
+        walk = np.cumsum(rng.standard_normal((n, 3)) * (rrw * np.sqrt(dt)), axis=0)
+        return np.asarray(bias, dtype=np.float64) + walk + rng.standard_normal((n, 3)) * (white * np.sqrt(rate))
+
+    gyro = axes(gyro_white, gyro_rrw, gyro_bias)
+    accel = axes(accel_white, accel_rrw, accel_bias) + np.asarray(gravity, dtype=np.float64)
+    truth = dict(rate=rate, gyro_white=gyro_white, accel_white=accel_white, gyro_rrw=gyro_rrw, accel_rrw=accel_rrw,
+                 gyro_bias=np.asarray(gyro_bias, dtype=np.float64), accel_bias=np.asarray(accel_bias, dtype=np.float64))
+    return dict(timestamps_ns=t_ns, accelerometer=accel, gyroscope=gyro), truth
