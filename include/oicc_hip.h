@@ -558,6 +558,83 @@ int oicc_ba_optimize_views(oicc_ba* p, int32_t max_iters, int32_t flags, int32_t
 /* GetReprojErrorOfView for every view: mean pixel distance of its observations, [nv] */
 int oicc_ba_view_reprojection_errors(oicc_ba* p, double* mean_px);
 
+/* ---- Static multi-pose IMU intrinsics (imu_tk) ---------------------------------------------------------------
+ * applications/static_imu_calibration.cc + core::StaticImuCalibrator (src/core/static_imu_calibrator.cc, residuals in
+ * include/OpenCameraCalibrator/core/static_imu_calibrator.h): accelerometer and gyroscope triads T*K*(x - B) from an
+ * initial still period and a series of still poses.  Parameter vectors, in the reference's order:
+ *   accelerometer [9]  misYZ misZY misZX sX sY sZ bX bY bZ            (MultiPosAccResidual; misXZ = misXY = misYX = 0)
+ *   gyroscope    [12]  misYZ misZY misZX misXZ misXY misYX sX sY sZ bX bY bZ   (MultiPosGyroResidual)
+ * with T = [[1,-misYZ,misZY],[misXZ,1,-misZX],[-misXY,misYX,1]], K = diag(s) (utils/types.h:171-330).
+ * Samples are [n][3] row-major, times in seconds.  No CPU fallback: OICC_ERR_NO_DEVICE without a usable HIP device. */
+enum {
+  OICC_SIMU_THRESHOLDS = 10,          /* th_mult = 1..10 (static_imu_calibrator.cc:79) */
+  OICC_SIMU_ACC_IMPOSSIBLE = 1,       /* oicc_static_imu_calibrate: no threshold gave min_num_intervals intervals */
+  OICC_SIMU_TERM_SKIPPED = -1,        /* threshold not solved: too few intervals */
+  OICC_SIMU_TERM_GRADIENT = 0,        /* Ceres CONVERGENCE: gradient tolerance */
+  OICC_SIMU_TERM_FUNCTION = 1,        /* Ceres CONVERGENCE: function tolerance */
+  OICC_SIMU_TERM_PARAMETER = 2,       /* Ceres CONVERGENCE: parameter tolerance */
+  OICC_SIMU_TERM_MAX_ITERATIONS = 3,  /* Ceres NO_CONVERGENCE */
+  OICC_SIMU_TERM_MIN_RADIUS = 4,      /* Ceres CONVERGENCE: minimum trust region radius */
+  OICC_SIMU_TERM_INVALID_STEPS = 5,   /* Ceres FAILURE: max_num_consecutive_invalid_steps */
+  OICC_SIMU_TERM_EVAL_FAILED = 6      /* the residuals could not be evaluated at the start point */
+};
+/* The StaticImuCalibrator setters (static_imu_calibrator.h); class defaults in brackets (.cc:44-52). */
+typedef struct oicc_static_imu_options {
+  double gravity_magnitude;           /* SetGravityMagnitude [9.81; the application passes 9.811107] */
+  double init_interval_duration_s;    /* SetInitStaticIntervalDuration [30; the application passes 10] */
+  double gyro_dt;                     /* SetGyroDataPeriod [-1]: <= 0 integrates with the sample timestamps */
+  int32_t interval_n_samples;         /* SetIntarvalsNumSamples [100] */
+  int32_t min_num_intervals;          /* [12] */
+  int32_t win_size;                   /* StaticIntervalsDetector window [101]; < 11 -> 11, even -> +1; at most 1025 here */
+  int32_t acc_use_means;              /* EnableAccUseMeans [0] */
+  int32_t optimize_gyro_bias;         /* EnableGyroBiasOptimization [0] */
+  int32_t reserved;
+} oicc_static_imu_options;
+typedef struct oicc_static_imu_report {
+  int32_t th_mult;                                 /* the threshold multiplier kept (strictly smallest final cost), or -1 */
+  int32_t num_intervals[OICC_SIMU_THRESHOLDS];     /* extracted intervals (>= interval_n_samples samples) per th_mult */
+  int32_t acc_iterations[OICC_SIMU_THRESHOLDS];    /* LM iterations after iteration 0 */
+  int32_t acc_termination[OICC_SIMU_THRESHOLDS];   /* OICC_SIMU_TERM_* */
+  int32_t gyro_num_blocks, gyro_iterations, gyro_termination;
+  double norm_th;                                  /* |variance| of the initial interval (.cc:72-73) */
+  double init_acc_bias[3];                         /* initial accelerometer bias (.cc:63-68) */
+  double acc_final_cost[OICC_SIMU_THRESHOLDS];     /* 0.5 sum r^2 at the solution; NaN where skipped */
+  double gyro_init_bias[3];                        /* mean of the initial interval of the gyroscope (.cc:209-211) */
+  double gyro_initial_cost, gyro_final_cost;
+  double ms_detector, ms_acc, ms_gyro;             /* device time: detector launches, batched fits, all gyro evaluations */
+} oicc_static_imu_report;
+/* utils::StaticIntervalsDetector (src/utils/imu_data_interval.cc:111-149) for num_thresholds (<= 10) thresholds in one
+ * pass: norm[i] = |DataVariance(acc, [i-h, i+h])| for i in [h, n-h) (sequential mean, sequential squared differences,
+ * / (w-1); |v| = sqrt((vx^2 + vy^2) + vz^2), no FMA contraction), compared with every threshold; an interval starts at
+ * norm < th and ends before norm >= th, one still open closes at n-h-1; w >= n gives none.  counts[t] is the number of
+ * intervals of threshold t; intervals[t][k] = (start, end) for k < min(counts[t], capacity) (row stride 2*capacity).
+ * norms (may be NULL): [n], NaN outside [h, n-h).  Samples must be finite (OICC_ERR_INVALID_ARG otherwise). */
+int oicc_static_imu_intervals(int32_t device_ordinal, int64_t n, const double* acc, int32_t num_thresholds,
+                              const double* thresholds, int32_t win_size, int32_t capacity, int32_t* counts,
+                              int32_t* intervals, double* norms, double* device_ms);
+/* MultiPosAccResidual (static_imu_calibrator.h:18-58) at params[9] for num samples: r = g_mag - |T K (x - b)| and its
+ * Jacobian (rows [num][9], may be NULL, as residuals), cost = 0.5 sum r^2, gram = J^T J [9][9] and gradient = J^T r
+ * reduced on the device in the order the batched fit uses. */
+int oicc_static_imu_eval_acc(int32_t device_ordinal, int64_t num, const double* samples, double g_mag, const double* params,
+                             double* residuals, double* jacobian, double* cost, double* gram, double* gradient);
+/* MultiPosGyroResidual (static_imu_calibrator.h:60-140) for num_blocks blocks: block b integrates the bias-free gyro
+ * samples ranges[b][0]..ranges[b][1] (RK4, utils/gyro_integration.h; dt = gyro_dt if > 0, else timestamp differences)
+ * and r_b = R^T g[b][0:3] - g[b][3:6].  Parameters: 9, or 12 with optimize_bias (params always has room for 12).
+ * residuals [3 num_blocks], jacobian [3 num_blocks][np] (either may be NULL), cost, gram [np][np], gradient [np].
+ * device_ms (may be NULL): time of the launch. */
+int oicc_static_imu_eval_gyro(int32_t device_ordinal, int64_t n, const double* t_s, const double* gyro, int32_t num_blocks,
+                              const int32_t* ranges, const double* g_versors, int32_t optimize_bias, double gyro_dt,
+                              const double* params, double* residuals, double* jacobian, double* cost, double* gram,
+                              double* gradient, double* device_ms);
+/* StaticImuCalibrator::CalibrateAccGyro (static_imu_calibrator.cc:188-337, CalibrateAcc :54-186): acc and gyro share
+ * the timestamps t_s [n].  acc_params: the accelerometer vector of the kept threshold; gyro_params: the final gyroscope
+ * triad (bias = initial-interval mean + fitted bias terms).  Returns OICC_OK, or OICC_SIMU_ACC_IMPOSSIBLE when no
+ * threshold leaves min_num_intervals intervals (then both outputs are the default triad: identity, zero bias, and the
+ * gyroscope is not fitted), or an error.  opt may be NULL (the class defaults); report may be NULL. */
+int oicc_static_imu_calibrate(int32_t device_ordinal, int64_t n, const double* t_s, const double* acc, const double* gyro,
+                              const oicc_static_imu_options* opt, double* acc_params, double* gyro_params,
+                              oicc_static_imu_report* report);
+
 #ifdef __cplusplus
 }
 #endif

@@ -201,3 +201,43 @@ class BoundAllan:
             fn.restype = res
             fn.argtypes = args
             setattr(self, name, fn)
+
+
+class StaticImuOptions(C.Structure):
+    """oicc_static_imu_options (include/oicc_hip.h)."""
+    _fields_ = [("gravity_magnitude", C.c_double), ("init_interval_duration_s", C.c_double), ("gyro_dt", C.c_double),
+                ("interval_n_samples", C.c_int32), ("min_num_intervals", C.c_int32), ("win_size", C.c_int32),
+                ("acc_use_means", C.c_int32), ("optimize_gyro_bias", C.c_int32), ("reserved", C.c_int32)]
+
+
+class StaticImuReport(C.Structure):
+    """oicc_static_imu_report (include/oicc_hip.h)."""
+    _fields_ = [("th_mult", C.c_int32), ("num_intervals", C.c_int32 * 10), ("acc_iterations", C.c_int32 * 10),
+                ("acc_termination", C.c_int32 * 10), ("gyro_num_blocks", C.c_int32), ("gyro_iterations", C.c_int32),
+                ("gyro_termination", C.c_int32), ("norm_th", C.c_double), ("init_acc_bias", C.c_double * 3),
+                ("acc_final_cost", C.c_double * 10), ("gyro_init_bias", C.c_double * 3), ("gyro_initial_cost", C.c_double),
+                ("gyro_final_cost", C.c_double), ("ms_detector", C.c_double), ("ms_acc", C.c_double), ("ms_gyro", C.c_double)]
+
+
+# Static multi-pose IMU intrinsics (oicc_static_imu_* in include/oicc_hip.h), a table of its own like ALLAN_SIGNATURES.
+STATIC_IMU_SIGNATURES = {
+    "intervals": (C.c_int, [C.c_int32, C.c_int64, c_dp, C.c_int32, c_dp, C.c_int32, C.c_int32, c_i32p, c_i32p, c_dp, c_dp]),
+    "eval_acc": (C.c_int, [C.c_int32, C.c_int64, c_dp, C.c_double, c_dp, c_dp, c_dp, c_dp, c_dp, c_dp]),
+    "eval_gyro": (C.c_int, [C.c_int32, C.c_int64, c_dp, c_dp, C.c_int32, c_i32p, c_dp, C.c_int32, C.c_double, c_dp, c_dp, c_dp,
+                            c_dp, c_dp, c_dp, c_dp]),
+    "calibrate": (C.c_int, [C.c_int32, C.c_int64, c_dp, c_dp, c_dp, C.POINTER(StaticImuOptions), c_dp, c_dp,
+                            C.POINTER(StaticImuReport)]),
+}
+
+
+class BoundStaticImu:
+    """Bound oicc_static_imu_* entry points of one library + prefix (``oicc_static_imu_`` for liboicc_hip.so)."""
+
+    def __init__(self, lib, prefix):
+        self.lib = lib
+        self.prefix = prefix
+        for name, (res, args) in STATIC_IMU_SIGNATURES.items():
+            fn = getattr(lib, prefix + name)  # AttributeError = missing symbol: fail loudly
+            fn.restype = res
+            fn.argtypes = args
+            setattr(self, name, fn)

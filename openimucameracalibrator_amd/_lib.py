@@ -7,13 +7,14 @@ fails when no HIP device is usable.
 import ctypes
 import os
 
-from ._abi import Bound, BoundAllan, BoundBa
+from ._abi import Bound, BoundAllan, BoundBa, BoundStaticImu
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OICC_DEV_LIB") or os.path.join(_HERE, "csrc", "liboicc_hip.so")   # OICC_DEV_LIB: another BUILD of the same library (developer A/B timing, scripts/build_variant.sh)
 _bound = None
 _bound_ba = None
 _bound_allan = None
+_bound_static_imu = None
 
 
 def load():
@@ -42,3 +43,11 @@ def load_allan():
     if _bound_allan is None:
         _bound_allan = BoundAllan(load().lib, "oicc_allan_")
     return _bound_allan
+
+
+def load_static_imu():
+    """oicc_static_imu_* entry points (static multi-pose IMU intrinsics) of the same library."""
+    global _bound_static_imu
+    if _bound_static_imu is None:
+        _bound_static_imu = BoundStaticImu(load().lib, "oicc_static_imu_")
+    return _bound_static_imu

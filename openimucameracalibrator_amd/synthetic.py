@@ -389,3 +389,63 @@ def make_stationary_imu(duration=7200.0, rate=200.0, gyro_white=2e-3, accel_whit
     truth = dict(rate=rate, gyro_white=gyro_white, accel_white=accel_white, gyro_rrw=gyro_rrw, accel_rrw=accel_rrw,
                  gyro_bias=np.asarray(gyro_bias, dtype=np.float64), accel_bias=np.asarray(accel_bias, dtype=np.float64))
     return dict(timestamps_ns=t_ns, accelerometer=accel, gyroscope=gyro), truth
+
+
+def _so3_log(R):
+    c = np.clip((np.trace(R) - 1.0) / 2.0, -1.0, 1.0)
+    a = np.arccos(c)
+    v = np.array([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    return v * (0.5 if a < 1e-12 else a / (2.0 * np.sin(a)))
+
+
+def make_static_multipose_imu(num_poses=36, rate=200.0, init_s=14.0, hold_s=4.0, move_s=2.0, gravity=9.811107, acc_noise=2e-3,
+                              gyro_noise=1e-4, acc_params=(1.5e-3, -2e-3, 1e-3, 1.01, 0.995, 1.004, 0.05, -0.03, 0.08),
+                              gyro_params=(2e-3, -1e-3, 1.5e-3, -2.5e-3, 1e-3, 2e-3, 0.99, 1.007, 1.012, 4e-3, -6e-3, 2e-3), seed=SEED):
+    """A multi-pose IMU recording (static_imu_calibration's input, imu_tk): still for init_s with gravity on +z, then
+    num_poses orientations, each held for hold_s and reached by a rotation about the IMU origin (no linear acceleration)
+    of move_s with the closed-form rate omega(t) = s'(t) phi, s = tau - sin(2 pi tau) / (2 pi).  True specific force
+    R^T (0, 0, g), true rate the body rate; raw = (T K)^-1 true + b + N(0, noise^2) per triad, parameters in the
+    reference's order (accelerometer 9: misYZ misZY misZX sX sY sZ bX bY bZ; gyroscope 12: + misXZ misXY misYX after
+    misZX).  Returns the telemetry dict (timestamps_ns, accelerometer, gyroscope) and the truth."""
+    rng = np.random.RandomState(seed)
+    n_init, n_hold, n_move = int(round(init_s * rate)), int(round(hold_s * rate)), int(round(move_s * rate))
+    n = n_init + num_poses * (n_move + n_hold)
+    t = np.arange(n) / rate
+    poses = [np.eye(3)]
+    while len(poses) < num_poses + 1:
+        q = rng.standard_normal(4); q /= np.linalg.norm(q)
+        R = mat_from_quat(q)
+        # a reachable, distinct orientation: rotation from the previous pose between 40 and 150 degrees
+        ang = np.linalg.norm(_so3_log(poses[-1].T @ R))
+        if np.deg2rad(40) < ang < np.deg2rad(150):
+            poses.append(R)
+    Rs = np.zeros((n, 3, 3)); w = np.zeros((n, 3))
+    Rs[:n_init] = np.eye(3)
+    k = n_init
+    for p in range(num_poses):
+        phi = _so3_log(poses[p].T @ poses[p + 1])
+        tau = np.arange(n_move) / n_move
+        s = tau - np.sin(2 * np.pi * tau) / (2 * np.pi)
+        sd = (1.0 - np.cos(2 * np.pi * tau)) / move_s
+        for j in range(n_move):
+            Rs[k + j] = poses[p] @ so3_exp_mat(s[j] * phi)
+            w[k + j] = sd[j] * phi
+        k += n_move
+        Rs[k:k + n_hold] = poses[p + 1]
+        k += n_hold
+    f_true = np.einsum("nji,j->ni", Rs, np.array([0.0, 0.0, gravity]))
+
+    def raw(true, p12, noise):
+        p = np.asarray(p12, dtype=np.float64)
+        T = np.array([[1.0, -p[0], p[1]], [p[3], 1.0, -p[2]], [-p[4], p[5], 1.0]])
+        MS = T @ np.diag(p[6:9])
+        return np.linalg.solve(MS, true.T).T + p[9:12] + rng.standard_normal(true.shape) * noise
+
+    a9 = np.asarray(acc_params, dtype=np.float64)
+    a12 = np.r_[a9[:3], 0.0, 0.0, 0.0, a9[3:]]
+    acc = raw(f_true, a12, acc_noise)
+    gyr = raw(w, gyro_params, gyro_noise)
+    t_ns = np.round(t * 1e9).astype(np.int64)
+    truth = dict(acc_params=a9, gyro_params=np.asarray(gyro_params, dtype=np.float64), gravity=gravity, rate=rate,
+                 acc_noise=acc_noise, gyro_noise=gyro_noise, num_poses=num_poses, n_init=n_init, n_hold=n_hold, n_move=n_move)
+    return dict(timestamps_ns=t_ns, accelerometer=acc, gyroscope=gyr), truth
