@@ -635,6 +635,52 @@ int oicc_static_imu_calibrate(int32_t device_ordinal, int64_t n, const double* t
                               const oicc_static_imu_options* opt, double* acc_params, double* gyro_params,
                               oicc_static_imu_report* report);
 
+/* ---- radon checkerboard extraction (board.hip) ------------------------------------------------------------------------
+ * applications/extract_board_to_json.cc + core::BoardExtractor (src/core/board_extractor.cc:200-225, 268-380) for
+ * BoardType::RADON: the reference calls cv::findChessboardCornersSB(CALIB_CB_LARGER | CALIB_CB_MARKER |
+ * CALIB_CB_EXHAUSTIVE) per frame after cv::resize(1 / downsample_factor) and BGR2GRAY.  This entry is our own detector
+ * (localized Radon response after Duda & Frese 2018, cornerSubPix's saddle refinement, homography grid growth, the
+ * target's three marker dots), specified by tests/board_restatement.py and DESIGN.md ("Board extraction").  A frame
+ * reports all W*H corners with ids i*W + j (pattern row i, column j) or none. */
+typedef struct oicc_board_options {
+  int32_t radius;                     /* line half length r (1..8) [3]; sub-pixel window half size r + 2 */
+  float threshold_rel;                /* candidates: response > threshold_rel * frame maximum [0.5] */
+  int32_t max_candidates;             /* per-frame cap (>= W*H); a frame with more candidates reports nothing [512] */
+  int32_t subpix_iterations;          /* cornerSubPix TermCriteria count [20] */
+  double subpix_eps;                  /* cornerSubPix TermCriteria epsilon (compared squared, as OpenCV) [0.01] */
+  int32_t batch;                      /* frames per launch chain; two batches are in flight [64] */
+  int32_t reserved;
+} oicc_board_options;
+typedef struct oicc_board_report {
+  int32_t frames_found, frames_overflow;           /* frames with a board; frames over max_candidates */
+  int32_t output_width, output_height;             /* the image size after the resize */
+  int64_t num_candidates;                          /* summed over frames */
+  double ms_resize, ms_response, ms_candidates, ms_subpix, ms_marker;   /* device time per kernel, summed */
+  double ms_assembly_host;                         /* grid assembly and marker decision on the host */
+  double ms_total;                                 /* wall time of the call */
+} oicc_board_report;
+/* Optional per-stage outputs for checking (any pointer may be NULL): gray and response [frames][h'][w'], candidates
+ * (x, y) and refined (x, y) [frames][capacity][2] in raster order of the candidates (entries beyond the frame's count
+ * are left untouched). */
+typedef struct oicc_board_stages {
+  uint8_t* gray;
+  float* response;
+  int32_t* candidates;
+  double* refined;
+  int32_t capacity;
+  int32_t reserved;
+} oicc_board_stages;
+/* The resize of ExtractImageFolderToJson (board_extractor.cc:317-318): output size round(width / factor). */
+int oicc_board_output_size(int32_t width, int32_t height, double downsample_factor, int32_t* out_width, int32_t* out_height);
+/* frames [num_frames][height][width][channels] u8 (channels 1 = gray, 3 = BGR as cv::imread gives), resized by
+ * 1 / downsample_factor and converted to gray (board_extractor.cc:317-322), then detected.  corners [num_frames][W*H][2]
+ * (NaN where not found), found [num_frames], candidates_per_frame [num_frames] (may be NULL), report and stages may be
+ * NULL. */
+int oicc_board_radon_detect(int32_t device_ordinal, int32_t num_frames, int32_t width, int32_t height, int32_t channels,
+                            const uint8_t* frames, double downsample_factor, int32_t W, int32_t H,
+                            const oicc_board_options* opt, double* corners, int32_t* found, int32_t* candidates_per_frame,
+                            oicc_board_report* report, const oicc_board_stages* stages);
+
 #ifdef __cplusplus
 }
 #endif

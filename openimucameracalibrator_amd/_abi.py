@@ -241,3 +241,46 @@ class BoundStaticImu:
             fn.restype = res
             fn.argtypes = args
             setattr(self, name, fn)
+
+
+class BoardOptions(C.Structure):
+    """oicc_board_options (include/oicc_hip.h)."""
+    _fields_ = [("radius", C.c_int32), ("threshold_rel", C.c_float), ("max_candidates", C.c_int32), ("subpix_iterations", C.c_int32),
+                ("subpix_eps", C.c_double), ("batch", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BoardReport(C.Structure):
+    """oicc_board_report (include/oicc_hip.h)."""
+    _fields_ = [("frames_found", C.c_int32), ("frames_overflow", C.c_int32), ("output_width", C.c_int32), ("output_height", C.c_int32),
+                ("num_candidates", C.c_int64), ("ms_resize", C.c_double), ("ms_response", C.c_double), ("ms_candidates", C.c_double),
+                ("ms_subpix", C.c_double), ("ms_marker", C.c_double), ("ms_assembly_host", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class BoardStages(C.Structure):
+    """oicc_board_stages (include/oicc_hip.h)."""
+    _fields_ = [("gray", c_u8p), ("response", C.POINTER(C.c_float)), ("candidates", c_i32p), ("refined", c_dp),
+                ("capacity", C.c_int32), ("reserved", C.c_int32)]
+
+
+# Radon checkerboard extraction (oicc_board_* in include/oicc_hip.h), a table of its own like ALLAN_SIGNATURES.
+BOARD_SIGNATURES = {
+    "output_size": (C.c_int, [C.c_int32, C.c_int32, C.c_double, c_i32p, c_i32p]),
+    "radon_detect": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_u8p, C.c_double, C.c_int32, C.c_int32,
+                               C.POINTER(BoardOptions), c_dp, c_i32p, c_i32p, C.POINTER(BoardReport), C.POINTER(BoardStages)]),
+}
+
+
+class BoundBoard:
+    """Bound oicc_board_* entry points of one library + prefix (``oicc_board_`` for liboicc_hip.so)."""
+
+    def __init__(self, lib, prefix):
+        self.lib = lib
+        self.prefix = prefix
+        for name, (res, args) in BOARD_SIGNATURES.items():
+            fn = getattr(lib, prefix + name)  # AttributeError = missing symbol: fail loudly
+            fn.restype = res
+            fn.argtypes = args
+            setattr(self, name, fn)

@@ -7,7 +7,7 @@ fails when no HIP device is usable.
 import ctypes
 import os
 
-from ._abi import Bound, BoundAllan, BoundBa, BoundStaticImu
+from ._abi import Bound, BoundAllan, BoundBa, BoundBoard, BoundStaticImu
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OICC_DEV_LIB") or os.path.join(_HERE, "csrc", "liboicc_hip.so")   # OICC_DEV_LIB: another BUILD of the same library (developer A/B timing, scripts/build_variant.sh)
@@ -15,6 +15,7 @@ _bound = None
 _bound_ba = None
 _bound_allan = None
 _bound_static_imu = None
+_bound_board = None
 
 
 def load():
@@ -51,3 +52,11 @@ def load_static_imu():
     if _bound_static_imu is None:
         _bound_static_imu = BoundStaticImu(load().lib, "oicc_static_imu_")
     return _bound_static_imu
+
+
+def load_board():
+    """oicc_board_* entry points (radon checkerboard extraction) of the same library."""
+    global _bound_board
+    if _bound_board is None:
+        _bound_board = BoundBoard(load().lib, "oicc_board_")
+    return _bound_board

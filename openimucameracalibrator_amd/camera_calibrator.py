@@ -266,10 +266,11 @@ class CameraCalibrator:
         """camera_calibrator.cc:221-377: views from the corner file (start pose and focal length per view, voxel filter),
         RunCalibration, outputs (`<out>.json`, `<out>.calibdata.json`, two PLY files)."""
         from . import io_files, planar_init
-        ids = sorted(int(k) for k in scene_json["scene_pts"])
+        scene_pts = io_files.scene_points(scene_json)
+        ids = sorted(scene_pts)
         index = {k: i for i, k in enumerate(ids)}
         self.point_ids_ = ids
-        points = np.array([[*scene_json["scene_pts"][str(k)][:3], 1.0] for k in ids], dtype=np.float64)
+        points = np.array([[*scene_pts[k][:3], 1.0] for k in ids], dtype=np.float64)
         w, h = int(scene_json["image_width"]), int(scene_json["image_height"])
         px, py = w / 2.0, h / 2.0                                          # initial principal point, camera_calibrator.cc:228-230
         views = []
@@ -482,11 +483,12 @@ class PoseEstimator:
     def EstimatePosesFromJson(self, scene_json, model, intrinsics, image_height, min_num_points=8):
         """pose_estimator.cc:92-190: every frame of the corner file -> normalised features, start pose, BundleAdjustView
         (all frames in one launch), back-projection test in pixels with the calibrated camera."""
-        from . import planar_init
-        ids = sorted(int(k) for k in scene_json["scene_pts"])
+        from . import io_files, planar_init
+        scene_pts = io_files.scene_points(scene_json)
+        ids = sorted(scene_pts)
         index = {k: i for i, k in enumerate(ids)}
         self.point_ids_ = ids
-        self.SetScenePoints(np.array([[*scene_json["scene_pts"][str(k)][:3], 1.0] for k in ids], dtype=np.float64))
+        self.SetScenePoints(np.array([[*scene_pts[k][:3], 1.0] for k in ids], dtype=np.float64))
         self.calib_ = (int(model), np.asarray(intrinsics, dtype=np.float64))
         self.max_reproj_error_ = 0.004 * image_height                        # pose_estimator.cc:97
         self.px_obs_ = []

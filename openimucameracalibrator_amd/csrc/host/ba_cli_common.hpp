@@ -24,7 +24,12 @@ inline bool load_scene(const std::string& path, Scene* sc) {
   Value j; if (!read_scene(path, &j)) return false;
   std::map<int, int> index;
   std::map<int, std::array<double, 4>> pts;
-  for (const auto& kv : j.at("scene_pts").obj) pts[std::stoi(kv.first)] = {kv.second.at(0).as_double(), kv.second.at(1).as_double(), kv.second.at(2).as_double(), 1.0};
+  // scene_pts: an object keyed by the id (charuco, apriltag) or, for radon, an array indexed by it (board_extractor.cc:252-257
+  // indexes with an int, which nlohmann turns into an array; read_scene.cc reads both with items())
+  const Value& sp = j.at("scene_pts");
+  auto point = [](const Value& p) { return std::array<double, 4>{p.at(0).as_double(), p.at(1).as_double(), p.at(2).as_double(), 1.0}; };
+  if (sp.is_array()) { for (size_t i = 0; i < sp.arr.size(); ++i) pts[int(i)] = point(sp.arr[i]); }
+  else for (const auto& kv : sp.obj) pts[std::stoi(kv.first)] = point(kv.second);
   for (const auto& kv : pts) { index[kv.first] = int(sc->points.size()); sc->points.push_back(kv.second); sc->point_ids.push_back(kv.first); }
   sc->width = int(j.at("image_width").as_double()); sc->height = int(j.at("image_height").as_double());
   sc->fps = j.contains("camera_fps") ? j.at("camera_fps").as_double() : 0.0;

@@ -243,4 +243,32 @@ class UbjsonReader {
   }
 };
 
+// nlohmann::json::to_ubjson without container optimisation (the corner file of board_extractor.cc:376-380): integers in
+// the smallest of i / U / I / l / L, every other number as D, object keys in std::map order.
+inline void write_ubjson(const Value& v, std::string* out) {
+  auto num_i = [&](int64_t n) {
+    auto be = [&](uint64_t u, int bytes) { for (int k = bytes - 1; k >= 0; --k) out->push_back(char((u >> (8 * k)) & 0xff)); };
+    if (n >= -128 && n <= 127) { out->push_back('i'); be(uint64_t(n), 1); }
+    else if (n >= 0 && n <= 255) { out->push_back('U'); be(uint64_t(n), 1); }
+    else if (n >= -32768 && n <= 32767) { out->push_back('I'); be(uint64_t(n), 2); }
+    else if (n >= -2147483648LL && n <= 2147483647LL) { out->push_back('l'); be(uint64_t(n), 4); }
+    else { out->push_back('L'); be(uint64_t(n), 8); }
+  };
+  switch (v.type) {
+    case Value::Null: out->push_back('Z'); break;
+    case Value::Bool: out->push_back(v.b ? 'T' : 'F'); break;
+    case Value::Number:
+      if (v.is_int) num_i(v.inum);
+      else { uint64_t u; std::memcpy(&u, &v.num, 8); out->push_back('D'); for (int k = 7; k >= 0; --k) out->push_back(char((u >> (8 * k)) & 0xff)); }
+      break;
+    case Value::String: out->push_back('S'); num_i(int64_t(v.str.size())); *out += v.str; break;
+    case Value::Array: out->push_back('['); for (const auto& x : v.arr) write_ubjson(x, out); out->push_back(']'); break;
+    case Value::Object:
+      out->push_back('{');
+      for (const auto& kv : v.obj) { num_i(int64_t(kv.first.size())); *out += kv.first; write_ubjson(kv.second, out); }
+      out->push_back('}');
+      break;
+  }
+}
+
 }  // namespace oicc_json

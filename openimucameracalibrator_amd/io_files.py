@@ -42,6 +42,33 @@ def ubjson_encode(v):
     raise TypeError(type(v))
 
 
+def nlohmann_order(v):
+    """Objects with their keys in std::map<std::string> order, as nlohmann::json stores (and to_ubjson writes) them."""
+    if isinstance(v, dict):
+        return {k: nlohmann_order(v[k]) for k in sorted(v, key=lambda k: str(k).encode())}
+    if isinstance(v, (list, tuple)):
+        return [nlohmann_order(x) for x in v]
+    return v
+
+
+def scene_points(scene_json):
+    """{id: [x, y, z]} of a corner file's scene_pts: an object keyed by the id as a string (charuco, apriltag) or an
+    array indexed by it (radon: board_extractor.cc:252-257 indexes with an int; read_scene.cc reads both with items())."""
+    sp = scene_json["scene_pts"]
+    if isinstance(sp, dict):
+        return {int(k): v for k, v in sp.items()}
+    return {i: v for i, v in enumerate(sp)}
+
+
+def write_image_folder(path, images, timestamps_ns):
+    """<timestamp_ns>.png per image (the input of extract_board_to_json): [h, w] gray or [h, w, 3] BGR u8."""
+    from PIL import Image
+    os.makedirs(path, exist_ok=True)
+    for im, t in zip(images, timestamps_ns):
+        im = np.asarray(im, dtype=np.uint8)
+        Image.fromarray(im if im.ndim == 2 else np.ascontiguousarray(im[..., ::-1])).save(os.path.join(path, "%d.png" % int(t)))
+
+
 def angle_axis_from_quat(q):
     q = np.asarray(q, dtype=np.float64)
     n = np.linalg.norm(q[:3])

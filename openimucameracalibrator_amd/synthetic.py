@@ -449,3 +449,134 @@ def make_static_multipose_imu(num_poses=36, rate=200.0, init_s=14.0, hold_s=4.0,
     truth = dict(acc_params=a9, gyro_params=np.asarray(gyro_params, dtype=np.float64), gravity=gravity, rate=rate,
                  acc_noise=acc_noise, gyro_noise=gyro_noise, num_poses=num_poses, n_init=n_init, n_hold=n_hold, n_move=n_move)
     return dict(timestamps_ns=t_ns, accelerometer=acc, gyroscope=gyr), truth
+
+
+# ---- the radon marker checkerboard (extract_board_to_json --board_type radon) ----------------------------------------
+# Geometry of the reference's resource/checkerboard_radon.png ("Target v1.0: 14x9 - 12.1 mm"), measured at 300 dpi:
+# (W+1) x (H+1) squares around W x H inner corners; black squares on the border have their outer half rounded into a
+# half disc; three dots of diameter 0.336 squares mark the origin ("Board extraction").
+RADON_DOT_RADIUS = 0.168
+RADON_BLACK, RADON_WHITE = 30.0, 220.0
+_RAY_CACHE = {}
+
+
+def radon_origin(W, H):
+    """Inner corner (row, column) of the origin: column W/2-1, row (H-1)/2 -> (4, 6) for 14 x 9."""
+    return (H - 1) // 2, W // 2 - 1
+
+
+def radon_board_shade(u, v, W, H):
+    """Reflectance (1 white, 0 black) at board coordinates u = X/s (pattern row) and v = Y/s (pattern column); torch or
+    numpy arrays.  Square (ci, cj) has inner corner (ci, cj) at its top-left; the origin square is white."""
+    import torch
+    xp = torch if isinstance(u, torch.Tensor) else np
+    r0, c0 = radon_origin(W, H)
+    ci, cj = xp.floor(u), xp.floor(v)
+    fu, fv = u - ci, v - cj
+    inside = (ci >= -1) & (ci <= H - 1) & (cj >= -1) & (cj <= W - 1)
+    black = inside & ((ci + cj + r0 + c0) % 2 == 1)
+    d2 = (fu - 0.5) ** 2 + (fv - 0.5) ** 2
+    # rounded tabs: on the outer half of a border square only points within 0.5 of the centre line's midpoint stay black
+    outer = (((ci == -1) & (fu < 0.5)) | ((ci == H - 1) & (fu > 0.5)) | ((cj == -1) & (fv < 0.5)) | ((cj == W - 1) & (fv > 0.5)))
+    black = black & ~(outer & (d2 > 0.25))
+    dot = (d2 <= RADON_DOT_RADIUS ** 2) & (((ci == r0) & (cj == c0)) | ((ci == r0 - 1) & (cj == c0)) | ((ci == r0) & (cj == c0 + 1)))
+    black = black ^ dot
+    return 1.0 - black.to(u.dtype) if xp is torch else 1.0 - black.astype(u.dtype)
+
+
+def _pixel_corner_rays(camera):
+    """Normalised rays (x, y) at the (w+1) x (h+1) pixel corners (x - 0.5, y - 0.5) of one CAMERAS entry (cached)."""
+    if camera not in _RAY_CACHE:
+        from . import planar_init
+        model, intr, w, h = CAMERAS[camera]
+        yy, xx = np.mgrid[0:h + 1, 0:w + 1]
+        uv = np.stack([xx.ravel() - 0.5, yy.ravel() - 0.5], 1).astype(np.float64)
+        _RAY_CACHE[camera] = planar_init.pixel_to_normalized(model, intr, uv).reshape(h + 1, w + 1, 2)
+    return _RAY_CACHE[camera]
+
+
+def radon_view_pose(W, H, square, f_px, img_h, rotation_deg, tilt_deg, tilt_axis_deg, fill=0.8, offset=(0.0, 0.0), distance_scale=1.0):
+    """Camera pose (R, t: X_cam = R X_board + t) that shows the board upright at rotation 0, turned in the image plane by
+    rotation_deg and tilted by tilt_deg about an in-plane axis at tilt_axis_deg; the board diagonal spans fill * img_h."""
+    def rot(axis, a):
+        a = np.deg2rad(a); c, s = np.cos(a), np.sin(a)
+        k = np.asarray(axis, dtype=np.float64); K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+        return np.eye(3) + s * K + (1 - c) * K @ K
+    R0 = np.array([[0.0, 1.0, 0.0], [1.0, 0.0, 0.0], [0.0, 0.0, -1.0]])    # board rows -> image down, columns -> right
+    ta = np.deg2rad(tilt_axis_deg)
+    R = rot([np.cos(ta), np.sin(ta), 0.0], tilt_deg) @ rot([0, 0, 1], rotation_deg) @ R0
+    diag = square * np.hypot(W + 1, H + 1)
+    D = distance_scale * f_px * diag / (fill * img_h)
+    centre = np.array([(H - 1) * square / 2.0, (W - 1) * square / 2.0, 0.0])
+    t = np.array([offset[0] * D, offset[1] * D, D]) - R @ centre
+    return R, t
+
+
+def render_radon_views(camera, num_views, W=14, H=9, square=0.0121, rotations=None, tilt_deg=20.0, supersample=4,
+                       blur_sigma=0.0, noise_sigma=0.0, seed=SEED, device="cpu", cover_marker=False, offsets=None,
+                       distance_scale=1.0):
+    """Images of the radon target through one CAMERAS model and the true pixel positions of its W*H inner corners.
+    Every pixel averages supersample^2 samples (a rank-1 lattice).  The exact rays (planar_init.pixel_to_normalized) are
+    computed at the pixel corners only; a sample's board point is interpolated bilinearly between the board points of
+    its pixel's four corners instead of unprojecting every sample (the error of that, second order in the distortion
+    over one pixel, is far below the detector's tolerances), and reads radon_board_shade.  Optional Gaussian blur
+    (sigma in px) and Gaussian noise (grey levels).  rotations: in-plane angles in degrees (default random);
+    offsets: per-view image-plane offsets of the board centre (fractions of the distance); cover_marker paints the
+    three marker squares grey.  Returns dict(images [n,h,w] u8, corners [n,W*H,2] with id i*W+j, visible [n] (all
+    corners inside the image), model, intrinsics, width, height, R, t)."""
+    import torch
+    model, intr, w, h = CAMERAS[camera]
+    rng = np.random.RandomState(seed)
+    rays = torch.as_tensor(_pixel_corner_rays(camera), dtype=torch.float64, device=device)
+    # supersample^2 samples per pixel on a rank-1 lattice (Korobov generator near N / golden ratio): every sample has
+    # its own x and its own y offset, so an edge along a pixel axis is resolved to 1/N px, not 1/supersample
+    N = int(supersample) ** 2
+    gen = max(1, int(round(N / 1.618033988749895)))
+    while np.gcd(gen, N) != 1:
+        gen += 1
+    images, corners, visible, Rs, ts = [], [], [], [], []
+    r0, c0 = radon_origin(W, H)
+    gi, gj = np.meshgrid(np.arange(H), np.arange(W), indexing="ij")
+    board_pts = np.stack([gi.ravel() * square, gj.ravel() * square, np.zeros(W * H)], 1)
+    for k in range(num_views):
+        rotd = float(rotations[k % len(rotations)]) if rotations is not None else rng.uniform(0, 360)
+        off = offsets[k % len(offsets)] if offsets is not None else rng.uniform(-0.08, 0.08, 2)
+        R, t = radon_view_pose(W, H, square, intr[0], h, rotd, tilt_deg * (rng.uniform(0.5, 1.0) if rotations is None else 1.0),
+                               rng.uniform(0, 360), offset=off, distance_scale=distance_scale)
+        # board coordinates at the pixel corners: X = R^T (lam d - t) with (R^T (lam d - t))_z = 0
+        Rt = torch.as_tensor(R.T, dtype=torch.float64, device=device)
+        tb = Rt @ torch.as_tensor(t, dtype=torch.float64, device=device)
+        d = torch.cat([rays, torch.ones_like(rays[..., :1])], -1) @ Rt.T
+        lam = tb[2] / d[..., 2]
+        XY = (lam[..., None] * d[..., :2] - tb[:2]) / square                   # [h+1, w+1, 2] board units (u, v)
+        acc = torch.zeros(h, w, dtype=torch.float64, device=device)
+        for q in range(N):
+            sx, sy = (q + 0.5) / N, ((q * gen) % N + 0.5) / N
+            top = XY[:-1, :-1] * (1 - sy) + XY[1:, :-1] * sy
+            bot = XY[:-1, 1:] * (1 - sy) + XY[1:, 1:] * sy
+            p = top * (1 - sx) + bot * sx
+            sh = radon_board_shade(p[..., 0], p[..., 1], W, H)
+            if cover_marker:
+                ci, cj = torch.floor(p[..., 0]), torch.floor(p[..., 1])
+                m = ((ci == r0) | (ci == r0 - 1)) & ((cj == c0) | (cj == c0 + 1))
+                sh = torch.where(m, torch.full_like(sh, 0.5), sh)
+            acc += sh
+        img = RADON_BLACK + (RADON_WHITE - RADON_BLACK) * acc / N
+        if blur_sigma > 0:
+            rad = int(np.ceil(4 * blur_sigma))
+            g = torch.exp(-0.5 * (torch.arange(-rad, rad + 1, dtype=torch.float64, device=device) / blur_sigma) ** 2)
+            g = (g / g.sum())
+            x = torch.nn.functional.pad(img[None, None], (rad, rad, rad, rad), mode="replicate")
+            x = torch.nn.functional.conv2d(x, g.view(1, 1, 1, -1)); x = torch.nn.functional.conv2d(x, g.view(1, 1, -1, 1))
+            img = x[0, 0]
+        img = img.cpu().numpy()
+        if noise_sigma > 0:
+            img = img + rng.standard_normal(img.shape) * noise_sigma
+        images.append(np.clip(np.rint(img), 0, 255).astype(np.uint8))
+        uv, _ = project(model, intr, board_pts @ R.T + t)
+        corners.append(uv)
+        visible.append(bool(np.all((uv > 0) & (uv < [w - 1, h - 1]))))
+        Rs.append(R); ts.append(t)
+    return dict(images=np.stack(images), corners=np.stack(corners), visible=np.array(visible), model=model,
+                intrinsics=np.asarray(intr, dtype=np.float64), width=w, height=h, R=np.stack(Rs), t=np.stack(ts), W=W, H=H,
+                square=square)

@@ -1,0 +1,116 @@
+"""oicc_board_radon_detect on the MI355X against the numpy restatement (tests/board_restatement.py) and the renderer's
+truth, and extract_board_to_json end to end into calibrate_camera."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import board_restatement as BR  # noqa: E402
+from openimucameracalibrator_amd import board_extractor as BE, io_files, synthetic as S  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+CSRC = os.path.join(ROOT, "openimucameracalibrator_amd", "csrc")
+
+
+def _views(camera, n, **kw):
+    return S.render_radon_views(camera, n, device="cuda", **kw)
+
+
+@pytest.mark.parametrize("factor,bgr,width", [(1.0, False, 960), (1.5, True, 960), (1.0, False, 957)])
+def test_stages_equal_restatement(factor, bgr, width):
+    d = _views("gopro9_division", 3, rotations=[0, 60, 200], tilt_deg=20)
+    frames = np.ascontiguousarray(d["images"][:, :, :width])     # 957: rows that are not whole 4-byte words
+    if bgr:   # a colour frame whose gray conversion is not the identity
+        frames = np.stack([frames, np.clip(frames.astype(int) + 7, 0, 255), np.clip(frames.astype(int) - 5, 0, 255)], -1).astype(np.uint8)
+    corners, found, ncand, rep, st = BE.radon_detect(frames, factor, 14, 9, stages=True)
+    rc, rf, dbg = BR.detect(frames, factor, 14, 9, debug=True)
+    assert np.array_equal(st["gray"], dbg["gray"])
+    scale = np.abs(dbg["response"]).max()
+    assert np.abs(st["response"] - dbg["response"]).max() <= 1e-5 * scale
+    for f in range(len(frames)):
+        yx, _ = dbg["candidates"][f]
+        assert ncand[f] == len(yx) and np.array_equal(st["candidates"][f], yx)
+        assert np.abs(st["refined"][f] - dbg["refined"][f]).max() <= 1e-3
+    assert np.array_equal(found, rf)
+    assert found.sum() >= (3 if factor == 1.0 else 1)
+    assert np.abs(corners[found] - rc[found]).max() <= 1e-3      # the same ids: a different id moves a corner by a square
+    assert rep["output_width"] == st["gray"].shape[2] and rep["frames_found"] == found.sum()
+
+
+@pytest.mark.parametrize("camera", ["gopro9_division", "gopro6_fisheye", "pinhole"])
+def test_accuracy_against_truth(camera):
+    d = _views(camera, 6, rotations=[0, 90, 180, 270, 33, 300], tilt_deg=25)
+    corners, found, _, _ = BE.radon_detect(d["images"], 1.0, 14, 9)
+    assert found.all()
+    e = np.hypot(*(corners - d["corners"]).reshape(-1, 2).T)
+    assert np.sqrt(np.mean(e ** 2)) <= 0.05 and e.max() <= 0.2, (np.sqrt(np.mean(e ** 2)), e.max())
+    dn = _views(camera, 6, rotations=[0, 90, 180, 270, 33, 300], tilt_deg=25, blur_sigma=0.8, noise_sigma=2.0)
+    corners, found, _, _ = BE.radon_detect(dn["images"], 1.0, 14, 9)
+    assert found.all()
+    e = np.hypot(*(corners - dn["corners"]).reshape(-1, 2).T)
+    assert np.sqrt(np.mean(e ** 2)) <= 0.15, np.sqrt(np.mean(e ** 2))
+
+
+def test_covered_marker_and_cut_board_report_nothing():
+    cov = _views("gopro9_division", 2, rotations=[10, 100], tilt_deg=10, cover_marker=True)
+    cut = _views("gopro9_division", 1, rotations=[0], tilt_deg=0, offsets=[(1.4, 0.0)])
+    for d in (cov, cut):
+        corners, found, _, _ = BE.radon_detect(d["images"], 1.0, 14, 9)
+        assert not found.any() and np.isnan(corners).all()
+
+
+def test_batch_of_64_equals_single_calls():
+    d = _views("gopro6_double_sphere", 16, tilt_deg=25, noise_sigma=1.0)
+    frames = np.concatenate([d["images"]] * 4)
+    cb, fb, nb, _ = BE.radon_detect(frames, 1.0, 14, 9, batch=64)
+    c2, f2, n2, _ = BE.radon_detect(frames, 1.0, 14, 9, batch=5)       # several launch chains, both slots in flight
+    assert fb.sum() >= 48
+    assert np.array_equal(fb, f2) and np.array_equal(nb, n2) and np.array_equal(cb, c2, equal_nan=True)
+    for k in range(len(frames)):
+        c1, f1, n1, _ = BE.radon_detect(frames[k:k + 1], 1.0, 14, 9)
+        assert f1[0] == fb[k] and n1[0] == nb[k] and np.array_equal(c1[0], cb[k], equal_nan=True)
+
+
+def test_extract_board_to_json_end_to_end(tmp_path):
+    d = _views("gopro9_division", 60, tilt_deg=30, noise_sigma=1.0, seed=7)
+    # 29 deltas of 33.3667 ms, then 30 of 40 ms: the reference's loop drops the last delta, so the median is the mean of
+    # the two kinds; over all 59 deltas it would be 40 ms
+    dt = np.array([33_366_700] * 29 + [40_000_000] * 30)
+    t_ns = 1_600_000_000_000_000_000 + np.concatenate([[0], np.cumsum(dt)])
+    folder = tmp_path / "frames"
+    io_files.write_image_folder(str(folder), d["images"], t_ns)
+    flags = ["--input_path", str(folder), "--board_type", "radon", "--checker_square_length_m", "0.0121", "--num_squares_x", "14",
+             "--num_squares_y", "9", "--aruco_detector_params", "p.yml", "--logtostderr=1"]
+    out = tmp_path / "corners.uson"
+    r = subprocess.run([sys.executable, "-m", "openimucameracalibrator_amd.extract_board_to_json", "--save_corners_json_path", str(out)] + flags,
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr
+    out_cpp = tmp_path / "corners_cpp.uson"
+    r = subprocess.run([os.path.join(CSRC, "extract_board_to_json"), "--save_corners_json_path", str(out_cpp)] + flags,
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr
+    assert out.read_bytes() == out_cpp.read_bytes()              # the C++ application and the Python module agree
+    sc = io_files.read_scene_bson(str(out))
+    assert isinstance(sc["scene_pts"], list) and sc["calibration_board_type"] == 1 and sc["image_width"] == 960
+    # (timestamps near 1.6e9 s in double seconds carry ~1e-7 s of rounding, hence rel 1e-5; without the quirk: 25 fps)
+    assert sc["camera_fps"] == pytest.approx(2.0 / (33_366_700e-9 + 40_000_000e-9), rel=1e-5)
+    assert len(sc["views"]) >= 50 and all(len(k.split(".")[1]) == 6 for k in sc["views"])
+    for k, v in sc["views"].items():
+        f = int(np.argmin(np.abs(t_ns * 1e-3 - float(k))))
+        uv = np.array([v["image_points"][str(i)] for i in range(126)])
+        assert np.abs(uv - d["corners"][f]).max() < 0.3
+    for cmd in ([sys.executable, "-m", "openimucameracalibrator_amd.calibrate_camera"], [os.path.join(CSRC, "calibrate_camera")]):
+        cal = tmp_path / ("py" if cmd[0] == sys.executable else "cpp")
+        r = subprocess.run(cmd + ["--input_corners=%s" % out, "--camera_model_to_calibrate=DIVISION_UNDISTORTION",
+                                  "--save_path_calib_dataset=%s" % cal, "--grid_size=0.001"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout + r.stderr
+        j = json.load(open(str(cal) + ".json"))
+        I = j["intrinsics"]
+        assert abs(I["focal_length"] - d["intrinsics"][0]) < 0.5, I
+        assert abs(I["principal_pt_x"] - d["intrinsics"][2]) < 0.5 and abs(I["principal_pt_y"] - d["intrinsics"][3]) < 0.5, I
+        assert j["final_reproj_error"] < 0.1
