@@ -681,6 +681,30 @@ int oicc_board_radon_detect(int32_t device_ordinal, int32_t num_frames, int32_t 
                             const oicc_board_options* opt, double* corners, int32_t* found, int32_t* candidates_per_frame,
                             oicc_board_report* report, const oicc_board_stages* stages);
 
+/* ---- robust start poses: planar RANSAC over the views of a corner file (planar_ransac.hip) --------------------------------
+ * The reference takes the start pose (and focal length) of every view from TheiaSfM's RANSAC minimal solvers [EXT]
+ * (camera_calibrator.cc:262-301, pose_estimator.cc:54-83) and, in the pose estimator, keeps only the RANSAC inliers.  This
+ * entry selects the inliers of ALL views in one launch (one workgroup per view, one lane per hypothesis); the start values
+ * themselves stay the closed forms of the host side, run on the inliers.  Model: the radial alignment constraint
+ *   u (q3 a + q4 b + q5) - v (q0 a + q1 b + q2) = 0
+ * for board plane coordinates (a, b) and features (u, v) relative to the distortion centre, five corners per sample;
+ * specified step by step by tests/planar_ransac_restatement.py and DESIGN.md ("Robust start poses").
+ *   corner_offsets [num_views + 1] (first 0), ab and xy [n][2] with n = corner_offsets[num_views];
+ *   mode 0: uncalibrated features (pixels relative to the principal point): vote, least-squares refit of q, tangential test;
+ *   mode 1: calibrated features (normalised image coordinates, f = 1): additionally the pose completed from q and the full
+ *           reprojection test;  threshold in the units of xy;  num_hypotheses 1..1024 per view, fixed;  seed of the sampler.
+ *   inlier [n] (0 / 1), num_inliers [num_views], q [num_views][6] (unit norm, sign towards the corners),
+ *   pose [num_views][12] = R row-major | t, board plane frame -> camera (mode 1; untouched in mode 0, may be NULL there),
+ *   hypothesis_counts [num_views][num_hypotheses] (may be NULL): the score of every hypothesis, for checking,
+ *   device_ms (may be NULL): kernel time by device events.
+ * A view with fewer than 5 corners, without a hypothesis of 5 inliers, or with board corners on one line gets
+ * num_inliers = 0 (zero q and pose), not an error.  OICC_ERR_INVALID_ARG for non-finite input, a threshold <= 0, a
+ * hypothesis count outside 1..1024, offsets that decrease or a view of more than 2^20 corners; OICC_ERR_NO_DEVICE without
+ * a usable HIP device (no CPU fallback). */
+int oicc_planar_ransac(int32_t device_ordinal, int32_t num_views, const int64_t* corner_offsets, const double* ab, const double* xy,
+                       int32_t mode, double threshold, int32_t num_hypotheses, uint64_t seed, uint8_t* inlier,
+                       int32_t* num_inliers, double* q, double* pose, int32_t* hypothesis_counts, double* device_ms);
+
 #ifdef __cplusplus
 }
 #endif

@@ -284,3 +284,24 @@ class BoundBoard:
             fn.restype = res
             fn.argtypes = args
             setattr(self, name, fn)
+
+
+# Robust start poses (oicc_planar_ransac in include/oicc_hip.h), a table of its own like ALLAN_SIGNATURES: SIGNATURES and
+# BA_SIGNATURES are also bound against the CPU checker, which has no counterpart of this entry.
+PLANAR_RANSAC_SIGNATURES = {
+    "ransac": (C.c_int, [C.c_int32, C.c_int32, c_i64p, c_dp, c_dp, C.c_int32, C.c_double, C.c_int32, C.c_uint64, c_u8p, c_i32p, c_dp,
+                         c_dp, c_i32p, c_dp]),
+}
+
+
+class BoundPlanarRansac:
+    """Bound oicc_planar_* entry points of one library + prefix (``oicc_planar_`` for liboicc_hip.so)."""
+
+    def __init__(self, lib, prefix):
+        self.lib = lib
+        self.prefix = prefix
+        for name, (res, args) in PLANAR_RANSAC_SIGNATURES.items():
+            fn = getattr(lib, prefix + name)  # AttributeError = missing symbol: fail loudly
+            fn.restype = res
+            fn.argtypes = args
+            setattr(self, name, fn)

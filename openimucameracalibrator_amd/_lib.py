@@ -7,7 +7,7 @@ fails when no HIP device is usable.
 import ctypes
 import os
 
-from ._abi import Bound, BoundAllan, BoundBa, BoundBoard, BoundStaticImu
+from ._abi import Bound, BoundAllan, BoundBa, BoundBoard, BoundPlanarRansac, BoundStaticImu
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OICC_DEV_LIB") or os.path.join(_HERE, "csrc", "liboicc_hip.so")   # OICC_DEV_LIB: another BUILD of the same library (developer A/B timing, scripts/build_variant.sh)
@@ -16,6 +16,7 @@ _bound_ba = None
 _bound_allan = None
 _bound_static_imu = None
 _bound_board = None
+_bound_planar_ransac = None
 
 
 def load():
@@ -60,3 +61,11 @@ def load_board():
     if _bound_board is None:
         _bound_board = BoundBoard(load().lib, "oicc_board_")
     return _bound_board
+
+
+def load_planar_ransac():
+    """oicc_planar_ransac (robust start poses) of the same library."""
+    global _bound_planar_ransac
+    if _bound_planar_ransac is None:
+        _bound_planar_ransac = BoundPlanarRansac(load().lib, "oicc_planar_")
+    return _bound_planar_ransac

@@ -6,8 +6,9 @@ CameraCalibrator::CalibrateCameraFromJson, src/core/camera_calibrator.cc:221-377
 
 Same flags, same input (the UBJSON corner file of extract_board_to_json) and the same calibration JSON keys
 (src/io/write_camera_calibration.cc).  Differences, all outside the bundle adjustment: the per-view start values come
-from planar_init.py (closed forms for a planar board) instead of Theia's RANSAC solvers [EXT]; the start focal length
-is the median over the views; `<out>.calibdata` is written as the JSON twin of the Theia archive.  The three
+from planar_init.py (closed forms for a planar board) instead of Theia's RANSAC solvers [EXT] -- over every corner by
+default, with --robust_init over the inliers of the RANSAC of robust_init.py (all views in one launch on the device;
+--ransac_hypotheses per view), which alone become observations; the start focal length is the median over the views; `<out>.calibdata` is written as the JSON twin of the Theia archive.  The three
 BundleAdjustViews stages and the view filters of RunCalibration run on the device (oicc_ba_*)."""
 import argparse
 import sys
@@ -21,14 +22,17 @@ def str2bool(v):
 
 
 def calibrate_camera_from_json(scene, camera_model, grid_size=0.04, output_path="", verbose=False, device=0, backend=None,
-                               optimize_board_points=False):
+                               optimize_board_points=False, robust_init=False, ransac_backend=None, ransac_hypotheses=256):
     """applications/calibrate_camera.cc:50-59: CameraCalibrator(model, optimize_board_points), SetGridSize, SetVerbose,
-    CalibrateCameraFromJson.  Returns the CameraCalibrator (or None on failure)."""
+    CalibrateCameraFromJson.  Returns the CameraCalibrator (or None on failure).  robust_init: see
+    CameraCalibrator.CalibrateCameraFromJson; ransac_backend None = the HIP library."""
     cal = CC.CameraCalibrator(camera_model, optimize_board_pts=optimize_board_points, device=device, backend=backend)
     cal.SetGridSize(grid_size)
     if verbose:
         cal.SetVerbose()
-    return cal if cal.CalibrateCameraFromJson(scene, output_path) else None
+    ok = cal.CalibrateCameraFromJson(scene, output_path, robust_init=robust_init, ransac_backend=ransac_backend,
+                                     ransac_hypotheses=ransac_hypotheses)
+    return cal if ok else None
 
 
 def main(argv=None):
@@ -39,10 +43,13 @@ def main(argv=None):
     ap.add_argument("--grid_size", type=float, default=0.04)
     ap.add_argument("--optimize_board_points", type=str2bool, nargs="?", const=True, default=False)
     ap.add_argument("--verbose", type=str2bool, nargs="?", const=True, default=False)
+    ap.add_argument("--robust_init", type=str2bool, nargs="?", const=True, default=False)
+    ap.add_argument("--ransac_hypotheses", type=int, default=256)
     a = io_files.parse_reference_flags(ap, argv)
     scene = io_files.read_scene_bson(a.input_corners)
     cal = calibrate_camera_from_json(scene, a.camera_model_to_calibrate, a.grid_size, a.save_path_calib_dataset, a.verbose,
-                                     optimize_board_points=a.optimize_board_points)
+                                     optimize_board_points=a.optimize_board_points, robust_init=a.robust_init,
+                                     ransac_hypotheses=a.ransac_hypotheses)
     if cal is None:
         return 1
     cal.PrintResult()

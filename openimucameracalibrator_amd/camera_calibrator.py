@@ -7,10 +7,11 @@ oicc_ba_* C-ABI (view bundle adjustment on the device).
                        BundleAdjustView of every view; OptimizeAllPoses)
 
 The reference stores views, tracks and the camera in a theia::Reconstruction [EXT]; here they are
-flat numpy arrays in the layout the C-ABI takes.  What stays outside (named, not silently skipped):
-the RANSAC pose / focal-length initialisation of CalibrateCameraFromJson (camera_calibrator.cc:247-316,
-theia::EstimateUncalibratedAbsolutePose / EstimateRadialDistUncalibratedAbsolutePose [EXT]) -- views enter
-through AddView with an initial pose, exactly as the reference's own AddView is fed -- and the empirical point
+flat numpy arrays in the layout the C-ABI takes.  The RANSAC pose / focal-length initialisation of the reference
+(camera_calibrator.cc:247-316, pose_estimator.cc:54-83, TheiaSfM minimal solvers [EXT]) has a counterpart of its own:
+with robust_init=True the corners of every view go through oicc_planar_ransac (robust_init.py, all views in one launch)
+and only the inliers become observations; the start values stay the closed forms of planar_init.py.  The default
+(robust_init=False) uses every corner.  What stays outside (named, not silently skipped): the empirical point
 covariances PoseEstimator::OptimizeBoardPoints prints (ceres::Covariance, pose_estimator.cc:209-223).
 """
 import ctypes as C
@@ -247,6 +248,8 @@ class CameraCalibrator:
         self.min_num_view_ = 10        # camera_calibrator.h
         self.grid_size_ = 0.04
         self.verbose_ = False
+        self.device = device
+        self.ransac_error_thresh_ = None   # robust_init: 0.003 * image height unless set (camera_calibrator.cc:270)
         self.ba = ViewBundleAdjuster(device=device, backend=backend)
         self.max_num_iterations = 100  # theia::BundleAdjustmentOptions default [EXT]
         self.summaries = []
@@ -259,13 +262,17 @@ class CameraCalibrator:
         self.grid_size_ = float(grid_size)
 
     def SetRansacErrorThresh(self, error_thresh=0.1):
-        """kept for interface parity: the start values here are closed forms, not RANSAC (planar_init.py)."""
+        """The inlier threshold of robust_init=True in pixels (distance of a corner from its radial line); without
+        robust_init the start values use every corner and this has no effect."""
         self.ransac_error_thresh_ = float(error_thresh)
 
-    def CalibrateCameraFromJson(self, scene_json, output_path=""):
+    def CalibrateCameraFromJson(self, scene_json, output_path="", robust_init=False, ransac_backend=None, ransac_hypotheses=256):
         """camera_calibrator.cc:221-377: views from the corner file (start pose and focal length per view, voxel filter),
-        RunCalibration, outputs (`<out>.json`, `<out>.calibdata.json`, two PLY files)."""
-        from . import io_files, planar_init
+        RunCalibration, outputs (`<out>.json`, `<out>.calibdata.json`, two PLY files).  robust_init=True: RANSAC over the
+        corners of every view first (robust_init.py); start values from the inliers, ONLY the inliers become observations
+        and a view with fewer than 6 is skipped.  (The reference adds every corner of a kept view, :337-339; its
+        RemoveViewsReprojError(5.0) judges a view by the mean corner error, which a few gross corners push over the limit.)"""
+        from . import io_files, planar_init, robust_init as RI
         scene_pts = io_files.scene_points(scene_json)
         ids = sorted(scene_pts)
         index = {k: i for i, k in enumerate(ids)}
@@ -273,14 +280,19 @@ class CameraCalibrator:
         points = np.array([[*scene_pts[k][:3], 1.0] for k in ids], dtype=np.float64)
         w, h = int(scene_json["image_width"]), int(scene_json["image_height"])
         px, py = w / 2.0, h / 2.0                                          # initial principal point, camera_calibrator.cc:228-230
-        views = []
+        views, cand = [], []
         for key in sorted(scene_json["views"]):                            # nlohmann::json (std::map) iterates the keys in string order
             ip = scene_json["views"][key]["image_points"]
             ip = {k: v for k, v in ip.items() if int(k) in index}              # ids without a board point are skipped while loading, as in the C++ loader ...
             if len(ip) < 4:                                                     # ... so the minimum count applies to the usable correspondences
                 continue
-            pid = np.array([index[int(k)] for k in ip], dtype=np.int32)
-            uv = np.array([ip[k][:2] for k in ip], dtype=np.float64)
+            cand.append((key, np.array([index[int(k)] for k in ip], dtype=np.int32), np.array([ip[k][:2] for k in ip], dtype=np.float64)))
+        if robust_init:
+            thr = self.ransac_error_thresh_ if self.ransac_error_thresh_ is not None else 0.003 * h
+            masks = RI.select_inliers(points, [(pid, uv - [px, py]) for _, pid, uv in cand], RI.UNCALIBRATED, thr,
+                                      num_hypotheses=ransac_hypotheses, device=self.device, backend=ransac_backend)
+            cand = [(key, pid[m], uv[m]) for (key, pid, uv), m in zip(cand, masks) if int(m.sum()) >= RI.MIN_INLIERS]
+        for key, pid, uv in cand:
             ok, R, C, f = planar_init.initialize_view(points, pid, uv - [px, py])
             if ok:   # success_init of the reference (camera_calibrator.cc:327): a view that does not determine a focal length is skipped
                 views.append([float(key) * 1e-6, pid, uv, f])
@@ -437,6 +449,7 @@ class PoseEstimator:
     def __init__(self, device=0, backend=None):
         self.views = _Views()
         self.points = None
+        self.device = device
         self.ba = ViewBundleAdjuster(device=device, backend=backend)
         self.model = CAM_PINHOLE
         self.intr = np.array([1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0])
@@ -454,13 +467,22 @@ class PoseEstimator:
         self.views.obs.append([(int(k), float(f[0]), float(f[1])) for k, f in zip(point_ids, features)])
         return len(self.views.pose) - 1
 
-    def EstimatePosePinhole(self, timestamp_s, correspondences_undist, board_pts3_ids):
-        """pose_estimator.cc:62-90 for one frame: start pose from the normalised correspondences (closed forms instead of the
-        reference's RANSAC PnP), the frame is added with its observations; its BundleAdjustView runs together with every other
-        frame's in the next OptimizeAllPoses (one launch).  correspondences_undist: [n,2] normalised image points."""
-        from . import planar_init
+    def EstimatePosePinhole(self, timestamp_s, correspondences_undist, board_pts3_ids, robust_init=False, ransac_threshold=None,
+                            ransac_backend=None, ransac_hypotheses=256):
+        """pose_estimator.cc:62-90 for one frame: start pose from the normalised correspondences (closed forms of
+        planar_init.py; with robust_init=True on the RANSAC inliers of robust_init.py, which alone become observations, as in
+        the reference), the frame is added with its observations; its BundleAdjustView runs together with every other
+        frame's in the next OptimizeAllPoses (one launch).  correspondences_undist: [n,2] normalised image points;
+        ransac_threshold in the same units (required with robust_init)."""
+        from . import planar_init, robust_init as RI
         pid = np.asarray(board_pts3_ids, dtype=np.int32)
         xy = np.asarray(correspondences_undist, dtype=np.float64).reshape(-1, 2)
+        if robust_init:
+            if ransac_threshold is None:
+                raise ValueError("robust_init needs ransac_threshold (normalised image units)")
+            m = RI.select_inliers(self.points, [(pid, xy)], RI.CALIBRATED, ransac_threshold, num_hypotheses=ransac_hypotheses,
+                                  device=self.device, backend=ransac_backend)[0]
+            pid, xy = pid[m], xy[m]
         if len(pid) < 6:                                                      # ransac_summary.inliers.size() < 6, :72-74
             return False
         ok, R, C, _ = planar_init.initialize_view(self.points, pid, xy, focal=1.0)
@@ -480,10 +502,15 @@ class PoseEstimator:
         self.views.pose = [out[i].copy() for i in range(len(out))]
         return it, fc
 
-    def EstimatePosesFromJson(self, scene_json, model, intrinsics, image_height, min_num_points=8):
+    def EstimatePosesFromJson(self, scene_json, model, intrinsics, image_height, min_num_points=8, robust_init=False,
+                              ransac_backend=None, ransac_hypotheses=256, ransac_threshold=None):
         """pose_estimator.cc:92-190: every frame of the corner file -> normalised features, start pose, BundleAdjustView
-        (all frames in one launch), back-projection test in pixels with the calibrated camera."""
-        from . import io_files, planar_init
+        (all frames in one launch), back-projection test in pixels with the calibrated camera.  robust_init=True: RANSAC
+        over the normalised corners of every frame first (robust_init.py, one launch); start pose from the inliers, only
+        the inliers become observations, a frame with fewer than 6 is skipped (pose_estimator.cc:65-83).  Threshold:
+        0.004 * image height / focal length, the pixel limit of the back-projection test in normalised units, unless
+        ransac_threshold is given."""
+        from . import io_files, planar_init, robust_init as RI
         scene_pts = io_files.scene_points(scene_json)
         ids = sorted(scene_pts)
         index = {k: i for i, k in enumerate(ids)}
@@ -492,6 +519,7 @@ class PoseEstimator:
         self.calib_ = (int(model), np.asarray(intrinsics, dtype=np.float64))
         self.max_reproj_error_ = 0.004 * image_height                        # pose_estimator.cc:97
         self.px_obs_ = []
+        cand = []
         for key in sorted(scene_json["views"]):                              # nlohmann::json (std::map) key order
             ip = scene_json["views"][key]["image_points"]
             ip = {k: v for k, v in ip.items() if int(k) in index}            # (an id without a board point would dereference a null track in the reference, :129)
@@ -500,6 +528,13 @@ class PoseEstimator:
             pid = np.array([index[int(k)] for k in ip], dtype=np.int32)
             uv = np.array([ip[k][:2] for k in ip], dtype=np.float64)
             xy = planar_init.pixel_to_normalized(model, intrinsics, uv)      # camera.PixelToNormalizedCoordinates, :119-121
+            cand.append((key, pid, uv, xy))
+        if robust_init:
+            thr = ransac_threshold if ransac_threshold is not None else self.max_reproj_error_ / float(self.calib_[1][0])
+            masks = RI.select_inliers(self.points, [(pid, xy) for _, pid, _, xy in cand], RI.CALIBRATED, thr,
+                                      num_hypotheses=ransac_hypotheses, device=self.device, backend=ransac_backend)
+            cand = [(key, pid[m], uv[m], xy[m]) for (key, pid, uv, xy), m in zip(cand, masks) if int(m.sum()) >= RI.MIN_INLIERS]
+        for key, pid, uv, xy in cand:
             ok, R, C, _ = planar_init.initialize_view(self.points, pid, xy, focal=1.0)
             if not ok:
                 continue

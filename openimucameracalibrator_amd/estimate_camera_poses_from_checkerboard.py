@@ -8,7 +8,8 @@ calibrated camera -- the pose data set continuous_time_imu_to_camera_calibration
 
 As in the reference the corners are taken to the normalised image plane and a PINHOLE camera with f = 1, c = 0 is
 adjusted (pose_estimator.cc:130-150).  The per-view start pose comes from planar_init.py instead of Theia's RANSAC PnP
-[EXT]; the per-view bundle adjustment (BundleAdjustView, Huber 1.345) of ALL views is one kernel launch on the device
+[EXT] -- over every corner by default; with --robust_init over the inliers of the RANSAC of robust_init.py (all frames in
+one launch on the device, --ransac_hypotheses per frame), which alone become observations as in the reference; the per-view bundle adjustment (BundleAdjustView, Huber 1.345) of ALL views is one kernel launch on the device
 (oicc_ba_optimize_views).  Output: the JSON twin of the Theia archive + `<out>.ply`."""
 import argparse
 import sys
@@ -19,11 +20,13 @@ from . import camera_calibrator as CC
 from . import io_files
 
 
-def estimate_poses_from_json(scene, model, intrinsics, image_height, device=0, backend=None, min_num_points=8, optimize_board_points=False):
+def estimate_poses_from_json(scene, model, intrinsics, image_height, device=0, backend=None, min_num_points=8, optimize_board_points=False,
+                             robust_init=False, ransac_backend=None, ransac_hypotheses=256):
     """applications/estimate_camera_poses_from_checkerboard.cc:55-70: EstimatePosesFromJson, optionally OptimizeBoardPoints +
     OptimizeAllPoses, FilterBadPoses, GetPoseDataset.  Returns (t_s, pose6, points, per-view mean reprojection error [px])."""
     pe = CC.PoseEstimator(device=device, backend=backend)
-    pe.EstimatePosesFromJson(scene, model, intrinsics, image_height, min_num_points=min_num_points)
+    pe.EstimatePosesFromJson(scene, model, intrinsics, image_height, min_num_points=min_num_points, robust_init=robust_init,
+                             ransac_backend=ransac_backend, ransac_hypotheses=ransac_hypotheses)
     if optimize_board_points and pe.views.pose:
         pe.OptimizeBoardPoints()
         pe.OptimizeAllPoses()
@@ -38,11 +41,15 @@ def main(argv=None):
     ap.add_argument("--camera_calibration_json", required=True)
     ap.add_argument("--output_pose_dataset", required=True)
     ap.add_argument("--optimize_board_points", nargs="?", const="true", default="false")
+    ap.add_argument("--robust_init", nargs="?", const="true", default="false")
+    ap.add_argument("--ransac_hypotheses", type=int, default=256)
     a = io_files.parse_reference_flags(ap, argv)
     scene = io_files.read_scene_bson(a.input_corners)
     model, intr, w, h, _ = io_files.read_camera_calibration(a.camera_calibration_json)
     t_s, pose, points, err = estimate_poses_from_json(scene, model, intr, h,
-                                                      optimize_board_points=str(a.optimize_board_points).lower() in ("1", "true", "yes", ""))
+                                                      optimize_board_points=str(a.optimize_board_points).lower() in ("1", "true", "yes", ""),
+                                                      robust_init=str(a.robust_init).lower() in ("1", "true", "yes", ""),
+                                                      ransac_hypotheses=a.ransac_hypotheses)
     print("Estimated %d camera poses, mean reprojection error %.4f px" % (len(t_s), float(np.mean(err)) if len(err) else float("nan")))
     io_files.write_pose_dataset(a.output_pose_dataset, t_s, pose, points, sorted(io_files.scene_points(scene)))
     io_files.write_ply_cameras(a.output_pose_dataset + ".ply", pose, points)

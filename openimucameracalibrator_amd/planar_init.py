@@ -5,7 +5,8 @@ The reference obtains them from TheiaSfM's RANSAC minimal solvers [EXT]: Estimat
 EstimateRadialDistUncalibratedAbsolutePose in utils::initialize_pinhole_camera / initialize_radial_undistortion_camera
 (camera_calibrator.cc:273-311) and EstimateCalibratedAbsolutePose (DLS PnP) in PoseEstimator::EstimatePosePinhole
 (pose_estimator.cc:62-71).  None of them is vendored, and their output is only a start value that the bundle adjustment
-overwrites, so this module uses the closed forms for a PLANAR target instead (the calibration boards of the reference are
+overwrites, so this module uses the closed forms for a PLANAR target instead; the other half of their job, rejecting
+wrong corners, is robust_init.py (off by default), which hands this module the inliers (the calibration boards of the reference are
 planar): normalised DLT homography, Zhang's two constraints on the image of the absolute conic for the focal length
 (principal point known, square pixels), pose from the homography columns.  Host-side numpy: O(views) tiny systems.
 """

@@ -4,6 +4,7 @@
 R=$(cd $(dirname $0)/.. && pwd); T=$(mktemp -d)
 for f in "$@"; do
   extra=""; [ "$f" = kernels_tiles ] && extra="-mllvm -amdgpu-mfma-vgpr-form"    # (as the Makefile builds it)
+  [ "$f" = planar_ransac ] && extra="-ffp-contract=off"
   /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics $extra --cuda-device-only -c $R/openimucameracalibrator_amd/csrc/$f.hip -o $T/$f.co 2>/dev/null || { echo "$f: compile failed"; continue; }
   /opt/rocm/lib/llvm/bin/clang-offload-bundler --unbundle --type=o --input=$T/$f.co --targets=hip-amdgcn-amd-amdhsa--gfx950 --output=$T/$f.elf
   echo "# $f.hip: kernel, vgpr_count (arch + acc), agpr_count, vgpr_spill_count, sgpr_spill_count, scratch bytes (private_segment_fixed_size), static LDS bytes (group_segment_fixed_size)"
