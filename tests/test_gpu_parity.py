@@ -6,11 +6,14 @@ Tolerances (fp64): residuals 1e-12 abs+rel, tangent Jacobians
 rel-to-scale as SURVEY proposes (round 6: tightened from 1e-9; measured <= 4e-14, scripts/dbg_ne_margins.py),
 LM iterates: cost 1e-8 rel, final parameters 1e-7 (the reference-option solves of the application's
 flag set: 1e-9 / 1e-9, profiles/r06l_parity_margins.log).
+The assembly tests assert J^T J / J^T r entry by entry as well (entry_err: every entry on its own scale d_i d_j; one global scale
+leaves the small blocks unchecked); tests/test_gpu_normal_equations_reference.py holds the full entry-wise comparison.
 """
 import numpy as np
 import pytest
 
 import oracle_backend
+import normal_equations_reference as NER
 from openimucameracalibrator_amd import synthetic, estimator as E
 
 pytestmark = pytest.mark.gpu
@@ -28,6 +31,15 @@ def build_pair(cfg="tiny", **kw):
 def rel_err(a, b, scale=None):
     s = np.abs(b).max() if scale is None else scale
     return np.abs(a - b).max() / max(s, 1e-300)
+
+
+def entry_err(tr, flags, Ha, Hb, ga, gb, cost):
+    """Entry-wise errors of (Ha, ga) against (Hb, gb): max |dH_ij| / (d_i d_j) and max |dg_i| / (d_i sqrt(2 cost)), d = sqrt(diag Hb)
+    (tests/normal_equations_reference.py) -- every entry on its own scale, where rel_err has one scale for the whole matrix."""
+    kinds = NER.column_kinds(tr.GetTangentLayout(flags))
+    eh, eg = NER.entrywise_error(Ha, Hb, kinds)[0], NER.gradient_error(ga, gb, Hb, cost, kinds)[0]
+    print("entry-wise: H %.2e g %.2e" % (eh, eg))
+    return eh, eg
 
 
 @pytest.fixture(scope="module")
@@ -66,7 +78,10 @@ def test_normal_equations(tiny, flags):
     assert abs(cg - cc) <= 1e-11 * cc
     assert rel_err(gg, gc) < 1e-10
     assert rel_err(Hg, Hc) < 1e-10
+    eh, eg = entry_err(gpu.trajectory_, flags, Hg, Hc, gg, gc, cc)
+    assert eh < 1e-10 and eg < 1e-10, (eh, eg)
     assert np.abs(Hg - Hg.T).max() <= 1e-13 * np.abs(Hg).max()   # arrow corner: two atomics per off-diagonal pair
+    assert NER.symmetry_error(Hg, Hc) <= 1e-13
     assert abs(gpu.trajectory_.EvaluateCost(flags) - cc) <= 1e-11 * cc
 
 
@@ -492,10 +507,21 @@ def test_c5_time_shards_sum_to_the_whole():
         c_sum += c; g_sum += g; blocks += part.num_blocks
     assert blocks == whole.num_blocks
     assert abs(c_sum - c_all) <= 1e-11 * c_all and rel_err(g_sum, g_all) < 1e-10
+    idx = np.arange(len(g_all))
+    diag = whole.trajectory_.EvaluateEntries(FLAGS1, idx, idx)
+    d = np.sqrt(diag)                       # every gradient entry on its own scale d_i sqrt(2 cost)
+    ok = (d > 0) & ~NER.weak_from_diagonal(diag, NER.column_kinds(whole.trajectory_.GetTangentLayout(FLAGS1)))
+    assert not g_sum[d == 0].any() and not g_all[d == 0].any()
+    eg = (np.abs(g_sum - g_all)[ok] / (d[ok] * np.sqrt(2 * c_all))).max()
+    print("entry-wise: g %.2e" % eg)
+    assert eg < 1e-10, eg
     # ... and the whole against the CPU oracle (forward-mode Jets, 410 000 residual blocks, P ~ 90 k): cost and gradient
     cpu = E.ImuCameraCalibrator(backend=oracle_backend.load()).BatchInitSpline(ds)
     c_cpu, _, g_cpu = cpu.trajectory_.Evaluate(FLAGS1, want_H=False)
     assert g_cpu.shape == g_all.shape and abs(c_all - c_cpu) <= 1e-10 * c_cpu and rel_err(g_all, g_cpu) < 1e-10
+    eg = (np.abs(g_all - g_cpu)[ok] / (d[ok] * np.sqrt(2 * c_cpu))).max()
+    print("entry-wise: g %.2e" % eg)
+    assert eg < 1e-10, eg
     s = whole.trajectory_.Optimize(1, FLAGS1)
     assert s["num_successful_steps"] == 1 and s["final_cost"] < 0.5 * s["initial_cost"] and s["band_dim"] > 85000
     # at this size the segment tables come once per parameter vector (written by the retraction kernel for the candidate);
@@ -578,7 +604,10 @@ def test_assembly_modes_match_the_oracle(tiny, mode, tile_windows, wide):
         cg, Hg, gg = gpu.trajectory_.Evaluate(flags); cc, Hc, gc = cpu.trajectory_.Evaluate(flags)
         assert abs(cg - cc) <= 1e-11 * cc, (flags, cg, cc)
         assert rel_err(Hg, Hc) < 1e-10 and rel_err(gg, gc) < 1e-10, (flags, rel_err(Hg, Hc), rel_err(gg, gc))
+        eh, eg = entry_err(gpu.trajectory_, flags, Hg, Hc, gg, gc, cc)
+        assert eh < 1e-10 and eg < 1e-10, (flags, eh, eg)
         assert np.abs(Hg - Hg.T).max() <= 1e-13 * np.abs(Hg).max()
+        assert NER.symmetry_error(Hg, Hc) <= 1e-13
         assert abs(gpu.trajectory_.EvaluateCost(flags) - cc) <= 1e-11 * cc
 
 
@@ -590,6 +619,8 @@ def test_tiles_are_run_to_run_reproducible_up_to_lds_order():
     c0, H0, g0 = gpu.trajectory_.Evaluate(FLAGS1)
     c1, H1, g1 = gpu.trajectory_.Evaluate(FLAGS1)
     assert abs(c0 - c1) <= 1e-14 * c0 and rel_err(H1, H0) < 1e-14 and rel_err(g1, g0) < 1e-13
+    eh, eg = entry_err(gpu.trajectory_, FLAGS1, H1, H0, g1, g0, c0)
+    assert eh < 1e-14 and eg < 1e-13, (eh, eg)
 
 
 @pytest.mark.parametrize("cfg,flags,chain", [("C2", FLAGS1, 0), ("C2", FLAGS1 | E.IMU_BIASES, 4), ("C3", FLAGS1, 3)])
@@ -611,6 +642,8 @@ def test_deterministic_accumulation_is_bit_identical(cfg, flags, chain):
     d = E.ImuCameraCalibrator().BatchInitSpline(ds)
     cd, Hd, gd = d.trajectory_.Evaluate(flags)
     assert abs(cd - c0) <= 1e-13 * c0 and rel_err(Hd, H0) < 1e-13 and rel_err(gd, g0) < 1e-12
+    eh, eg = entry_err(d.trajectory_, flags, Hd, H0, gd, g0, c0)
+    assert eh < 1e-13 and eg < 1e-12, (eh, eg)
 
 
 @pytest.mark.parametrize("cfg,chain,tile_windows", [("C2", 3, 0), ("C2", 7, 4), ("C3", 2, 0), ("C3", 25, 0), ("C1", 100, 2)])
@@ -627,6 +660,10 @@ def test_chains_of_tiles_equal_single_tiles(cfg, chain, tile_windows):
     ca, Ha, ga = a.trajectory_.Evaluate(FLAGS1); cb, Hb, gb = b.trajectory_.Evaluate(FLAGS1); cc, Hc, gc = c.trajectory_.Evaluate(FLAGS1)
     assert abs(ca - cb) <= 1e-13 * cb and rel_err(Ha, Hb) < 1e-13 and rel_err(ga, gb) < 1e-12
     assert abs(ca - cc) <= 1e-12 * cc and rel_err(Ha, Hc) < 1e-12 and rel_err(ga, gc) < 1e-11
+    eh, eg = entry_err(a.trajectory_, FLAGS1, Ha, Hb, ga, gb, cb)
+    assert eh < 1e-13 and eg < 1e-12, (eh, eg)
+    eh, eg = entry_err(a.trajectory_, FLAGS1, Ha, Hc, ga, gc, cc)
+    assert eh < 1e-12 and eg < 1e-11, (eh, eg)
     assert abs(a.trajectory_.EvaluateCost(FLAGS1) - ca) <= 1e-13 * ca      # the cost-only pass walks the same chains
     sa = a.trajectory_.Optimize(8, FLAGS1); sb = b.trajectory_.Optimize(8, FLAGS1)
     assert sa["num_iterations"] == sb["num_iterations"] and abs(sa["final_cost"] - sb["final_cost"]) <= 1e-9 * sb["final_cost"]
@@ -658,11 +695,15 @@ def test_interior_rows_stored_by_the_tile_equal_the_slab_route(cfg, tile_windows
     b.trajectory_.SetOption("debug_no_direct_rows", 1)
     ca, Ha, ga = a.trajectory_.Evaluate(flags); cb, Hb, gb = b.trajectory_.Evaluate(flags)
     assert abs(ca - cb) <= 1e-14 * cb and rel_err(Ha, Hb) < 1e-13 and rel_err(ga, gb) < 1e-12
+    eh, eg = entry_err(a.trajectory_, flags, Ha, Hb, ga, gb, cb)
+    assert eh < 1e-13 and eg < 1e-12, (eh, eg)
     assert np.abs(Ha - Ha.T).max() <= 1e-13 * np.abs(Ha).max()
     cpu = E.ImuCameraCalibrator(backend=oracle_backend.load()).BatchInitSpline(ds)
     cpu.trajectory_.SetOption("analytic_jacobians", 0)   # forward-mode Jets: none of the product's closed forms on the checker's side
     cc, Hc, gc = cpu.trajectory_.Evaluate(flags)
     assert abs(ca - cc) <= 1e-11 * cc and rel_err(Ha, Hc) < 1e-10 and rel_err(ga, gc) < 1e-10
+    eh, eg = entry_err(a.trajectory_, flags, Ha, Hc, ga, gc, cc)
+    assert eh < 1e-10 and eg < 1e-10 and NER.symmetry_error(Ha, Hc) <= 1e-13, (eh, eg)
     sa = a.trajectory_.Optimize(6, flags); sb = b.trajectory_.Optimize(6, flags)
     assert sa["num_iterations"] == sb["num_iterations"] and abs(sa["final_cost"] - sb["final_cost"]) <= 1e-9 * sb["final_cost"]
 
@@ -1296,10 +1337,14 @@ def test_measurements_added_out_of_time_order():
         assert (np.abs(Jg - Jc) / scale).max() < 1e-8, kind
     cg, Hg, gg = gpu.trajectory_.Evaluate(FLAGS1); cc, Hc, gc = cpu.trajectory_.Evaluate(FLAGS1)
     assert abs(cg - cc) <= 1e-11 * cc and rel_err(gg, gc) < 1e-10 and rel_err(Hg, Hc) < 1e-10
+    eh, eg = entry_err(gpu.trajectory_, FLAGS1, Hg, Hc, gg, gc, cc)
+    assert eh < 1e-10 and eg < 1e-10, (eh, eg)
     # ... and equal to the time-ordered problem's
     ref = E.ImuCameraCalibrator().BatchInitSpline(ds)
     cr, Hr, gr = ref.trajectory_.Evaluate(FLAGS1)
     assert abs(cg - cr) <= 1e-12 * cr and rel_err(Hg, Hr) < 1e-12
+    eh, eg = entry_err(gpu.trajectory_, FLAGS1, Hg, Hr, gg, gr, cr)
+    assert eh < 1e-12 and eg < 1e-12, (eh, eg)
     for c in (gpu, cpu, ref):
         c.trajectory_.UseReferenceSolverOptions()
     sg = gpu.trajectory_.Optimize(50, FLAGS1); sc = cpu.trajectory_.Optimize(50, FLAGS1); sr = ref.trajectory_.Optimize(50, FLAGS1)
