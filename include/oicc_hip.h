@@ -705,6 +705,16 @@ int oicc_planar_ransac(int32_t device_ordinal, int32_t num_views, const int64_t*
                        int32_t mode, double threshold, int32_t num_hypotheses, uint64_t seed, uint8_t* inlier,
                        int32_t* num_inliers, double* q, double* pose, int32_t* hypothesis_counts, double* device_ms);
 
+/* ---- the elimination plan of the block cyclic reduction (kernels_bcr.hip), host arithmetic only: needs no device ----------
+ * The damped LM system of n 64-column blocks is reduced level by level.  Level l: the active blocks are origin + k stride,
+ * k < active; those with k mod 2 == parity are its pivots (parity 0 when `active` is odd -- both ends are pivots --, else 1;
+ * odd_only != 0: parity 1 at every level, the order of the distributed reduction; ghost != 0: that reduction's extra right
+ * neighbour, one more coupling per level).  levels [cap_levels][6] = origin, stride, parity, active, pivots, first slot of
+ * the level's couplings (active - 1 + ghost of them, slot + k: active blocks k and k + 1); info[3] = the block that is
+ * left at the end, the slot behind the last level's couplings, the slots the solver's workspace reserves.
+ * Returns the number of levels (= inversions in sequence - 1), OICC_ERR_INVALID_ARG for n < 1 or too small a cap_levels. */
+int oicc_debug_bcr_plan(int32_t n, int32_t ghost, int32_t odd_only, int64_t* levels, int32_t cap_levels, int64_t info[3]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -286,6 +286,26 @@ class BoundBoard:
             setattr(self, name, fn)
 
 
+# Elimination plan of the block cyclic reduction (oicc_debug_bcr_plan in include/oicc_hip.h; host arithmetic, no device), a table of
+# its own like ALLAN_SIGNATURES.
+BCR_PLAN_SIGNATURES = {
+    "plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_i64p, C.c_int32, c_i64p]),
+}
+
+
+class BoundBcrPlan:
+    """Bound oicc_debug_bcr_* entry points of one library + prefix (``oicc_debug_bcr_`` for liboicc_hip.so)."""
+
+    def __init__(self, lib, prefix):
+        self.lib = lib
+        self.prefix = prefix
+        for name, (res, args) in BCR_PLAN_SIGNATURES.items():
+            fn = getattr(lib, prefix + name)  # AttributeError = missing symbol: fail loudly
+            fn.restype = res
+            fn.argtypes = args
+            setattr(self, name, fn)
+
+
 # Robust start poses (oicc_planar_ransac in include/oicc_hip.h), a table of its own like ALLAN_SIGNATURES: SIGNATURES and
 # BA_SIGNATURES are also bound against the CPU checker, which has no counterpart of this entry.
 PLANAR_RANSAC_SIGNATURES = {

@@ -7,7 +7,7 @@ fails when no HIP device is usable.
 import ctypes
 import os
 
-from ._abi import Bound, BoundAllan, BoundBa, BoundBoard, BoundPlanarRansac, BoundStaticImu
+from ._abi import Bound, BoundAllan, BoundBa, BoundBcrPlan, BoundBoard, BoundPlanarRansac, BoundStaticImu
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OICC_DEV_LIB") or os.path.join(_HERE, "csrc", "liboicc_hip.so")   # OICC_DEV_LIB: another BUILD of the same library (developer A/B timing, scripts/build_variant.sh)
@@ -17,6 +17,7 @@ _bound_allan = None
 _bound_static_imu = None
 _bound_board = None
 _bound_planar_ransac = None
+_bound_bcr_plan = None
 
 
 def load():
@@ -69,3 +70,11 @@ def load_planar_ransac():
     if _bound_planar_ransac is None:
         _bound_planar_ransac = BoundPlanarRansac(load().lib, "oicc_planar_")
     return _bound_planar_ransac
+
+
+def load_bcr_plan():
+    """oicc_debug_bcr_plan (elimination plan of the block cyclic reduction; needs no device) of the same library."""
+    global _bound_bcr_plan
+    if _bound_bcr_plan is None:
+        _bound_bcr_plan = BoundBcrPlan(load().lib, "oicc_debug_bcr_")
+    return _bound_bcr_plan

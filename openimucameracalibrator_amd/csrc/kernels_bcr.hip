@@ -7,12 +7,17 @@
 // columns, which makes it block tridiagonal; the arrow rows (T_i_c, gravity, line delay,
 // biases, intrinsics) and the right-hand side ride along as dense border rows.
 //
-//   level l (stride s = 2^l): the active blocks are 0, s, 2s, ...; every block at an ODD
-//   position is a pivot, all pivots of a level are eliminated concurrently, THROUGH THE EXPLICIT INVERSE of the pivot's 64 x 64
-//   diagonal block (round 3): only that block is factored in one workgroup, the pivot's border rows become matrix products on
-//   other CUs and the back substitution a matrix-vector product (bcri_* kernels below).
-//   After ceil(log2 n) levels block 0 is alone: its workgroup also factors the arrow
-//   corner, solves it and starts the back substitution, which then runs two levels per launch in reverse.
+//   level l (stride s = 2^l): the active blocks are o, o + s, o + 2 s, ... (m of them); an ODD m makes every block at an EVEN
+//   position a pivot -- both ends included: ceil(m / 2) pivots, an independent set of the chain --, an even m every block at an odd
+//   position (bcr_plan below; origin, stride and parity reach the kernels as launch arguments).  All pivots of a level are eliminated
+//   concurrently, THROUGH THE EXPLICIT INVERSE of the pivot's 64 x 64 diagonal block (round 3): only that block is factored in one
+//   workgroup, the pivot's border rows become matrix products on other CUs and the back substitution a matrix-vector product
+//   (bcri_* kernels below).  A pivot at an end has one neighbour only: the Schur groups of the missing side leave at once and the
+//   back substitution masks that side's rows of T.
+//   After floor(log2 n) levels one block is alone (block 13 of 29; block 0 when n is a power of two): its workgroup also factors the
+//   arrow corner, solves it and does the back substitution of the top level's one or two pivots, which then runs two levels per
+//   launch in reverse.  (Until the end blocks became pivots only the odd positions were, block 0 stood until the end and the depth
+//   was ceil(log2 n) + 1 inversions: one more whenever n is no power of two.  The distributed reduction keeps that order.)
 //
 // History: rounds 1-2 factored each pivot WITH its 138 + a border rows in one workgroup (solver_algorithm 2) and round 3 added a
 // parallel form of that (algorithm 3: every block a pivot at every level); both stayed in the library as independent solvers
@@ -24,6 +29,7 @@
 #include "oicc_device.h"
 #include "lm_decide.h"
 #include "lm_launch.h"
+#include "../../include/oicc_hip.h"
 
 namespace oicc {
 
@@ -39,9 +45,20 @@ struct BcrArgs {
   long long* prof;   // optional cycle counters of block 0 / wave 0 (debug)
   int n, a, Pb, rtf, LD;
   int delay;                   // debug: panel waves > 0 sleep this many x ~1000 cycles before they read a panel (makes that hazard deterministic)
-  int s;                       // stride of this level
+  // This level of the plan (bcr_plan): the active blocks are o + k s, k < m; block k is a pivot iff k mod 2 == p.  The couplings the
+  // level writes are stored pivot major for the NEXT level, whose parity is pn.  The plan travels in the kernel arguments: a table
+  // on the device would put a dependent global load at the head of every launch of a solve.
+  int o, s, p, m, pn;
   int64_t offS_in, offS_out;   // first coupling of this level / of the next one
-  int top;                     // bcri_invert_kernel<LAST>: the one pivot of the top level (> 0), whose back substitution block 0's workgroup does as well
+  int carry;                   // distributed reduction: m if the last active block is no pivot at this level (its coupling to the ghost block moves on), else 0
+  int last;                    // bcri_invert_kernel<LAST>: the block that is left when every level is done
+  // A top level of two pivots (three active blocks): both update the last block's D, F and the corner, and two atomic additions
+  // land in either order.  With side != 0 the pivot left of the last block writes its updates with plain stores into the factor rows
+  // of the last block (never a pivot: [D part 64*64 | F part 64*a1 | corner part a1*a1] fits its (192 + a1) * 64 doubles) and the
+  // last block's workgroup adds them when it loads: a solve of three blocks stays reproducible bit by bit, as it was when every
+  // level of it had one pivot.
+  int side;
+  int top_l, top_r;            // bcri_invert_kernel<LAST>: the pivots of the top level left / right of `last` (-1: none), whose back substitution that workgroup does as well
   // Distributed reduction (round 6, launch_bcr_dist_*): this system is the block range [b0, b0 + n) of a longer band.  `ghost`: the
   // range has a right neighbour outside -- the first block of the next rank's range -- which is never a pivot here: it sits at
   // storage index n (D, F start at zero and collect this range's Schur updates for its owner; x holds its solution for the back
@@ -167,7 +184,6 @@ __device__ __forceinline__ void bcr_corner_solve(double* C, double* da, int* fai
 //                        the neighbours, their coupling, the arrow rows and the corner
 //   bcri_backward_kernel x_i = T_rhs - T_left^T x_il - T_right^T x_ir - T_arrow^T x_arrow: a matrix-vector product, no
 //                        triangular solve on the way back
-// Block 0 after the last level still goes through bcr_eliminate_kernel<LD, 1> (factor + corner + its back substitution).
 // Error: forward errors of B D^-1 B^T through the explicit inverse and through the Cholesky factor are both
 // O(cond(D_i) eps); the LM tests hold both to the oracle's steps.
 // =====================================================================================================================
@@ -195,11 +211,11 @@ __device__ __forceinline__ bcr_v4d bcri_z_tile(const double* W, int yt, int li, 
   return g;   // g[r] <-> (x row 16 XT + li, y row 16 yt + lq + 4 r)
 }
 
-// What follows the factorisation of [D_i ; I] (all waves, after a workgroup barrier): Z = X X^T, and for block 0 (LAST) the arrow
+// What follows the factorisation of [D_i ; I] (all waves, after a workgroup barrier): Z = X X^T, and for the last block (LAST) the arrow
 // corner and the first back substitution.
 template <bool LAST>
 __device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* da, int* failp, const double* Fs, double* Zg, int tid, int wave, int lane, bool report,
-                                          const double (&ttop)[12], const double ytop, double* x0s) {
+                                          const double (&ttop)[16], const double ytop, double* x0s) {
   constexpr int LD = kInvLD, NW = kInvWaves, NT = 64 * NW, FLD = 65;
   const int li = lane & 15, lq = lane >> 4;
   const int a = A.a, a1 = a + 1;
@@ -251,9 +267,10 @@ __device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* d
 #pragma unroll
     for (int kk = 0; kk < 16; ++kk) g = __builtin_amdgcn_mfma_f64_16x16x4f64(vf[kk], vt[kk], g, 0, 0, 0);
     // g[r] <-> (row q1 = 16 t1 + li, column q2 = 16 t2 + lq + 4 r)
+    const double* Sm = A.side != 0 ? A.Lf + (int64_t)A.last * (192 + a1) * 64 + 4096 + 64 * a1 : nullptr;   // (BcrArgs::side: the corner part)
     double mc[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { const int q1 = 16 * t1 + li, q2 = 16 * t2 + lq + 4 * r; mc[r] = (q1 < a1 && q2 < a1) ? A.Mc[q1 * a1 + q2] : 0.0; }
+    for (int r = 0; r < 4; ++r) { const int q1 = 16 * t1 + li, q2 = 16 * t2 + lq + 4 * r; mc[r] = (q1 < a1 && q2 < a1) ? A.Mc[q1 * a1 + q2] + (Sm != nullptr ? Sm[q1 * a1 + q2] : 0.0) : 0.0; }
 #pragma unroll
     for (int r = 0; r < 4; ++r) { const int q1 = 16 * t1 + li, q2 = 16 * t2 + lq + 4 * r; if (q1 < a1 && q2 < a1) W[q2 * LD + q1] = mc[r] - g[r]; }
   }
@@ -270,36 +287,40 @@ __device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* d
 #pragma unroll
       for (int k = 0; k < 8; ++k) v = fma(-t8[k], d8[k], v);
     }
-    if (lane < A.Pb) A.x[lane] = v;
-    x0s[lane] = lane < A.Pb ? v : 0.0;
+    const int gi = A.last * 64 + lane;
+    if (gi < A.Pb) A.x[gi] = v;
+    x0s[lane] = gi < A.Pb ? v : 0.0;
   }
   __syncthreads();
   if (tid == 0 && *failp) atomicOr(A.fail, 1);
-  if (A.top > 0) {
-    // the one pivot of the top level (left neighbour block 0, no right neighbour): x = T_rhs - T_left^T x_0 - T_arrow^T x_arrow;
-    // its rows of T were loaded when the kernel started
-    double sum = 0.0;
+  if (A.top_l >= 0 || A.top_r >= 0) {
+    // the pivots of the top level (one: right of the last block; two: the ends of three active blocks), whose only neighbour is the
+    // last block: x = T_rhs - T_nb^T x_last - T_arrow^T x_arrow; their rows of T were loaded when the kernel started
+    double sum_r = 0.0, sum_l = 0.0;
 #pragma unroll
-    for (int k = 0; k < 12; ++k) {
+    for (int k = 0; k < 4; ++k) {
       const int r = wave + NW * k;
-      const double xv = r < 64 ? x0s[r] : ((r >= 128 && r < 128 + a) ? da[r - 128] : 0.0);
-      sum = fma(ttop[k], xv, sum);
+      const double xn = x0s[r], xa = r < a ? da[r] : 0.0;
+      sum_r = fma(ttop[k], xn, sum_r);     sum_r = fma(ttop[4 + k], xa, sum_r);
+      sum_l = fma(ttop[8 + k], xn, sum_l); sum_l = fma(ttop[12 + k], xa, sum_l);
     }
-    W[wave * 64 + lane] = sum;            // (W is free: NW x 64 partial sums)
+    W[wave * 64 + lane] = sum_r;            // (W is free: 2 x NW x 64 partial sums)
+    W[(NW + wave) * 64 + lane] = sum_l;
     __syncthreads();
-    if (wave == 0) {
+    if (wave < 2) {
+      const int blk = wave == 0 ? A.top_r : A.top_l;
       double acc = 0.0;
 #pragma unroll
-      for (int w = 0; w < NW; ++w) acc += W[w * 64 + lane];
-      const int gi = A.top * 64 + lane;
-      if (gi < A.Pb) A.x[gi] = ytop - acc;
+      for (int w = 0; w < NW; ++w) acc += W[(wave * NW + w) * 64 + lane];
+      const int gi = blk * 64 + lane;
+      if (blk >= 0 && gi < A.Pb) A.x[gi] = ytop - acc;
     }
   }
 }
 
 
-// LAST: block 0 after the last level -- the inverse stays in LDS, T = F_0 Z, the arrow corner minus T F_0^T, its solution and
-// x_0 = T_rhs - T_arrow^T x_arrow, all in this workgroup
+// LAST: the block left after the last level -- the inverse stays in LDS, T = F Z, the arrow corner minus T F^T, its solution and
+// x = T_rhs - T_arrow^T x_arrow, all in this workgroup
 template <bool LAST, bool PROF, class LoadD>
 __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, LoadD load_d, const bool report = true) {
   constexpr int LD = kInvLD, NW = kInvWaves, NT = 64 * NW, NTILE = 20, SLOTS = (NTILE + NW - 1) / NW, RU = 128, NAW = 3, FLD = 65;
@@ -315,19 +336,30 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
   double* const Fs = dg + 256;           // LAST: [64][FLD] border rows of block 0, Fs[k * FLD + q]
   const int a1 = A.a + 1;
   double* Zg = A.Lf + (int64_t)i * (192 + a1) * 64;
+  const double* Fg = A.F + (int64_t)i * 64 * a1;
+  const double* Sf = (LAST && A.side != 0) ? Zg + 4096 : nullptr;   // (BcrArgs::side: the F part)
   const bool prof = PROF && A.prof != nullptr && blockIdx.x == 0 && wave == 0;
   long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   long long tprev = prof ? clock64() : 0;
 #define BCR_MARK(k) do { if (PROF && prof) { const long long tn_ = clock64(); pc[k] += tn_ - tprev; tprev = tn_; } } while (0)
   if (tid == 0) *failp = 0;
-  double ttop[12], ytop = 0.0;
+  // rows of T of the top level's pivots: [0..4) the rows against the last block and [4..8) the arrow rows of the pivot right of it
+  // (whose left neighbour it is: rows 0..63 of T), [8..16) the same of the pivot left of it (rows 64..127); wave 0 / 1 their rhs row
+  double ttop[16], ytop = 0.0;
 #pragma unroll
-  for (int k = 0; k < 12; ++k) ttop[k] = 0.0;
-  if (LAST && A.top > 0) {
-    const double* Tt = A.Lf + (int64_t)A.top * (192 + a1) * 64 + 4096;
+  for (int k = 0; k < 16; ++k) ttop[k] = 0.0;
+  if (LAST && (A.top_l >= 0 || A.top_r >= 0)) {
+    const int64_t ru64 = (int64_t)(192 + a1) * 64;
+    const double* Tr = A.Lf + (A.top_r >= 0 ? A.top_r : 0) * ru64 + 4096;
+    const double* Tl = A.Lf + (A.top_l >= 0 ? A.top_l : 0) * ru64 + 4096;
 #pragma unroll
-    for (int k = 0; k < 12; ++k) { const int r = wave + NW * k; if (r < 64 || (r >= 128 && r < 128 + A.a)) ttop[k] = Tt[r * 64 + lane]; }
-    if (wave == 0) ytop = Tt[(128 + A.a) * 64 + lane];
+    for (int k = 0; k < 4; ++k) {
+      const int r = wave + NW * k;
+      if (A.top_r >= 0) { ttop[k] = Tr[r * 64 + lane]; if (r < A.a) ttop[4 + k] = Tr[(128 + r) * 64 + lane]; }
+      if (A.top_l >= 0) { ttop[8 + k] = Tl[(64 + r) * 64 + lane]; if (r < A.a) ttop[12 + k] = Tl[(128 + r) * 64 + lane]; }
+    }
+    if (wave == 0 && A.top_r >= 0) ytop = Tr[(128 + A.a) * 64 + lane];
+    if (wave == 1 && A.top_l >= 0) ytop = Tl[(128 + A.a) * 64 + lane];
     asm volatile("" ::: "memory");   // (issued here, used after the corner: the loads must not sink to their use)
   }
   {
@@ -337,7 +369,7 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
     for (int k = 0; k < PER; ++k) {
       const int e = tid + k * NT;
       gd[k] = load_d(e);
-      if (LAST) { const int c = e >> 6, q = e & 63; gf[k] = q < a1 ? A.F[c * a1 + q] : 0.0; }
+      if (LAST) { const int c = e >> 6, q = e & 63; gf[k] = q < a1 ? Fg[c * a1 + q] + (Sf != nullptr ? Sf[c * a1 + q] : 0.0) : 0.0; }
     }
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
@@ -445,9 +477,10 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
 template <bool LAST, bool PROF>
 __global__ __launch_bounds__(64 * kInvWaves) void bcri_invert_kernel(BcrArgs A) {
   BCR_RETURN_IF_DONE(A);
-  const int i = LAST ? 0 : A.s * (2 * (int)blockIdx.x + 1);
+  const int i = LAST ? A.last : A.o + A.s * (2 * (int)blockIdx.x + A.p);
   const double* Dg = A.D + (int64_t)i * 4096;
-  bcri_invert_body<LAST, PROF>(A, i, [Dg](int e) { return Dg[e]; });
+  const double* Sd = (LAST && A.side != 0) ? A.Lf + (int64_t)i * (192 + A.a + 1) * 64 : nullptr;   // (BcrArgs::side)
+  bcri_invert_body<LAST, PROF>(A, i, [Dg, Sd](int e) { double v = Dg[e]; if (LAST && Sd != nullptr && (e & 63) >= (e >> 6)) v += Sd[e]; return v; });
 }
 
 // one workgroup (4 waves) per (pivot, 16-row tile x of the border rows, group of up to four column tiles y)
@@ -458,27 +491,30 @@ __global__ __launch_bounds__(256) void bcri_schur_kernel(BcrArgs A) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lq = lane >> 4;
   const int a1 = A.a + 1, rtf = A.rtf, s = A.s;
-  if ((int)blockIdx.y == (int)gridDim.y - 1 && A.top < 0) {
+  if ((int)blockIdx.y == (int)gridDim.y - 1 && A.carry > 0) {
     // distributed reduction, odd number of active blocks: the last one is no pivot at this level, its coupling to the ghost block
     // moves on to the next level's table unchanged (the workgroups of this extra row of the grid copy it)
-    const int m = -A.top;
+    const int m = A.carry;
     const double* src = A.S + (A.offS_in + (m - 1)) * 4096; double* dst = A.S + (A.offS_out + (m - 1) / 2) * 4096;
     for (int e = (int)blockIdx.x * 256 + tid; e < 4096; e += (int)gridDim.x * 256) dst[e] = src[e];
     return;
   }
-  const int i = s * (2 * (int)blockIdx.y + 1), il = i - s, ir = i + s;
-  const bool ghostR = A.ghost != 0 && ir >= A.n;    // the right neighbour is the next rank's first block
-  const bool hasR = ir < A.n || ghostR;             // (a pivot always has its left neighbour)
-  const int irs = ir < A.n ? ir : A.n;              // where the right neighbour's D / F live
+  const int k = 2 * (int)blockIdx.y + A.p;          // position among the active blocks
+  const int i = A.o + k * s, il = i - s, ir = i + s;
+  const bool hasL = k > 0;                          // (a pivot at position 0 -- odd number of active blocks -- has no left neighbour)
+  const bool ghostR = A.ghost != 0 && k == A.m - 1; // the right neighbour is the next rank's first block
+  const bool hasR = k < A.m - 1 || ghostR;
+  const int irs = ghostR ? A.n : ir;                // where the right neighbour's D / F live
   // group -> row tile (kind xk: 0 left, 1 right, 2 arrow rows / rhs; index xt), column tiles (kind yk, ny of them), and who stores T
   int g = (int)blockIdx.x, xk, xt, yk, ny; bool store_t;
   if (g < 4) { xk = 0; xt = g; yk = 0; ny = g + 1; store_t = true; }
   else if (g < 8) { xk = 1; xt = g - 4; yk = 0; ny = 4; store_t = false; }
   else if (g < 12) { xk = 1; xt = g - 8; yk = 1; ny = xt + 1; store_t = true; }
-  else { g -= 12; yk = g / rtf; xt = g - yk * rtf; xk = 2; ny = yk < 2 ? 4 : xt + 1; store_t = yk == 0; }
+  else { g -= 12; yk = g / rtf; xt = g - yk * rtf; xk = 2; ny = yk < 2 ? 4 : xt + 1; store_t = yk == (hasL ? 0 : 1); }   // (the arrow rows of T: once per pivot)
   if ((xk == 1 || yk == 1) && !hasR) return;
-  const double* SL = A.S + (A.offS_in + il / s) * 4096;
-  const double* SR = A.S + (A.offS_in + i / s) * 4096;
+  if ((xk == 0 || yk == 0) && !hasL) return;
+  const double* SL = A.S + (A.offS_in + (hasL ? k - 1 : 0)) * 4096;
+  const double* SR = A.S + (A.offS_in + k) * 4096;
   const double* Fg = A.F + (int64_t)i * 64 * a1;
   double* Zg = A.Lf + (int64_t)i * (192 + a1) * 64;
   double* Tg = Zg + 4096;
@@ -517,8 +553,9 @@ __global__ __launch_bounds__(256) void bcri_schur_kernel(BcrArgs A) {
   __syncthreads();
   if (wave >= ny) return;
   const int yt = wave;
-  // orientation of the new coupling (il, ir): the pivot of the next level is the one at an odd position
-  const bool il_is_pivot = ((il / (2 * s)) & 1) != 0;
+  // orientation of the new coupling (il, ir): il is at position kn of the next level, whose pivots have parity pn
+  const int kn = hasL ? (k - 2 + A.p) / 2 : 0;
+  const bool il_is_pivot = (kn & 1) == A.pn;
   const bool swap = xk == 1 && yk == 0 && !il_is_pivot && !ghostR;
   double vt[16];
 #pragma unroll
@@ -540,9 +577,13 @@ __global__ __launch_bounds__(256) void bcri_schur_kernel(BcrArgs A) {
   }
   gq += gq2;
   // not swapped: gq[r] <-> (x row li, y row lq + 4 r); swapped: (y row li, x row lq + 4 r)
-  double* Dl = A.D + (int64_t)il * 4096; double* Dr = A.D + (int64_t)irs * 4096;
-  double* Fl = A.F + (int64_t)il * 64 * a1; double* Fr = A.F + (int64_t)irs * 64 * a1;
-  double* So = A.S + (A.offS_out + il / (2 * s)) * 4096;
+  const int ils = hasL ? il : i;
+  double* Dl = A.D + (int64_t)ils * 4096; double* Dr = A.D + (int64_t)irs * 4096;
+  double* Fl = A.F + (int64_t)ils * 64 * a1; double* Fr = A.F + (int64_t)irs * 64 * a1;
+  double* So = A.S + (A.offS_out + kn) * 4096;
+  // (two-pivot top level: the updates of the pivot left of the last block go to the side buffer, see BcrArgs::side)
+  const bool to_side = A.side != 0 && !hasL;
+  double* Sd = A.Lf + (int64_t)irs * (192 + a1) * 64;
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const double v = -gq[r];
@@ -551,13 +592,16 @@ __global__ __launch_bounds__(256) void bcri_schur_kernel(BcrArgs A) {
       else       { const int y = 16 * yt + li, x = 16 * xt + lq + 4 * r; So[x * 64 + y] = v; }    // Q[c = ir var][r = il var]
     } else if (xk < 2) {
       const int x = 16 * xt + li, y = 16 * yt + lq + 4 * r;
-      if (x >= y && v != 0.0) unsafeAtomicAdd((xk == 0 ? Dl : Dr) + y * 64 + x, v);
+      if (to_side) { if (x >= y) Sd[y * 64 + x] = v; }
+      else if (x >= y && v != 0.0) unsafeAtomicAdd((xk == 0 ? Dl : Dr) + y * 64 + x, v);
     } else if (yk < 2) {
       const int q = 16 * xt + li, y = 16 * yt + lq + 4 * r;
-      if (q < a1 && v != 0.0) unsafeAtomicAdd((yk == 0 ? Fl : Fr) + y * a1 + q, v);
+      if (to_side) { if (q < a1) Sd[4096 + y * a1 + q] = v; }
+      else if (q < a1 && v != 0.0) unsafeAtomicAdd((yk == 0 ? Fl : Fr) + y * a1 + q, v);
     } else {
       const int q1 = 16 * xt + li, q2 = 16 * yt + lq + 4 * r;
-      if (q1 < a1 && q2 <= q1 && v != 0.0) {
+      if (to_side) { if (q1 < a1 && q2 <= q1) { Sd[4096 + 64 * a1 + q1 * a1 + q2] = v; Sd[4096 + 64 * a1 + q2 * a1 + q1] = v; } }
+      else if (q1 < a1 && q2 <= q1 && v != 0.0) {
         unsafeAtomicAdd(A.Mc + q1 * a1 + q2, v);
         if (q1 != q2) unsafeAtomicAdd(A.Mc + q2 * a1 + q1, v);
       }
@@ -573,21 +617,23 @@ __global__ __launch_bounds__(64 * kBackWaves) void bcri_backward_kernel(BcrArgs 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int a = A.a, a1 = a + 1, s = A.s;
-  const int i = s * (2 * (int)blockIdx.x + 1), il = i - s;
-  const bool hasR = i + s < A.n || A.ghost != 0;
-  const int ir = i + s < A.n ? i + s : A.n;         // (distributed reduction: the ghost block's solution sits behind the local blocks)
+  const int kp = 2 * (int)blockIdx.x + A.p;         // position among the active blocks
+  const int i = A.o + kp * s, il = i - s;
+  const bool hasL = kp > 0;
+  const bool hasR = kp < A.m - 1 || A.ghost != 0;
+  const int ir = kp < A.m - 1 ? i + s : A.n;        // (distributed reduction: the ghost block's solution sits behind the local blocks)
   const double* Tg = A.Lf + (int64_t)i * (192 + a1) * 64 + 4096;
   constexpr int RW = 192 / kBackWaves;
   double lv[RW];
 #pragma unroll
   for (int k = 0; k < RW; ++k) {
     const int r = wave + kBackWaves * k;
-    const bool ok = r < 128 + a && (hasR || r < 64 || r >= 128);
+    const bool ok = r < 128 + a && (hasL || r >= 64) && (hasR || r < 64 || r >= 128);
     lv[k] = ok ? Tg[r * 64 + lane] : 0.0;
   }
   const double yv = wave == 0 ? Tg[(128 + a) * 64 + lane] : 0.0;
   double xin = 0.0;
-  if (tid < 64) { const int gi = il * 64 + tid; xin = gi < A.Pb ? A.x[gi] : 0.0; }
+  if (tid < 64) { const int gi = il * 64 + tid; xin = (hasL && gi < A.Pb) ? A.x[gi] : 0.0; }
   else if (tid < 128) { const int gi = ir * 64 + (tid - 64); xin = (hasR && gi < A.Pb) ? A.x[gi] : 0.0; }
   else if (tid < 128 + a) xin = A.x[A.Pb + (tid - 128)];
   if (tid < 192) xs[tid] = xin;
@@ -608,9 +654,11 @@ __global__ __launch_bounds__(64 * kBackWaves) void bcri_backward_kernel(BcrArgs 
 
 // Two levels of the back substitution in one launch: a workgroup takes a pivot j of the upper level (stride 2 s) and then, eight
 // waves each, its two neighbours j - s and j + s, which are pivots of the lower level (stride s) and need x_j -- it stays in LDS.
-// Every row of T the three products read is in flight before the first barrier.  A lower pivot whose upper neighbour lies beyond
-// the last block (at most one) gets a workgroup of its own behind the others.
-__global__ __launch_bounds__(1024) void bcri_backward2_kernel(BcrArgs A, int npiv_upper, int orphan) {
+// Every row of T the three products read is in flight before the first barrier.  A (the plan fields o, s, p, m) describes the lower
+// level; ou, pu, mu the upper one.  An upper pivot at an end may lack the child on that side.  An orphan -- a lower pivot at an end of
+// the active blocks whose only neighbour is no pivot of the upper level (at most one per end) -- gets a workgroup of its own behind
+// the others: orphan_l / orphan_r, its block, or -1.
+__global__ __launch_bounds__(1024) void bcri_backward2_kernel(BcrArgs A, int ou, int pu, int mu, int npiv_upper, int orphan_l, int orphan_r) {
   BCR_RETURN_IF_DONE(A);
   constexpr int NW = 16, RW1 = 192 / NW, RW2 = 192 / (NW / 2);
   __shared__ double xs[4][64];            // x of j - 2 s, j, j + 2 s, the arrow part
@@ -619,38 +667,45 @@ __global__ __launch_bounds__(1024) void bcri_backward2_kernel(BcrArgs A, int npi
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int a = A.a, a1 = a + 1, s = A.s, n = A.n;
   const int64_t ru64 = (int64_t)(192 + a1) * 64;
-  const bool lone = (int)blockIdx.x >= npiv_upper;                  // the orphan: only a "left child", its right neighbour does not exist
-  const int j = lone ? orphan + s : 2 * s * (2 * (int)blockIdx.x + 1);
+  // an orphan's workgroup stands where the missing upper pivot j would be: right of the left-end orphan (its "right child"), left
+  // of the right-end one (its "left child")
+  const int lone_ix = (int)blockIdx.x - npiv_upper;
+  const bool lone = lone_ix >= 0;
+  const bool lone_l = lone && orphan_l >= 0 && lone_ix == 0, lone_r = lone && !lone_l;
+  const int ku = 2 * (int)blockIdx.x + pu;                          // position of j among the upper level's active blocks
+  const int j = lone_l ? orphan_l - s : (lone_r ? orphan_r + s : ou + ku * 2 * s);
   const int jl = j - 2 * s, jr = j + 2 * s;
   // (distributed reduction: a right neighbour beyond the local blocks is the ghost block, whose solution sits behind them)
   const bool ghost = A.ghost != 0;
-  const bool has_jr = !lone && (jr < n || ghost);
-  const int jrs = jr < n ? jr : n;
+  const bool has_jl = lone_r || (!lone && ku > 0);
+  const bool has_jr = lone_l || (!lone && (ku < mu - 1 || ghost));
+  const int jrs = (!lone && ku == mu - 1) ? n : jr;
   // lower pivots: half 0 = j - s (neighbours jl, j), half 1 = j + s (neighbours j, jr)
   const int half = wave >> 3, hw = wave & 7;
   const int ci = half == 0 ? j - s : j + s;
-  const bool child = half == 0 ? true : (!lone && ci < n);
-  const bool child_hasR = half == 0 ? (!lone || ghost) : (jr < n || ghost);
+  const bool child = lone ? (half == 0 ? lone_r : lone_l) : (half == 0 ? ci >= A.o : ci <= A.o + (A.m - 1) * s);
+  const bool child_hasL = half == 0 ? has_jl : !lone;
+  const bool child_hasR = half == 0 ? (!lone || ghost) : has_jr;
   auto xin = [&](int blk, int r) { const int gi = blk * 64 + r; return gi < A.Pb ? A.x[gi] : 0.0; };
-  if (tid < 64) xs[0][tid] = xin(jl, tid);
+  if (tid < 64) xs[0][tid] = has_jl ? xin(jl, tid) : 0.0;
   else if (tid < 128) xs[2][tid - 64] = has_jr ? xin(jrs, tid - 64) : 0.0;
   else if (tid < 192) xs[3][tid - 128] = tid - 128 < a ? A.x[A.Pb + (tid - 128)] : 0.0;
-  else if (tid < 256 && lone) xs[1][tid - 192] = ghost ? xin(n, tid - 192) : 0.0;   // (the orphan's right neighbour: none, or the ghost block)
+  else if (tid < 256 && lone) xs[1][tid - 192] = (lone_r && ghost) ? xin(n, tid - 192) : 0.0;   // (in place of x_j: nothing, or the right-end orphan's ghost block)
   double l1[RW1], l2[RW2], y1 = 0.0, y2 = 0.0;
   {
-    const double* T1 = A.Lf + j * ru64 + 4096;
+    const double* T1 = A.Lf + (lone ? 0 : j) * ru64 + 4096;
 #pragma unroll
     for (int k = 0; k < RW1; ++k) {
       const int r = wave + NW * k;
-      const bool ok = !lone && r < 128 + a && (has_jr || r < 64 || r >= 128);
+      const bool ok = !lone && r < 128 + a && (has_jl || r >= 64) && (has_jr || r < 64 || r >= 128);
       l1[k] = ok ? T1[r * 64 + lane] : 0.0;
     }
     if (wave == 0 && !lone) y1 = T1[(128 + a) * 64 + lane];
-    const double* T2 = A.Lf + ci * ru64 + 4096;
+    const double* T2 = A.Lf + (child ? ci : 0) * ru64 + 4096;
 #pragma unroll
     for (int k = 0; k < RW2; ++k) {
       const int r = hw + 8 * k;
-      const bool ok = child && r < 128 + a && (child_hasR || r < 64 || r >= 128);
+      const bool ok = child && r < 128 + a && (child_hasL || r >= 64) && (child_hasR || r < 64 || r >= 128);
       l2[k] = ok ? T2[r * 64 + lane] : 0.0;
     }
     if (hw == 0 && child) y2 = T2[(128 + a) * 64 + lane];
@@ -737,8 +792,8 @@ __device__ __forceinline__ void bcr_build_body(const NormalEq& ne, const Tangent
       A.D[e] = v;
     }
     if (blk < n - 1 || A.ghost != 0) {
-      // coupling (blk, blk+1): the pivot of level 0 is the odd one (the ghost block behind the last local one never is)
-      const bool right = (blk & 1) != 0 || blk == n - 1;     // pivot = blk, neighbour = blk+1 (its right)
+      // coupling (blk, blk+1): the pivot of level 0 is the one of parity A.p (the ghost block behind the last local one never is)
+      const bool right = (blk & 1) == A.p || blk == n - 1;   // pivot = blk, neighbour = blk+1 (its right)
       const int64_t gr = r0 + (int64_t)(blk + 1) * 64 + (right ? r : c);
       const int64_t gc = r0 + (int64_t)blk * 64 + (right ? c : r);
       const int64_t k = gr - gc;
@@ -789,17 +844,17 @@ __global__ void bcr_build_kernel(NormalEq ne, TangentLayout tl, SolveBuffers sb,
 }
 
 // The build and the first level's inversions in ONE launch (cyclic reduction through the inverses): the workgroups of the
-// pivots of level 0 (the odd blocks) take their D_i straight from the band of the normal equations -- same expressions as
+// pivots of level 0 (parity A.p: floor or ceil of n / 2 blocks) take their D_i straight from the band of the normal equations -- same expressions as
 // the build, which still writes every block for the later levels -- while the other workgroups build the system.
 __global__ __launch_bounds__(64 * kInvWaves) void bcri_build_invert_kernel(NormalEq ne, TangentLayout tl, SolveBuffers sb, int reuse_diagonal,
                                                                            double min_diag, double max_diag, BcrArgs A) {
-  if (!lm_ctl_build_inputs(ne, sb, reuse_diagonal, (int)blockIdx.x == A.n / 2 && threadIdx.x == 0)) return;   // (the writer: thread 0 of the first build workgroup, which also resets LmState for this step)
-  const int npiv = A.n / 2;
+  const int npiv = (A.n + 1 - A.p) / 2;
+  if (!lm_ctl_build_inputs(ne, sb, reuse_diagonal, (int)blockIdx.x == npiv && threadIdx.x == 0)) return;   // (the writer: thread 0 of the first build workgroup, which also resets LmState for this step)
   if ((int)blockIdx.x >= npiv) {
     bcr_build_body(ne, tl, sb, reuse_diagonal, min_diag, max_diag, A, (int64_t)((int)blockIdx.x - npiv) * blockDim.x + threadIdx.x, (int64_t)((int)gridDim.x - npiv) * blockDim.x);
     return;
   }
-  const int i = 2 * (int)blockIdx.x + 1;
+  const int i = 2 * (int)blockIdx.x + A.p;
   const int Pb = tl.Pb, Wd = tl.W, hb = tl.hb;
   const double radius = sb.radius;
   const double* band = ne.band();
@@ -836,13 +891,14 @@ static void bcr_allow_lds(const void* fn, size_t bytes) {
 
 static inline int bcr_blocks(int Pb) { return (Pb + 63) / 64; }
 static size_t bcr_lds_inv() { return ((size_t)64 * kInvLD + 64 + 8 + 256) * sizeof(double); }
+static int64_t bcr_coupling_slots(int nblk) { return 2 * (int64_t)nblk + 40; }   // the coupling tables of all levels (sum of active - 1 + ghost < 2 nblk) and of the one behind them
 static void bcr_carve(BcrArgs& A, double* w, int nblk, int a1) {   // nblk: blocks incl. a ghost
   A.D = w; w += (int64_t)nblk * 4096;
   A.F = w; w += (int64_t)nblk * 64 * a1;
-  A.S = w; w += (int64_t)(2 * nblk + 40) * 4096;
+  A.S = w; w += bcr_coupling_slots(nblk) * 4096;
   A.Lf = w;
 }
-static int64_t bcr_carve_doubles(int nblk, int a1) { return (int64_t)nblk * 4096 + (int64_t)nblk * 64 * a1 + (int64_t)(2 * nblk + 40) * 4096 + (int64_t)nblk * (192 + a1) * 64 + 64; }
+static int64_t bcr_carve_doubles(int nblk, int a1) { return (int64_t)nblk * 4096 + (int64_t)nblk * 64 * a1 + bcr_coupling_slots(nblk) * 4096 + (int64_t)nblk * (192 + a1) * 64 + 64; }
 // Arrow limit: the kernels take up to 63 arrow columns (four 16-row border tiles).  Round 2 saw sporadic NaN pivots with more than
 // two border tiles; the cause was the in-place read of the panel's diagonal block by waves that start a panel late (see the panel
 // factorisation and tests/test_gpu_parity.py::test_bcr_wide_borders_and_the_panel_hazard, which makes it deterministic); with the
@@ -856,19 +912,49 @@ int64_t bcr_workspace_doubles(const TangentLayout& tl) {
 }
 
 // ---- the launch sequence in pieces (shared by the one-GPU solve and the distributed one) ----
-struct BcrLevels { int strides[40]; int npivs[40]; int nlev = 0; int64_t off_end = 0; };   // off_end: index of the coupling table behind the last level (distributed: the final coupling (block 0, ghost))
+// The elimination plan.  Level l: active blocks origin + k stride, k < active; the pivots are the positions of parity `parity` (an
+// independent set of the block-tridiagonal chain).  An ODD number of active blocks takes the even positions, both ends included --
+// ceil(m / 2) pivots, where the odd positions give (m - 1) / 2 and leave block 0 standing until the very end; an even number takes
+// the odd positions.  The depth is floor(log2 n) + 1 inversions instead of ceil(log2 n) + 1 (the same for n a power of two, whose
+// plan has parity 1 throughout).  odd_only: the odd positions at every level -- the order of the distributed reduction, whose ghost
+// block is a right neighbour that is never a pivot and whose message layout describes that order.
+struct BcrLevels {
+  int origin[40], strides[40], parity[40], active[40], npivs[40];
+  int64_t offS[41];        // first coupling of each level (active - 1 + ghost of them); [nlev]: the table behind the last level (distributed: the final coupling (block 0, ghost))
+  int nlev = 0, last = 0;  // last: the block that is left
+  int64_t off_end = 0;     // = offS[nlev]
+};
+static BcrLevels bcr_plan(int n, int ghost, bool odd_only) {
+  BcrLevels L;
+  const int g = ghost != 0 ? 1 : 0;
+  int o = 0, s = 1, m = n; int64_t off = 0;
+  while (m > 1) {
+    const int p = (odd_only || (m & 1) == 0) ? 1 : 0;
+    const int npiv = (m + 1 - p) / 2, l = L.nlev++;
+    L.origin[l] = o; L.strides[l] = s; L.parity[l] = p; L.active[l] = m; L.npivs[l] = npiv; L.offS[l] = off;
+    off += m - 1 + g; o += (1 - p) * s; s *= 2; m -= npiv;
+  }
+  L.offS[L.nlev] = off; L.off_end = off; L.last = o;
+  return L;
+}
+static void bcr_set_level(BcrArgs& A, const BcrLevels& L, int l) {
+  A.o = L.origin[l]; A.s = L.strides[l]; A.p = L.parity[l]; A.m = L.active[l];
+  A.pn = l + 1 < L.nlev ? L.parity[l + 1] : 1;
+  A.offS_in = L.offS[l]; A.offS_out = L.offS[l + 1];
+}
 // build + the inversions of level 0 in one launch (while the level-0 pivots fit on the chip at once)
 static bool bcr_fused_build(int n, const long long* prof) { return n >= 2 && n <= 512 && prof == nullptr; }
 // the damped system in block form (+ the inversions of level 0 in the same launch when they fit the chip at once); returns whether level 0 is inverted
-static bool bcr_launch_build(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb, int reuse_diagonal, double min_diag, double max_diag, BcrArgs A, hipStream_t st) {
+static bool bcr_launch_build(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb, int reuse_diagonal, double min_diag, double max_diag, BcrArgs A, const BcrLevels& L, hipStream_t st) {
   const int n = A.n;
   const bool fused_build = bcr_fused_build(n, A.prof);
   const int64_t work = (int64_t)(n + A.ghost) * 4096;
-  A.s = 1; A.offS_in = 0; A.offS_out = 0;
+  A.o = 0; A.s = 1; A.p = 1; A.m = n; A.pn = 1; A.offS_in = 0; A.offS_out = 0;
+  if (L.nlev > 0) bcr_set_level(A, L, 0);
   if (fused_build) {
     int grid = int((work + 1023) / 1024); if (grid > 1024) grid = 1024;
     bcr_allow_lds(reinterpret_cast<const void*>(bcri_build_invert_kernel), bcr_lds_inv());
-    hipLaunchKernelGGL(bcri_build_invert_kernel, dim3(n / 2 + grid), dim3(64 * kInvWaves), bcr_lds_inv(), st, ne, tl, sb, reuse_diagonal, min_diag, max_diag, A);
+    hipLaunchKernelGGL(bcri_build_invert_kernel, dim3(L.npivs[0] + grid), dim3(64 * kInvWaves), bcr_lds_inv(), st, ne, tl, sb, reuse_diagonal, min_diag, max_diag, A);
   } else {
     int grid = int((work + 255) / 256); if (grid > 4096) grid = 4096;
     hipLaunchKernelGGL(bcr_build_kernel, dim3(grid), dim3(256), 0, st, ne, tl, sb, reuse_diagonal, min_diag, max_diag, A);
@@ -876,47 +962,52 @@ static bool bcr_launch_build(const NormalEq& ne, const TangentLayout& tl, const 
   return fused_build;
 }
 // forward levels while more than one (local) block is active: inversions of the pivots, Schur complements onto their neighbours
-static void bcr_launch_forward(BcrArgs A, bool level0_inverted, BcrLevels& L, hipStream_t st) {
+static void bcr_launch_forward(BcrArgs A, bool level0_inverted, const BcrLevels& L, hipStream_t st) {
   using KernelFn = void (*)(BcrArgs);
   KernelFn k_inv = A.prof ? bcri_invert_kernel<false, true> : bcri_invert_kernel<false, false>;
   bcr_allow_lds(reinterpret_cast<const void*>(k_inv), bcr_lds_inv());
-  const int n = A.n, g = A.ghost != 0 ? 1 : 0;
-  int64_t off = 0; L.nlev = 0;
-  for (int s = 1; s < n; s *= 2) {
-    const int m = (n + s - 1) / s;          // active blocks
-    const int npiv = m / 2;
-    A.s = s; A.offS_in = off; A.offS_out = off + (m - 1 + g);
+  const int g = A.ghost != 0 ? 1 : 0;
+  for (int l = 0; l < L.nlev; ++l) {
+    const int m = L.active[l], npiv = L.npivs[l];
+    bcr_set_level(A, L, l);
+    A.side = (l == L.nlev - 1 && L.parity[l] == 0) ? 1 : 0;   // (the top level with two pivots)
     const bool carry = g != 0 && (m & 1) != 0;   // the last active block is no pivot: its coupling to the ghost block moves on unchanged
-    A.top = carry ? -m : 0;
-    {
-      BcrArgs Ai = A; if (s != 1) Ai.prof = nullptr;
-      if (!(level0_inverted && s == 1)) hipLaunchKernelGGL(k_inv, dim3(npiv), dim3(64 * kInvWaves), bcr_lds_inv(), st, Ai);
-      hipLaunchKernelGGL(bcri_schur_kernel, dim3(12 + 3 * A.rtf, npiv + (carry ? 1 : 0)), dim3(256), 0, st, A);
-    }
-    L.strides[L.nlev] = s; L.npivs[L.nlev] = npiv; ++L.nlev;
-    off += m - 1 + g;
+    A.carry = carry ? m : 0;
+    BcrArgs Ai = A; if (l != 0) Ai.prof = nullptr;
+    if (!(level0_inverted && l == 0)) hipLaunchKernelGGL(k_inv, dim3(npiv), dim3(64 * kInvWaves), bcr_lds_inv(), st, Ai);
+    hipLaunchKernelGGL(bcri_schur_kernel, dim3(12 + 3 * A.rtf, npiv + (carry ? 1 : 0)), dim3(256), 0, st, A);
   }
-  L.off_end = off;
 }
-// block 0 with the arrow corner, then the back substitution below the top level: two levels per launch from the bottom up
+// the back substitution of the levels top, top - 1, ..., 0: two levels per launch from the bottom up (an odd count: the uppermost alone, first)
+static void bcr_launch_back(BcrArgs A, const BcrLevels& L, int top, hipStream_t st) {
+  int l = top;
+  if (l >= 0 && !(l & 1)) { bcr_set_level(A, L, l); hipLaunchKernelGGL(bcri_backward_kernel, dim3(L.npivs[l]), dim3(64 * kBackWaves), 0, st, A); --l; }
+  for (; l >= 1; l -= 2) {
+    const int lo = l - 1;   // the lower level of the pair
+    // orphans: a lower pivot at an end of the active blocks whose one neighbour is no pivot of the upper level
+    const int orphan_l = (L.parity[lo] == 0 && L.parity[l] == 1) ? L.origin[lo] : -1;
+    const int orphan_r = (((L.active[lo] - 1) & 1) == L.parity[lo] && ((L.active[l] - 1) & 1) != L.parity[l]) ? L.origin[lo] + (L.active[lo] - 1) * L.strides[lo] : -1;
+    bcr_set_level(A, L, lo);
+    hipLaunchKernelGGL(bcri_backward2_kernel, dim3(L.npivs[l] + (orphan_l >= 0 ? 1 : 0) + (orphan_r >= 0 ? 1 : 0)), dim3(1024), 0, st, A, L.origin[l], L.parity[l], L.active[l], L.npivs[l], orphan_l, orphan_r);
+  }
+}
+// the last block with the arrow corner and the top level's back substitution (one or two pivots, whose only neighbour is the last
+// block), then the levels below
 static void bcr_launch_last_and_back(BcrArgs A, const BcrLevels& L, hipStream_t st) {
   using KernelFn = void (*)(BcrArgs);
   KernelFn k_inv_last = bcri_invert_kernel<true, false>;
   const size_t lds_inv_last = bcr_lds_inv() + (size_t)64 * 65 * sizeof(double);
   bcr_allow_lds(reinterpret_cast<const void*>(k_inv_last), lds_inv_last);
   const int nlev = L.nlev;
-  A.s = 0; A.offS_in = 0; A.offS_out = 0;
-  A.top = nlev >= 1 ? L.strides[nlev - 1] : 0;     // (the top level has one pivot, block `stride`)
-  hipLaunchKernelGGL(k_inv_last, dim3(1), dim3(64 * kInvWaves), lds_inv_last, st, A);
-  int l = nlev - 2;        // (the top level went with block 0)
-  if (l >= 0 && !(l & 1)) { A.s = L.strides[l]; hipLaunchKernelGGL(bcri_backward_kernel, dim3(L.npivs[l]), dim3(64 * kBackWaves), 0, st, A); --l; }
-  for (; l >= 1; l -= 2) {
-    const int s = L.strides[l - 1];
-    int orphan = -1;      // the lower pivot s (2 c + 1), c even, whose upper neighbour would be block >= n
-    if (L.npivs[l - 1] > 2 * L.npivs[l]) orphan = s * (2 * (L.npivs[l - 1] - 1) + 1);    // (4 q + 2 active blocks at the lower level)
-    A.s = s;
-    hipLaunchKernelGGL(bcri_backward2_kernel, dim3(L.npivs[l] + (orphan >= 0 ? 1 : 0)), dim3(1024), 0, st, A, L.npivs[l], orphan);
+  A.o = 0; A.s = 0; A.p = 1; A.m = 1; A.pn = 1; A.offS_in = 0; A.offS_out = 0; A.carry = 0;
+  A.last = L.last; A.top_l = -1; A.top_r = -1; A.side = (nlev >= 1 && L.parity[nlev - 1] == 0) ? 1 : 0;
+  if (nlev >= 1) {   // two active blocks: the pivot right of the last block; three: the two ends
+    const int t = nlev - 1;
+    A.top_r = L.last + L.strides[t];
+    if (L.parity[t] == 0) A.top_l = L.last - L.strides[t];
   }
+  hipLaunchKernelGGL(k_inv_last, dim3(1), dim3(64 * kInvWaves), lds_inv_last, st, A);
+  bcr_launch_back(A, L, nlev - 2, st);        // (the top level went with the last block)
 }
 
 // the route of one cyclic-reduction solve (lm_solve_route): fused or separate build, or kRouteNone where it does not apply
@@ -935,8 +1026,8 @@ int launch_bcr_solve(const NormalEq& ne, const TangentLayout& tl, const SolveBuf
   A.Mc = sb.Mc; A.x = sb.step_s; A.fail = &sb.st->chol_failed; A.prof = sb.prof;
   A.n = n; A.a = tl.a; A.Pb = tl.Pb; A.delay = sb.bcr_delay;
   A.rtf = (a1 + 15) / 16; A.ctl = sb.ctl;
-  const bool inverted = bcr_launch_build(ne, tl, sb, reuse_diagonal, min_diag, max_diag, A, st);
-  BcrLevels L;
+  const BcrLevels L = bcr_plan(n, 0, false);
+  const bool inverted = bcr_launch_build(ne, tl, sb, reuse_diagonal, min_diag, max_diag, A, L, st);
   bcr_launch_forward(A, inverted, L, st);
   bcr_launch_last_and_back(A, L, st);
   return 0;
@@ -955,7 +1046,8 @@ int launch_bcr_solve(const NormalEq& ne, const TangentLayout& tl, const SolveBuf
 //     + block 0: the same kernels), which leaves x of all separators and of the arrow on every rank;
 //   backward, no communication: the local levels in reverse; then ONE all-gather of the ranks' solutions (<= 0.72 MB in all at
 //     BASELINE config 5) puts the step on every rank.
-// Per-rank depth: ceil(log2(n / N)) + ceil(log2 N) + 1 inversions instead of ceil(log2 n) + 1, each over 1 / N of the pivots.
+// Per-rank depth: ceil(log2(n / N)) + ceil(log2 N) + 1 inversions instead of floor(log2 n) + 1, each over 1 / N of the pivots.
+// Both the local range and the top system keep the odd-positions-only order (bcr_plan's odd_only).
 // =================================================================================================================================
 __global__ void bcr_dist_pack_kernel(BcrArgs A, int64_t off_final, double* msg) {   // this rank's slot of the first gather
   const int a1 = A.a + 1; const int64_t fsz = (int64_t)64 * a1;
@@ -1049,8 +1141,8 @@ int launch_bcr_dist_forward(const NormalEq& ne, const TangentLayout& tl, const S
   if (!bcr_applicable(tl) || tl.a + 1 > sb_in.bcr_max_border || d.ws == nullptr || d.n_loc < 1 || d.nranks < 2 || d.ws_doubles < bcr_dist_workspace_doubles(tl, d.n_loc, d.nranks)) return -1;
   DistViews v = bcr_dist_views(tl, sb_in, d);
   SolveBuffers sb = sb_in; sb.Mc = v.A.Mc; sb.ctl = nullptr;   // (the build writes the corner where the Schur kernels add to it)
-  const bool inverted = bcr_launch_build(ne, tl, sb, reuse_diagonal, min_diag, max_diag, v.A, st);
-  BcrLevels L;
+  const BcrLevels L = bcr_plan(v.A.n, v.A.ghost, true);
+  const bool inverted = bcr_launch_build(ne, tl, sb, reuse_diagonal, min_diag, max_diag, v.A, L, st);
   bcr_launch_forward(v.A, inverted, L, st);
   const int64_t total = bcr_dist_msg_doubles(tl);
   hipLaunchKernelGGL(bcr_dist_pack_kernel, dim3(int((total + 255) / 256)), dim3(256), 0, st, v.A, L.off_end, d.msg + (int64_t)d.rank * d.msg_piece);
@@ -1062,25 +1154,14 @@ int launch_bcr_dist_middle(const TangentLayout& tl, const SolveBuffers& sb, cons
   const int a1 = tl.a + 1, N = d.nranks;
   const int64_t work = (int64_t)N * 4096 + (int64_t)N * 64 * a1 + (int64_t)(N - 1) * 4096 + (int64_t)a1 * a1;
   hipLaunchKernelGGL(bcr_dist_top_kernel, dim3(int(std::min<int64_t>(1024, (work + 255) / 256))), dim3(256), 0, st, v.T, d.msg, d.msg_piece);
-  BcrLevels LT;
+  const BcrLevels LT = bcr_plan(N, 0, true);   // (the top system's level-0 couplings come from bcr_dist_top_kernel, which orients them for odd pivots)
   bcr_launch_forward(v.T, false, LT, st);
   bcr_launch_last_and_back(v.T, LT, st);
   hipLaunchKernelGGL(bcr_dist_scatter_kernel, dim3(1), dim3(256), 0, st, v.A, v.xt, N, d.rank);
-  // the local levels in reverse (the strides follow from the block count alone)
+  // the local levels in reverse (the plan follows from the block count alone)
   BcrArgs A = v.A;
-  int strides[40], npivs[40], nlev = 0;
-  for (int s = 1; s < A.n; s *= 2) { const int m = (A.n + s - 1) / s; strides[nlev] = s; npivs[nlev] = m / 2; ++nlev; }
-  {   // two levels per launch as on one GPU (an even count of levels below: the uppermost alone, first)
-    int l = nlev - 1;
-    if (l >= 0 && !(l & 1)) { A.s = strides[l]; hipLaunchKernelGGL(bcri_backward_kernel, dim3(npivs[l]), dim3(64 * kBackWaves), 0, st, A); --l; }
-    for (; l >= 1; l -= 2) {
-      const int s = strides[l - 1];
-      int orphan = -1;
-      if (npivs[l - 1] > 2 * npivs[l]) orphan = s * (2 * (npivs[l - 1] - 1) + 1);
-      A.s = s;
-      hipLaunchKernelGGL(bcri_backward2_kernel, dim3(npivs[l] + (orphan >= 0 ? 1 : 0)), dim3(1024), 0, st, A, npivs[l], orphan);
-    }
-  }
+  const BcrLevels L = bcr_plan(A.n, A.ghost, true);
+  bcr_launch_back(A, L, L.nlev - 1, st);
   const int64_t nx = (int64_t)A.n * 64 + A.a;
   hipLaunchKernelGGL(bcr_dist_pack_x_kernel, dim3(int((nx + 255) / 256)), dim3(256), 0, st, v.A, d.xg + (int64_t)d.rank * d.x_piece, (int64_t)d.max_loc * 64);
   return 0;
@@ -1092,3 +1173,15 @@ void launch_bcr_dist_finish(const TangentLayout& tl, const SolveBuffers& sb, con
 }
 
 }  // namespace oicc
+
+extern "C" int oicc_debug_bcr_plan(int32_t n, int32_t ghost, int32_t odd_only, int64_t* levels, int32_t cap_levels, int64_t info[3]) {
+  if (n < 1 || levels == nullptr || info == nullptr) return OICC_ERR_INVALID_ARG;
+  const oicc::BcrLevels L = oicc::bcr_plan(n, ghost, odd_only != 0);
+  if (L.nlev > cap_levels) return OICC_ERR_INVALID_ARG;
+  for (int l = 0; l < L.nlev; ++l) {
+    int64_t* o = levels + 6 * l;
+    o[0] = L.origin[l]; o[1] = L.strides[l]; o[2] = L.parity[l]; o[3] = L.active[l]; o[4] = L.npivs[l]; o[5] = L.offS[l];
+  }
+  info[0] = L.last; info[1] = L.off_end; info[2] = oicc::bcr_coupling_slots(n + (ghost != 0 ? 1 : 0));
+  return L.nlev;
+}
