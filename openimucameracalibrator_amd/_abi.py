@@ -306,6 +306,26 @@ class BoundBcrPlan:
             setattr(self, name, fn)
 
 
+# One LM solve with the retraction as the loops run it, and the stand-alone retraction kernel on the same step (oicc_debug_lm_retract,
+# outside include/oicc_hip.h: oicc_exchange.hip), a table of its own like BCR_PLAN_SIGNATURES.
+LM_RETRACT_SIGNATURES = {
+    "retract": (C.c_int, [C.c_void_p, C.c_int32, C.c_double, c_i64p] + [c_dp] * 9),
+}
+
+
+class BoundLmRetract:
+    """Bound oicc_debug_lm_retract of one library + prefix (``oicc_debug_lm_`` for liboicc_hip.so)."""
+
+    def __init__(self, lib, prefix):
+        self.lib = lib
+        self.prefix = prefix
+        for name, (res, args) in LM_RETRACT_SIGNATURES.items():
+            fn = getattr(lib, prefix + name)  # AttributeError = missing symbol: fail loudly
+            fn.restype = res
+            fn.argtypes = args
+            setattr(self, name, fn)
+
+
 # Robust start poses (oicc_planar_ransac in include/oicc_hip.h), a table of its own like ALLAN_SIGNATURES: SIGNATURES and
 # BA_SIGNATURES are also bound against the CPU checker, which has no counterpart of this entry.
 PLANAR_RANSAC_SIGNATURES = {

@@ -7,7 +7,7 @@ fails when no HIP device is usable.
 import ctypes
 import os
 
-from ._abi import Bound, BoundAllan, BoundBa, BoundBcrPlan, BoundBoard, BoundPlanarRansac, BoundStaticImu
+from ._abi import Bound, BoundAllan, BoundBa, BoundBcrPlan, BoundBoard, BoundLmRetract, BoundPlanarRansac, BoundStaticImu
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OICC_DEV_LIB") or os.path.join(_HERE, "csrc", "liboicc_hip.so")   # OICC_DEV_LIB: another BUILD of the same library (developer A/B timing, scripts/build_variant.sh)
@@ -18,6 +18,7 @@ _bound_static_imu = None
 _bound_board = None
 _bound_planar_ransac = None
 _bound_bcr_plan = None
+_bound_lm_retract = None
 
 
 def load():
@@ -78,3 +79,11 @@ def load_bcr_plan():
     if _bound_bcr_plan is None:
         _bound_bcr_plan = BoundBcrPlan(load().lib, "oicc_debug_bcr_")
     return _bound_bcr_plan
+
+
+def load_lm_retract():
+    """oicc_debug_lm_retract (one LM solve with its retraction, and the stand-alone retraction kernel on the same step) of the same library."""
+    global _bound_lm_retract
+    if _bound_lm_retract is None:
+        _bound_lm_retract = BoundLmRetract(load().lib, "oicc_debug_lm_")
+    return _bound_lm_retract

@@ -19,6 +19,12 @@
 //   launch in reverse.  (Until the end blocks became pivots only the odd positions were, block 0 stood until the end and the depth
 //   was ceil(log2 n) + 1 inversions: one more whenever n is no power of two.  The distributed reduction keeps that order.)
 //
+// The LAST launch of a whole-band solve -- the back substitution that ends at level 0 -- also retracts: its workgroups hold every entry
+// of the step in LDS when they store it, so the candidate parameters x (+) scale .* step and the step's three scalars (LmState) are
+// written there, with the functions lm_retract_kernel uses (lm_retract.h), and the step costs one dependent launch fewer
+// (launch_bcr_solve's retraction request; bcr_retract_* below).  Plans of fewer than three levels (n < 8 blocks: their last launch is
+// the one-level kernel or the last block's), the distributed reduction and scaled steps (line search) keep lm_retract_kernel.
+//
 // History: rounds 1-2 factored each pivot WITH its 138 + a border rows in one workgroup (solver_algorithm 2) and round 3 added a
 // parallel form of that (algorithm 3: every block a pivot at every level); both stayed in the library as independent solvers
 // until round 4 removed them (three kernels, ten instantiations: git history) -- the band sweep (kernels_cholesky.hip, algorithm 1)
@@ -29,6 +35,7 @@
 #include "oicc_device.h"
 #include "lm_decide.h"
 #include "lm_launch.h"
+#include "lm_retract.h"
 #include "../../include/oicc_hip.h"
 
 namespace oicc {
@@ -609,6 +616,89 @@ __global__ __launch_bounds__(256) void bcri_schur_kernel(BcrArgs A) {
   }
 }
 
+// ---- the retraction inside the LAST launch of a whole-band solve (lm_retract.h; used by the two-level back-substitution kernel) ----
+// The workgroups that produce the step also retract with it: lm_retract_kernel's work without its launch.  Every tangent entry of the
+// band has exactly one owner among the workgroups of the last launch (the ranges are stated at the two kernels); a parameter block
+// belongs to the owner of its FIRST tangent entry, its other entries lie at most two further, inside a block whose solution an
+// EARLIER launch wrote and the workgroup holds in LDS anyway.  So every step entry a workgroup retracts with is one it computed itself
+// or one an earlier launch wrote: nothing another workgroup of the same launch writes is read -- no flag, no wait.  Workgroup 0 also
+// owns the arrow entries (x_arrow is final since the last block's kernel).  The owned parameter blocks are found through the entry
+// map (oicc_device.h: RetractReq); map, scale, D2, gradient and parameters are loaded before the first barrier, with the T rows.  One
+// block reduction and one atomic per scalar and workgroup.
+struct BcrOwn {
+  int e = -1, code = -1;                 // this thread's tangent entry; kind and parameter offset of the block that starts there (lm_rmap_code), or -1
+  double sc0 = 0.0, d2 = 0.0, g = 0.0;   // scale, D2, gradient of the entry
+  const double* x = nullptr; double* xc = nullptr;
+};
+constexpr int kRetractPark = 12;         // doubles parked in LDS per owner: parameters [7], further scales [5]
+// Thread tid < 64 NB takes entry 64 b_lo + tid of the blocks [b_lo, b_hi); in the arrow workgroup the next `a` threads take the arrow entries.
+template <int NB>
+__device__ __forceinline__ BcrOwn bcr_retract_claim(const BcrArgs& A, const RetractReq& R, const SolveBuffers& sb, int b_lo, int b_hi, bool arrow_wg, int tid) {
+  BcrOwn o; o.x = R.x; o.xc = R.xc;
+  NormalEq ne = R.ne;
+  if (A.ctl != nullptr) { o.x = A.ctl->xp[0]; o.xc = A.ctl->xp[1]; ne.base = A.ctl->nep[0]; }
+  const int e_hi = b_hi * 64 < A.Pb ? b_hi * 64 : A.Pb;
+  if (tid < 64 * NB) { const int e = b_lo * 64 + tid; if (e < e_hi) o.e = e; }
+  else if (tid < 64 * NB + A.a && arrow_wg) o.e = A.Pb + (tid - 64 * NB);
+  if (o.e >= 0) { o.code = R.rmap[o.e]; o.sc0 = sb.scale[o.e]; o.d2 = sb.D2[o.e]; o.g = ne.g()[o.e]; }
+  return o;
+}
+__device__ __forceinline__ int bcr_rm_steps(int kind) { return kind == kRmEucl ? 1 : (kind == kRmTic ? 6 : 3); }
+__device__ __forceinline__ int bcr_rm_params(int kind) { return kind == kRmEucl ? 1 : (kind == kRmTic ? 7 : (kind == kRmSo3 || kind == kRmPt ? 4 : 3)); }
+// the parameters and the further scales of the owned block: into LDS (rpark[c * stride + tid]), not into registers, until the step is there
+__device__ __forceinline__ void bcr_retract_park(const SolveBuffers& sb, const BcrOwn& o, double* rpark, int stride, int tid) {
+  if (o.code < 0) return;
+  const int kind = o.code & 7; const int64_t po = o.code >> 3;
+  const int nd = bcr_rm_steps(kind), np = bcr_rm_params(kind);
+  for (int c = 0; c < np; ++c) rpark[c * stride + tid] = o.x[po + c];
+  for (int c = 1; c < nd; ++c) rpark[(6 + c) * stride + tid] = sb.scale[o.e + c];
+}
+// Behind the workgroup's last store of the step.  xflat: the band part of the step in LDS, entry e at xflat[e - e_base]; xarrow: the
+// arrow part.  red: 3 x 64 doubles of LDS nobody reads any more.  OW: the waves that hold owners.  Called by all threads.
+template <int OW>
+__device__ __forceinline__ void bcr_retract_finish(const BcrArgs& A, const RetractReq& R, const SolveBuffers& sb, const BcrOwn& o, const double* xflat, int e_base,
+                                                   const double* xarrow, const double* rpark, int stride, double* red, int tid, int wave, int lane) {
+  __syncthreads();
+  if (blockIdx.x == 0 && tid == 0) {
+    // "the solve is done" of the device-side loop: behind the barrier, so every wave of this workgroup has issued its stores of the
+    // step -- the end of ONE workgroup's solve, no launch boundary any more (the others finish within the same launch)
+    if (A.ctl != nullptr) { if (A.ctl->stamps != nullptr && A.ctl->seq < A.ctl->trace_cap) A.ctl->stamps[3 * A.ctl->seq + 1] = wall_clock64(); }
+    else *R.ne.cost() = 0.0;   // (the host-driven loop: the cost slot is cleared for the candidate cost pass)
+  }
+  double step_sq = 0.0, x_sq = 0.0, model = 0.0;
+  if (o.e >= 0) {
+    auto step_at = [&](int e) { return e >= A.Pb ? xarrow[e - A.Pb] : xflat[e - e_base]; };
+    model = lm_model_term(step_at(o.e), o.d2, o.g, o.sc0);
+    if (o.code >= 0) {
+      const int kind = o.code & 7;
+      const double alpha = R.alpha;
+      const int nd = bcr_rm_steps(kind), np = bcr_rm_params(kind);
+      double d[6], sc[6], pv[7];
+#pragma unroll
+      for (int c = 0; c < 6; ++c) { d[c] = c < nd ? step_at(o.e + c) : 0.0; sc[c] = c == 0 ? o.sc0 : (c < nd ? rpark[(6 + c) * stride + tid] : 0.0); }
+#pragma unroll
+      for (int c = 0; c < 7; ++c) pv[c] = c < np ? rpark[c * stride + tid] : 0.0;
+      double* out = o.xc + (o.code >> 3);
+      if (kind == kRmSo3) lm_store_so3(lm_retract_so3(Quat{pv[0], pv[1], pv[2], pv[3]}, d, sc, alpha), pv, out, step_sq, x_sq);
+      else if (kind == kRmEucl) lm_retract_eucl(pv[0], d[0], sc[0], alpha, out, step_sq, x_sq);
+      else if (kind == kRmAb || kind == kRmGb) { const double bound = kind == kRmAb ? R.max_ab : R.max_gb; for (int c = 0; c < 3; ++c) lm_retract_box(pv[c], d[c], sc[c], alpha, bound, out + c, step_sq, x_sq); }
+      else if (kind == kRmPt) lm_retract_point(pv, d, sc, alpha, out, step_sq, x_sq);
+      else if (kind == kRmTic) lm_retract_tic(pv, d, sc, alpha, out, step_sq, x_sq);
+    }
+  }
+  if (wave < OW) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { step_sq += __shfl_xor(step_sq, off); x_sq += __shfl_xor(x_sq, off); model += __shfl_xor(model, off); }
+    if (lane == 0) { red[wave] = step_sq; red[64 + wave] = x_sq; red[128 + wave] = model; }
+  }
+  __syncthreads();
+  if (tid < 3) {
+    double acc = 0.0;
+    for (int w = 0; w < OW; ++w) acc += red[64 * tid + w];
+    unsafeAtomicAdd(tid == 0 ? &sb.st->step_norm_sq : (tid == 1 ? &sb.st->x_norm_sq : &sb.st->model_cost_change), acc);
+  }
+}
+
 // back substitution of the pivots of one level: lane = column of T, the 128 + a rows spread over the waves
 __global__ __launch_bounds__(64 * kBackWaves) void bcri_backward_kernel(BcrArgs A) {
   BCR_RETURN_IF_DONE(A);
@@ -658,11 +748,17 @@ __global__ __launch_bounds__(64 * kBackWaves) void bcri_backward_kernel(BcrArgs 
 // level; ou, pu, mu the upper one.  An upper pivot at an end may lack the child on that side.  An orphan -- a lower pivot at an end of
 // the active blocks whose only neighbour is no pivot of the upper level (at most one per end) -- gets a workgroup of its own behind
 // the others: orphan_l / orphan_r, its block, or -1.
-__global__ __launch_bounds__(1024) void bcri_backward2_kernel(BcrArgs A, int ou, int pu, int mu, int npiv_upper, int orphan_l, int orphan_r) {
-  BCR_RETURN_IF_DONE(A);
+//
+// RETRACT (the levels (1, 0) as the last launch of a whole-band solve, s = 1; see the helpers above): the workgroup of the upper pivot j
+// owns the blocks j - 2 .. j + 1 (upper pivots are four blocks apart), clipped to the band; the last upper pivot also takes block
+// j + 2 when no right-end orphan stands there; an orphan's workgroup takes the orphan (left end) or the orphan and the block left of it
+// (right end).  The children's solutions go to LDS as well as to global memory, for their owners.
+template <bool RETRACT>
+__device__ __forceinline__ void bcri_backward2_body(const BcrArgs& A, int ou, int pu, int mu, int npiv_upper, int orphan_l, int orphan_r, const RetractReq& R, const SolveBuffers& sb) {
   constexpr int NW = 16, RW1 = 192 / NW, RW2 = 192 / (NW / 2);
-  __shared__ double xs[4][64];            // x of j - 2 s, j, j + 2 s, the arrow part
+  __shared__ double xw[6][64];            // x of the blocks j - 2 s, j - s, j, j + s, j + 2 s (the children's rows only under RETRACT), the arrow part
   __shared__ double part[NW][64];
+  double* const xs0 = xw[0]; double* const xs1 = xw[2]; double* const xs2 = xw[4]; double* const xs3 = xw[5];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int a = A.a, a1 = a + 1, s = A.s, n = A.n;
@@ -687,10 +783,22 @@ __global__ __launch_bounds__(1024) void bcri_backward2_kernel(BcrArgs A, int ou,
   const bool child_hasL = half == 0 ? has_jl : !lone;
   const bool child_hasR = half == 0 ? (!lone || ghost) : has_jr;
   auto xin = [&](int blk, int r) { const int gi = blk * 64 + r; return gi < A.Pb ? A.x[gi] : 0.0; };
-  if (tid < 64) xs[0][tid] = has_jl ? xin(jl, tid) : 0.0;
-  else if (tid < 128) xs[2][tid - 64] = has_jr ? xin(jrs, tid - 64) : 0.0;
-  else if (tid < 192) xs[3][tid - 128] = tid - 128 < a ? A.x[A.Pb + (tid - 128)] : 0.0;
-  else if (tid < 256 && lone) xs[1][tid - 192] = (lone_r && ghost) ? xin(n, tid - 192) : 0.0;   // (in place of x_j: nothing, or the right-end orphan's ghost block)
+  if (tid < 64) xs0[tid] = has_jl ? xin(jl, tid) : 0.0;
+  else if (tid < 128) xs2[tid - 64] = has_jr ? xin(jrs, tid - 64) : 0.0;
+  else if (tid < 192) xs3[tid - 128] = tid - 128 < a ? A.x[A.Pb + (tid - 128)] : 0.0;
+  else if (tid < 256 && lone) xs1[tid - 192] = (lone_r && ghost) ? xin(n, tid - 192) : 0.0;   // (in place of x_j: nothing, or the right-end orphan's ghost block)
+  // ---- RETRACT: what this thread owns; its entry of the map, scale, D2 and gradient are loaded here, the parameters of the block
+  // that starts at the entry behind the T rows (they need the map's answer), all of it before the first barrier
+  __shared__ double rpark[RETRACT ? kRetractPark : 1][384];
+  BcrOwn own;
+  if (RETRACT) {
+    // (j is virtual for an orphan's workgroup: -1 left of the band (owns block 0), n right of it (owns n - 2, n - 1); with it or an
+    // upper pivot j = 0 the window's base (j - 2) * 64 is negative: only owned entries, all >= b_lo * 64, are ever looked up in xw[])
+    const int b_lo = j - 2 > 0 ? j - 2 : 0;
+    int b_hi = j + 2 < n ? j + 2 : n;
+    if (!lone && (int)blockIdx.x == npiv_upper - 1 && orphan_r < 0) b_hi = n;   // (then n <= j + 3)
+    own = bcr_retract_claim<5>(A, R, sb, b_lo, b_hi, blockIdx.x == 0, tid);
+  }
   double l1[RW1], l2[RW2], y1 = 0.0, y2 = 0.0;
   {
     const double* T1 = A.Lf + (lone ? 0 : j) * ru64 + 4096;
@@ -710,13 +818,14 @@ __global__ __launch_bounds__(1024) void bcri_backward2_kernel(BcrArgs A, int ou,
     }
     if (hw == 0 && child) y2 = T2[(128 + a) * 64 + lane];
   }
+  if (RETRACT) bcr_retract_park(sb, own, &rpark[0][0], 384, tid);
   __syncthreads();
   if (!lone) {
     double sum = 0.0;
 #pragma unroll
     for (int k = 0; k < RW1; ++k) {
       const int r = wave + NW * k;
-      const double xv = r < 64 ? xs[0][r] : (r < 128 ? xs[2][r - 64] : (r < 128 + a ? xs[3][r - 128] : 0.0));
+      const double xv = r < 64 ? xs0[r] : (r < 128 ? xs2[r - 64] : (r < 128 + a ? xs3[r - 128] : 0.0));
       sum = fma(l1[k], xv, sum);
     }
     part[wave][lane] = sum;
@@ -727,19 +836,19 @@ __global__ __launch_bounds__(1024) void bcri_backward2_kernel(BcrArgs A, int ou,
       for (int w = 0; w < NW; ++w) acc += part[w][lane];
       const double xv = y1 - acc;
       const int gi = j * 64 + lane;
-      xs[1][lane] = gi < A.Pb ? xv : 0.0;
+      xs1[lane] = gi < A.Pb ? xv : 0.0;
       if (gi < A.Pb) A.x[gi] = xv;
     }
     __syncthreads();
   }
   {
-    const double* xl = half == 0 ? xs[0] : xs[1];
-    const double* xr = half == 0 ? xs[1] : xs[2];
+    const double* xl = half == 0 ? xs0 : xs1;
+    const double* xr = half == 0 ? xs1 : xs2;
     double sum = 0.0;
 #pragma unroll
     for (int k = 0; k < RW2; ++k) {
       const int r = hw + 8 * k;
-      const double xv = r < 64 ? xl[r] : (r < 128 ? xr[r - 64] : (r < 128 + a ? xs[3][r - 128] : 0.0));
+      const double xv = r < 64 ? xl[r] : (r < 128 ? xr[r - 64] : (r < 128 + a ? xs3[r - 128] : 0.0));
       sum = fma(l2[k], xv, sum);
     }
     part[wave][lane] = sum;
@@ -749,9 +858,20 @@ __global__ __launch_bounds__(1024) void bcri_backward2_kernel(BcrArgs A, int ou,
 #pragma unroll
       for (int w = 0; w < 8; ++w) acc += part[8 * half + w][lane];
       const int gi = ci * 64 + lane;
-      if (gi < A.Pb) A.x[gi] = y2 - acc;
+      const double xv = y2 - acc;
+      if (gi < A.Pb) A.x[gi] = xv;
+      if (RETRACT) xw[half == 0 ? 1 : 3][lane] = gi < A.Pb ? xv : 0.0;
     }
   }
+  if (RETRACT) bcr_retract_finish<6>(A, R, sb, own, &xw[0][0], (j - 2) * 64, xs3, &rpark[0][0], 384, &part[0][0], tid, wave, lane);
+}
+__global__ __launch_bounds__(1024) void bcri_backward2_kernel(BcrArgs A, int ou, int pu, int mu, int npiv_upper, int orphan_l, int orphan_r) {
+  BCR_RETURN_IF_DONE(A);
+  bcri_backward2_body<false>(A, ou, pu, mu, npiv_upper, orphan_l, orphan_r, RetractReq{}, SolveBuffers{});
+}
+__global__ __launch_bounds__(1024) void bcri_backward2_retract_kernel(BcrArgs A, int ou, int pu, int mu, int npiv_upper, int orphan_l, int orphan_r, RetractReq R, SolveBuffers sb) {
+  BCR_RETURN_IF_DONE(A);
+  bcri_backward2_body<true>(A, ou, pu, mu, npiv_upper, orphan_l, orphan_r, R, sb);
 }
 
 // ---- damped, scaled system in block form:  M = S H S + clamp(diag)/radius, rhs = -S g -----
@@ -979,8 +1099,11 @@ static void bcr_launch_forward(BcrArgs A, bool level0_inverted, const BcrLevels&
   }
 }
 // the back substitution of the levels top, top - 1, ..., 0: two levels per launch from the bottom up (an odd count: the uppermost alone, first)
-static void bcr_launch_back(BcrArgs A, const BcrLevels& L, int top, hipStream_t st) {
+// R (optional): the retraction request of a whole-band solve -- honoured by the two-level launch on the levels (1, 0), the last one of
+// the solve (bcri_backward2_retract_kernel); returns whether it was
+static bool bcr_launch_back(BcrArgs A, const BcrLevels& L, int top, hipStream_t st, const RetractReq* R = nullptr, const SolveBuffers* sb = nullptr) {
   int l = top;
+  bool fused = false;
   if (l >= 0 && !(l & 1)) { bcr_set_level(A, L, l); hipLaunchKernelGGL(bcri_backward_kernel, dim3(L.npivs[l]), dim3(64 * kBackWaves), 0, st, A); --l; }
   for (; l >= 1; l -= 2) {
     const int lo = l - 1;   // the lower level of the pair
@@ -988,12 +1111,17 @@ static void bcr_launch_back(BcrArgs A, const BcrLevels& L, int top, hipStream_t 
     const int orphan_l = (L.parity[lo] == 0 && L.parity[l] == 1) ? L.origin[lo] : -1;
     const int orphan_r = (((L.active[lo] - 1) & 1) == L.parity[lo] && ((L.active[l] - 1) & 1) != L.parity[l]) ? L.origin[lo] + (L.active[lo] - 1) * L.strides[lo] : -1;
     bcr_set_level(A, L, lo);
-    hipLaunchKernelGGL(bcri_backward2_kernel, dim3(L.npivs[l] + (orphan_l >= 0 ? 1 : 0) + (orphan_r >= 0 ? 1 : 0)), dim3(1024), 0, st, A, L.origin[l], L.parity[l], L.active[l], L.npivs[l], orphan_l, orphan_r);
+    const dim3 grid(L.npivs[l] + (orphan_l >= 0 ? 1 : 0) + (orphan_r >= 0 ? 1 : 0));
+    if (lo == 0 && R != nullptr) {   // (R: launch_bcr_solve decided; it hands a request down only where it is to be honoured)
+      hipLaunchKernelGGL(bcri_backward2_retract_kernel, grid, dim3(1024), 0, st, A, L.origin[l], L.parity[l], L.active[l], L.npivs[l], orphan_l, orphan_r, *R, *sb);
+      fused = true;
+    } else hipLaunchKernelGGL(bcri_backward2_kernel, grid, dim3(1024), 0, st, A, L.origin[l], L.parity[l], L.active[l], L.npivs[l], orphan_l, orphan_r);
   }
+  return fused;
 }
 // the last block with the arrow corner and the top level's back substitution (one or two pivots, whose only neighbour is the last
 // block), then the levels below
-static void bcr_launch_last_and_back(BcrArgs A, const BcrLevels& L, hipStream_t st) {
+static bool bcr_launch_last_and_back(BcrArgs A, const BcrLevels& L, hipStream_t st, const RetractReq* R = nullptr, const SolveBuffers* sb = nullptr) {
   using KernelFn = void (*)(BcrArgs);
   KernelFn k_inv_last = bcri_invert_kernel<true, false>;
   const size_t lds_inv_last = bcr_lds_inv() + (size_t)64 * 65 * sizeof(double);
@@ -1007,7 +1135,7 @@ static void bcr_launch_last_and_back(BcrArgs A, const BcrLevels& L, hipStream_t 
     if (L.parity[t] == 0) A.top_l = L.last - L.strides[t];
   }
   hipLaunchKernelGGL(k_inv_last, dim3(1), dim3(64 * kInvWaves), lds_inv_last, st, A);
-  bcr_launch_back(A, L, nlev - 2, st);        // (the top level went with the last block)
+  return bcr_launch_back(A, L, nlev - 2, st, R, sb);        // (the top level went with the last block)
 }
 
 // the route of one cyclic-reduction solve (lm_solve_route): fused or separate build, or kRouteNone where it does not apply
@@ -1017,8 +1145,13 @@ int bcr_route(const TangentLayout& tl, const SolveBuffers& sb) {
   return bcr_fused_build(bcr_blocks(tl.Pb), sb.prof) ? kRouteBcrFused : kRouteBcrUnfused;
 }
 // build + factor + solve; the solution lands in sb.step_s.  Returns 0, or -1 if not applicable.
+// retract (optional): also the retraction x_cand = x (+) scale .* step and the step's three scalars, inside the last launch -- where
+// the plan has at least three levels (n >= 8 blocks: the last launch is then the two-level back substitution of the levels (1, 0)),
+// the unscaled step is asked for (alpha = 1) and no segment tables are (the request carries none); *fused tells whether it was done,
+// and the caller launches lm_retract_kernel exactly when it was not.
 int launch_bcr_solve(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb, int reuse_diagonal,
-                     double min_diag, double max_diag, hipStream_t st) {
+                     double min_diag, double max_diag, hipStream_t st, const RetractReq* retract, bool* fused) {
+  if (fused) *fused = false;
   if (bcr_route(tl, sb) == kRouteNone) return -1;
   const int n = bcr_blocks(tl.Pb), a1 = tl.a + 1;
   BcrArgs A{};
@@ -1029,7 +1162,12 @@ int launch_bcr_solve(const NormalEq& ne, const TangentLayout& tl, const SolveBuf
   const BcrLevels L = bcr_plan(n, 0, false);
   const bool inverted = bcr_launch_build(ne, tl, sb, reuse_diagonal, min_diag, max_diag, A, L, st);
   bcr_launch_forward(A, inverted, L, st);
-  bcr_launch_last_and_back(A, L, st);
+  // the ONE place that decides: a request that is on, for the unscaled step, and a plan whose last launch is the two-level back
+  // substitution on the levels (1, 0); this entry always solves the whole band (b0 = 0, no ghost block)
+  const bool honour = retract != nullptr && retract->on != 0 && retract->rmap != nullptr && retract->alpha == 1.0 && L.nlev >= 3 && A.ghost == 0 && A.b0 == 0;
+  RetractReq R{}; if (honour) { R = *retract; R.ne = ne; }
+  const bool did = bcr_launch_last_and_back(A, L, st, honour ? &R : nullptr, &sb);
+  if (fused) *fused = did;
   return 0;
 }
 

@@ -25,6 +25,7 @@
 #include "spline_seg.h"
 #include "ba_math.h"   // homogeneous_plus4: the board points under SplineOptimFlags::POINTS
 #include "lm_decide.h"
+#include "lm_retract.h"
 
 namespace oicc {
 
@@ -110,29 +111,9 @@ __global__ void lm_gradmax_kernel(NormalEq ne, int P, LmState* st) {
 }
 
 // ---- retraction x_cand = x (+) (scale .* step_s), reductions -------------------
-// LieLocalParameterization::Plus: SO3 knots T*exp(d) (ceres_local_param.h:84-92,
-// so3.hpp:326-340,584-621), T_i_c SE3 with the coupled exp (se3.hpp:761-782),
-// Euclidean blocks x + d, bias knots projected onto their box (impl.h:213-218).
-__device__ __forceinline__ void se3_exp_dev(const double a6[6], Quat* q, double t[3]) {
-  const double om[3] = {a6[3], a6[4], a6[5]};
-  double theta;
-  *q = so3_exp(om, &theta);
-  double V[9];
-  if (theta < kSophusEps) {
-    so3_matrix(*q, V);
-  } else {
-    const double tsq = theta * theta;
-    double s, c; fast_sincos(theta, &s, &c);
-    const double c1 = (1.0 - c) / tsq, c2 = (theta - s) / (tsq * theta);
-    const double x = om[0], y = om[1], z = om[2];
-    // I + c1 [om]x + c2 [om]x^2
-    V[0] = 1.0 - c2 * (y * y + z * z); V[1] = -c1 * z + c2 * x * y;       V[2] = c1 * y + c2 * x * z;
-    V[3] = c1 * z + c2 * x * y;        V[4] = 1.0 - c2 * (x * x + z * z); V[5] = -c1 * x + c2 * y * z;
-    V[6] = -c1 * y + c2 * x * z;       V[7] = c1 * x + c2 * y * z;        V[8] = 1.0 - c2 * (x * x + y * y);
-  }
-  mat3_vec(V, a6, t);
-}
-
+// The per-block bodies (LieLocalParameterization::Plus and the box projection of the bias knots) live in lm_retract.h: the last
+// launch of the cyclic-reduction solve retracts with the same functions where it applies (kernels_bcr.hip), and this kernel is
+// then not launched.
 // alpha scales the step (1 for the trust-region candidate; the bounds line search of oicc_optimize re-retracts with its
 // step sizes, and then the model cost change of the FULL step is kept: with_model = 0).
 // SEG: also the candidate's segment tables (multi-round problems); without it that code -- a second retraction per knot -- does not exist
@@ -153,58 +134,41 @@ __global__ void lm_retract_kernel(const double* x, double* xc, ParamLayout pl, T
   // all active blocks are rewritten here.  The cost slot is cleared for the candidate cost pass.
   else if (tid == 0) *ne.cost() = 0.0;
   // model cost change = 0.5 * d.(D2 d - g_s)  (from (H_s + D2) d = -g_s)
-  if (with_model) for (int64_t i = tid; i < tl.P; i += nthreads) {
-    const double d = sb.step_s[i];
-    model += 0.5 * d * (sb.D2[i] * d - ne.g()[i] * sb.scale[i]);
-  }
+  if (with_model) for (int64_t i = tid; i < tl.P; i += nthreads) model += lm_model_term(sb.step_s[i], sb.D2[i], ne.g()[i], sb.scale[i]);
   for (int64_t k = tid; k < pl.n_so3; k += nthreads) {
     const int o = tl.so3[k];
     const double* q0 = x + pl.so3 + 4 * k;
-    double* q1 = xc + pl.so3 + 4 * k;
     auto moved = [&](int64_t kk) {   // knot kk of the candidate
       const int ok = tl.so3[kk];
       const double* q = x + pl.so3 + 4 * kk;
       const Quat qk{q[0], q[1], q[2], q[3]};
       if (ok < 0) return qk;
-      const double om[3] = {alpha * (sb.step_s[ok] * sb.scale[ok]), alpha * (sb.step_s[ok + 1] * sb.scale[ok + 1]), alpha * (sb.step_s[ok + 2] * sb.scale[ok + 2])};
-      return so3_mul(qk, so3_exp(om));
+      return lm_retract_so3(qk, sb.step_s + ok, sb.scale + ok, alpha);
     };
     const Quat r = moved(k);
-    if (o >= 0) {
-      q1[0] = r.x; q1[1] = r.y; q1[2] = r.z; q1[3] = r.w;
-      for (int c = 0; c < 4; ++c) { const double dd = q1[c] - q0[c]; step_sq += dd * dd; x_sq += q0[c] * q0[c]; }
-    }
+    if (o >= 0) { const double q0v[4] = {q0[0], q0[1], q0[2], q0[3]}; lm_store_so3(r, q0v, xc + pl.so3 + 4 * k, step_sq, x_sq); }
     // segment table of the candidate's knot pair (k, k+1) for the residual passes at xc (tiles.h: TileDyn::seg); the neighbour's
     // retraction is repeated here with the same operations, hence the same bits as its own thread stores
     if (SEG && seg_out != nullptr && k + 1 < pl.n_so3) so3_segment_prepare(r, moved(k + 1), seg_out + k * kSegStride);
   }
   for (int64_t k = tid; k < pl.n_r3; k += nthreads) {
     const int o = tl.r3[k];
-    if (o >= 0) for (int c = 0; c < 3; ++c) {
-      const double v0 = x[pl.r3 + 3 * k + c]; const double dd = alpha * (sb.step_s[o + c] * sb.scale[o + c]);
-      const double v1 = v0 + dd; xc[pl.r3 + 3 * k + c] = v1; step_sq += (v1 - v0) * (v1 - v0); x_sq += v0 * v0; }
+    if (o >= 0) for (int c = 0; c < 3; ++c) lm_retract_eucl(x[pl.r3 + 3 * k + c], sb.step_s[o + c], sb.scale[o + c], alpha, xc + pl.r3 + 3 * k + c, step_sq, x_sq);
   }
   for (int64_t k = tid; k < pl.n_ab; k += nthreads) {
     const int o = tl.ab[k];
-    if (o >= 0) for (int c = 0; c < 3; ++c) {
-      const double v0 = x[pl.ab + 3 * k + c];
-      const double v1 = fmin(fmax(v0 + alpha * (sb.step_s[o + c] * sb.scale[o + c]), -max_ab), max_ab);
-      xc[pl.ab + 3 * k + c] = v1; step_sq += (v1 - v0) * (v1 - v0); x_sq += v0 * v0; }
+    if (o >= 0) for (int c = 0; c < 3; ++c) lm_retract_box(x[pl.ab + 3 * k + c], sb.step_s[o + c], sb.scale[o + c], alpha, max_ab, xc + pl.ab + 3 * k + c, step_sq, x_sq);
   }
   for (int64_t k = tid; k < pl.n_gb; k += nthreads) {
     const int o = tl.gb[k];
-    if (o >= 0) for (int c = 0; c < 3; ++c) {
-      const double v0 = x[pl.gb + 3 * k + c];
-      const double v1 = fmin(fmax(v0 + alpha * (sb.step_s[o + c] * sb.scale[o + c]), -max_gb), max_gb);
-      xc[pl.gb + 3 * k + c] = v1; step_sq += (v1 - v0) * (v1 - v0); x_sq += v0 * v0; }
+    if (o >= 0) for (int c = 0; c < 3; ++c) lm_retract_box(x[pl.gb + 3 * k + c], sb.step_s[o + c], sb.scale[o + c], alpha, max_gb, xc + pl.gb + 3 * k + c, step_sq, x_sq);
   }
   for (int64_t k = tid; k < tl.n_pts; k += nthreads) {   // SplineOptimFlags::POINTS: ceres::HomogeneousVectorParameterization(4)::Plus
     const int o = tl.pts[k];
     if (o >= 0) {
-      const double d3[3] = {alpha * (sb.step_s[o] * sb.scale[o]), alpha * (sb.step_s[o + 1] * sb.scale[o + 1]), alpha * (sb.step_s[o + 2] * sb.scale[o + 2])};
       const double* X0 = x + pl.pts + 4 * k;
-      double X1[4]; homogeneous_plus4(X0, d3, X1);
-      for (int c = 0; c < 4; ++c) { xc[pl.pts + 4 * k + c] = X1[c]; const double dd = X1[c] - X0[c]; step_sq += dd * dd; x_sq += X0[c] * X0[c]; }
+      const double X0v[4] = {X0[0], X0[1], X0[2], X0[3]};
+      lm_retract_point(X0v, sb.step_s + o, sb.scale + o, alpha, xc + pl.pts + 4 * k, step_sq, x_sq);
     }
   }
   // the extrinsics (coupled SE(3) exponential) and the small Euclidean blocks are each one thread's work: threads that have no
@@ -213,24 +177,15 @@ __global__ void lm_retract_kernel(const double* x, double* xc, ParamLayout pl, T
   const int64_t t_tic = busy < nthreads ? busy : nthreads - 1, t_eu = busy + 64 < nthreads ? busy + 64 : nthreads - 1;
   if (tid == t_tic) {
     if (tl.tic >= 0) {
-      double a6[6];
-      for (int c = 0; c < 6; ++c) a6[c] = alpha * (sb.step_s[tl.tic + c] * sb.scale[tl.tic + c]);
-      Quat dq; double dt[3];
-      se3_exp_dev(a6, &dq, dt);
-      const double* T0 = x + pl.tic; double* T1 = xc + pl.tic;
-      const Quat q{T0[0], T0[1], T0[2], T0[3]};
-      double rt[3]; so3_rotate(q, dt, rt);
-      const Quat r = so3_mul(q, dq);
-      T1[0] = r.x; T1[1] = r.y; T1[2] = r.z; T1[3] = r.w;
-      for (int c = 0; c < 3; ++c) T1[4 + c] = T0[4 + c] + rt[c];
-      for (int c = 0; c < 7; ++c) { const double dd = T1[c] - T0[c]; step_sq += dd * dd; x_sq += T0[c] * T0[c]; }
+      const double* T0 = x + pl.tic;
+      const double T0v[7] = {T0[0], T0[1], T0[2], T0[3], T0[4], T0[5], T0[6]};
+      lm_retract_tic(T0v, sb.step_s + tl.tic, sb.scale + tl.tic, alpha, xc + pl.tic, step_sq, x_sq);
     }
   }
   if (tid == t_eu) {
     auto eucl = [&](int off, int64_t po, int n) {
       if (off < 0) return;
-      for (int c = 0; c < n; ++c) { const double v0 = x[po + c]; const double v1 = v0 + alpha * (sb.step_s[off + c] * sb.scale[off + c]);
-        xc[po + c] = v1; step_sq += (v1 - v0) * (v1 - v0); x_sq += v0 * v0; }
+      for (int c = 0; c < n; ++c) lm_retract_eucl(x[po + c], sb.step_s[off + c], sb.scale[off + c], alpha, xc + po + c, step_sq, x_sq);
     };
     eucl(tl.g, pl.g, 3); eucl(tl.ld, pl.ld, 1); eucl(tl.ai, pl.ai, 6); eucl(tl.gi, pl.gi, 9);
   }

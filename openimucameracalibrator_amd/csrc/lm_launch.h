@@ -26,7 +26,7 @@ int bcr_route(const TangentLayout& tl, const SolveBuffers& sb);              // 
 void launch_lm_solve_residual(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb, double* acc, hipStream_t st);
 int64_t bcr_workspace_doubles(const TangentLayout& tl);
 int launch_bcr_solve(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb, int reuse_diagonal, double min_diag,
-                     double max_diag, hipStream_t st);
+                     double max_diag, hipStream_t st, const RetractReq* retract = nullptr, bool* fused = nullptr);
 bool bcr_applicable(const TangentLayout& tl);
 // distributed block cyclic reduction (kernels_bcr.hip): rank-local forward part / top system + local back substitution / the gathered step
 int64_t bcr_dist_workspace_doubles(const TangentLayout& tl, int n_loc, int nranks);
@@ -41,13 +41,15 @@ static inline LmRoute lm_solve_route(const TangentLayout& tl, const SolveBuffers
   if (sb.algo >= 2 && tl.Pb > 0) return LmRoute{kRouteNone, 0};
   return band_arrow_route(tl, sb);
 }
-// damped system + factorisation + solve (solution in sb.step_s) on the route above
+// damped system + factorisation + solve (solution in sb.step_s) on the route above.  retract / fused: the retraction inside the
+// solve's last launch (launch_bcr_solve); *fused stays false on every other route, and the caller then launches lm_retract_kernel
 static inline int launch_lm_solve(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb_in, double radius, int reuse_diagonal,
-                                  double min_diag, double max_diag, hipStream_t st) {
+                                  double min_diag, double max_diag, hipStream_t st, const RetractReq* retract = nullptr, bool* fused = nullptr) {
   SolveBuffers sb = sb_in; sb.radius = radius;
+  if (fused) *fused = false;
   const LmRoute r = lm_solve_route(tl, sb);
   if (r.route == kRouteNone) return -1;
-  if (r.route == kRouteBcrFused || r.route == kRouteBcrUnfused) return launch_bcr_solve(ne, tl, sb, reuse_diagonal, min_diag, max_diag, st);
+  if (r.route == kRouteBcrFused || r.route == kRouteBcrUnfused) return launch_bcr_solve(ne, tl, sb, reuse_diagonal, min_diag, max_diag, st, retract, fused);
   launch_lm_build(ne, tl, sb, reuse_diagonal, min_diag, max_diag, st);
   return launch_band_arrow_cholesky(tl, sb, st);
 }

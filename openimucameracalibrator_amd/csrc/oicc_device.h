@@ -104,6 +104,9 @@ constexpr size_t kLmStepResultsOffset = 2 * sizeof(double);
 // The two parameter buffers and the two normal-equation buffers are addressed THROUGH this block ([0] current, [1] candidate):
 // an accepted step swaps the entries, so the host enqueues iteration k + 1 without knowing the outcome of iteration k and only
 // polls a pinned word (LmHostMsg) one iteration behind.  Every kernel of the loop returns at once when `done` is set.
+// The loop's kernels per iteration: the build kernel (with the previous iteration's decision), the levels of the solve -- whose last
+// launch also retracts (kernels_bcr.hip: bcri_backward2_retract_kernel; else lm_retract_kernel
+// behind the solve: other routes, multi-round problems, option fused_retract = 0) --, tile_kernel, slab_merge_kernel.
 struct LmIterRec {            // = oicc_iteration (include/oicc_hip.h), checked by a static_assert on the host side
   int32_t iteration, step_is_successful;
   double cost, cost_change, gradient_max_norm, step_norm, relative_decrease, trust_region_radius;
@@ -120,7 +123,7 @@ struct LmCtl {
   int32_t trace_cap, trace_n, pad;
   long long seq;              // decisions taken since the loop started
   LmIterRec* trace;           // [trace_cap]
-  long long* stamps;          // [3 * trace_cap] wall_clock64 of every iteration: the build kernel, the retraction (= the solve is done), the decision (seconds_* of the summary)
+  long long* stamps;          // [3 * trace_cap] wall_clock64 of every iteration: the build kernel, the retraction (= the solve is done: with the retraction inside the solve's last launch, the moment workgroup 0 of that launch has stored its part of the step -- one workgroup's end, no launch boundary), the decision (seconds_* of the summary)
   LmHostMsg* host;
 };
 // LmCtl::done: 0 = running, else why the loop ended (the host turns it into oicc_termination + Ceres' message)
@@ -150,6 +153,23 @@ struct SolveBuffers {
   // with and its results; every workgroup derives *ctl from them, one stores it (the control block and LmState alternate between two
   // slots from iteration to iteration, so nobody reads what another workgroup of the same launch writes)
   const LmCtl* ctl_prev = nullptr; const LmState* st_prev = nullptr; int64_t off_cost = 0;
+};
+
+// ---- the retraction inside the last launch of the cyclic-reduction solve (kernels_bcr.hip) ---------------------------------
+// Entry map of the tangent layout ([P] int32, built on the host with the layout, uploaded with it): for the FIRST tangent entry of a
+// parameter block the block's kind and where it lies in the parameter vector, -1 for every other entry.  A workgroup of the fused
+// launch finds the blocks it owns by reading the map at the tangent entries it owns: no scan over knots, and no assumption that
+// a family's offsets ascend with the knot index.  Euclidean blocks are mapped entry by entry (every entry is "first").
+enum { kRmSo3 = 0, kRmEucl = 1, kRmAb = 2, kRmGb = 3, kRmPt = 4, kRmTic = 5 };
+constexpr int64_t kRmapMaxParams = int64_t(1) << 28;   // parameter offsets the code holds; a longer parameter vector keeps the separate retraction launch (retract_request)
+__host__ __device__ inline int32_t lm_rmap_code(int kind, int64_t param_off) { return int32_t((param_off << 3) | kind); }
+
+struct RetractReq {
+  int on;                      // 0: no request (the solve leaves the step only)
+  const double* x; double* xc; // current / candidate parameters (ctl != nullptr: taken from the control block instead)
+  const int32_t* rmap;         // [P] entry map
+  NormalEq ne;                 // gradient (model cost change); ctl == nullptr: its cost slot is cleared for the candidate cost pass
+  double max_ab, max_gb, alpha;
 };
 
 // One rank's part of the distributed block cyclic reduction (kernels_bcr.hip: launch_bcr_dist_*; host side oicc_exchange.hip)

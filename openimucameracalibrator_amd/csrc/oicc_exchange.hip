@@ -199,10 +199,12 @@ int dist_solve(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb_in, d
   ++ds.solves; ds.last_step_gathered = true;
   return OICC_OK;
 }
-int lm_solve_any(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st) {
+// retract / fused: the retraction inside the solve's last launch (launch_bcr_solve); the distributed reduction never takes it
+int lm_solve_any(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st, const RetractReq* retract, bool* fused) {
   p->dist.last_step_gathered = false;
+  if (fused) *fused = false;
   if (p->shard_n > 1 && p->reduce != nullptr && dist_solve_usable(p)) return dist_solve(p, ne, sb, radius, reuse_diagonal, min_diag, max_diag, st);
-  if (launch_lm_solve(ne, p->tl, sb, radius, reuse_diagonal, min_diag, max_diag, st) != 0) {
+  if (launch_lm_solve(ne, p->tl, sb, radius, reuse_diagonal, min_diag, max_diag, st, retract, fused) != 0) {
     p->err = "band/arrow geometry exceeds the single-workgroup solver (half bandwidth or arrow too large for 160 KB LDS)"; return OICC_ERR_UNSUPPORTED; }
   return OICC_OK;
 }
@@ -443,6 +445,58 @@ int oicc_debug_lm_step(oicc_problem* p, int32_t flags, double radius, int32_t re
   HIPCK(p, hipMemcpyAsync(&hs, p->d_state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
   HIPCK(p, hipStreamSynchronize(st));
   *chol_failed = hs.chol_failed;
+  return OICC_OK;
+}
+// Debug read-out (outside include/oicc_hip.h; tests): ONE damped solve of the system at the current point WITH the retraction of the
+// trust-region candidate, as the LM loops run it (lm_solve_and_retract: inside the solve's last launch where the route, the plan
+// and option fused_retract allow, else lm_retract_kernel behind it), and then, for the same step_s, lm_retract_kernel alone.
+// The candidate buffer is filled with the byte 0xff (a NaN no retraction produces) before either, so whatever a retraction did not
+// write is still that pattern.  info = [1 if the retraction rode in the solve's last launch, P, length of the parameter vector,
+// n = ceil(Pb / 64)].  Copied out: the parameters x, the candidate and LmState's [model_cost_change, step_norm_sq, x_norm_sq] of
+// the loop's way (xc_loop, s_loop) and of the stand-alone kernel (xc_alone, s_alone), and step_s, scale, D2, g [P] for a host
+// recomputation.  x = NULL: info only (no pass, no solve; info[0] = 0).
+int oicc_debug_lm_retract(oicc_problem* p, int32_t flags, double radius, int64_t info[4], double* x, double* xc_loop, double s_loop[3],
+                          double* xc_alone, double s_alone[3], double* step_s, double* scale, double* D2, double* g) {
+  int rc = prepare(p, flags); if (rc) return rc;
+  const bool run = x != nullptr;
+  ARG(p, info != nullptr && radius > 0.0 && (!run || (xc_loop && s_loop && xc_alone && s_alone && step_s && scale && D2 && g)), "debug_lm_retract: arguments");
+  const TangentLayout& tl = p->tl;
+  ARG(p, tl.P > 0, "debug_lm_retract: no parameters");
+  const int64_t P = tl.P, N = p->pl.total;
+  info[0] = 0; info[1] = P; info[2] = N; info[3] = (tl.Pb + 63) / 64;
+  if (!run) return OICC_OK;
+  hipStream_t st = p->stream;
+  SolveBuffers sb = solve_buffers(p);
+  auto saved = p->reduce; p->reduce = nullptr;
+  rc = eval_pass(p, p->d_x.p, true); p->reduce = saved; if (rc) return rc;
+  launch_lm_scale(p->ne, tl, sb.scale, p->opt["jacobi_scaling"] != 0, st);
+  HIPCK(p, hipMemsetAsync(p->d_state.p, 0, sizeof(LmState), st));
+  auto d2h = [&](double* dst, const double* src, int64_t count) { return count <= 0 ? hipSuccess : hipMemcpyAsync(dst, src, size_t(count) * sizeof(double), hipMemcpyDeviceToHost, st); };
+  LmState hs;
+  HIPCK(p, hipMemsetAsync(p->d_xc.p, 0xff, size_t(N) * sizeof(double), st));
+  bool fused = false;
+  p->reduce = nullptr;
+  rc = lm_solve_and_retract(p, sb, radius, 0, p->opt["min_lm_diagonal"], p->opt["max_lm_diagonal"], st, &fused); p->reduce = saved; if (rc) return rc;
+  HIPCK(p, hipGetLastError());
+  HIPCK(p, d2h(xc_loop, p->d_xc.p, N));
+  HIPCK(p, hipMemcpyAsync(&hs, p->d_state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+  HIPCK(p, hipStreamSynchronize(st));
+  s_loop[0] = hs.model_cost_change; s_loop[1] = hs.step_norm_sq; s_loop[2] = hs.x_norm_sq;
+  const bool failed = hs.chol_failed != 0;
+  HIPCK(p, hipMemsetAsync(p->d_xc.p, 0xff, size_t(N) * sizeof(double), st));
+  HIPCK(p, hipMemsetAsync(&p->d_state.p->model_cost_change, 0, 3 * sizeof(double), st));   // model_cost_change, step_norm_sq, x_norm_sq
+  launch_lm_retract(p->d_x.p, p->d_xc.p, p->pl, tl, sb, p->ne, p->max_ab, p->max_gb, st, 1.0, 1, nullptr);
+  HIPCK(p, hipGetLastError());
+  HIPCK(p, d2h(xc_alone, p->d_xc.p, N)); HIPCK(p, d2h(x, p->d_x.p, N));
+  HIPCK(p, d2h(step_s, sb.step_s, P)); HIPCK(p, d2h(scale, sb.scale, P)); HIPCK(p, d2h(D2, sb.D2, P)); HIPCK(p, d2h(g, p->ne.g(), P));
+  HIPCK(p, hipMemcpyAsync(&hs, p->d_state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+  // the candidate buffer as every other entry expects it: equal to x on the inactive entries
+  HIPCK(p, hipMemcpyAsync(p->d_xc.p, p->d_x.p, size_t(N) * sizeof(double), hipMemcpyDeviceToDevice, st));
+  HIPCK(p, hipStreamSynchronize(st));
+  p->seg_invalidate(p->d_xc.p);
+  s_alone[0] = hs.model_cost_change; s_alone[1] = hs.step_norm_sq; s_alone[2] = hs.x_norm_sq;
+  info[0] = fused ? 1 : 0;
+  if (failed) { p->err = "debug_lm_retract: the factorisation failed"; return OICC_ERR_STATE; }
   return OICC_OK;
 }
 // debug read-out (outside include/oicc_hip.h; tests, bench.py): out4 = [distributed solves run so far, this rank's first block, its block count, ranks]

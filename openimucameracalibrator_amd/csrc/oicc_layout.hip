@@ -256,6 +256,19 @@ void make_layout_host(oicc_problem* p, int flags) {
     for (int32_t& o : L.pts) if (o == 0) { o = off; off += 3; L.a_pts += 3; }
   }
   L.P = off; L.a = off - L.Pb;
+  {   // entry map (oicc_device.h: RetractReq): the parameter block that starts at each tangent entry
+    L.rmap.assign(size_t(off), -1);
+    if (pl.total < kRmapMaxParams) {   // (else the codes do not hold the offsets: the map stays empty and retract_request keeps the request off)
+    for (int i = 0; i < pl.n_so3; ++i) if (L.so3[i] >= 0) L.rmap[L.so3[i]] = lm_rmap_code(kRmSo3, pl.so3 + 4 * int64_t(i));
+    auto eucl = [&](int o, int64_t po, int n) { if (o >= 0) for (int c = 0; c < n; ++c) L.rmap[o + c] = lm_rmap_code(kRmEucl, po + c); };
+    for (int i = 0; i < pl.n_r3; ++i) eucl(L.r3[i], pl.r3 + 3 * int64_t(i), 3);
+    for (int i = 0; i < pl.n_ab; ++i) if (L.ab[i] >= 0) L.rmap[L.ab[i]] = lm_rmap_code(kRmAb, pl.ab + 3 * int64_t(i));
+    for (int i = 0; i < pl.n_gb; ++i) if (L.gb[i] >= 0) L.rmap[L.gb[i]] = lm_rmap_code(kRmGb, pl.gb + 3 * int64_t(i));
+    for (size_t i = 0; i < L.pts.size(); ++i) if (L.pts[i] >= 0) L.rmap[L.pts[i]] = lm_rmap_code(kRmPt, pl.pts + 4 * int64_t(i));
+    if (L.other[0] >= 0) L.rmap[L.other[0]] = lm_rmap_code(kRmTic, pl.tic);
+    eucl(L.other[1], pl.g, 3); eucl(L.other[2], pl.ld, 1); eucl(L.other[3], pl.ai, 6); eucl(L.other[4], pl.gi, 9);
+    }
+  }
   int hb = 0;
   auto span = [&](int s_so3, int s_r3) {
     int lo = 1 << 30, hi = -1;
@@ -295,6 +308,7 @@ int make_layout_device(oicc_problem* p, int flags, std::thread* tiles_thread, in
   DevArena& LA = p->layout_arena;   // tangent offsets + every buffer of the normal equations and the solve: one block, one copy
   LA.add(p->d_tl_so3, L.so3); LA.add(p->d_tl_r3, L.r3); LA.add(p->d_tl_ab, L.ab); LA.add(p->d_tl_gb, L.gb);
   if (L.a_pts > 0) LA.add(p->d_tl_pts, L.pts);
+  LA.add(p->d_tl_rmap, L.rmap);
   TangentLayout& tl = p->tl;
   NormalEq& ne = p->ne;
   const int64_t nband = int64_t(tl.Pb) * tl.W;

@@ -84,6 +84,7 @@ struct HostLayout {
   std::vector<int32_t> so3, r3, ab, gb;
   int32_t other[5];
   int32_t P, Pb, a, hb;
+  std::vector<int32_t> rmap;   // [P] entry map of the retraction inside the solve's last launch (oicc_device.h: RetractReq)
   std::vector<int32_t> pts; int32_t a_pts = 0;   // SplineOptimFlags::POINTS: the last a_pts arrow columns (3 per observed board point, in point order)
 };
 
@@ -173,7 +174,7 @@ struct oicc_problem {
   DevBuf<int64_t> d_view_c0; DevBuf<uint8_t> d_view_rs, d_view_rs_all; std::vector<uint8_t> h_view_rs_all;
   DevArena meas_arena, layout_arena, tile_arena, plan_arena;   // one device block + one copy per group of arrays
   ImuDev d_acc, d_gyr;
-  DevBuf<int32_t> d_tl_so3, d_tl_r3, d_tl_ab, d_tl_gb, d_tl_pts;
+  DevBuf<int32_t> d_tl_so3, d_tl_r3, d_tl_ab, d_tl_gb, d_tl_pts, d_tl_rmap;
   DevBuf<double> d_ws;
   DevBuf<double> d_rank_pack;   // all-reduce hook path: [candidate | step scalars | rank count] (make_rank_consistent)
   DevBuf<double> d_ne2;   // second normal-equation buffer: the Jacobian pass at the candidate runs while the host decides
@@ -236,6 +237,7 @@ struct oicc_problem {
     opt["owner_computes_sweeps"] = 1;   // time-sharded ranks with the owner-computes exchange: a rank sweeps only the knot blocks it owns, owners broadcast after every set (0: replicated sweeps)
     opt["inner_shared_launch_slots"] = 65536;   // a block every view / sample depends on with at least this many item slots is minimised by a sequence of launches over the whole device instead of resident workgroups that wait for each other (0: never)
     opt["inner_wave_blocks"] = 0;   // inner sweeps, which sets run one WAVE per block (inner_wave_kernel) instead of one workgroup: 0 = sets of at least 4 x compute units knot blocks (throughput bound), 1 = every eligible set, 2 = none
+    opt["fused_retract"] = 1;   // 1: the last launch of the cyclic-reduction solve also retracts (kernels_bcr.hip) where that applies; 0: always lm_retract_kernel, a launch of its own (A/B runs, tests)
     opt["device_lm"] = 1;   // 1: plain Levenberg-Marquardt (no inner iterations / line search / collective) takes its trust-region decisions on the device
                             //    (LmCtl, lm_decide_kernel): the host enqueues iterations and polls a pinned word one iteration behind.  0: the host-driven loop
     opt["inner_shared_residency"] = 0.5;     // share of the device's resident workgroups the parts of a set's shared blocks (T_i_c, gravity, line delay, IMU intrinsics) may take together
@@ -303,6 +305,11 @@ int eval_pass(oicc_problem* p, const double* x, bool jac, double* dbg_res = null
               bool cost_already_zero = false, const NormalEq* target = nullptr, bool force_rs = false, long long* prof = nullptr, bool want_gmax = false,
               double* cost_out = nullptr, const LmCtl* ctl = nullptr);
 SolveBuffers solve_buffers(oicc_problem* p, long long* prof = nullptr);
+// the retraction d_x -> d_xc a solve may do inside its last launch (oicc_device.h: RetractReq); off (on = 0) with option
+// fused_retract = 0 and for problems whose retraction also writes the candidate's segment tables (multi-round problems keep the separate launch)
+RetractReq retract_request(oicc_problem* p);
+// solve + retraction of the trust-region candidate d_x -> d_xc: fused where the route allows, else lm_retract_kernel behind the solve
+int lm_solve_and_retract(oicc_problem* p, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st, bool* fused_out = nullptr);
 int read_cost(oicc_problem* p, double* cost);
 void rccl_release(oicc_problem* p);   // destroys the problem's communicator, if any
 int rccl_reduce_in_place(void* user, void* device_ptr, int64_t count, void* stream);
@@ -316,5 +323,5 @@ int shard_broadcast_end(oicc_problem* p);
 int owner_exchange(oicc_problem* p, const NormalEq& ne, hipStream_t st, int64_t* bytes_moved = nullptr);
 bool dist_solve_usable(const oicc_problem* p);   // (decided by the exchange agreement of the current layout: every rank answers alike; false before it)
 int dist_solve(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st);
-int lm_solve_any(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st);   // the distributed solve on agreed shards, else launch_lm_solve
+int lm_solve_any(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st, const RetractReq* retract = nullptr, bool* fused = nullptr);   // the distributed solve on agreed shards, else launch_lm_solve
 }  // namespace oicc

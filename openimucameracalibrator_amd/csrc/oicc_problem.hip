@@ -96,8 +96,26 @@ int read_cost(oicc_problem* p, double* cost) {
 }
 
 
-// ---- device-side LM control (oicc_device.h: LmCtl; kernels: the build kernels, lm_retract_kernel, tile_kernel, slab_merge_kernel,
-// lm_decide_kernel) ---------------------------------------------------------------------------------------------------------------
+RetractReq retract_request(oicc_problem* p) {
+  RetractReq R{};
+  R.on = (p->opt["fused_retract"] != 0.0 && !p->seg_precomputed() && p->d_tl_rmap.p != nullptr && p->pl.total < kRmapMaxParams) ? 1 : 0;
+  R.x = p->d_x.p; R.xc = p->d_xc.p; R.rmap = p->d_tl_rmap.p; R.ne = p->ne;
+  R.max_ab = p->max_ab; R.max_gb = p->max_gb; R.alpha = 1.0;
+  return R;
+}
+int lm_solve_and_retract(oicc_problem* p, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st, bool* fused_out) {
+  const RetractReq R = retract_request(p);
+  bool fused = false;
+  const int rc = lm_solve_any(p, p->ne, sb, radius, reuse_diagonal, min_diag, max_diag, st, &R, &fused); if (rc) return rc;
+  if (fused_out) *fused_out = fused;
+  oicc_problem::SegTable* sgt = p->seg_of(p->d_xc.p);
+  if (!fused) launch_lm_retract(p->d_x.p, p->d_xc.p, p->pl, p->tl, sb, p->ne, p->max_ab, p->max_gb, st, 1.0, 1, (sgt && p->seg_precomputed()) ? sgt->buf.p : nullptr);
+  if (sgt) sgt->valid = !fused && p->seg_precomputed();
+  return OICC_OK;
+}
+
+// ---- device-side LM control (oicc_device.h: LmCtl; kernels: the build kernels, the solve -- whose last launch retracts, else
+// lm_retract_kernel --, tile_kernel, slab_merge_kernel, lm_decide_kernel) ---------------------------------------------------------------------------------------------------------------
 static_assert(sizeof(LmIterRec) == sizeof(oicc_iteration) && offsetof(LmIterRec, trust_region_radius) == offsetof(oicc_iteration, trust_region_radius), "LmIterRec mirrors oicc_iteration");
 
 // Can this solve run under device-side control?  Plain LM on one rank with the tile assembly (the merge leaves max |g| in LmState).
@@ -130,9 +148,11 @@ int device_lm_enqueue(oicc_problem* p, SolveBuffers sb, double min_diag, double 
   LmCtl* const cur = p->d_ctl.p + (k & 1); LmState* const stc = p->d_state.p + (k & 1);
   sb.ctl = cur; sb.st = stc; sb.off_cost = p->ne.off_cost;
   sb.ctl_prev = k > 0 ? p->d_ctl.p + ((k - 1) & 1) : nullptr; sb.st_prev = k > 0 ? p->d_state.p + ((k - 1) & 1) : nullptr;
-  if (launch_lm_solve(p->ne, p->tl, sb, 0.0, 0, min_diag, max_diag, st) != 0) {
+  const RetractReq R = retract_request(p);   // (the buffers come from the control block; multi-round problems keep the separate launch, which also writes the segment tables)
+  bool fused = false;
+  if (launch_lm_solve(p->ne, p->tl, sb, 0.0, 0, min_diag, max_diag, st, &R, &fused) != 0) {
     p->err = "band/arrow geometry exceeds the single-workgroup solver (half bandwidth or arrow too large for 160 KB LDS)"; return OICC_ERR_UNSUPPORTED; }
-  launch_lm_retract(p->d_x.p, p->d_xc.p, p->pl, p->tl, sb, p->ne, p->max_ab, p->max_gb, st, 1.0, 1, p->seg_precomputed() ? p->seg_tab[0].buf.p : nullptr);
+  if (!fused) launch_lm_retract(p->d_x.p, p->d_xc.p, p->pl, p->tl, sb, p->ne, p->max_ab, p->max_gb, st, 1.0, 1, p->seg_precomputed() ? p->seg_tab[0].buf.p : nullptr);
   p->lm_state_cur = stc;
   const int rc = eval_pass(p, p->d_xc.p, true, nullptr, nullptr, -1, false, &p->ne2, false, nullptr, true, nullptr, cur);
   p->lm_state_cur = nullptr;
@@ -692,12 +712,9 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
 #endif
     HIPCK(p, hipEventRecord(ev[0], st));
     if (p->opt["debug_poison_lds"] != 0.0) launch_lds_poison(st);
-    rc = lm_solve_any(p, p->ne, sb, radius, reuse_diagonal ? 1 : 0, min_diag, max_diag, st); if (rc) return rc;   // (agreed shards: the distributed cyclic reduction, oicc_exchange.hip)
-    {   // the retraction also leaves the candidate's segment tables (one kernel fewer per cost pass)
-      oicc_problem::SegTable* sgt = p->seg_of(p->d_xc.p);
-      launch_lm_retract(p->d_x.p, p->d_xc.p, p->pl, tl, sb, p->ne, p->max_ab, p->max_gb, st, 1.0, 1, (sgt && p->seg_precomputed()) ? sgt->buf.p : nullptr);
-      if (sgt) sgt->valid = p->seg_precomputed();
-    }
+    // (agreed shards: the distributed cyclic reduction, oicc_exchange.hip.)  The retraction rides in the solve's last launch where the
+    // route allows; the separate launch also leaves the candidate's segment tables (one kernel fewer per cost pass)
+    rc = lm_solve_and_retract(p, sb, radius, reuse_diagonal ? 1 : 0, min_diag, max_diag, st); if (rc) return rc;
     HIPCK(p, hipGetLastError());
     // Several ranks: every rank solved the same (all-reduced) system, but the fp64 atomics of its own solve leave last-bit
     // differences in the step.  Rank 0's candidate parameters (<= 0.9 MB at C5) and its step scalars (model cost change, step
@@ -906,12 +923,7 @@ int oicc_run_lm_iterations(oicc_problem* p, int32_t flags, int32_t steps) {
     return OICC_OK;
   }
   for (int it = 0; it < steps; ++it) {
-    rc = lm_solve_any(p, p->ne, sb, p->opt["initial_trust_region_radius"], 0, p->opt["min_lm_diagonal"], p->opt["max_lm_diagonal"], st); if (rc) return rc;
-    {
-      oicc_problem::SegTable* sgt = p->seg_of(p->d_xc.p);
-      launch_lm_retract(p->d_x.p, p->d_xc.p, p->pl, tl, sb, p->ne, p->max_ab, p->max_gb, st, 1.0, 1, (sgt && p->seg_precomputed()) ? sgt->buf.p : nullptr);
-      if (sgt) sgt->valid = p->seg_precomputed();
-    }
+    rc = lm_solve_and_retract(p, sb, p->opt["initial_trust_region_radius"], 0, p->opt["min_lm_diagonal"], p->opt["max_lm_diagonal"], st); if (rc) return rc;
     if (p->reduce != nullptr && !(p->rccl_comm != nullptr && p->rccl_nranks <= 1)) {
       const bool same = p->dist.last_step_gathered;
       rc = make_rank_consistent(p, p->d_xc.p, true, st, same); if (rc) return rc;

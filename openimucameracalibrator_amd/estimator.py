@@ -405,6 +405,27 @@ class SplineTrajectoryEstimator:
             out.update(arr); out["chol_failed"] = bool(failed.value)
         return out
 
+    def DebugLmRetract(self, flags, radius=1e4, run=True):
+        """Debug read-out (device library only): one damped LM solve at the current point with the retraction of the candidate as the LM
+        loops run it -- inside the solve's last launch where the route, the plan and option fused_retract allow (`fused`), else the
+        retraction kernel behind it -- and the stand-alone retraction kernel on the same step.  The candidate buffer is filled with
+        0xff bytes before each, so entries no retraction wrote read back as that NaN.  Returns fused, n (blocks), the parameters x,
+        xc_loop / xc_alone, s_loop / s_alone = [model_cost_change, step_norm_sq, x_norm_sq], and step_s, scale, D2, g.
+        run=False: fused=False, P, N, n only."""
+        from . import _lib
+        fn = _lib.load_lm_retract().retract
+        info = (C.c_int64 * 4)()
+        self._ck(fn(self._h, int(flags), float(radius), info, *([None] * 9)))
+        P, N = int(info[1]), int(info[2])
+        out = dict(fused=False, P=P, N=N, n=int(info[3]))
+        if run:
+            arr = dict(x=np.zeros(N), xc_loop=np.zeros(N), s_loop=np.zeros(3), xc_alone=np.zeros(N), s_alone=np.zeros(3), step_s=np.zeros(P),
+                       scale=np.zeros(P), D2=np.zeros(P), g=np.zeros(P))
+            self._ck(fn(self._h, int(flags), float(radius), info,
+                        *(_dp(arr[k]) for k in ("x", "xc_loop", "s_loop", "xc_alone", "s_alone", "step_s", "scale", "D2", "g"))))
+            out.update(arr); out["fused"] = bool(info[0])
+        return out
+
     def TimeExchange(self, flags, repeats=10):
         """(ms per owner-computes exchange of the packed normal equations, bytes this rank moved); a collective: every rank calls it."""
         ms = C.c_double(0.0); nb = C.c_int64(0)
