@@ -393,6 +393,45 @@ int oicc_time_linear_solve(oicc_problem* p, int32_t flags, int32_t repeats,
  * M = S JtJ S + clamp(diag)/radius, rhs = -S Jtr (S: Jacobi scaling). */
 int oicc_solve_residual(oicc_problem* p, int32_t flags, double radius, double out[3]);
 
+/* ---- covariance estimation -------------------------------------------------
+ * What ceres::Covariance returns with the local parameterisations (the reference asks it for the board points only,
+ * src/core/pose_estimator.cc:193-223): (J^T J)^-1 at the current parameters in the tangent space of
+ * oicc_get_tangent_layout (T_i_c: upsilon | omega of the right perturbation).  The residuals are already weighted.
+ * Computed on the device as a SELECTED inverse of the band + arrow normal equations of one Jacobian pass: the whole
+ * a x a arrow block, the 3 x 3 diagonal block of every knot and the 3 x a block of every knot with the arrow -- never
+ * a dense P x P inverse.  The matrix is scaled to unit diagonal first (S H S, s_i = H_ii^-1/2, no damping) and the
+ * result unscaled, cov_ij = s_i s_j Zs_ij.
+ *   status           OICC_COV_OK; OICC_COV_RANK_DEFICIENT: a pivot of the factorisation was not positive, or
+ *                    rcond < option covariance_min_rcond (1e-12): no covariance is handed out;
+ *                    OICC_COV_ZERO_COLUMN: a diagonal entry of J^T J is not finite and positive (oicc_last_error
+ *                    names the column)
+ *   rcond            1 / max_i Zs_ii over all P diagonal entries: lambda_min(S H S) <= rcond <= P lambda_min(S H S)
+ *   variance_factor  2 cost / (num_residuals - P), num_residuals = 2 corners + 3 accelerometer + 3 gyroscope samples
+ *                    of the accepted measurements; returned separately, nothing is multiplied by it
+ * oicc_estimate_covariance returns OICC_OK for each of the three statuses (info->status tells them apart) and
+ * OICC_ERR_UNSUPPORTED, with the reason in oicc_last_error, for OICC_POINTS in flags (the board gauge makes J^T J
+ * singular), time-sharded problems (oicc_set_shard) and problems with a reduction across ranks installed (oicc_set_allreduce,
+ * oicc_rccl_init), a half bandwidth above 120 and more than 63 arrow columns.
+ * The getters return OICC_ERR_STATE unless the last estimate has status OICC_COV_OK and still belongs to the current
+ * parameters: any setter, Add*Measurement, oicc_set_option and oicc_optimize invalidate it. */
+typedef enum oicc_covariance_status { OICC_COV_OK = 0, OICC_COV_RANK_DEFICIENT = 1, OICC_COV_ZERO_COLUMN = 2 } oicc_covariance_status;
+typedef struct oicc_covariance_info {
+  int32_t status, P, Pb, a, hb;
+  int64_t num_residuals;
+  double cost, variance_factor, rcond;
+} oicc_covariance_info;
+int oicc_estimate_covariance(oicc_problem* p, int32_t flags, oicc_covariance_info* info);
+/* cov [a][a] row major, in the arrow order of oicc_get_tangent_layout; a_capacity >= a */
+int oicc_get_covariance_arrow(const oicc_problem* p, double* cov, int32_t a_capacity);
+/* the 3 x 3 diagonal blocks of the knots, 9 doubles per knot (row major), NaN for knots outside the active set;
+ * either pointer may be NULL; n_so3 / n_r3 = the knot counts */
+int oicc_get_covariance_knots(const oicc_problem* p, double* so3_blocks, int64_t n_so3, double* r3_blocks, int64_t n_r3);
+/* cross [3][a]: the covariance of one knot (kind 0 = SO(3), 1 = R^3) with the arrow; NaN outside the active set */
+int oicc_get_covariance_knot_arrow(const oicc_problem* p, int32_t kind, int64_t knot, double* cross);
+/* Device time of the last estimate's kernels in ms: build, forward factor, arrow corner, backward sweep (with the
+ * knot / cross block kernel behind it). */
+int oicc_get_covariance_timing(const oicc_problem* p, double ms[4]);
+
 /* ---- read-back: mirrors the getters ------------------------------------- */
 int oicc_get_T_i_c(const oicc_problem* p, double q_xyzw_t_xyz[7]);  /* impl.h:1133 */
 int oicc_get_gravity(const oicc_problem* p, double g[3]);           /* impl.h:1128 */
@@ -555,6 +594,12 @@ int oicc_ba_get_iterations(const oicc_ba* p, oicc_iteration* out, int32_t cap);
  * view runs that view's whole Levenberg-Marquardt loop.  iterations / final_cost: [nv] or NULL; a view without
  * observations, or whose residuals cannot be evaluated at the start, is left untouched and reports -1 / NaN. */
 int oicc_ba_optimize_views(oicc_ba* p, int32_t max_iters, int32_t flags, int32_t* iterations, double* final_cost);
+/* The covariances the reference takes from theia::BundleAdjustTracks / ceres::Covariance [EXT] after the board point refinement
+ * (pose_estimator.cc:193-223): for OICC_BA_POINTS with every camera constant the 3 x 3 diagonal blocks of J^T J are independent, and
+ * cov9 [n][9] receives the inverse of every variable point's block at the current parameters (tangent space of the homogeneous
+ * point, robustified residuals as oicc_ba_evaluate), NaN for constant points; n = the number of scene points.
+ * variance_factor (may be NULL) = 2 cost / (2 observations - 3 variable points); nothing is multiplied by it. */
+int oicc_ba_point_covariances(oicc_ba* p, double* cov9, int64_t n, double* variance_factor);
 /* GetReprojErrorOfView for every view: mean pixel distance of its observations, [nv] */
 int oicc_ba_view_reprojection_errors(oicc_ba* p, double* mean_px);
 

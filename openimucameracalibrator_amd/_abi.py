@@ -49,6 +49,15 @@ class Iteration(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CovarianceInfo(C.Structure):
+    """oicc_covariance_info (include/oicc_hip.h)."""
+    _fields_ = [("status", C.c_int32), ("P", C.c_int32), ("Pb", C.c_int32), ("a", C.c_int32), ("hb", C.c_int32),
+                ("num_residuals", C.c_int64), ("cost", C.c_double), ("variance_factor", C.c_double), ("rcond", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p)   # oicc_exchange_fn
 
@@ -121,6 +130,11 @@ DEVICE_ONLY = {
     "set_shard": (C.c_int, [H, C.c_int32, C.c_int32]),
     "set_exchange": (C.c_int, [H, EXCHANGE_FN, C.c_void_p]),
     "declare_remote_measurements_from": (C.c_int, [H, C.c_int32, C.c_int32, C.c_int64, c_i64p]),
+    "estimate_covariance": (C.c_int, [H, C.c_int32, C.POINTER(CovarianceInfo)]),
+    "get_covariance_arrow": (C.c_int, [H, c_dp, C.c_int32]),
+    "get_covariance_knots": (C.c_int, [H, c_dp, C.c_int64, c_dp, C.c_int64]),
+    "get_covariance_knot_arrow": (C.c_int, [H, C.c_int32, C.c_int64, c_dp]),
+    "get_covariance_timing": (C.c_int, [H, c_dp]),
     "sew_knot_spacing_and_variance": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, c_dp, c_dp, C.c_double, C.c_double, C.c_double,
                                                 c_dp, c_dp, c_i32p]),
 }
@@ -147,7 +161,10 @@ BA_SIGNATURES = {
     "get_iterations": (C.c_int, [HB, C.POINTER(Iteration), C.c_int32]),
     "optimize_views": (C.c_int, [HB, C.c_int32, C.c_int32, c_i32p, c_dp]),
     "view_reprojection_errors": (C.c_int, [HB, c_dp]),
+    "point_covariances": (C.c_int, [HB, c_dp, C.c_int64, c_dp]),
 }
+# Entries of BA_SIGNATURES that only the device library has: the CPU checker, bound with the same table, has no counterpart.
+BA_DEVICE_ONLY = ("point_covariances",)
 
 
 class BoundBa:
@@ -157,6 +174,8 @@ class BoundBa:
         self.lib = lib
         self.prefix = prefix
         for name, (res, args) in BA_SIGNATURES.items():
+            if name in BA_DEVICE_ONLY and prefix != "oicc_ba_" and not hasattr(lib, prefix + name):
+                continue
             fn = getattr(lib, prefix + name)  # AttributeError = missing symbol: fail loudly
             fn.restype = res
             fn.argtypes = args

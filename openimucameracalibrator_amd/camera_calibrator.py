@@ -11,8 +11,8 @@ flat numpy arrays in the layout the C-ABI takes.  The RANSAC pose / focal-length
 (camera_calibrator.cc:247-316, pose_estimator.cc:54-83, TheiaSfM minimal solvers [EXT]) has a counterpart of its own:
 with robust_init=True the corners of every view go through oicc_planar_ransac (robust_init.py, all views in one launch)
 and only the inliers become observations; the start values stay the closed forms of planar_init.py.  The default
-(robust_init=False) uses every corner.  What stays outside (named, not silently skipped): the empirical point
-covariances PoseEstimator::OptimizeBoardPoints prints (ceres::Covariance, pose_estimator.cc:209-223).
+(robust_init=False) uses every corner.  The empirical point covariances PoseEstimator::OptimizeBoardPoints prints
+(ceres::Covariance, pose_estimator.cc:209-223) come from oicc_ba_point_covariances (PoseEstimator.GetBoardPointCovariances).
 """
 import ctypes as C
 
@@ -193,6 +193,14 @@ class ViewBundleAdjuster:
         s = _abi.Summary()
         self._ck(self.b.optimize(self.h, int(max_iters), int(flags), int(mask), C.byref(s)))
         return s.as_dict()
+
+    def PointCovariances(self):
+        """oicc_ba_point_covariances: ([n, 3, 3] inverse of every variable point's block of J^T J under BA_POINTS with constant
+        cameras -- NaN for constant points --, variance factor 2 cost / (2 observations - 3 variable points)).  The blocks are
+        not multiplied by the variance factor."""
+        cov = np.zeros((self.np_, 3, 3)); vf = C.c_double()
+        self._ck(self.b.point_covariances(self.h, _dp(cov), self.np_, C.byref(vf)))
+        return cov, vf.value
 
     def Iterations(self, cap=256):
         arr = (_abi.Iteration * cap)()
@@ -579,18 +587,52 @@ class PoseEstimator:
         theia::WriteReconstruction."""
         return list(self.views.t_s), self.Poses(), self.points
 
-    def OptimizeBoardPoints(self, min_num_obs_for_optim=30):
-        """pose_estimator.cc:192-224: BundleAdjustTracks over the tracks seen in more than 30 views, cameras constant
-        (the empirical covariances the reference prints afterwards are not computed)."""
+    def _upload_board_point_problem(self, min_num_obs_for_optim):
         pose, off, uv, pid = self.views.flat()
         counts = np.bincount(pid, minlength=len(self.points))
         self.ba.SetCamera(self.model, self.intr)
         self.ba.SetScenePoints(self.points)
         self.ba.SetViews(pose, off, uv, pid)
         self.ba.SetVariablePoints((counts > min_num_obs_for_optim).astype(np.uint8))
+
+    def OptimizeBoardPoints(self, min_num_obs_for_optim=30):
+        """pose_estimator.cc:192-224: BundleAdjustTracks over the tracks seen in more than 30 views, cameras constant
+        (the empirical covariances the reference prints afterwards: GetBoardPointCovariances)."""
+        self._upload_board_point_problem(min_num_obs_for_optim)
         s = self.ba.Optimize(self.max_num_iterations, BA_POINTS, 0)
         self.points = self.ba.GetScenePoints()
+        # the covariances at the refined points, on the problem that is on the device already (GetBoardPointCovariances hands them out)
+        self.board_point_covariances_ = self.ba.PointCovariances() if hasattr(self.ba.b, "point_covariances") else None
         return s
+
+    def GetBoardPointCovariances(self, min_num_obs_for_optim=30):
+        """What pose_estimator.cc:193-223 takes from theia::BundleAdjustTracks (ceres::Covariance [EXT]): (covariances [n, 3, 3], NaN
+        for the tracks that were not optimised; empirical variance factor) -- as OptimizeBoardPoints left them (the refined points,
+        the poses it ran with), else computed at the current points and poses.  Our definition --
+        Theia's own cannot be read here: the covariance of a track is the inverse of its 3 x 3 block of J^T J (cameras constant, so
+        the blocks are independent; tangent space of the homogeneous point, robustified residuals) and the variance factor is
+        2 cost / (2 observations - 3 optimised tracks).  The blocks are NOT multiplied by the variance factor;
+        print_board_point_covariances reports sqrt(variance factor * diagonal)."""
+        if getattr(self, "board_point_covariances_", None) is not None:   # as OptimizeBoardPoints left them
+            return self.board_point_covariances_
+        self._upload_board_point_problem(min_num_obs_for_optim)
+        return self.ba.PointCovariances()
+
+    def PrintBoardPointCovariances(self, min_num_obs_for_optim=30, out=None):
+        """The three kinds of line the reference prints after the board point optimisation (pose_estimator.cc:212-223)."""
+        import sys
+        out = out or sys.stdout
+        cov, vf = self.GetBoardPointCovariances(min_num_obs_for_optim)
+        print("Empirical variance factor after board point optimization: %g" % vf, file=out)
+        stds = []
+        for i in range(len(cov)):
+            if np.isfinite(cov[i]).all():
+                sd = np.sqrt(vf * np.diag(cov[i])) * 1e3
+                stds.append(sd)
+                print("Track Id: %d std dev: %g %g %g mm" % (i, sd[0], sd[1], sd[2]), file=out)
+        mean = np.mean(stds, axis=0) if stds else np.full(3, np.nan)
+        print("Mean board point standard deviation after optimization: %g %g %g mm" % tuple(mean), file=out)
+        return cov, vf
 
     def Poses(self):
         return np.asarray(self.views.pose).reshape(-1, 6)

@@ -105,6 +105,12 @@ class ViewBundleAdjuster {   // theia::BundleAdjuster for one shared camera and 
   }
   void SetVariablePoints(const std::vector<uint8_t>& mask) { Check(oicc_ba_set_variable_points(h_, mask.data(), int64_t(mask.size()))); }
   oicc_summary Optimize(int max_iters, int flags, int mask) { oicc_summary s; Check(oicc_ba_optimize(h_, max_iters, flags, mask, &s)); return s; }
+  // oicc_ba_point_covariances: 9 doubles per scene point (NaN for constant points), not multiplied by the variance factor
+  std::vector<double> PointCovariances(size_t num_points, double* variance_factor) {
+    std::vector<double> cov(9 * num_points, 0.0);
+    Check(oicc_ba_point_covariances(h_, cov.data(), int64_t(num_points), variance_factor));
+    return cov;
+  }
   void OptimizeViews(int max_iters, std::vector<int32_t>* it, std::vector<double>* cost) {
     it->resize(size_t(nv_)); cost->resize(size_t(nv_));
     Check(oicc_ba_optimize_views(h_, max_iters, OICC_BA_POSITION | OICC_BA_ORIENTATION, it->data(), cost->data()));
@@ -209,24 +215,52 @@ class PoseEstimator {   // bundle-adjustment half of pose_estimator.cc: poses of
     ba_.OptimizeViews(100, &it, &cost);
     ba_.Download(nullptr, &views_);
   }
-  // pose_estimator.cc:192-224: BundleAdjustTracks over the tracks with more than 30 observations, cameras constant (the
-  // empirical covariances the reference prints afterwards are not computed)
+  // pose_estimator.cc:192-224: BundleAdjustTracks over the tracks with more than 30 observations, cameras constant, then the
+  // empirical covariances the reference prints afterwards (:212-223)
   void OptimizeBoardPoints(size_t min_num_obs_for_optim = 30) {
     if (views_.pose.empty()) return;
+    UploadBoardPointProblem(min_num_obs_for_optim);
+    const oicc_summary s = ba_.Optimize(100, OICC_BA_POINTS, 0);
+    ba_.DownloadPoints(&points_);
+    std::cout << "Board point optimization: cost " << s.initial_cost << " -> " << s.final_cost << " in " << s.num_iterations << " iterations\n";
+    // the covariances at the refined points, on the problem that is on the device already
+    board_point_cov_ = ba_.PointCovariances(points_.size(), &board_point_variance_factor_);
+    const double variance_factor = board_point_variance_factor_;
+    const std::vector<double>& cov = board_point_cov_;
+    std::cout << "Empirical variance factor after board point optimization: " << variance_factor << "\n";
+    double mean[3] = {0, 0, 0}; size_t n = 0;
+    for (size_t i = 0; i < points_.size(); ++i) {
+      if (std::isnan(cov[9 * i])) continue;
+      const double sd[3] = {std::sqrt(variance_factor * cov[9 * i]) * 1e3, std::sqrt(variance_factor * cov[9 * i + 4]) * 1e3, std::sqrt(variance_factor * cov[9 * i + 8]) * 1e3};
+      for (int c = 0; c < 3; ++c) mean[c] += sd[c];
+      ++n;
+      std::cout << "Track Id: " << i << " std dev: " << sd[0] << " " << sd[1] << " " << sd[2] << " mm\n";
+    }
+    for (double& m : mean) m = n ? m / double(n) : std::nan("");
+    std::cout << "Mean board point standard deviation after optimization: " << mean[0] << " " << mean[1] << " " << mean[2] << " mm\n";
+  }
+  // What the reference takes from theia::BundleAdjustTracks (ceres::Covariance [EXT]): 9 doubles per track, NaN for the tracks that are
+  // not optimised, and the empirical variance factor.  Our definition (Theia's cannot be read here): the inverse of the track's 3 x 3
+  // block of J^T J (cameras constant; tangent space of the homogeneous point) and 2 cost / (2 observations - 3 optimised tracks);
+  // the blocks are not multiplied by the factor, the printed standard deviations are sqrt(factor * diagonal).
+  std::vector<double> GetBoardPointCovariances(double* variance_factor, size_t min_num_obs_for_optim = 30) {
+    if (board_point_cov_.size() == 9 * points_.size() && !points_.empty()) { if (variance_factor) *variance_factor = board_point_variance_factor_; return board_point_cov_; }   // as OptimizeBoardPoints left them
+    UploadBoardPointProblem(min_num_obs_for_optim);
+    return ba_.PointCovariances(points_.size(), variance_factor);
+  }
+  BaViews& Views() { return views_; }
+  const std::vector<std::array<double, 4>>& Points() const { return points_; }
+ private:
+  void UploadBoardPointProblem(size_t min_num_obs_for_optim) {
     std::vector<size_t> nobs(points_.size(), 0);
     for (const auto& o : views_.obs) for (const auto& e : o) ++nobs[size_t(e[0])];
     std::vector<uint8_t> mask(points_.size(), 0);
     for (size_t i = 0; i < points_.size(); ++i) mask[i] = nobs[i] > min_num_obs_for_optim ? 1 : 0;
     ba_.Upload(OICC_CAM_PINHOLE, {1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0}, points_, views_);
     ba_.SetVariablePoints(mask);
-    const oicc_summary s = ba_.Optimize(100, OICC_BA_POINTS, 0);
-    ba_.DownloadPoints(&points_);
-    std::cout << "Board point optimization: cost " << s.initial_cost << " -> " << s.final_cost << " in " << s.num_iterations << " iterations\n";
   }
-  BaViews& Views() { return views_; }
-  const std::vector<std::array<double, 4>>& Points() const { return points_; }
- private:
   ViewBundleAdjuster ba_; BaViews views_; std::vector<std::array<double, 4>> points_;
+  std::vector<double> board_point_cov_; double board_point_variance_factor_ = 0.0;
 };
 
 }  // namespace core

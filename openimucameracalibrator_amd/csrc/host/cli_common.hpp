@@ -16,6 +16,28 @@ namespace oicc_cli {
 using namespace OpenICC;
 using oicc_json::Value;
 
+// The object "covariance" of a calibration result: status and rcond always; with status "ok" the variance factor, the names of the
+// arrow columns, the a x a matrix (J^T J)^-1 and the named standard deviations (sqrt(variance_factor * diagonal) when sd.scaled).
+// A rank-deficient estimate is {"status": "rank_deficient", "rcond": ...}: the calibration itself succeeded.
+inline Value covariance_json(const CalibrationStdDevs& sd) {
+  Value cv;
+  cv["status"] = Value(sd.status); cv["rcond"] = Value(sd.rcond);
+  if (sd.status != "ok") return cv;
+  auto arr = [](const std::vector<double>& v) { Value o; o.type = Value::Array; for (double x : v) o.push_back(Value(x)); return o; };
+  cv["variance_factor"] = Value(sd.variance_factor);
+  cv["scaled"] = Value(sd.scaled);
+  Value order; order.type = Value::Array; for (const std::string& n : sd.tangent_order) order.push_back(Value(n));
+  cv["tangent_order"] = order;
+  Value M; M.type = Value::Array;
+  for (int r = 0; r < sd.a; ++r) M.push_back(arr(std::vector<double>(sd.covariance.begin() + size_t(r) * size_t(sd.a), sd.covariance.begin() + size_t(r + 1) * size_t(sd.a))));
+  cv["matrix"] = M;
+  Value& st = cv["std_devs"]; st.type = Value::Object;
+  const std::pair<const char*, const std::vector<double>*> named[] = {{"t_i_c_m", &sd.t_i_c}, {"q_i_c_rad", &sd.q_i_c}, {"gravity", &sd.gravity},
+    {"line_delay_s", &sd.line_delay}, {"accl_intrinsics", &sd.accl_intrinsics}, {"gyro_intrinsics", &sd.gyro_intrinsics}, {"accl_bias", &sd.accl_bias}, {"gyro_bias", &sd.gyro_bias}};
+  for (const auto& kv : named) if (!kv.second->empty()) st[kv.first] = arr(*kv.second);
+  return cv;
+}
+
 // gflags-style command line: --name=value, --name value, --bool / --nobool; the table gives names and defaults
 struct Flags {
   std::map<std::string, std::string> s;

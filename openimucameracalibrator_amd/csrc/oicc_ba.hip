@@ -21,6 +21,7 @@
 #include "oicc_device.h"
 #include "lm_launch.h"
 #include "ba_device.h"
+#include "covariance.h"
 
 using namespace oicc;
 
@@ -249,6 +250,23 @@ int oicc_ba_evaluate(oicc_ba* p, int32_t flags, int32_t mask, double* cost, doub
     for (int r = 0; r < tl.a; ++r) for (int c = 0; c < tl.a; ++c) H[size_t(tl.Pb + r) * Pcap + tl.Pb + c] = h[P.ne.off_C + size_t(r) * tl.a + c];
   }
   if (g) std::copy(h.begin() + P.ne.off_g, h.begin() + P.ne.off_g + tl.P, g);
+  return OICC_OK;
+}
+
+// ceres::Covariance of the board points after theia::BundleAdjustTracks (pose_estimator.cc:193-223): with every camera constant the
+// points' 3 x 3 blocks of J^T J are independent, so the covariance of a point is the inverse of its block (kernels_covariance.hip).
+int oicc_ba_point_covariances(oicc_ba* p, double* cov9, int64_t n, double* variance_factor) {
+  Prepared P; int rc = prepare(p, OICC_BA_POINTS, 0, &P); if (rc) return rc;
+  ARG(p, n == P.d.n_points && (cov9 != nullptr || n == 0), "point count mismatch");
+  rc = eval_pass(p, P, p->d_x.p, true); if (rc) return rc;
+  if (!p->d_out.resize(size_t(std::max<int64_t>(9 * n, 1)))) { p->err = "hipMalloc point covariances"; return OICC_ERR_HIP; }
+  launch_ba_point_covariances(P.ne.band(), p->d_point_tangent.p, n, p->d_out.p, p->stream);
+  HIPCK(p, hipGetLastError());
+  double cost = 0.0;
+  if (n > 0) HIPCK(p, hipMemcpyAsync(cov9, p->d_out.p, size_t(9 * n) * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  HIPCK(p, hipMemcpyAsync(&cost, P.ne.cost(), sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  HIPCK(p, hipStreamSynchronize(p->stream));
+  if (variance_factor) { const double dof = 2.0 * double(P.d.n_corners) - double(P.tl.P); *variance_factor = dof > 0.0 ? 2.0 * cost / dof : std::nan(""); }
   return OICC_OK;
 }
 

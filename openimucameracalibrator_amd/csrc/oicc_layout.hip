@@ -44,7 +44,7 @@ void rebuild_param_layout(oicc_problem* p, int64_t n_so3, int64_t n_r3, int64_t 
   keep(so3, pl.so3, 4 * n_so3); keep(r3, pl.r3, 3 * n_r3); keep(ab, pl.ab, 3 * n_ab); keep(gb, pl.gb, 3 * n_gb);
   std::memcpy(xs(p, pl.tic), T_i_c, sizeof(T_i_c)); std::memcpy(xs(p, pl.g), g, sizeof(g)); p->x[pl.ld] = ld;
   std::memcpy(xs(p, pl.ai), ai, sizeof(ai)); std::memcpy(xs(p, pl.gi), gi, sizeof(gi));
-  p->x_host_dirty = true; p->layout_flags = -1;
+  p->x_host_dirty = true; p->layout_flags = -1; p->cov.valid = false;
 }
 
 int sync_params_to_device(oicc_problem* p) {

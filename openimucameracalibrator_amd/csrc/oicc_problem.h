@@ -28,6 +28,7 @@
 #include "tiles.h"
 #include "inner_plan.h"
 #include "line_search.h"
+#include "covariance.h"
 
 
 namespace oicc {
@@ -219,6 +220,14 @@ struct oicc_problem {
   // layout_flags = -1 invalidates (measurements, knot counts, line delay set by the caller); otherwise the layout and the tiles are
   // rebuilt only when the flags, the zero-ness of the line delay (active_set) or an option changed since they were built
   int layout_flags = -1; bool layout_ld_zero = false; int64_t opt_gen = 0, layout_opt_gen = -1, layout_gen = 0;
+  // covariance estimate (oicc_covariance.hip): device buffers of the selected inverse and the host copy the getters hand out;
+  // valid = made at the current parameters, measurements and options (every setter and oicc_optimize clear it)
+  struct Cov { bool valid = false; int flags = 0; int P = 0, Pb = 0, a = 0; oicc_covariance_info info{};
+               std::vector<int32_t> so3, r3;                 // first band column of every knot, -1 outside the active set
+               std::vector<double> arrow, cov3, cross;       // [a][a], [Pb][3], [Pb][a]
+               DevBuf<double> d_s, d_Cs, d_Sc, d_Zaa, d_aa, d_zb, d_G, d_cov3, d_cross, d_zs; DevBuf<int32_t> d_flags;
+               double ms[4] = {0, 0, 0, 0};                  // device time of the last estimate: build, forward factor, corner, backward sweep + finish
+             } cov;
   HostLayout L; TangentLayout tl{}; TangentLayout tl_tiles{}; NormalEq ne{}; NormalEq ne2{};   // tl_tiles: tl without the point columns (SplineOptimFlags::POINTS), what the tile pass sees
   Active act{};
 
@@ -259,6 +268,7 @@ struct oicc_problem {
     opt["bcr_max_border"] = 64;        // arrow + rhs rows the block cyclic reduction accepts (kernels_bcr.hip: up to 64 by construction; round 2 held it at 32 until the panel hazard was settled, test_bcr_wide_borders_and_the_panel_hazard)
     opt["debug_check_ne"] = 0;   // 1: before every linear solve compare the current normal equations with a host copy taken when they became current
     opt["debug_sync"] = 0;       // 1: drain the stream after every pass (debugging of inter-kernel hazards)
+    opt["covariance_min_rcond"] = 1e-12;   // oicc_estimate_covariance: below this reciprocal condition estimate of the unit-diagonal normal equations no covariance is handed out (OICC_COV_RANK_DEFICIENT)
     opt["debug_poison_lds"] = 0; // 1: fill every CU's LDS with NaNs before each Jacobian / cost pass and each linear solve (tests)
   }
 };

@@ -29,6 +29,10 @@ def estimate_poses_from_json(scene, model, intrinsics, image_height, device=0, b
                              ransac_backend=ransac_backend, ransac_hypotheses=ransac_hypotheses)
     if optimize_board_points and pe.views.pose:
         pe.OptimizeBoardPoints()
+        if hasattr(pe.ba.b, "point_covariances"):
+            pe.PrintBoardPointCovariances()   # pose_estimator.cc:212-223
+        else:   # a backend other than liboicc_hip (the test suite's CPU checker) has no such entry
+            print("Board point covariances: not available from this backend, not printed")
         pe.OptimizeAllPoses()
     err = pe.FilterBadPoses()
     t_s, pose, points = pe.GetPoseDataset()

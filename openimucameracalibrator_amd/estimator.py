@@ -443,6 +443,44 @@ class SplineTrajectoryEstimator:
         self._ck(self._b.solve_residual(self._h, int(flags), float(radius), out))
         return out[0], out[1], bool(out[2])
 
+    # ---- covariance ---------------------------------------------------------
+    COV_OK, COV_RANK_DEFICIENT, COV_ZERO_COLUMN = 0, 1, 2
+    COV_STATUS_NAMES = ("ok", "rank_deficient", "zero_column")
+
+    def EstimateCovariance(self, flags):
+        """(J^T J)^-1 at the current parameters for `flags` (oicc_estimate_covariance: what ceres::Covariance returns with the local
+        parameterisations; the residuals are already weighted), computed on the device as a selected inverse.  Returns a dict:
+        info (status, P, Pb, a, hb, num_residuals, cost, variance_factor = 2 cost / (num_residuals - P), rcond), status_name, layout
+        (GetTangentLayout) and -- with status COV_OK only, else None -- arrow [a, a] in the arrow order of the layout, so3 / r3
+        [n, 3, 3]: the diagonal block of every knot (NaN outside the active set).  Nothing is multiplied by the variance factor.
+        Raises OiccError where the library answers OICC_ERR_UNSUPPORTED (POINTS, time shards, half bandwidth > 120)."""
+        info = _abi.CovarianceInfo()
+        self._ck(self._b.estimate_covariance(self._h, int(flags), C.byref(info)))
+        out = dict(info=info.as_dict(), status_name=self.COV_STATUS_NAMES[info.status], layout=self.GetTangentLayout(flags),
+                   message=self._b.last_error(self._h).decode() if info.status != self.COV_OK else "", arrow=None, so3=None, r3=None)
+        self._last_cov_a = int(info.a)
+        if info.status == self.COV_OK:
+            arrow = np.zeros((info.a, info.a)); so3 = np.zeros((self.GetNumSO3Knots(), 3, 3)); r3 = np.zeros((self.GetNumR3Knots(), 3, 3))
+            self._ck(self._b.get_covariance_arrow(self._h, _dp(arrow), info.a))
+            self._ck(self._b.get_covariance_knots(self._h, _dp(so3), len(so3), _dp(r3), len(r3)))
+            out.update(arrow=arrow, so3=so3, r3=r3)
+        return out
+
+    def GetCovarianceKnotArrow(self, kind, knot):
+        """The [3, a] covariance block of one knot (kind 0: SO(3), 1: R^3) with the arrow, of the last EstimateCovariance."""
+        a = int(getattr(self, "_last_cov_a", 0))
+        out = np.zeros((3, max(a, 1)))
+        rc = self._b.get_covariance_knot_arrow(self._h, int(kind), int(knot), _dp(out))
+        if rc != 0:
+            raise OiccError("no covariance estimate for the current parameters, or no such knot (status %d)" % rc)
+        return out[:, :a]
+
+    def CovarianceTiming(self):
+        """Device ms of the last estimate's kernels: build, forward factor, arrow corner, backward sweep."""
+        ms = np.zeros(4)
+        self._ck(self._b.get_covariance_timing(self._h, _dp(ms)))
+        return dict(build=ms[0], forward=ms[1], corner=ms[2], backward=ms[3])
+
     # ---- getters ------------------------------------------------------------
     def GetNumSO3Knots(self):
         return int(self._b.get_num_so3_knots(self._h))
@@ -702,6 +740,70 @@ class ImuCameraCalibrator:
         """imu_camera_calibrator.cc:163-168: returns the mean reprojection error."""
         self.summary = self.trajectory_.Optimize(iterations, optim_flags)
         return self.trajectory_.GetMeanReprojectionError()
+
+    def GetCalibrationStdDevs(self, flags, scaled=True):
+        """Named standard deviations of the calibration from SplineTrajectoryEstimator.EstimateCovariance(flags): the square roots of
+        the diagonal of the arrow covariance, each multiplied by sqrt(variance_factor) when `scaled`.  Keys (None where the block is
+        not in the active set): t_i_c [m] and q_i_c [rad] (upsilon | omega of the right perturbation of T_i_c), gravity, line_delay
+        [s], accl_intrinsics (6), gyro_intrinsics (9), accl_bias / gyro_bias ([knots, 3], NaN for knots outside the active set);
+        plus status, variance_factor, rcond, scaled, tangent_order (names of the arrow columns) and covariance (the unscaled
+        [a, a] arrow block).  A rank-deficient estimate returns status / rcond only."""
+        cov = self.trajectory_.EstimateCovariance(flags)
+        info = cov["info"]
+        out = dict(status=cov["status_name"], rcond=info["rcond"], variance_factor=info["variance_factor"], scaled=bool(scaled))
+        if info["status"] != SplineTrajectoryEstimator.COV_OK:
+            out["message"] = cov["message"]
+            return out
+        Pb, lay = info["Pb"], cov["layout"]
+        f = float(np.sqrt(info["variance_factor"])) if scaled else 1.0
+        d = f * np.sqrt(np.diag(cov["arrow"]))
+        order = [""] * info["a"]
+
+        def seg(name, o, n, first=0):
+            if o < 0:
+                return None
+            for k in range(n):
+                order[o - Pb + k] = "%s[%d]" % (name, first + k)
+            return d[o - Pb:o - Pb + n].copy()
+
+        def knots(name, offs):
+            v = np.full((len(offs), 3), np.nan)
+            for k, o in enumerate(offs):
+                if o >= 0:
+                    v[k] = seg("%s[%d]" % (name, k), int(o), 3)
+            return v if len(offs) and np.isfinite(v).any() else None
+        other = [int(o) for o in lay["other"]]
+        out["t_i_c"] = seg("T_i_c", other[0], 3)
+        out["q_i_c"] = seg("T_i_c", other[0] + 3, 3, 3) if other[0] >= 0 else None
+        out["gravity"] = seg("gravity", other[1], 3)
+        ld = seg("line_delay", other[2], 1)
+        out["line_delay"] = None if ld is None else float(ld[0])
+        out["accl_bias"] = knots("accl_bias", lay["accl_bias"])
+        out["gyro_bias"] = knots("gyro_bias", lay["gyro_bias"])
+        out["accl_intrinsics"] = seg("accl_intrinsics", other[3], 6)
+        out["gyro_intrinsics"] = seg("gyro_intrinsics", other[4], 9)
+        out["tangent_order"] = order
+        out["covariance"] = cov["arrow"]
+        return out
+
+    def CovarianceJson(self, flags, scaled=True):
+        """The object "covariance" of a calibration result, as csrc/host/cli_common.hpp covariance_json builds it from the C++ facade:
+        status and rcond always; with status "ok" variance_factor, scaled, tangent_order, matrix ([a][a], (J^T J)^-1) and std_devs
+        (t_i_c_m, q_i_c_rad, gravity, line_delay_s, accl_intrinsics, gyro_intrinsics, accl_bias, gyro_bias: the active ones; bias
+        knots flattened, None for entries outside the active set).  A rank-deficient estimate is {"status": "rank_deficient",
+        "rcond": ...}: the calibration itself succeeded."""
+        sd = self.GetCalibrationStdDevs(flags, scaled)
+        out = dict(status=sd["status"], rcond=float(sd["rcond"]))
+        if sd["status"] != "ok":
+            return out
+        flat = lambda v: [None if not np.isfinite(x) else float(x) for x in np.asarray(v, dtype=np.float64).reshape(-1)]
+        out.update(variance_factor=float(sd["variance_factor"]), scaled=bool(scaled), tangent_order=list(sd["tangent_order"]),
+                   matrix=[[float(x) for x in row] for row in sd["covariance"]], std_devs={})
+        for key, src in (("t_i_c_m", "t_i_c"), ("q_i_c_rad", "q_i_c"), ("gravity", "gravity"), ("line_delay_s", "line_delay"),
+                         ("accl_intrinsics", "accl_intrinsics"), ("gyro_intrinsics", "gyro_intrinsics"), ("accl_bias", "accl_bias"), ("gyro_bias", "gyro_bias")):
+            if sd[src] is not None:
+                out["std_devs"][key] = flat(sd[src])
+        return out
 
     def GetCalibratedRSLineDelay(self):
         return self.trajectory_.GetRSLineDelay()
