@@ -52,7 +52,7 @@ int oicc_estimate_covariance(oicc_problem* p, int32_t flags, oicc_covariance_inf
   if (tl.hb > kCovMaxHalfBandwidth) return unsupported(p, "half bandwidth " + std::to_string(tl.hb) + " exceeds " + std::to_string(kCovMaxHalfBandwidth) + " (the LDS window of the backward sweep)");
   if (a > kCovMaxArrow) return unsupported(p, std::to_string(a) + " arrow columns exceed " + std::to_string(kCovMaxArrow));
   ARG(p, P > 0, "no active parameters");
-  rc = eval_pass(p, p->d_x.p, true); if (rc) return rc;
+  rc = eval_pass(p, jacobian_pass(p->d_x.p)); if (rc) return rc;
 
   const size_t aa = std::max<size_t>(size_t(a) * a, 1), pb = std::max<size_t>(Pb, 1);
   if (!cv.d_s.resize(P) || !cv.d_Cs.resize(aa) || !cv.d_Sc.resize(aa) || !cv.d_Zaa.resize(aa) || !cv.d_aa.resize(aa) || !cv.d_zb.resize(pb * 3) ||

@@ -200,16 +200,16 @@ int dist_solve(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb_in, d
   return OICC_OK;
 }
 // retract / fused: the retraction inside the solve's last launch (launch_bcr_solve); the distributed reduction never takes it
-int lm_solve_any(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st, const RetractReq* retract, bool* fused) {
+int lm_solve_any(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st, const RetractReq* retract, bool* fused, bool local) {
   p->dist.last_step_gathered = false;
   if (fused) *fused = false;
-  if (p->shard_n > 1 && p->reduce != nullptr && dist_solve_usable(p)) return dist_solve(p, ne, sb, radius, reuse_diagonal, min_diag, max_diag, st);
+  if (!local && p->shard_n > 1 && p->reduce != nullptr && dist_solve_usable(p)) return dist_solve(p, ne, sb, radius, reuse_diagonal, min_diag, max_diag, st);
   if (launch_lm_solve(ne, p->tl, sb, radius, reuse_diagonal, min_diag, max_diag, st, retract, fused) != 0) {
     p->err = "band/arrow geometry exceeds the single-workgroup solver (half bandwidth or arrow too large for 160 KB LDS)"; return OICC_ERR_UNSUPPORTED; }
   return OICC_OK;
 }
 
-int owner_exchange(oicc_problem* p, const NormalEq& ne, hipStream_t st, int64_t* bytes_moved) {
+int owner_exchange(oicc_problem* p, const NormalEq& ne, hipStream_t st, bool full_system, int64_t* bytes_moved) {
   const oicc_problem::OwnerPlan& op = p->owner;
   const TangentLayout& tl = p->tl;
   const int n = p->shard_n, me = p->shard_rank, L = tl.W + tl.a + 1;
@@ -249,7 +249,7 @@ int owner_exchange(oicc_problem* p, const NormalEq& ne, hipStream_t st, int64_t*
   //     Slot k of the gather buffer belongs to rank k; native: one in-place ncclAllGather of equal (padded) slots, or one broadcast
   //     per owner where that entry point is missing; hook transport: one broadcast per owner.
   double* slots = p->d_xgather.p;   // (sized for the packed rows of the largest owned range on every rank: the gathered band fits)
-  if (!p->full_system && dist_solve_usable(p)) {
+  if (!full_system && dist_solve_usable(p)) {
     // distributed solve (round 6): the band rows stay where they are -- the owner eliminates them; every rank still needs the
     // diagonal (Jacobi scaling, Levenberg-Marquardt diagonal) and the gradient of ALL rows: two doubles per row
     const int64_t piece2 = int64_t(std::max(op.max_owned, 1)) * 2;
@@ -293,7 +293,6 @@ int owner_exchange(oicc_problem* p, const NormalEq& ne, hipStream_t st, int64_t*
 
 }  // namespace oicc
 
-namespace { struct EventPair { hipEvent_t a = nullptr, b = nullptr; ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } }; }   // (destroyed on every exit of the timing entry points)
 namespace oicc {
 // The emulated distributed cyclic reduction (oicc_debug_dist_solve_emulated, oicc_debug_lm_step): applicable to nranks ranks?
 static bool dist_emulated_applies(const oicc_problem* p, int nranks) {
@@ -386,23 +385,11 @@ int oicc_set_exchange(oicc_problem* p, oicc_exchange_fn fn, void* user) { p->exc
 // device: what ONE rank of an N-GPU run spends in the solve besides the two gathers).  Block ranges: equal split of the blocks.
 int oicc_debug_dist_solve_emulated(oicc_problem* p, int32_t flags, int32_t nranks, double radius, int32_t repeats, double* out) {
   int rc = prepare(p, flags); if (rc) return rc;
-  hipStream_t st = p->stream;
-  auto saved = p->reduce; p->reduce = nullptr;
-  rc = eval_pass(p, p->d_x.p, true); p->reduce = saved; if (rc) return rc;
-  const TangentLayout& tl = p->tl;
   ARG(p, out != nullptr && dist_emulated_applies(p, nranks), "distributed solve: ranks / geometry");
   SolveBuffers sb = solve_buffers(p); sb.radius = radius;
-  launch_lm_scale(p->ne, tl, sb.scale, p->opt["jacobi_scaling"] != 0, st);
-  HIPCK(p, hipMemsetAsync(p->d_state.p, 0, sizeof(LmState), st));
+  rc = system_at_current_point(p, local_pass(p->d_x.p, true), sb.scale, p->opt["jacobi_scaling"] != 0, 0.0); if (rc) return rc;
   rc = dist_solve_emulated(p, sb, nranks, 0, std::max<int>(repeats, 1), out + 2); if (rc) return rc;
-  DevBuf<double> acc; if (!acc.resize(2 + size_t(tl.a))) return OICC_ERR_HIP;
-  launch_lm_solve_residual(p->ne, tl, sb, acc.p, st);
-  double h[2] = {0, 0}; LmState hs;
-  HIPCK(p, hipMemcpyAsync(h, acc.p, sizeof(h), hipMemcpyDeviceToHost, st));
-  HIPCK(p, hipMemcpyAsync(&hs, p->d_state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
-  HIPCK(p, hipStreamSynchronize(st));
-  out[0] = h[1] > 0.0 ? std::sqrt(h[0] / h[1]) : std::sqrt(h[0]); out[1] = double(hs.chol_failed);
-  return OICC_OK;
+  return read_solve_residual(p, sb, &out[0], nullptr, &out[1]);
 }
 // Debug read-out (outside include/oicc_hip.h; tests): ONE damped solve of the system at the current point, as oicc_solve_residual runs
 // it, and everything a host reference needs to redo it.  nranks = 0: the route the options select (lm_solve_route); nranks >= 2: the
@@ -426,10 +413,7 @@ int oicc_debug_lm_step(oicc_problem* p, int32_t flags, double radius, int32_t re
   if (!solve) return OICC_OK;
   ARG(p, route.route != kRouteNone, "debug_lm_step: solver geometry unsupported");
   hipStream_t st = p->stream;
-  auto saved = p->reduce; p->reduce = nullptr;
-  rc = eval_pass(p, p->d_x.p, true); p->reduce = saved; if (rc) return rc;
-  launch_lm_scale(p->ne, tl, sb.scale, p->opt["jacobi_scaling"] != 0, st);
-  HIPCK(p, hipMemsetAsync(p->d_state.p, 0, sizeof(LmState), st));
+  rc = system_at_current_point(p, local_pass(p->d_x.p, true), sb.scale, p->opt["jacobi_scaling"] != 0, 0.0); if (rc) return rc;
   if (p->opt["debug_poison_lds"] != 0.0) launch_lds_poison(st);
   const double min_diag = p->opt["min_lm_diagonal"], max_diag = p->opt["max_lm_diagonal"];
   if (nranks == 0) {
@@ -467,16 +451,12 @@ int oicc_debug_lm_retract(oicc_problem* p, int32_t flags, double radius, int64_t
   if (!run) return OICC_OK;
   hipStream_t st = p->stream;
   SolveBuffers sb = solve_buffers(p);
-  auto saved = p->reduce; p->reduce = nullptr;
-  rc = eval_pass(p, p->d_x.p, true); p->reduce = saved; if (rc) return rc;
-  launch_lm_scale(p->ne, tl, sb.scale, p->opt["jacobi_scaling"] != 0, st);
-  HIPCK(p, hipMemsetAsync(p->d_state.p, 0, sizeof(LmState), st));
+  rc = system_at_current_point(p, local_pass(p->d_x.p, true), sb.scale, p->opt["jacobi_scaling"] != 0, 0.0); if (rc) return rc;
   auto d2h = [&](double* dst, const double* src, int64_t count) { return count <= 0 ? hipSuccess : hipMemcpyAsync(dst, src, size_t(count) * sizeof(double), hipMemcpyDeviceToHost, st); };
   LmState hs;
   HIPCK(p, hipMemsetAsync(p->d_xc.p, 0xff, size_t(N) * sizeof(double), st));
   bool fused = false;
-  p->reduce = nullptr;
-  rc = lm_solve_and_retract(p, sb, radius, 0, p->opt["min_lm_diagonal"], p->opt["max_lm_diagonal"], st, &fused); p->reduce = saved; if (rc) return rc;
+  rc = lm_solve_and_retract(p, sb, radius, 0, p->opt["min_lm_diagonal"], p->opt["max_lm_diagonal"], st, &fused, /*local=*/true); if (rc) return rc;
   HIPCK(p, hipGetLastError());
   HIPCK(p, d2h(xc_loop, p->d_xc.p, N));
   HIPCK(p, hipMemcpyAsync(&hs, p->d_state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
@@ -536,9 +516,9 @@ int oicc_time_exchange(oicc_problem* p, int32_t flags, int32_t repeats, double* 
   HIPCK(p, hipMemsetAsync(p->d_ne2.p, 0, p->ne.total * sizeof(double), st));   // (the second buffer: the current system stays intact)
   EventPair ev; HIPCK(p, hipEventCreate(&ev.a)); HIPCK(p, hipEventCreate(&ev.b)); hipEvent_t e0 = ev.a, e1 = ev.b;
   int64_t moved = 0;
-  rc = owner_exchange(p, p->ne2, st, &moved); if (rc) return rc;                  // warm-up (connection set-up)
+  rc = owner_exchange(p, p->ne2, st, false, &moved); if (rc) return rc;                  // warm-up (connection set-up)
   HIPCK(p, hipEventRecord(e0, st));
-  for (int i = 0; i < repeats; ++i) { rc = owner_exchange(p, p->ne2, st, &moved); if (rc) return rc; }
+  for (int i = 0; i < repeats; ++i) { rc = owner_exchange(p, p->ne2, st, false, &moved); if (rc) return rc; }
   HIPCK(p, hipEventRecord(e1, st)); HIPCK(p, hipEventSynchronize(e1));
   float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
   if (ms_per_call) *ms_per_call = double(ms) / std::max(repeats, 1);

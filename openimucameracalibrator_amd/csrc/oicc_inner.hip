@@ -422,7 +422,7 @@ int inner_sweep(oicc_problem* p, double* xv, hipStream_t st, oicc_problem* shard
     if (!p->d_dbg_cost.resize(1)) { p->err = "hipMalloc debug cost"; return OICC_ERR_HIP; }
     HIPCK(p, hipMemsetAsync(p->d_dbg_cost.p, 0, sizeof(double), st));
     p->seg_invalidate(xv);
-    int rc = eval_pass(p, xv, false, nullptr, nullptr, -1, true, nullptr, false, nullptr, false, p->d_dbg_cost.p); if (rc) return rc;
+    int rc = eval_pass(p, cost_pass(xv, p->d_dbg_cost.p)); if (rc) return rc;
     double c = 0.0;
     HIPCK(p, hipMemcpyAsync(&c, p->d_dbg_cost.p, sizeof(double), hipMemcpyDeviceToHost, st)); HIPCK(p, hipStreamSynchronize(st));
     p->inner_set_costs.push_back(nblocks); p->inner_set_costs.push_back(c);

@@ -1,6 +1,7 @@
 // liboicc_hip, host side: the problem state behind the opaque oicc_problem of include/oicc_hip.h and the functions the host
 // translation units share (internal; not part of the ABI).
-//   oicc_problem.hip    C-ABI entry points, residual / Jacobian pass, Levenberg-Marquardt driver, timers, getters
+//   oicc_problem.hip    C-ABI entry points, residual / Jacobian pass (eval_pass, asked for by a PassRequest below), Levenberg-Marquardt
+//                       drivers (host loop, device-side control), timers, getters
 //   oicc_layout.hip     parameter vector, uploads, tangent layout, buffers of the normal equations, prepare()
 //   oicc_tiles.hip      time tiles, chains and row formats of the Jacobian pass (tiles.h)
 //   oicc_inner.hip      plan and sweep of the inner iterations (inner_plan.h)
@@ -138,7 +139,6 @@ struct oicc_problem {
                      int64_t agreed_gen = -1; bool agreed = false;   // all ranks agreed (once per layout, through the installed reduction) that every one of them can run the exchange on the same cuts
                      uint32_t hash = 0; } owner;
   DevBuf<int32_t> d_xrows, d_xcut; DevBuf<double> d_xsend, d_xrecv, d_xgather, d_xagree;
-  bool full_system = false;   // the exchange of a Jacobian pass leaves the WHOLE system on every rank (oicc_evaluate*, the solver profile): no distributed-solve branch
   // distributed linear solve (round 6; kernels_bcr.hip launch_bcr_dist_*, oicc_exchange.hip dist_solve): every rank reduces the 64-column
   // blocks of its own range, the ranks' separators are gathered and solved by all, the step is gathered -- the band never travels
   // usable: decided together with the exchange agreement of layout `gen` (owner_exchange_agree) -- never before it
@@ -184,7 +184,6 @@ struct oicc_problem {
   DevBuf<LmState> d_state; DevBuf<double> d_ls; int64_t line_search_steps = 0;   // d_ls: slope and max norm of the step (bounds line search)
   // device-side LM control (oicc_device.h: LmCtl): the control block, the iteration records and kernel time stamps it fills, and the
   // pinned word the decision kernel writes for the host (polled one iteration behind; no copy, no event in the loop)
-  LmState* lm_state_cur = nullptr;   // device-side control: the LmState slot of the iteration being enqueued (the control block and LmState alternate between two slots)
   DevBuf<LmCtl> d_ctl; DevBuf<LmIterRec> d_trace; DevBuf<long long> d_stamps; LmHostMsg* hmsg = nullptr; LmHostMsg* hmsg_dev = nullptr; double wall_clock_hz = 1e8;
   struct HostPin { LmState st; double cost; double radius; double ls[2]; unsigned int inner_words[32]; };   // inner_words: command words of a set's large shared blocks (inner_sweep)
   HostPin* pin = nullptr;   // pinned: one read-back (state + candidate cost) and one 8-byte write per LM iteration
@@ -195,7 +194,6 @@ struct oicc_problem {
   DevBuf<TileDesc> d_tiles; DevBuf<UnitDesc> d_units; DevBuf<int32_t> d_tile_rows; DevBuf<double> d_slabs;
   RowFmt fv{}, fa{}, fg{}; TileParams tp{}; int tile_T = 0;   // tile_T: knot windows per tile as chosen by the host part of the tiles
   std::unique_ptr<TileStatic> h_tstatic; DevBuf<TileStatic> d_tstatic; bool tstatic_valid = false;   // problem-constant kernel arguments in device memory
-  bool gmax_folded = false;   // the last Jacobian pass already left max |g| in LmState (slab merge), no lm_gradmax launch needed
   // inner iterations (inner_plan.h): blocks in processing order, independent sets, item -> block maps per set
   struct InnerPlan {
     std::vector<InnerBlock> blocks; std::vector<int32_t> group_first; std::vector<InnerRun> runs; std::vector<InnerWg> wgs; std::vector<int32_t> group_wg0; std::vector<char> group_r3only;   // set g holds nothing but R^3 knots of at most 1024 item slots: the 8-wave build of the kernel   // workgroups of set g: wgs[group_wg0[g] .. group_wg0[g + 1])
@@ -311,15 +309,40 @@ InnerPlanOptions inner_plan_options(oicc_problem* p, int flags, int64_t layout_g
 void start_inner_plan(oicc_problem* p, int flags, int64_t layout_gen);
 int build_inner_plan(oicc_problem* p, int flags);
 int inner_sweep(oicc_problem* p, double* xv, hipStream_t st, oicc_problem* shard = nullptr, bool* owner_computes = nullptr);
-int eval_pass(oicc_problem* p, const double* x, bool jac, double* dbg_res = nullptr, double* dbg_jac = nullptr, int only_kind = -1,
-              bool cost_already_zero = false, const NormalEq* target = nullptr, bool force_rs = false, long long* prof = nullptr, bool want_gmax = false,
-              double* cost_out = nullptr, const LmCtl* ctl = nullptr);
+// What one residual / Jacobian / cost pass is asked to do (eval_pass).  Everything but x has a default; the makers below fill the common shapes.
+struct PassRequest {
+  const double* x = nullptr;          // parameter buffer (device)
+  bool jac = false;                   // Jacobian pass (normal equations, gradient and cost) or cost pass
+  const NormalEq* target = nullptr;   // where the pass accumulates (nullptr: the problem's current system, p->ne)
+  double* cost_out = nullptr;         // cost passes: device address the cost is added to instead of the target's cost slot
+  bool cost_already_zero = false;     // cost passes: that address was cleared by an earlier launch
+  const LmCtl* ctl = nullptr;         // device-side LM control: the pass runs at the control block's candidate into its second buffer
+  double* dbg_res = nullptr; double* dbg_jac = nullptr;   // dumps of the residuals / Jacobian rows of the blocks ...
+  int only_kind = -1;                 // ... of this residual family alone (0 views, 1 accelerometer, 2 gyroscope; -1: all)
+  bool force_rs = false;              // every view through the rolling-shutter functor
+  long long* prof = nullptr;          // cycle counters of the tile kernel
+  LmState* gmax_into = nullptr;       // Jacobian passes: max |g| is wanted in this slot; the slab merge leaves it there where the gradient is final then
+  bool* gmax_folded = nullptr;        // out: it did (else the caller launches lm_gradmax / the projected norm)
+  bool local = false;                 // no exchange across ranks: this rank's sums only
+  bool full_system = false;           // time shards: the exchange leaves the WHOLE system on every rank (the gathered band) even where they agreed on the distributed solve
+};
+inline PassRequest jacobian_pass(const double* x, const NormalEq* target = nullptr) { PassRequest rq; rq.x = x; rq.jac = true; rq.target = target; return rq; }
+inline PassRequest cost_pass(const double* x, double* cost_out = nullptr) { PassRequest rq; rq.x = x; rq.cost_out = cost_out; rq.cost_already_zero = cost_out != nullptr; return rq; }   // (a cost_out is cleared by its owner)
+inline PassRequest local_pass(const double* x, bool jac, int only_kind = -1) { PassRequest rq; rq.x = x; rq.jac = jac; rq.only_kind = only_kind; rq.local = true; return rq; }
+int eval_pass(oicc_problem* p, const PassRequest& rq);
+// events of one entry point, destroyed on every exit
+struct EventPair { hipEvent_t a = nullptr, b = nullptr; ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } };
 SolveBuffers solve_buffers(oicc_problem* p, long long* prof = nullptr);
 // the retraction d_x -> d_xc a solve may do inside its last launch (oicc_device.h: RetractReq); off (on = 0) with option
 // fused_retract = 0 and for problems whose retraction also writes the candidate's segment tables (multi-round problems keep the separate launch)
 RetractReq retract_request(oicc_problem* p);
 // solve + retraction of the trust-region candidate d_x -> d_xc: fused where the route allows, else lm_retract_kernel behind the solve
-int lm_solve_and_retract(oicc_problem* p, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st, bool* fused_out = nullptr);
+// (local: the single-rank solve even on agreed shards)
+int lm_solve_and_retract(oicc_problem* p, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st, bool* fused_out = nullptr, bool local = false);
+// the opening of the solve entries and debug read-outs: Jacobian pass `rq` at the current point, column scaling into `scale`, LmState zero but for `radius`
+int system_at_current_point(oicc_problem* p, const PassRequest& rq, double* scale, bool jacobi_scaling, double radius);
+// ||M delta - rhs|| / ||rhs||, ||rhs|| (may be NULL) and the Cholesky failure flag of the solve just run on `sb`
+int read_solve_residual(oicc_problem* p, const SolveBuffers& sb, double* relative, double* rhs_norm, double* chol_failed);
 int read_cost(oicc_problem* p, double* cost);
 void rccl_release(oicc_problem* p);   // destroys the problem's communicator, if any
 int rccl_reduce_in_place(void* user, void* device_ptr, int64_t count, void* stream);
@@ -330,8 +353,8 @@ int owner_exchange_agree(oicc_problem* p, hipStream_t st, bool* use);   // colle
 int shard_broadcast_begin(oicc_problem* p);                                                      // pieces of the parameter vector from their owners, in place:
 int shard_broadcast(oicc_problem* p, double* ptr, int64_t count, int root, hipStream_t st);      // native RCCL (one group) or the transport hook
 int shard_broadcast_end(oicc_problem* p);
-int owner_exchange(oicc_problem* p, const NormalEq& ne, hipStream_t st, int64_t* bytes_moved = nullptr);
+int owner_exchange(oicc_problem* p, const NormalEq& ne, hipStream_t st, bool full_system, int64_t* bytes_moved = nullptr);   // full_system: the gathered band even where the ranks agreed on the distributed solve
 bool dist_solve_usable(const oicc_problem* p);   // (decided by the exchange agreement of the current layout: every rank answers alike; false before it)
 int dist_solve(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st);
-int lm_solve_any(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st, const RetractReq* retract = nullptr, bool* fused = nullptr);   // the distributed solve on agreed shards, else launch_lm_solve
+int lm_solve_any(oicc_problem* p, const NormalEq& ne, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st, const RetractReq* retract = nullptr, bool* fused = nullptr, bool local = false);   // the distributed solve on agreed shards (unless local), else launch_lm_solve
 }  // namespace oicc

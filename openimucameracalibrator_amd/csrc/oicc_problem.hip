@@ -12,14 +12,13 @@
 
 namespace oicc {
 
-// One residual(+Jacobian+normal equation) pass at parameter vector x (device).
-int eval_pass(oicc_problem* p, const double* x, bool jac, double* dbg_res, double* dbg_jac, int only_kind,
-              bool cost_already_zero, const NormalEq* target, bool force_rs, long long* prof, bool want_gmax,
-              double* cost_out, const LmCtl* ctl) {   // cost_out (tile assembly, cost passes): device address the cost is added to instead of the cost slot
-                                                      // ctl (device-side LM control): the pass runs at the control block's candidate into its second buffer
-  p->gmax_folded = false;
+// One residual (+ Jacobian + normal equation) pass as `rq` asks for it (oicc_problem.h: PassRequest), followed by the exchange across
+// ranks where a reduction is installed and the request is not local.
+int eval_pass(oicc_problem* p, const PassRequest& rq) {
+  const double* const x = rq.x; const bool jac = rq.jac; const int only_kind = rq.only_kind;
+  const oicc_allreduce_fn reduce = rq.local ? nullptr : p->reduce;
   hipStream_t st = p->stream;
-  const NormalEq ne = target ? *target : p->ne;   // where this pass accumulates
+  const NormalEq ne = rq.target ? *rq.target : p->ne;   // where this pass accumulates
   if (p->opt["debug_poison_lds"] != 0.0) launch_lds_poison(st);
   {                                     // time tiles (kernels_tiles.hip): the slab merge writes every entry of the packed buffer
     const bool with_points = jac && p->tl.a_pts > 0 && (only_kind < 0 || only_kind == 0);   // SplineOptimFlags::POINTS
@@ -29,9 +28,10 @@ int eval_pass(oicc_problem* p, const double* x, bool jac, double* dbg_res, doubl
       HIPCK(p, hipMemsetAsync(ne.base + ne.off_E + int64_t(a_np) * p->tl.Pb, 0, size_t(ne.off_g - ne.off_E - int64_t(a_np) * p->tl.Pb) * sizeof(double), st));
       HIPCK(p, hipMemsetAsync(ne.g() + p->tl.Pb + a_np, 0, size_t(p->tl.a_pts) * sizeof(double), st));
     }
-    else if (!jac && !cost_already_zero) HIPCK(p, hipMemsetAsync(ne.cost(), 0, sizeof(double), st));
+    else if (!jac && !rq.cost_already_zero) HIPCK(p, hipMemsetAsync(ne.cost(), 0, sizeof(double), st));
     const TileParams& tp = p->tp;
-    p->gmax_folded = jac && want_gmax && !tp.direct && tp.n_tiles > 0 && !p->reduce && p->tl.a_pts == 0;   // (with an all-reduce, or with point columns, the gradient is only final afterwards)
+    const bool gmax_folded = jac && rq.gmax_into != nullptr && !tp.direct && tp.n_tiles > 0 && !reduce && p->tl.a_pts == 0;   // (with an all-reduce, or with point columns, the gradient is only final afterwards)
+    if (rq.gmax_folded) *rq.gmax_folded = gmax_folded;
     // the problem-constant arguments live in device memory (tiles.h: TileStatic); uploaded when they differ from the last upload
     if (!p->h_tstatic) { p->h_tstatic.reset(new TileStatic); std::memset(p->h_tstatic.get(), 0, sizeof(TileStatic)); p->tstatic_valid = false; }
     {
@@ -50,17 +50,17 @@ int eval_pass(oicc_problem* p, const double* x, bool jac, double* dbg_res, doubl
       }
     }
     TileDyn dyn{};
-    dyn.ctl = ctl;
-    if (ctl != nullptr) { if (p->seg_precomputed()) dyn.seg = p->seg_tab[0].buf.p; }   // (non-null = "tables exist": the kernel takes the candidate's from the control block, the retraction wrote them)
+    dyn.ctl = rq.ctl;
+    if (rq.ctl != nullptr) { if (p->seg_precomputed()) dyn.seg = p->seg_tab[0].buf.p; }   // (non-null = "tables exist": the kernel takes the candidate's from the control block, the retraction wrote them)
     else if (p->seg_precomputed()) {
       oicc_problem::SegTable* sgt = p->seg_of(x);
       if (sgt == nullptr) { p->err = "residual pass on an unknown parameter buffer"; return OICC_ERR_STATE; }
       if (!sgt->valid) { launch_inner_seg(x + p->pl.so3, int(p->pl.n_so3 - 1), sgt->buf.p, st); sgt->valid = true; }
       dyn.seg = sgt->buf.p;
     }
-    dyn.x = x; dyn.ne_base = ne.base; dyn.cost_out = (!jac && cost_out) ? cost_out : ne.cost(); dyn.dbg_res = dbg_res; dyn.dbg_jac = dbg_jac; dyn.prof = prof; dyn.only_kind = only_kind;
-    dyn.gmax = p->gmax_folded ? &(p->lm_state_cur ? p->lm_state_cur : p->d_state.p)->gradient_max_norm : nullptr;
-    dyn.view_rs = force_rs ? p->d_view_rs_all.p : p->d_view_rs.p;
+    dyn.x = x; dyn.ne_base = ne.base; dyn.cost_out = (!jac && rq.cost_out) ? rq.cost_out : ne.cost(); dyn.dbg_res = rq.dbg_res; dyn.dbg_jac = rq.dbg_jac; dyn.prof = rq.prof; dyn.only_kind = only_kind;
+    dyn.gmax = gmax_folded ? &rq.gmax_into->gradient_max_norm : nullptr;
+    dyn.view_rs = rq.force_rs ? p->d_view_rs_all.p : p->d_view_rs.p;
     if (launch_tile_pass(*p->h_tstatic, p->d_tstatic.p, dyn, jac, st) != 0) {
       p->err = "tile kernel launch failed"; return OICC_ERR_HIP; }
     if (with_points) {   // rows, columns and gradient entries of the board points, behind the merge
@@ -70,14 +70,14 @@ int eval_pass(oicc_problem* p, const double* x, bool jac, double* dbg_res, doubl
   }
   HIPCK(p, hipGetLastError());
   if (p->opt["debug_sync"] != 0.0) HIPCK(p, hipStreamSynchronize(st));
-  if (p->reduce) {
-    double* cdst = (!jac && cost_out) ? cost_out : ne.cost();
+  if (reduce) {
+    double* cdst = (!jac && rq.cost_out) ? rq.cost_out : ne.cost();
     int rc;
     if (jac && p->shard_n > 1) {   // owner-computes: halo rows, gather of the owned ranges, all-reduce of the corner -- if ALL ranks can (agreed once per layout)
       bool use = false; rc = owner_exchange_agree(p, st, &use); if (rc) return rc;
-      if (use) return owner_exchange(p, ne, st);
+      if (use) return owner_exchange(p, ne, st, rq.full_system);
     }
-    rc = jac ? p->reduce(p->reduce_user, ne.base, ne.total, st) : p->reduce(p->reduce_user, cdst, 1, st);
+    rc = jac ? reduce(p->reduce_user, ne.base, ne.total, st) : reduce(p->reduce_user, cdst, 1, st);
     if (rc != 0) { p->err = "allreduce callback failed"; return OICC_ERR_STATE; }
   }
   return OICC_OK;
@@ -103,10 +103,10 @@ RetractReq retract_request(oicc_problem* p) {
   R.max_ab = p->max_ab; R.max_gb = p->max_gb; R.alpha = 1.0;
   return R;
 }
-int lm_solve_and_retract(oicc_problem* p, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st, bool* fused_out) {
+int lm_solve_and_retract(oicc_problem* p, const SolveBuffers& sb, double radius, int reuse_diagonal, double min_diag, double max_diag, hipStream_t st, bool* fused_out, bool local) {
   const RetractReq R = retract_request(p);
   bool fused = false;
-  const int rc = lm_solve_any(p, p->ne, sb, radius, reuse_diagonal, min_diag, max_diag, st, &R, &fused); if (rc) return rc;
+  const int rc = lm_solve_any(p, p->ne, sb, radius, reuse_diagonal, min_diag, max_diag, st, &R, &fused, local); if (rc) return rc;
   if (fused_out) *fused_out = fused;
   oicc_problem::SegTable* sgt = p->seg_of(p->d_xc.p);
   if (!fused) launch_lm_retract(p->d_x.p, p->d_xc.p, p->pl, p->tl, sb, p->ne, p->max_ab, p->max_gb, st, 1.0, 1, (sgt && p->seg_precomputed()) ? sgt->buf.p : nullptr);
@@ -153,10 +153,8 @@ int device_lm_enqueue(oicc_problem* p, SolveBuffers sb, double min_diag, double 
   if (launch_lm_solve(p->ne, p->tl, sb, 0.0, 0, min_diag, max_diag, st, &R, &fused) != 0) {
     p->err = "band/arrow geometry exceeds the single-workgroup solver (half bandwidth or arrow too large for 160 KB LDS)"; return OICC_ERR_UNSUPPORTED; }
   if (!fused) launch_lm_retract(p->d_x.p, p->d_xc.p, p->pl, p->tl, sb, p->ne, p->max_ab, p->max_gb, st, 1.0, 1, p->seg_precomputed() ? p->seg_tab[0].buf.p : nullptr);
-  p->lm_state_cur = stc;
-  const int rc = eval_pass(p, p->d_xc.p, true, nullptr, nullptr, -1, false, &p->ne2, false, nullptr, true, nullptr, cur);
-  p->lm_state_cur = nullptr;
-  if (rc) return rc;
+  PassRequest rq = jacobian_pass(p->d_xc.p, &p->ne2); rq.ctl = cur; rq.gmax_into = stc;
+  const int rc = eval_pass(p, rq); if (rc) return rc;
   HIPCK(p, hipGetLastError());
   return OICC_OK;
 }
@@ -200,6 +198,56 @@ int device_lm_end(oicc_problem* p, int k_last, LmCtl* out, std::vector<LmIterRec
   HIPCK(p, hipStreamSynchronize(st));
   if (out->xp[0] != p->d_x.p) { std::swap(p->d_x.p, p->d_xc.p); std::swap(p->ne.base, p->ne2.base); }   // (an odd number of accepted steps)
   p->seg_invalidate(p->d_x.p); p->seg_invalidate(p->d_xc.p);
+  return OICC_OK;
+}
+// The control block a device-side loop starts with: the problem's options and where the loop stands.  hold = 1: every decision is
+// recorded but not applied (the benchmark mode of oicc_run_lm_iterations).
+LmCtl device_lm_control(oicc_problem* p, double radius, double cost, double gmax, int max_iters, int hold) {
+  LmCtl h; std::memset(&h, 0, sizeof(h));
+  h.radius = radius; h.decrease_factor = 2.0; h.cost = cost; h.gmax = gmax;
+  h.ftol = p->opt["function_tolerance"]; h.ptol = p->opt["parameter_tolerance"]; h.gtol = p->opt["gradient_tolerance"];
+  h.min_radius = p->opt["min_trust_region_radius"]; h.max_radius = p->opt["max_trust_region_radius"]; h.min_rel_dec = p->opt["min_relative_decrease"];
+  h.reuse_diagonal = 0; h.max_iters = max_iters; h.max_invalid = int(p->opt["max_num_consecutive_invalid_steps"]); h.hold = hold;
+  return h;
+}
+// The loop under device-side control, from *h (h->max_iters >= 1) to the control block the device ends with, also in *h: per iteration
+// the host enqueues solve -> retraction -> Jacobian pass at the candidate and looks at the pinned word two iterations behind what it
+// has enqueued; iterations enqueued past the end return at their first instruction (LmCtl::done).
+int device_lm_run(oicc_problem* p, const SolveBuffers& sb, LmCtl* h, std::vector<LmIterRec>* recs, std::vector<long long>* stamps) {
+  const int max_iters = h->max_iters; const double min_diag = p->opt["min_lm_diagonal"], max_diag = p->opt["max_lm_diagonal"];
+  int rc = device_lm_begin(p, *h, max_iters); if (rc) return rc;
+  int done = 0, k_last = -1;
+  for (int k = 0; k < max_iters && done == 0; ++k) {
+    rc = device_lm_enqueue(p, sb, min_diag, max_diag, k); if (rc) return rc;
+    k_last = k;
+    if (k >= 2) { rc = device_lm_wait(p, k - 1, &done); if (rc) return rc; }   // the decision of iteration k - 2 (taken by the build kernel of iteration k - 1): the host stays two iterations ahead
+  }
+  rc = device_lm_settle(p, k_last); if (rc) return rc;
+  return device_lm_end(p, k_last, h, recs, stamps);
+}
+
+// The damped system at the current point, as the solve entries and the debug read-outs open: the Jacobian pass `rq` (at d_x into
+// p->ne), the column scaling into `scale` and an LmState that is zero but for `radius` (0: all of it).
+int system_at_current_point(oicc_problem* p, const PassRequest& rq, double* scale, bool jacobi_scaling, double radius) {
+  hipStream_t st = p->stream;
+  const int rc = eval_pass(p, rq); if (rc) return rc;
+  launch_lm_scale(p->ne, p->tl, scale, jacobi_scaling ? 1 : 0, st);
+  if (radius == 0.0) { HIPCK(p, hipMemsetAsync(p->d_state.p, 0, sizeof(LmState), st)); return OICC_OK; }
+  LmState hs; std::memset(&hs, 0, sizeof(hs)); hs.radius = radius;
+  HIPCK(p, hipMemcpyAsync(p->d_state.p, &hs, sizeof(hs), hipMemcpyHostToDevice, st));   // (pageable source: staged before the call returns)
+  return OICC_OK;
+}
+// The solve just run on `sb`, checked against the packed normal equations themselves: ||M delta - rhs||_2 / ||rhs||_2, ||rhs||_2 and the
+// Cholesky failure flag, with M = S H S + D^2 / radius, rhs = -S g.
+int read_solve_residual(oicc_problem* p, const SolveBuffers& sb, double* relative, double* rhs_norm, double* chol_failed) {
+  hipStream_t st = p->stream;
+  DevBuf<double> acc; if (!acc.resize(2 + size_t(p->tl.a))) return OICC_ERR_HIP;
+  launch_lm_solve_residual(p->ne, p->tl, sb, acc.p, st);
+  double h[2] = {0, 0}; LmState hs;
+  HIPCK(p, hipMemcpyAsync(h, acc.p, sizeof(h), hipMemcpyDeviceToHost, st));
+  HIPCK(p, hipMemcpyAsync(&hs, p->d_state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+  HIPCK(p, hipStreamSynchronize(st));
+  *relative = h[1] > 0.0 ? std::sqrt(h[0] / h[1]) : std::sqrt(h[0]); if (rhs_norm) *rhs_norm = std::sqrt(h[1]); *chol_failed = double(hs.chol_failed);
   return OICC_OK;
 }
 
@@ -443,15 +491,10 @@ int oicc_get_scene_point_offsets(oicc_problem* p, int32_t flags, int32_t* offset
 
 // A Jacobian pass whose exchange leaves the WHOLE system on every rank of a time-sharded problem: the gathered band, even where the
 // ranks agreed on the distributed solve (whose pass leaves the foreign rows' band and arrow entries as this rank's partial sums).
-static int eval_pass_full_system(oicc_problem* p) {
-  p->full_system = true;
-  const int rc = eval_pass(p, p->d_x.p, true);
-  p->full_system = false;
-  return rc;
-}
+static PassRequest full_system_pass(oicc_problem* p) { PassRequest rq = jacobian_pass(p->d_x.p); rq.full_system = true; return rq; }
 int oicc_evaluate(oicc_problem* p, int32_t flags, double* cost, double* H, double* g, int32_t Pcap) {
   int rc = prepare(p, flags); if (rc) return rc;
-  rc = eval_pass_full_system(p); if (rc) return rc;
+  rc = eval_pass(p, full_system_pass(p)); if (rc) return rc;
   std::vector<double> h(p->ne.total);
   HIPCK(p, hipMemcpyAsync(h.data(), p->ne.base, h.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
   HIPCK(p, hipStreamSynchronize(p->stream));
@@ -471,7 +514,7 @@ int oicc_evaluate(oicc_problem* p, int32_t flags, double* cost, double* H, doubl
 int oicc_evaluate_entries(oicc_problem* p, int32_t flags, int64_t n, const int32_t* rows, const int32_t* cols, double* values) {
   ARG(p, n >= 0 && (n == 0 || (rows && cols && values)), "entries");
   int rc = prepare(p, flags); if (rc) return rc;
-  rc = eval_pass_full_system(p); if (rc) return rc;
+  rc = eval_pass(p, full_system_pass(p)); if (rc) return rc;
   std::vector<double> h(p->ne.total);
   HIPCK(p, hipMemcpyAsync(h.data(), p->ne.base, h.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
   HIPCK(p, hipStreamSynchronize(p->stream));
@@ -491,7 +534,7 @@ int oicc_evaluate_entries(oicc_problem* p, int32_t flags, int64_t n, const int32
 }
 int oicc_evaluate_cost(oicc_problem* p, int32_t flags, double* cost) {
   int rc = prepare(p, flags); if (rc) return rc;
-  rc = eval_pass(p, p->d_x.p, false); if (rc) return rc;
+  rc = eval_pass(p, cost_pass(p->d_x.p)); if (rc) return rc;
   return read_cost(p, cost);
 }
 int oicc_evaluate_blocks(oicc_problem* p, int32_t flags, int32_t kind, double* residuals, double* jacobians) {
@@ -501,10 +544,9 @@ int oicc_evaluate_blocks(oicc_problem* p, int32_t flags, int32_t kind, double* r
   const size_t ncols = kind == 0 ? 43 : (kind == 1 ? 54 : 36);
   if (rows == 0) return OICC_OK;
   if (!p->d_dbg_res.resize(rows) || (jacobians && !p->d_dbg_jac.resize(rows * ncols))) { p->err = "hipMalloc dbg"; return OICC_ERR_HIP; }
-  auto saved = p->reduce; p->reduce = nullptr;   // block dumps are local
-  rc = eval_pass(p, p->d_x.p, jacobians != nullptr, p->d_dbg_res.p, jacobians ? p->d_dbg_jac.p : nullptr, kind);
-  p->reduce = saved;
-  if (rc) return rc;
+  PassRequest rq = local_pass(p->d_x.p, jacobians != nullptr, kind);   // block dumps are local
+  rq.dbg_res = p->d_dbg_res.p; rq.dbg_jac = jacobians ? p->d_dbg_jac.p : nullptr;
+  rc = eval_pass(p, rq); if (rc) return rc;
   HIPCK(p, hipMemcpyAsync(residuals, p->d_dbg_res.p, rows * sizeof(double), hipMemcpyDeviceToHost, p->stream));
   if (jacobians) HIPCK(p, hipMemcpyAsync(jacobians, p->d_dbg_jac.p, rows * ncols * sizeof(double), hipMemcpyDeviceToHost, p->stream));
   HIPCK(p, hipStreamSynchronize(p->stream));
@@ -575,19 +617,16 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
   oicc_problem::HostPin* pin = p->pin;
   hipEvent_t* ev = p->ev;
   // The candidate's cost is accumulated in LmState::cand_cost (tile assembly), so that ONE small copy brings back everything the
-  // host decides on; the cost slot of the normal equations is only read where a Jacobian pass left the cost there.
-  constexpr bool cost_in_state = true;
+  // host decides on; the cost slot of the normal equations is only read where a Jacobian pass left the cost there (pin->cost).
   double* const cand_dst = &p->d_state.p->cand_cost;
-  auto cand_cost_of = [&]() { return cost_in_state ? pin->st.cand_cost : pin->cost; };
   auto read_back = [&](bool with_ne_cost = false) -> int {
     HIPCK(p, hipMemcpyAsync(&pin->st, p->d_state.p, sizeof(LmState), hipMemcpyDeviceToHost, st));
-    if (with_ne_cost || !cost_in_state) HIPCK(p, hipMemcpyAsync(&pin->cost, p->ne.cost(), sizeof(double), hipMemcpyDeviceToHost, st));
+    if (with_ne_cost) HIPCK(p, hipMemcpyAsync(&pin->cost, p->ne.cost(), sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCK(p, hipStreamSynchronize(st)); return OICC_OK; };
-  // read-back without draining the stream: the host waits for an event recorded right after the two copies, so that
+  // read-back without draining the stream: the host waits for an event recorded right after the copy, so that
   // work enqueued behind it (the Jacobian pass at the candidate) runs while the host takes the accept/reject decision
   auto read_back_begin = [&]() -> int {
     HIPCK(p, hipMemcpyAsync(&pin->st, p->d_state.p, sizeof(LmState), hipMemcpyDeviceToHost, st));
-    if (!cost_in_state) HIPCK(p, hipMemcpyAsync(&pin->cost, p->ne.cost(), sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCK(p, hipEventRecord(ev[5], st)); return OICC_OK; };
   auto read_back_wait = [&]() -> int { HIPCK(p, hipEventSynchronize(ev[5])); return OICC_OK; };
   auto elapsed_s = [&](hipEvent_t a, hipEvent_t b) { float ms = 0; return hipEventElapsedTime(&ms, a, b) == hipSuccess ? double(ms) * 1e-3 : 0.0; };
@@ -595,10 +634,14 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
   double t0 = now_s();
   HIPCK(p, hipMemsetAsync(p->d_state.p, 0, sizeof(LmState), st));
   const bool projected_gmax = p->opt["projected_gradient_norm"] != 0.0 && (p->act.ab || p->act.gb);   // Ceres: is_constrained
+  bool gmax_folded = false;   // the last Jacobian pass already left max |g| in LmState (slab merge): no lm_gradmax launch
+  auto jacobian_at = [&](const double* xbuf, const NormalEq* nq) {   // the Jacobian pass of the loop: max |g| rides in the merge where it can
+    PassRequest rq = jacobian_pass(xbuf, nq); rq.gmax_into = projected_gmax ? nullptr : p->d_state.p; rq.gmax_folded = &gmax_folded;
+    return eval_pass(p, rq); };
   auto gradient_norm = [&](const double* xbuf, const NormalEq& nq) {   // after a Jacobian pass at xbuf into nq
     if (projected_gmax) launch_lm_projected_gradient(xbuf, p->pl, tl, nq, p->max_ab, p->max_gb, p->d_state.p, st);
-    else if (!p->gmax_folded) launch_lm_gradmax(nq, P, p->d_state.p, st); };
-  rc = eval_pass(p, p->d_x.p, true, nullptr, nullptr, -1, false, nullptr, false, nullptr, !projected_gmax); if (rc) return rc;
+    else if (!gmax_folded) launch_lm_gradmax(nq, P, p->d_state.p, st); };
+  rc = jacobian_at(p->d_x.p, nullptr); if (rc) return rc;
   SolveBuffers sb = solve_buffers(p);
   if (P > 0) { launch_lm_scale(p->ne, tl, sb.scale, p->opt["jacobi_scaling"] != 0, st); gradient_norm(p->d_x.p, p->ne); }
   rc = read_back(true); if (rc) return rc;
@@ -645,22 +688,11 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
   // host looks at a pinned word that kernel wrote, two iterations behind what it has enqueued: no copy, no event, no synchronisation
   // inside the loop; iterations enqueued past the end return at their first instruction (LmCtl::done).
   if (device_lm_applicable(p, inner_enabled || p->opt["inner_iterations"] != 0.0, line_search, projected_gmax)) {
-    LmCtl h; std::memset(&h, 0, sizeof(h));
-    h.radius = radius; h.decrease_factor = 2.0; h.cost = cost; h.gmax = gmax;
-    h.ftol = ftol; h.ptol = ptol; h.gtol = gtol; h.min_radius = min_radius; h.max_radius = max_radius; h.min_rel_dec = min_rel_dec;
-    h.reuse_diagonal = 0; h.max_iters = max_iters; h.max_invalid = max_invalid; h.hold = 0;
     if (max_iters <= 0) return finish(OICC_NO_CONVERGENCE, "Maximum number of iterations reached.");
     if (radius <= min_radius) return finish(OICC_CONVERGENCE, "Minimum trust region radius reached.");
-    rc = device_lm_begin(p, h, max_iters); if (rc) return rc;
-    int done = 0, k_last = -1;
-    for (int k = 0; k < max_iters && done == 0; ++k) {
-      rc = device_lm_enqueue(p, sb, min_diag, max_diag, k); if (rc) return rc;
-      k_last = k;
-      if (k >= 2) { rc = device_lm_wait(p, k - 1, &done); if (rc) return rc; }   // the decision of iteration k - 2 (taken by the build kernel of iteration k - 1): the host stays two iterations ahead
-    }
-    rc = device_lm_settle(p, k_last); if (rc) return rc;
+    LmCtl h = device_lm_control(p, radius, cost, gmax, max_iters, 0);
     std::vector<LmIterRec> recs; std::vector<long long> stamps;
-    rc = device_lm_end(p, k_last, &h, &recs, &stamps); if (rc) return rc;
+    rc = device_lm_run(p, sb, &h, &recs, &stamps); if (rc) return rc;
     for (const LmIterRec& r : recs) { oicc_iteration it; std::memcpy(&it, &r, sizeof(it)); p->trace.push_back(it);
       if (verbose) std::printf("[oicc] iter %d %s cost %.12e change %.3e rho %.3f |step| %.3e gmax %.3e radius %.3e (device-side control)\n", it.iteration, it.step_is_successful ? "ok " : "rej", it.cost, it.cost_change, it.relative_decrease, it.step_norm, it.gradient_max_norm, it.trust_region_radius); }
     const double tick = 1.0 / p->wall_clock_hz;
@@ -731,7 +763,7 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
       if (!same) p->seg_invalidate(p->d_xc.p);   // rank 0's knots replaced this rank's
     }
     HIPCK(p, hipEventRecord(ev[1], st));
-    rc = eval_pass(p, p->d_xc.p, false, nullptr, nullptr, -1, true, nullptr, false, nullptr, false, cand_dst); if (rc) return rc;   // (cost slot cleared by lm_retract_kernel, cand_cost by the solver's build kernel)
+    rc = eval_pass(p, cost_pass(p->d_xc.p, cand_dst)); if (rc) return rc;   // (cost slot cleared by lm_retract_kernel, cand_cost by the solver's build kernel)
     // Bounds line search (TrustRegionMinimizer::DoLineSearch): with box-bounded bias knots among the variables Ceres shortens
     // the step by an Armijo search along x(alpha) = project(x (+) alpha delta), alpha_0 = 1, cubic interpolation, before the
     // candidate is judged.  Host-driven: every trial is one retraction + cost pass, a failed trial adds one Jacobian pass for
@@ -753,16 +785,16 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
           launch_lm_retract(p->d_x.p, p->d_xc.p, p->pl, tl, sb, p->ne, p->max_ab, p->max_gb, st, alpha, 0);
           p->seg_invalidate(p->d_xc.p);
           if (p->reduce != nullptr) { int rr = make_rank_consistent(p, p->d_xc.p, true, st); if (rr) return rr; }
-          int r = eval_pass(p, p->d_xc.p, false, nullptr, nullptr, -1, true, nullptr, false, nullptr, false, cand_dst); if (r) return r;
+          int r = eval_pass(p, cost_pass(p->d_xc.p, cand_dst)); if (r) return r;
           r = read_back(); if (r) return r;
-          *value = cand_cost_of(); return OICC_OK; };
+          *value = pin->st.cand_cost; return OICC_OK; };
         LsSample init, prev, cur; bool have_prev = false, success = true; int its = 0;
         init.x = 0.0; init.value = cost; init.gradient = g0; init.has_gradient = true;
-        cur.x = 1.0; cur.value = cand_cost_of();
+        cur.x = 1.0; cur.value = pin->st.cand_cost;
         while (!std::isfinite(cur.value) || cur.value > cost + 1e-4 * g0 * cur.x) {
           if (++its >= 20) { success = false; break; }
           if (!cur.has_gradient && std::isfinite(cur.value)) {   // slope at the trial point: gradient there (in its own tangent space) . delta
-            rc = eval_pass(p, p->d_xc.p, true, nullptr, nullptr, -1, false, &p->ne2, false, nullptr, false); if (rc) return rc;
+            rc = eval_pass(p, jacobian_pass(p->d_xc.p, &p->ne2)); if (rc) return rc;
             launch_lm_step_slope(p->ne2.g(), sb, P, p->d_ls.p, st);
             HIPCK(p, hipMemcpyAsync(pin->ls, p->d_ls.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
             HIPCK(p, hipStreamSynchronize(st));
@@ -785,7 +817,7 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
     if (plan_pending) { rc = join_plan(); if (rc) return rc; }
     if (inner_enabled) {
       rc = read_back(); if (rc) return rc;
-      cand_before_inner = cand_cost_of();
+      cand_before_inner = pin->st.cand_cost;
       if (std::isfinite(cand_before_inner)) {
         HIPCK(p, hipEventRecord(ev[6], st));
         bool owned_sweep = false;
@@ -794,16 +826,14 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
         if (owned_sweep) any_owned_sweep = true;
         HIPCK(p, hipEventRecord(ev[7], st));
         p->seg_invalidate(p->d_xc.p);
-        if (cost_in_state) HIPCK(p, hipMemsetAsync(&p->d_state.p->cand_cost, 0, sizeof(double), st));
-        rc = eval_pass(p, p->d_xc.p, false, nullptr, nullptr, -1, cost_in_state, nullptr, false, nullptr, false, cand_dst); if (rc) return rc;
+        HIPCK(p, hipMemsetAsync(cand_dst, 0, sizeof(double), st));
+        rc = eval_pass(p, cost_pass(p->d_xc.p, cand_dst)); if (rc) return rc;
         HIPCK(p, hipMemsetAsync(&p->d_state.p->step_norm_sq, 0, sizeof(double), st));
         launch_inner_diff_norm(p->d_x.p, p->d_xc.p, q->inner.d_blocks.p, int(q->inner.blocks.size()), &p->d_state.p->step_norm_sq, st);
         inner_ran = true;
       }
     }
     HIPCK(p, hipEventRecord(ev[2], st));
-    // (several ranks: see the broadcast behind the retraction above)
-    const bool rank_consistent = p->rccl_comm != nullptr && p->rccl_nranks > 1;
     rc = read_back_begin(); if (rc) return rc;
     // Jacobian pass + gradient norm at the CANDIDATE into the second buffer, before the host knows whether the step is
     // accepted (it is, on 4 of 4 iterations of the C2 calibration): the read-back latency hides behind it.  A rejected
@@ -811,14 +841,13 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
     const bool speculate = p->opt["debug_sync"] != 3.0;
     HIPCK(p, hipEventRecord(ev[3], st));
     if (speculate) {
-      rc = eval_pass(p, p->d_xc.p, true, nullptr, nullptr, -1, false, &p->ne2, false, nullptr, !projected_gmax); if (rc) return rc;
+      rc = jacobian_at(p->d_xc.p, &p->ne2); if (rc) return rc;
       gradient_norm(p->d_xc.p, p->ne2);
     }
     HIPCK(p, hipEventRecord(ev[4], st));
     rc = read_back_wait(); if (rc) return rc;
     LmState hs = pin->st;
-    (void)rank_consistent;
-    const double cand_cost = cand_cost_of();
+    const double cand_cost = pin->st.cand_cost;
     bool inner_useful = false;
     if (inner_ran) {
       hs.model_cost_change += cand_before_inner - cand_cost;
@@ -859,7 +888,7 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
     }
     if (rel_dec > min_rel_dec || inner_useful) {   // IsStepSuccessful
       if (!speculate) {
-        rc = eval_pass(p, p->d_xc.p, true, nullptr, nullptr, -1, false, &p->ne2, false, nullptr, !projected_gmax); if (rc) return rc;
+        rc = jacobian_at(p->d_xc.p, &p->ne2); if (rc) return rc;
         gradient_norm(p->d_xc.p, p->ne2);
       }
       std::swap(p->d_x.p, p->d_xc.p);          // accept: candidate becomes current ...
@@ -888,7 +917,7 @@ int oicc_get_inner_set_costs(const oicc_problem* p, double* out, int32_t cap) {
 // pass + assembly, [all-reduce], gradient norm, damped system build, band+arrow
 // Cholesky solve, retraction, candidate cost pass, state read-back), repeated
 // `steps` times at the current point without accepting the step.  bench.py times
-// this as its "step"; it is exactly the loop body of oicc_optimize.
+// this as its "step": under device-side control it is oicc_optimize's own loop (device_lm_run) with the decisions held.
 int oicc_run_lm_iterations(oicc_problem* p, int32_t flags, int32_t steps) {
   int rc = prepare(p, flags); if (rc) return rc;
   if (steps <= 0) return OICC_OK;   // (nothing to enqueue: the device-side control block would be read uninitialised)
@@ -901,27 +930,17 @@ int oicc_run_lm_iterations(oicc_problem* p, int32_t flags, int32_t steps) {
   p->seg_invalidate(p->d_xc.p);
   // Same pipeline as oicc_optimize with every step accepted: the Jacobian pass of the NEXT iteration (here: at x again)
   // is enqueued into the second buffer right behind the read-back copies, the host waits for the copies only.
-  rc = eval_pass(p, p->d_x.p, true, nullptr, nullptr, -1, false, nullptr, false, nullptr, true); if (rc) return rc;
+  bool gmax_folded = false;
+  auto jacobian_at_x = [&](const NormalEq* nq) { PassRequest rq = jacobian_pass(p->d_x.p, nq); rq.gmax_into = p->d_state.p; rq.gmax_folded = &gmax_folded; return eval_pass(p, rq); };
+  rc = jacobian_at_x(nullptr); if (rc) return rc;
   launch_lm_scale(p->ne, tl, sb.scale, p->opt["jacobi_scaling"] != 0, st);
-  if (!p->gmax_folded) launch_lm_gradmax(p->ne, tl.P, p->d_state.p, st);
+  if (!gmax_folded) launch_lm_gradmax(p->ne, tl.P, p->d_state.p, st);
   if (device_lm_applicable(p, p->opt["inner_iterations"] != 0.0, p->opt["bounds_line_search"] != 0.0 && (p->act.ab || p->act.gb), p->opt["projected_gradient_norm"] != 0.0 && (p->act.ab || p->act.gb))) {
     // the loop of oicc_optimize under device-side control, in its benchmark mode: every iteration solves the system at x, retracts,
     // runs the Jacobian pass at the candidate and takes the decision -- which is recorded but not applied (LmCtl::hold)
     double c0 = 0.0; rc = read_cost(p, &c0); if (rc) return rc;
-    LmCtl h; std::memset(&h, 0, sizeof(h));
-    h.radius = p->opt["initial_trust_region_radius"]; h.decrease_factor = 2.0; h.cost = c0; h.gmax = 0.0;
-    h.ftol = p->opt["function_tolerance"]; h.ptol = p->opt["parameter_tolerance"]; h.gtol = p->opt["gradient_tolerance"];
-    h.min_radius = p->opt["min_trust_region_radius"]; h.max_radius = p->opt["max_trust_region_radius"]; h.min_rel_dec = p->opt["min_relative_decrease"];
-    h.max_iters = steps; h.max_invalid = int(p->opt["max_num_consecutive_invalid_steps"]); h.hold = 1;
-    rc = device_lm_begin(p, h, steps); if (rc) return rc;
-    int done = 0, k_last = -1;
-    for (int it = 0; it < steps && done == 0; ++it) {
-      rc = device_lm_enqueue(p, sb, p->opt["min_lm_diagonal"], p->opt["max_lm_diagonal"], it); if (rc) return rc;
-      k_last = it;
-      if (it >= 2) { rc = device_lm_wait(p, it - 1, &done); if (rc) return rc; }
-    }
-    if (k_last >= 0) { rc = device_lm_settle(p, k_last); if (rc) return rc; }
-    rc = device_lm_end(p, std::max(k_last, 0), &h, nullptr, nullptr); if (rc) return rc;
+    LmCtl h = device_lm_control(p, p->opt["initial_trust_region_radius"], c0, 0.0, steps, 1);
+    rc = device_lm_run(p, sb, &h, nullptr, nullptr); if (rc) return rc;
     if (h.done != 0 || h.seq != steps) { p->err = "Cholesky failed in benchmark iteration"; return OICC_ERR_STATE; }
     return OICC_OK;
   }
@@ -932,11 +951,11 @@ int oicc_run_lm_iterations(oicc_problem* p, int32_t flags, int32_t steps) {
       rc = make_rank_consistent(p, p->d_xc.p, true, st, same); if (rc) return rc;
       if (!same) p->seg_invalidate(p->d_xc.p);
     }
-    rc = eval_pass(p, p->d_xc.p, false, nullptr, nullptr, -1, true, nullptr, false, nullptr, false, &p->d_state.p->cand_cost); if (rc) return rc;   // as in oicc_optimize: the candidate cost comes back inside LmState
+    rc = eval_pass(p, cost_pass(p->d_xc.p, &p->d_state.p->cand_cost)); if (rc) return rc;   // as in oicc_optimize: the candidate cost comes back inside LmState
     HIPCK(p, hipMemcpyAsync(&pin->st, p->d_state.p, sizeof(LmState), hipMemcpyDeviceToHost, st));
     HIPCK(p, hipEventRecord(p->ev[5], st));
-    rc = eval_pass(p, p->d_x.p, true, nullptr, nullptr, -1, false, &p->ne2, false, nullptr, true); if (rc) return rc;
-    if (!p->gmax_folded) launch_lm_gradmax(p->ne2, tl.P, p->d_state.p, st);
+    rc = jacobian_at_x(&p->ne2); if (rc) return rc;
+    if (!gmax_folded) launch_lm_gradmax(p->ne2, tl.P, p->d_state.p, st);
     HIPCK(p, hipEventSynchronize(p->ev[5]));
     if (pin->st.chol_failed) { p->err = "Cholesky failed in benchmark iteration"; return OICC_ERR_STATE; }
     std::swap(p->ne.base, p->ne2.base);
@@ -948,23 +967,20 @@ int oicc_run_lm_iterations(oicc_problem* p, int32_t flags, int32_t steps) {
 int oicc_time_jacobian_pass(oicc_problem* p, int32_t flags, int32_t repeats, double* ms_per_pass, double kernel_ms[3]) {
   int rc = prepare(p, flags); if (rc) return rc;
   hipStream_t st = p->stream;
-  hipEvent_t e0, e1; HIPCK(p, hipEventCreate(&e0)); HIPCK(p, hipEventCreate(&e1));
-  auto saved = p->reduce; p->reduce = nullptr;
-  rc = eval_pass(p, p->d_x.p, true);   // warm-up
-  if (!rc) { HIPCK(p, hipEventRecord(e0, st)); for (int i = 0; i < repeats && !rc; ++i) rc = eval_pass(p, p->d_x.p, true); HIPCK(p, hipEventRecord(e1, st)); HIPCK(p, hipEventSynchronize(e1)); }
-  float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
-  if (ms_per_pass) *ms_per_pass = double(ms) / std::max(repeats, 1);
-  if (kernel_ms && !rc) {
-    for (int k = 0; k < 3 && !rc; ++k) {
-      HIPCK(p, hipEventRecord(e0, st));
-      for (int i = 0; i < repeats && !rc; ++i) rc = eval_pass(p, p->d_x.p, true, nullptr, nullptr, k);   // this residual family only
-      HIPCK(p, hipEventRecord(e1, st)); HIPCK(p, hipEventSynchronize(e1));
-      (void)hipEventElapsedTime(&ms, e0, e1); kernel_ms[k] = double(ms) / std::max(repeats, 1);
-    }
-    rc = eval_pass(p, p->d_x.p, true);   // leave a consistent system behind
+  EventPair ev; HIPCK(p, hipEventCreate(&ev.a)); HIPCK(p, hipEventCreate(&ev.b));
+  auto timed = [&](int only_kind, double* ms_out) -> int {   // `repeats` local passes between the two events
+    HIPCK(p, hipEventRecord(ev.a, st));
+    for (int i = 0; i < repeats; ++i) { const int r = eval_pass(p, local_pass(p->d_x.p, true, only_kind)); if (r) return r; }
+    HIPCK(p, hipEventRecord(ev.b, st)); HIPCK(p, hipEventSynchronize(ev.b));
+    float ms = 0; (void)hipEventElapsedTime(&ms, ev.a, ev.b);
+    if (ms_out) *ms_out = double(ms) / std::max(repeats, 1);
+    return OICC_OK; };
+  rc = eval_pass(p, local_pass(p->d_x.p, true)); if (rc) return rc;   // warm-up
+  rc = timed(-1, ms_per_pass); if (rc) return rc;
+  if (kernel_ms) {
+    for (int k = 0; k < 3; ++k) { rc = timed(k, &kernel_ms[k]); if (rc) return rc; }   // this residual family only
+    rc = eval_pass(p, local_pass(p->d_x.p, true));   // leave a consistent system behind
   }
-  p->reduce = saved;
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   return rc;
 }
 int oicc_time_linear_solve(oicc_problem* p, int32_t flags, int32_t repeats, double* ms_per_solve) {
@@ -973,24 +989,20 @@ int oicc_time_linear_solve(oicc_problem* p, int32_t flags, int32_t repeats, doub
   // time-sharded ranks (oicc_set_shard + a reduction): the pass runs with its exchange and the solve is the one oicc_optimize
   // uses there -- the distributed cyclic reduction where the ranks agreed on it -- so every rank must make this call
   const bool sharded = p->shard_n > 1 && p->reduce != nullptr;
-  auto saved = p->reduce; if (!sharded) p->reduce = nullptr;
-  rc = eval_pass(p, p->d_x.p, true); p->reduce = saved; if (rc) return rc;
-  const TangentLayout& tl = p->tl;
-  if (tl.P == 0) { if (ms_per_solve) *ms_per_solve = 0; return OICC_OK; }
+  const double radius = p->opt["initial_trust_region_radius"], min_diag = p->opt["min_lm_diagonal"], max_diag = p->opt["max_lm_diagonal"];
   SolveBuffers sb = solve_buffers(p);
-  launch_lm_scale(p->ne, tl, sb.scale, p->opt["jacobi_scaling"] != 0, st);
-  LmState hs; std::memset(&hs, 0, sizeof(hs)); hs.radius = p->opt["initial_trust_region_radius"];
-  HIPCK(p, hipMemcpyAsync(p->d_state.p, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
-  hipEvent_t e0, e1; HIPCK(p, hipEventCreate(&e0)); HIPCK(p, hipEventCreate(&e1));
-  rc = lm_solve_any(p, p->ne, sb, p->opt["initial_trust_region_radius"], 0, p->opt["min_lm_diagonal"], p->opt["max_lm_diagonal"], st); if (rc) return rc;
-  HIPCK(p, hipEventRecord(e0, st));
+  PassRequest rq = jacobian_pass(p->d_x.p); rq.local = !sharded;
+  rc = system_at_current_point(p, rq, sb.scale, p->opt["jacobi_scaling"] != 0, radius); if (rc) return rc;
+  if (p->tl.P == 0) { if (ms_per_solve) *ms_per_solve = 0; return OICC_OK; }
+  EventPair ev; HIPCK(p, hipEventCreate(&ev.a)); HIPCK(p, hipEventCreate(&ev.b));
+  rc = lm_solve_any(p, p->ne, sb, radius, 0, min_diag, max_diag, st); if (rc) return rc;
+  HIPCK(p, hipEventRecord(ev.a, st));
   for (int i = 0; i < repeats; ++i) {
-    rc = lm_solve_any(p, p->ne, sb, p->opt["initial_trust_region_radius"], 0, p->opt["min_lm_diagonal"], p->opt["max_lm_diagonal"], st); if (rc) return rc;
+    rc = lm_solve_any(p, p->ne, sb, radius, 0, min_diag, max_diag, st); if (rc) return rc;
   }
-  HIPCK(p, hipEventRecord(e1, st)); HIPCK(p, hipEventSynchronize(e1));
-  float ms = 0; (void)hipEventElapsedTime(&ms, e0, e1);
+  HIPCK(p, hipEventRecord(ev.b, st)); HIPCK(p, hipEventSynchronize(ev.b));
+  float ms = 0; (void)hipEventElapsedTime(&ms, ev.a, ev.b);
   if (ms_per_solve) *ms_per_solve = double(ms) / std::max(repeats, 1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
   return OICC_OK;
 }
 
@@ -998,23 +1010,11 @@ int oicc_time_linear_solve(oicc_problem* p, int32_t flags, int32_t repeats, doub
 // out = {||M delta - rhs||_2 / ||rhs||_2, ||rhs||_2, Cholesky failure flag} with M = S H S + D^2 / radius, rhs = -S g.
 int oicc_solve_residual(oicc_problem* p, int32_t flags, double radius, double out[3]) {
   int rc = prepare(p, flags); if (rc) return rc;
-  hipStream_t st = p->stream;
-  auto saved = p->reduce; p->reduce = nullptr;
-  rc = eval_pass(p, p->d_x.p, true); p->reduce = saved; if (rc) return rc;
-  const TangentLayout& tl = p->tl;
-  if (tl.P == 0) { out[0] = out[1] = out[2] = 0.0; return OICC_OK; }
   SolveBuffers sb = solve_buffers(p);
-  launch_lm_scale(p->ne, tl, sb.scale, p->opt["jacobi_scaling"] != 0, st);
-  HIPCK(p, hipMemsetAsync(p->d_state.p, 0, sizeof(LmState), st));
-  if (launch_lm_solve(p->ne, tl, sb, radius, 0, p->opt["min_lm_diagonal"], p->opt["max_lm_diagonal"], st) != 0) { p->err = "solver geometry unsupported"; return OICC_ERR_UNSUPPORTED; }
-  DevBuf<double> acc; if (!acc.resize(2 + size_t(tl.a))) return OICC_ERR_HIP;
-  launch_lm_solve_residual(p->ne, tl, sb, acc.p, st);
-  double h[2] = {0, 0}; LmState hs;
-  HIPCK(p, hipMemcpyAsync(h, acc.p, sizeof(h), hipMemcpyDeviceToHost, st));
-  HIPCK(p, hipMemcpyAsync(&hs, p->d_state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
-  HIPCK(p, hipStreamSynchronize(st));
-  out[1] = std::sqrt(h[1]); out[0] = h[1] > 0.0 ? std::sqrt(h[0] / h[1]) : std::sqrt(h[0]); out[2] = double(hs.chol_failed);
-  return OICC_OK;
+  rc = system_at_current_point(p, local_pass(p->d_x.p, true), sb.scale, p->opt["jacobi_scaling"] != 0, 0.0); if (rc) return rc;
+  if (p->tl.P == 0) { out[0] = out[1] = out[2] = 0.0; return OICC_OK; }
+  if (launch_lm_solve(p->ne, p->tl, sb, radius, 0, p->opt["min_lm_diagonal"], p->opt["max_lm_diagonal"], p->stream) != 0) { p->err = "solver geometry unsupported"; return OICC_ERR_UNSUPPORTED; }
+  return read_solve_residual(p, sb, &out[0], &out[1], &out[2]);
 }
 
 
@@ -1032,13 +1032,10 @@ double oicc_debug_ls_next_step_size(const double init[3], const double* prev, in
 int oicc_debug_solver_profile(oicc_problem* p, int32_t flags, long long out[12]) {
   int rc = prepare(p, flags); if (rc) return rc;
   hipStream_t st = p->stream;
-  rc = eval_pass_full_system(p); if (rc) return rc;   // (time shards: every rank profiles the solve of the whole system)
   const TangentLayout& tl = p->tl;
   DevBuf<long long> d; if (!d.resize(12)) return OICC_ERR_HIP;
   SolveBuffers sb = solve_buffers(p, d.p);
-  launch_lm_scale(p->ne, tl, sb.scale, 1, st);
-  LmState hs; std::memset(&hs, 0, sizeof(hs)); hs.radius = 1e4;
-  HIPCK(p, hipMemcpyAsync(p->d_state.p, &hs, sizeof(hs), hipMemcpyHostToDevice, st));
+  rc = system_at_current_point(p, full_system_pass(p), sb.scale, true, 1e4); if (rc) return rc;   // (time shards: every rank profiles the solve of the whole system)
   for (int rep = 0; rep < 2; ++rep) {
     if (launch_lm_solve(p->ne, tl, sb, 1e4, 0, 1e-6, 1e32, st) != 0) return OICC_ERR_UNSUPPORTED;
   }
@@ -1049,29 +1046,18 @@ int oicc_debug_solver_profile(oicc_problem* p, int32_t flags, long long out[12])
 
 // Debug: cycle counters of one mid-grid view block: [phase 1 (spline+residual+Jacobian rows), phase 2+3 (Gram + atomic flush)]
 // kind 0: views, 1: accelerometer, 2: gyroscope -- [evaluation phase, Gram+scatter, MFMA part, scatter part] of the middle chunk
-int oicc_debug_tile_profile(oicc_problem* p, int32_t flags, int32_t kind, long long out[16]) {   // kind -1: all units of the tile
+static int tile_profile(oicc_problem* p, int32_t flags, int32_t kind, long long* out, int n_out) {
   int rc = prepare(p, flags); if (rc) return rc;
   DevBuf<long long> d; if (!d.resize(16)) return OICC_ERR_HIP;
   HIPCK(p, hipMemsetAsync(d.p, 0, 16 * sizeof(long long), p->stream));
-  auto saved = p->reduce; p->reduce = nullptr;
-  rc = eval_pass(p, p->d_x.p, true, nullptr, nullptr, kind, false, nullptr, false, d.p);
-  p->reduce = saved; if (rc) return rc;
-  HIPCK(p, hipMemcpyAsync(out, d.p, 16 * sizeof(long long), hipMemcpyDeviceToHost, p->stream));
+  PassRequest rq = local_pass(p->d_x.p, true, kind); rq.prof = d.p;
+  rc = eval_pass(p, rq); if (rc) return rc;
+  HIPCK(p, hipMemcpyAsync(out, d.p, size_t(n_out) * sizeof(long long), hipMemcpyDeviceToHost, p->stream));
   HIPCK(p, hipStreamSynchronize(p->stream));
   return OICC_OK;
 }
-int oicc_debug_block_profile(oicc_problem* p, int32_t flags, int32_t kind, long long out[4]) {
-  int rc = prepare(p, flags); if (rc) return rc;
-  DevBuf<long long> d; if (!d.resize(16)) return OICC_ERR_HIP;
-  HIPCK(p, hipMemsetAsync(d.p, 0, 16 * sizeof(long long), p->stream));
-  kind %= 10;
-  auto saved = p->reduce; p->reduce = nullptr;
-  rc = eval_pass(p, p->d_x.p, true, nullptr, nullptr, kind, false, nullptr, false, d.p);
-  p->reduce = saved; if (rc) return rc;
-  HIPCK(p, hipMemcpyAsync(out, d.p, 4 * sizeof(long long), hipMemcpyDeviceToHost, p->stream));
-  HIPCK(p, hipStreamSynchronize(p->stream));
-  return OICC_OK;
-}
+int oicc_debug_tile_profile(oicc_problem* p, int32_t flags, int32_t kind, long long out[16]) { return tile_profile(p, flags, kind, out, 16); }   // kind -1: all units of the tile
+int oicc_debug_block_profile(oicc_problem* p, int32_t flags, int32_t kind, long long out[4]) { return tile_profile(p, flags, kind % 10, out, 4); }
 int oicc_debug_view_profile(oicc_problem* p, int32_t flags, long long out[4]) { return oicc_debug_block_profile(p, flags, 0, out); }
 
 int oicc_get_T_i_c(const oicc_problem* p, double v[7]) { std::memcpy(v, p->x.data() + p->pl.tic, 7 * sizeof(double)); return OICC_OK; }
@@ -1093,9 +1079,9 @@ int oicc_get_mean_reprojection_error(oicc_problem* p, double* mean_px, int64_t* 
   for (size_t v = 0; v + 1 < p->view_c0.size(); ++v) if (p->view_c0[v + 1] == p->view_c0[v]) { *mean_px = 0.0; if (num) *num = 0; return OICC_OK; }  // quirk Q6
   if (nc == 0) { *mean_px = std::nan(""); if (num) *num = 0; return OICC_OK; }
   if (!p->d_dbg_res.resize(2 * nc)) { p->err = "hipMalloc"; return OICC_ERR_HIP; }
-  { auto saved = p->reduce; p->reduce = nullptr;   // residual dump of the RS functor for every view (also in GS mode, impl.h:1021-1056)
-    rc = eval_pass(p, p->d_x.p, false, p->d_dbg_res.p, nullptr, 0, false, nullptr, /*force_rs=*/true);
-    p->reduce = saved; if (rc) return rc; }
+  PassRequest rq = local_pass(p->d_x.p, false, 0);   // residual dump of the RS functor for every view (also in GS mode, impl.h:1021-1056)
+  rq.dbg_res = p->d_dbg_res.p; rq.force_rs = true;
+  rc = eval_pass(p, rq); if (rc) return rc;
   std::vector<double> r(2 * nc);
   HIPCK(p, hipMemcpyAsync(r.data(), p->d_dbg_res.p, r.size() * sizeof(double), hipMemcpyDeviceToHost, p->stream));
   HIPCK(p, hipStreamSynchronize(p->stream));
