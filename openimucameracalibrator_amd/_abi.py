@@ -199,6 +199,22 @@ class Bound:
         self.device = device
 
 
+# Debug read-outs of the inner iterations (device library only, outside include/oicc_hip.h: csrc/oicc_inner.hip, csrc/inner_iterations.hip):
+# full symbol name -> (restype, argtypes); bound on first use (bind_inner_debug).
+INNER_DEBUG_SIGNATURES = {
+    "oicc_debug_inner_first_evaluations": (C.c_int, [H, C.c_int32, c_i32p, c_dp, C.c_int32]),
+    "oicc_debug_inner_cholesky": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, c_dp, c_dp, c_dp, c_u8p]),
+}
+INNER_ROUTES = ("set_kernel<0>", "set_kernel<1>", "set_kernel<2>", "wave_kernel", "shared: resident workgroups", "shared: launches")
+INNER_KINDS = ("so3", "r3", "T_i_c", "gravity", "line_delay", "accl_bias", "gyro_bias", "accl_intrinsics", "gyro_intrinsics", "point")   # InnerKind, csrc/inner_plan.h
+
+
+def bind_inner_debug(lib, name):
+    fn = getattr(lib, name)  # AttributeError = missing symbol: fail loudly
+    fn.restype, fn.argtypes = INNER_DEBUG_SIGNATURES[name]
+    return fn
+
+
 # IMU noise characterisation (oicc_allan_* in include/oicc_hip.h): name -> (restype, argtypes).  A table of its own:
 # SIGNATURES is also bound against the CPU checker, which has no counterpart of these entries.
 ALLAN_SIGNATURES = {

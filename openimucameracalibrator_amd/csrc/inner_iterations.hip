@@ -575,7 +575,9 @@ __global__ void inner_records_kernel(ViewData vd, ImuData ia, ImuData ig, InnerI
 }
 
 // wave w of workgroup g: block b0 + g * (T / 64) + w of the plan (a set's knot blocks are contiguous there)
-template <bool R3ONLY, int NWV>
+// READ_OUT (here and in inner_set_kernel / inner_shared_advance_kernel): the instantiations of the debug read-out of the blocks' first evaluations
+// (InnerArgs::first_eval, oicc_debug_inner_first_evaluations); the kernels of a solve are compiled without it
+template <bool R3ONLY, int NWV, bool READ_OUT = false>
 __global__ void __launch_bounds__((InnerWaveCfg<R3ONLY, NWV>::T), (InnerWaveCfg<R3ONLY, NWV>::OCC)) inner_wave_kernel(const InnerArgs* __restrict__ Sp, double* xv, int b0, int n_blocks) {
   using CFG = InnerWaveCfg<R3ONLY, NWV>;
   constexpr int T = CFG::T, NW = T / 64;
@@ -655,10 +657,13 @@ __global__ void __launch_bounds__((InnerWaveCfg<R3ONLY, NWV>::T), (InnerWaveCfg<
       }
     }
     wave_sync();
+    const bool read_out = READ_OUT && S.first != 0 && A.first_eval != nullptr;   // debug read-out of the first evaluation (inner_plan.h; S.first: no advance ran yet)
+    if (read_out && lane < 56) A.first_eval[(size_t)(b0 + bi) * 56 + lane] = lane < nv ? row[lane] : 0.0;
     if (lane == 0) {
       double* x = xv + blk.xoff;
       int nc;
-      if (R3ONLY) nc = inner_lm_advance<3, 3>(S, IK_R3, cmd, row, x, xl, A.max_ab, A.max_gb);
+      if (read_out && A.stop_first) nc = INNER_CMD_DONE;
+      else if (R3ONLY) nc = inner_lm_advance<3, 3>(S, IK_R3, cmd, row, x, xl, A.max_ab, A.max_gb);
       else if (blk.kind == IK_SO3) nc = inner_lm_advance<3, 4>(S, IK_SO3, cmd, row, x, xl, A.max_ab, A.max_gb);
       else nc = inner_lm_advance<3, 3>(S, blk.kind, cmd, row, x, xl, A.max_ab, A.max_gb);
       s_cmd[wave] = nc;
@@ -739,6 +744,7 @@ __global__ void __launch_bounds__((InnerCfg<0>::T), 2) inner_shared_eval_kernel(
   if (tid < 56) { double t = 0.0; for (int w = 0; w < T / 64; ++w) t += s_part[w][tid]; partials[((size_t)blk.ctl * max_parts + wg.part) * 56 + tid] = t; }
 }
 // one wave per shared block of the set: the rows of its parts added in order, the loop advanced, the next command published
+template <bool READ_OUT>
 __global__ void __launch_bounds__(512) inner_shared_advance_kernel(const InnerArgs* __restrict__ Sp, double* xv, const int32_t* __restrict__ block_ids, const int32_t* __restrict__ block_parts,
                                                                    const double* partials, int max_parts, InnerLm* states, int count_iterations) {
   const InnerArgs& A = *Sp;
@@ -774,8 +780,10 @@ __global__ void __launch_bounds__(512) inner_shared_advance_kernel(const InnerAr
   __syncthreads();
   if (tid < 64) { double t = 0.0; for (int w = 0; w < NW; ++w) t += s_w[w][tid]; s_tot[tid] = t; }
   __syncthreads();
+  const bool read_out = READ_OUT && (word >> 2) == 0u && A.first_eval != nullptr;   // debug read-out of the first evaluation (inner_plan.h)
+  if (read_out && tid < 56) A.first_eval[(size_t)block_ids[blockIdx.x] * 56 + tid] = s_tot[tid];   // (the parts' rows are zero behind the block's sums)
   if (tid == 0) {
-    const int nc = inner_advance_dispatch<0>(S, blk, cmd, s_tot, xv + blk.xoff, nullptr, A.max_ab, A.max_gb);
+    const int nc = read_out && A.stop_first ? int(INNER_CMD_DONE) : inner_advance_dispatch<0>(S, blk, cmd, s_tot, xv + blk.xoff, nullptr, A.max_ab, A.max_gb);
     if (nc == INNER_CMD_DONE && count_iterations && A.lm_iterations != nullptr) atomicAdd(A.lm_iterations, (unsigned long long)S.iter);
     ctl->word = (((word >> 2) + 1u) << 2) | (unsigned)nc;
   }
@@ -790,7 +798,7 @@ __global__ void inner_seg_kernel(const double* so3, int n_pairs, double* seg) {
 
 // workgroup = (block of the set, part): the block's whole Levenberg-Marquardt loop
 // prof: debug (option debug_inner_profile): shader clock of workgroup 0 / thread 0 at every phase boundary, [0] = count
-template <int MODE>
+template <int MODE, bool READ_OUT = false>
 __global__ void __launch_bounds__(InnerCfg<MODE>::T) inner_set_kernel(const InnerArgs* __restrict__ Sp, double* xv, const InnerWg* __restrict__ wgs, long long* prof_buf) {
   using CFG = InnerCfg<MODE>;
   constexpr bool R3ONLY = CFG::R3ONLY;
@@ -892,9 +900,11 @@ __global__ void __launch_bounds__(InnerCfg<MODE>::T) inner_set_kernel(const Inne
     }
     __syncthreads();
     if (master) {
+      const bool read_out = READ_OUT && round == 0 && A.first_eval != nullptr;   // debug read-out of the first evaluation (inner_plan.h)
+      if (read_out && tid < 56) A.first_eval[(size_t)wg.block * 56 + tid] = tid < nv ? s_tot[tid] : 0.0;
       if (tid == 0) {
         double* x = xv + blk.xoff;
-        const int nc = inner_advance_dispatch<MODE>(S, blk, cmd, s_tot, x, xl, A.max_ab, A.max_gb);
+        const int nc = read_out && A.stop_first ? int(INNER_CMD_DONE) : inner_advance_dispatch<MODE>(S, blk, cmd, s_tot, x, xl, A.max_ab, A.max_gb);
         s_cmd = nc;
       }
       INNER_MARK();
@@ -956,8 +966,14 @@ __global__ void inner_diff_norm_kernel(const double* x, const double* xc, const 
 void launch_inner_seg(const double* so3, int n_pairs, double* seg, hipStream_t st) {
   if (n_pairs > 0) hipLaunchKernelGGL(inner_seg_kernel, dim3((n_pairs + 127) / 128), dim3(128), 0, st, so3, n_pairs, seg);
 }
-void launch_inner_set(const InnerArgs* dA, double* xv, const InnerWg* wgs, long long* prof, int n_wgs, int mode, hipStream_t st) {   // mode (InnerCfg): 1 = every block of the set is an R^3 knot with at most 1024 item slots, 2 = the plan holds board-point blocks
+void launch_inner_set(const InnerArgs* dA, double* xv, const InnerWg* wgs, long long* prof, int n_wgs, int mode, hipStream_t st, bool read_out) {   // mode (InnerCfg): 1 = every block of the set is an R^3 knot with at most 1024 item slots, 2 = the plan holds board-point blocks
   if (n_wgs <= 0) return;
+  if (read_out) {   // (debug read-out of the first evaluations: instantiations of their own)
+    if (mode == 1) hipLaunchKernelGGL((inner_set_kernel<1, true>), dim3(n_wgs), dim3(InnerCfg<1>::T), 0, st, dA, xv, wgs, prof);
+    else if (mode == 2) hipLaunchKernelGGL((inner_set_kernel<2, true>), dim3(n_wgs), dim3(InnerCfg<2>::T), 0, st, dA, xv, wgs, prof);
+    else hipLaunchKernelGGL((inner_set_kernel<0, true>), dim3(n_wgs), dim3(InnerCfg<0>::T), 0, st, dA, xv, wgs, prof);
+    return;
+  }
   if (mode == 1) hipLaunchKernelGGL(inner_set_kernel<1>, dim3(n_wgs), dim3(InnerCfg<1>::T), 0, st, dA, xv, wgs, prof);
   else if (mode == 2) hipLaunchKernelGGL(inner_set_kernel<2>, dim3(n_wgs), dim3(InnerCfg<2>::T), 0, st, dA, xv, wgs, prof);
   else hipLaunchKernelGGL(inner_set_kernel<0>, dim3(n_wgs), dim3(InnerCfg<0>::T), 0, st, dA, xv, wgs, prof);
@@ -969,12 +985,18 @@ void launch_inner_records(const ViewData& vd, const ImuData& ia, const ImuData& 
 void launch_inner_shared_eval(const InnerArgs* dA, double* xv, const InnerWg* wgs, int n_wgs, double* partials, int max_parts, hipStream_t st) {
   if (n_wgs > 0) hipLaunchKernelGGL(inner_shared_eval_kernel, dim3(n_wgs), dim3(InnerCfg<0>::T), 0, st, dA, xv, wgs, partials, max_parts);
 }
-void launch_inner_shared_advance(const InnerArgs* dA, double* xv, const int32_t* block_ids, const int32_t* block_parts, int n_blocks, const double* partials, int max_parts, void* states, bool count_iterations, hipStream_t st) {
-  if (n_blocks > 0) hipLaunchKernelGGL(inner_shared_advance_kernel, dim3(n_blocks), dim3(512), 0, st, dA, xv, block_ids, block_parts, partials, max_parts, static_cast<InnerLm*>(states), count_iterations ? 1 : 0);
+void launch_inner_shared_advance(const InnerArgs* dA, double* xv, const int32_t* block_ids, const int32_t* block_parts, int n_blocks, const double* partials, int max_parts, void* states, bool count_iterations, hipStream_t st, bool read_out) {
+  if (n_blocks > 0 && read_out) hipLaunchKernelGGL(inner_shared_advance_kernel<true>, dim3(n_blocks), dim3(512), 0, st, dA, xv, block_ids, block_parts, partials, max_parts, static_cast<InnerLm*>(states), count_iterations ? 1 : 0);
+  else if (n_blocks > 0) hipLaunchKernelGGL(inner_shared_advance_kernel<false>, dim3(n_blocks), dim3(512), 0, st, dA, xv, block_ids, block_parts, partials, max_parts, static_cast<InnerLm*>(states), count_iterations ? 1 : 0);
 }
 size_t inner_lm_state_bytes() { return sizeof(InnerLm); }
-void launch_inner_wave(const InnerArgs* dA, double* xv, int b0, int n_blocks, bool r3_only, hipStream_t st) {   // one wave per block: blocks [b0, b0 + n_blocks) of the plan
+void launch_inner_wave(const InnerArgs* dA, double* xv, int b0, int n_blocks, bool r3_only, hipStream_t st, bool read_out) {   // one wave per block: blocks [b0, b0 + n_blocks) of the plan
   if (n_blocks <= 0) return;
+  if (read_out) {
+    if (r3_only) hipLaunchKernelGGL((inner_wave_kernel<true, 1, true>), dim3(n_blocks), dim3(64), 0, st, dA, xv, b0, n_blocks);
+    else hipLaunchKernelGGL((inner_wave_kernel<false, 1, true>), dim3(n_blocks), dim3(64), 0, st, dA, xv, b0, n_blocks);
+    return;
+  }
   if (r3_only) hipLaunchKernelGGL((inner_wave_kernel<true, 1>), dim3(n_blocks), dim3(64), 0, st, dA, xv, b0, n_blocks);
   else hipLaunchKernelGGL((inner_wave_kernel<false, 1>), dim3(n_blocks), dim3(64), 0, st, dA, xv, b0, n_blocks);
 }
@@ -990,3 +1012,42 @@ void launch_inner_diff_norm(const double* x, const double* xc, const InnerBlock*
 }
 
 }  // namespace oicc
+
+// ---- debug entry point outside include/oicc_hip.h (tests/test_gpu_inner_evaluation.py): inner_cholesky_solve<D> itself, one lane per
+// system, so that the reciprocal-square-root form of the small solve can be held against a plain extended-precision solve ----
+namespace oicc {
+template <int D>
+__global__ void inner_cholesky_debug_kernel(int64_t n, const double* M, const double* rhs, double* x, unsigned char* ok) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  double m[D * D], r[D], s[D];
+#pragma unroll
+  for (int k = 0; k < D * D; ++k) m[k] = M[i * (D * D) + k];
+#pragma unroll
+  for (int k = 0; k < D; ++k) { r[k] = rhs[i * D + k]; s[k] = 0.0; }
+  const bool good = inner_cholesky_solve<D>(m, r, s);
+#pragma unroll
+  for (int k = 0; k < D; ++k) x[i * D + k] = s[k];
+  ok[i] = good ? 1 : 0;
+}
+}  // namespace oicc
+extern "C" int oicc_debug_inner_cholesky(int32_t device, int32_t D, int64_t n, const double* M, const double* rhs, double* x, uint8_t* ok) {
+  if (n <= 0 || !M || !rhs || !x || !ok || (D != 1 && D != 3 && D != 6 && D != 9)) return 2;
+  if (hipSetDevice(device) != hipSuccess) return 5;
+  const size_t nm = size_t(n) * size_t(D * D), nd = size_t(n) * size_t(D);
+  double* d = nullptr; unsigned char* dk = nullptr;
+  if (hipMalloc(&d, (nm + 2 * nd) * sizeof(double)) != hipSuccess) return 4;
+  if (hipMalloc(&dk, size_t(n)) != hipSuccess) { (void)hipFree(d); return 4; }
+  bool good = hipMemcpy(d, M, nm * sizeof(double), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d + nm, rhs, nd * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
+  if (good) {
+    const dim3 grid(unsigned((n + 63) / 64)), block(64);
+    if (D == 1) hipLaunchKernelGGL(oicc::inner_cholesky_debug_kernel<1>, grid, block, 0, nullptr, n, d, d + nm, d + nm + nd, dk);
+    else if (D == 3) hipLaunchKernelGGL(oicc::inner_cholesky_debug_kernel<3>, grid, block, 0, nullptr, n, d, d + nm, d + nm + nd, dk);
+    else if (D == 6) hipLaunchKernelGGL(oicc::inner_cholesky_debug_kernel<6>, grid, block, 0, nullptr, n, d, d + nm, d + nm + nd, dk);
+    else hipLaunchKernelGGL(oicc::inner_cholesky_debug_kernel<9>, grid, block, 0, nullptr, n, d, d + nm, d + nm + nd, dk);
+    good = hipGetLastError() == hipSuccess && hipMemcpy(x, d + nm + nd, nd * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
+           hipMemcpy(ok, dk, size_t(n), hipMemcpyDeviceToHost) == hipSuccess;
+  }
+  (void)hipFree(d); (void)hipFree(dk);
+  return good ? 0 : 4;
+}

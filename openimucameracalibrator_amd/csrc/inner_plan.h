@@ -58,6 +58,10 @@ struct InnerArgs {
   unsigned long long* lm_iterations;
   double max_ab, max_gb;
   const InnerItemRec* rec[3];   // per-item records of the wave-per-block kernel: corners, accelerometer samples, gyroscope samples
+  // debug read-out (oicc_debug_inner_first_evaluations, oicc_inner.hip; null / 0 in every sweep of a solve): row [56] of block b of the plan =
+  // the sums [H upper | g | cost] of the block's FIRST evaluation, and with stop_first every block's loop ends right behind it
+  double* first_eval;
+  int32_t stop_first, pad;
 };
 
 }  // namespace oicc

@@ -395,7 +395,7 @@ static int build_rank_part(oicc_problem* p, oicc_problem* shard) {
   return OICC_OK;
 }
 
-int inner_sweep(oicc_problem* p, double* xv, hipStream_t st, oicc_problem* shard, bool* owner_computes) {   // p: the problem whose measurements and plan are used (xv may belong to another problem with the same spline)
+int inner_sweep(oicc_problem* p, double* xv, hipStream_t st, oicc_problem* shard, bool* owner_computes, const InnerFirstEval* fe) {   // p: the problem whose measurements and plan are used (xv may belong to another problem with the same spline)
   oicc_problem::InnerPlan& ip = p->inner;
   const bool owned = shard != nullptr && shard != p && shard->shard_n > 1 && shard->owner.valid && shard->owner.agreed && shard->owner.agreed_gen == shard->layout_gen &&
                      shard->opt["owner_computes_sweeps"] != 0.0;
@@ -407,17 +407,24 @@ int inner_sweep(oicc_problem* p, double* xv, hipStream_t st, oicc_problem* shard
   A.seg = ip.d_seg.p; A.blocks = ip.d_blocks.p; A.runs = ip.d_runs.p; A.ctls = ip.d_ctls.p;
   A.lm_iterations = ip.d_lm_iterations.p; A.max_ab = p->max_ab; A.max_gb = p->max_gb;
   for (int k = 0; k < 3; ++k) A.rec[k] = ip.d_rec[k].p;
-  if (!ip.h_args) { ip.h_args.reset(new InnerArgs); std::memset(ip.h_args.get(), 0, sizeof(InnerArgs)); ip.args_valid = false; }
-  if (!ip.args_valid || std::memcmp(&A, ip.h_args.get(), sizeof(A)) != 0) {   // (rare: plan, layout or measurement changes)
+  const InnerArgs* dA = nullptr;
+  if (fe != nullptr) {   // debug read-out: scratch tables and arguments of the caller's, no counters (the cached arguments of the solves stay as they are)
+    A.seg = fe->seg; A.ctls = fe->ctls; A.lm_iterations = nullptr; A.first_eval = fe->rows; A.stop_first = 1;
+    HIPCK(p, hipMemcpyAsync(fe->d_args, &A, sizeof(InnerArgs), hipMemcpyHostToDevice, st));
+    HIPCK(p, hipStreamSynchronize(st));
+    dA = fe->d_args;
+  }
+  if (fe == nullptr && !ip.h_args) { ip.h_args.reset(new InnerArgs); std::memset(ip.h_args.get(), 0, sizeof(InnerArgs)); ip.args_valid = false; }
+  if (fe == nullptr && (!ip.args_valid || std::memcmp(&A, ip.h_args.get(), sizeof(A)) != 0)) {   // (rare: plan, layout or measurement changes)
     if (!ip.d_args.resize(1)) { p->err = "hipMalloc inner-iteration arguments"; return OICC_ERR_HIP; }
     *ip.h_args = A;
     HIPCK(p, hipMemcpyAsync(ip.d_args.p, ip.h_args.get(), sizeof(InnerArgs), hipMemcpyHostToDevice, st));
     HIPCK(p, hipStreamSynchronize(st));   // the host copy may be rewritten right away
     ip.args_valid = true;
   }
-  ++ip.sweeps;
+  if (fe == nullptr) { dA = ip.d_args.p; ++ip.sweeps; }
   // debug_inner_set_costs: the total cost before the sweep and behind every independent set (one cost pass + one read-back each)
-  const bool trace_sets = p->opt["debug_inner_set_costs"] != 0.0 && (shard == nullptr || shard == p);
+  const bool trace_sets = p->opt["debug_inner_set_costs"] != 0.0 && (shard == nullptr || shard == p) && fe == nullptr;
   auto trace_cost = [&](double nblocks) -> int {
     if (!p->d_dbg_cost.resize(1)) { p->err = "hipMalloc debug cost"; return OICC_ERR_HIP; }
     HIPCK(p, hipMemsetAsync(p->d_dbg_cost.p, 0, sizeof(double), st));
@@ -428,9 +435,9 @@ int inner_sweep(oicc_problem* p, double* xv, hipStream_t st, oicc_problem* shard
     p->inner_set_costs.push_back(nblocks); p->inner_set_costs.push_back(c);
     return OICC_OK; };
   if (trace_sets) { const int rc = trace_cost(-1.0); if (rc) return rc; }
-  launch_inner_seg(xv + p->pl.so3, std::max(p->pl.n_so3 - 1, 0), ip.d_seg.p, st);
-  if (ip.n_ctls > 0) HIPCK(p, hipMemsetAsync(ip.d_ctls.p, 0, size_t(ip.n_ctls) * sizeof(InnerCtl), st));
-  const int prof_set = int(p->opt["debug_inner_profile"]) - 1;   // debug: phase clocks of workgroup 0 of this set
+  launch_inner_seg(xv + p->pl.so3, std::max(p->pl.n_so3 - 1, 0), A.seg, st);
+  if (ip.n_ctls > 0) HIPCK(p, hipMemsetAsync(A.ctls, 0, size_t(ip.n_ctls) * sizeof(InnerCtl), st));
+  const int prof_set = fe != nullptr ? -1 : int(p->opt["debug_inner_profile"]) - 1;   // debug: phase clocks of workgroup 0 of this set
   DevBuf<long long> d_prof;
   for (size_t g = 0; g + 1 < ip.group_wg0.size(); ++g) {
     long long* prof = nullptr;
@@ -446,13 +453,13 @@ int inner_sweep(oicc_problem* p, double* xv, hipStream_t st, oicc_problem* shard
       std::vector<unsigned char> hc(pinned_words ? 0 : size_t(ip.n_ctls) * sizeof(InnerCtl));
       for (int pairs = 0, batch = 6; pairs < 256; pairs += batch, batch = 2) {   // two or three LM iterations = four or six pairs are the rule; pairs behind the end return at once (~3 us each, against ~30 us for another look at the command words)
         for (int k = 0; k < batch; ++k) {
-          launch_inner_shared_eval(ip.d_args.p, xv, ip.d_big_wgs.p + ip.group_bigwg0[g], nbw, ip.d_partials.p, ip.big_max_parts, st);
-          launch_inner_shared_advance(ip.d_args.p, xv, ip.d_big_blocks.p + ip.group_bigb0[g], ip.d_big_parts.p + ip.group_bigb0[g], nbb, ip.d_partials.p, ip.big_max_parts, ip.d_lm_states.p, count, st);
+          launch_inner_shared_eval(dA, xv, ip.d_big_wgs.p + ip.group_bigwg0[g], nbw, ip.d_partials.p, ip.big_max_parts, st);
+          launch_inner_shared_advance(dA, xv, ip.d_big_blocks.p + ip.group_bigb0[g], ip.d_big_parts.p + ip.group_bigb0[g], nbb, ip.d_partials.p, ip.big_max_parts, ip.d_lm_states.p, count, st, fe != nullptr);
         }
         if (pinned_words) {
           for (int k = 0; k < nbb; ++k) { const InnerBlock& bb = ip.blocks[size_t(ip.big_blocks[size_t(ip.group_bigb0[g] + k)])];
-            HIPCK(p, hipMemcpyAsync(&ph->pin->inner_words[k], &ip.d_ctls.p[bb.ctl].word, sizeof(unsigned int), hipMemcpyDeviceToHost, st)); }
-        } else HIPCK(p, hipMemcpyAsync(hc.data(), ip.d_ctls.p, hc.size(), hipMemcpyDeviceToHost, st));
+            HIPCK(p, hipMemcpyAsync(&ph->pin->inner_words[k], &A.ctls[bb.ctl].word, sizeof(unsigned int), hipMemcpyDeviceToHost, st)); }
+        } else HIPCK(p, hipMemcpyAsync(hc.data(), A.ctls, hc.size(), hipMemcpyDeviceToHost, st));
         HIPCK(p, hipStreamSynchronize(st));
         bool all_done = true;
         for (int k = 0; k < nbb; ++k) { const InnerBlock& bb = ip.blocks[size_t(ip.big_blocks[size_t(ip.group_bigb0[g] + k)])];
@@ -463,13 +470,13 @@ int inner_sweep(oicc_problem* p, double* xv, hipStream_t st, oicc_problem* shard
       }
     }
     if (!owned) {
-      if (ip.group_wave[g] && prof == nullptr) launch_inner_wave(ip.d_args.p, xv, ip.group_first[g], ip.group_first[g + 1] - ip.group_first[g], ip.group_r3only[g] != 0, st);   // one wave per block: large sets of knot blocks
-      else launch_inner_set(ip.d_args.p, xv, ip.d_wgs.p + ip.group_wg0[g], prof, ip.group_wg0[g + 1] - ip.group_wg0[g], mode, st);
+      if (ip.group_wave[g] && prof == nullptr) launch_inner_wave(dA, xv, ip.group_first[g], ip.group_first[g + 1] - ip.group_first[g], ip.group_r3only[g] != 0, st, fe != nullptr);   // one wave per block: large sets of knot blocks
+      else launch_inner_set(dA, xv, ip.d_wgs.p + ip.group_wg0[g], prof, ip.group_wg0[g + 1] - ip.group_wg0[g], mode, st, fe != nullptr);
       if (trace_sets) { const int rc = trace_cost(double(ip.group_first[g + 1] - ip.group_first[g])); if (rc) return rc; }
       continue;
     }
     const oicc_problem::InnerPlan::RankPart& rp = ip.rank_part;
-    launch_inner_set(ip.d_args.p, xv, rp.d_wgs.p + rp.group_wg0[g], prof, rp.group_wg0[g + 1] - rp.group_wg0[g], mode, st);
+    launch_inner_set(dA, xv, rp.d_wgs.p + rp.group_wg0[g], prof, rp.group_wg0[g + 1] - rp.group_wg0[g], mode, st);
     // what the set changed, from its owners (every rank takes part, whether or not it had a block in the set)
     const ParamLayout& pl = p->pl; const uint8_t kinds = rp.group_kinds[g]; const int n = shard->shard_n;
     int rc = shard_broadcast_begin(shard);
@@ -481,7 +488,7 @@ int inner_sweep(oicc_problem* p, double* xv, hipStream_t st, oicc_problem* shard
     if (!rc && (kinds & 8) && pl.n_pts > 0) rc = shard_broadcast(shard, xv + pl.pts, 4 * int64_t(pl.n_pts), 0, st);   // SplineOptimFlags::POINTS: the board points are replicated blocks too (advisor, round 5)
     const int rc2 = shard_broadcast_end(shard);
     if (rc || rc2) { p->err = shard->err; return rc ? rc : rc2; }
-    if (kinds & 1) launch_inner_seg(xv + pl.so3, std::max(pl.n_so3 - 1, 0), ip.d_seg.p, st);   // the segment tables of the knots that came in
+    if (kinds & 1) launch_inner_seg(xv + pl.so3, std::max(pl.n_so3 - 1, 0), A.seg, st);   // the segment tables of the knots that came in
   }
   HIPCK(p, hipGetLastError());
   if (prof_set >= 0 && d_prof.p) {
@@ -533,6 +540,55 @@ int oicc_debug_host_inner_plan(oicc_problem* p, int32_t flags, int32_t* out8, in
       int32_t* o8 = out8 + 8 * size_t(b);
       o8[0] = int32_t(g); o8[1] = k.kind; o8[2] = k.idx; o8[3] = k.n_items; o8[4] = k.n_slots;
       o8[5] = k.nruns > 0 ? ip.runs[size_t(k.run0)].kind : -1; o8[6] = k.nruns > 0 ? ip.runs[size_t(k.run0)].first : -1; o8[7] = k.nruns;
+    }
+  return nb;
+}
+// Which code sums block b of set g of the plan -- from the plan fields inner_sweep branches on, in its order: 0 / 1 / 2 inner_set_kernel<0 / 1 / 2>
+// with one workgroup, 3 inner_wave_kernel, 4 parts on resident workgroups of the set kernel (control block, atomics), 5 the sequence of
+// (evaluation, advance) launches; *nparts: the workgroups that share the block
+static int inner_block_route(const oicc_problem::InnerPlan& ip, size_t g, int b, int* nparts) {
+  *nparts = 1;
+  for (int k = ip.group_bigb0[g]; k < ip.group_bigb0[g + 1]; ++k) if (ip.big_blocks[size_t(k)] == b) { *nparts = ip.big_parts[size_t(k)]; return 5; }
+  if (ip.group_wave[g]) return 3;
+  if (ip.blocks[size_t(b)].ctl >= 0) {
+    for (int w = ip.group_wg0[g]; w < ip.group_wg0[g + 1]; ++w) if (ip.wgs[size_t(w)].block == b) { *nparts = ip.wgs[size_t(w)].nparts; break; }
+    return 4;
+  }
+  return ip.group_r3only[g] ? 1 : (ip.has_points ? 2 : 0);
+}
+// Debug read-out (tests/test_gpu_inner_evaluation.py): the sums [upper triangle of H_b | g_b | cost_b] every block of the plan forms at its
+// FIRST evaluation, by the launches of a sweep (inner_sweep itself, InnerArgs::first_eval / stop_first: every loop ends right behind that
+// evaluation, so nothing moves and every block of every set is evaluated at the problem's current parameters).  Works on a scratch copy of
+// the parameter vector, scratch segment tables and control blocks: parameters, the sweep counter and the counter of LM iterations
+// stay as they are.  info8 [cap][8] = [set, kind (InnerKind), idx, dim, n_items, n_slots, route (inner_block_route), nparts], sums56
+// [cap][56] (zero behind the block's NV = dim (dim + 1) / 2 + dim + 1 sums), per block in plan order.  Returns the number of blocks,
+// -needed if cap_blocks is too small, INT32_MIN - status on an error.
+int oicc_debug_inner_first_evaluations(oicc_problem* p, int32_t flags, int32_t* info8, double* sums56, int32_t cap_blocks) {
+  if (!p || !info8 || !sums56 || p->device < 0) return INT32_MIN - OICC_ERR_INVALID_ARG;
+  int rc = prepare(p, flags); if (rc) return INT32_MIN - rc;
+  rc = build_inner_plan(p, flags); if (rc) return INT32_MIN - rc;
+  oicc_problem::InnerPlan& ip = p->inner;
+  const int nb = int(ip.blocks.size());
+  if (nb > cap_blocks) return -nb;
+  if (nb == 0) return 0;
+  hipStream_t st = p->stream;
+  DevBuf<double> xs, rows, seg; DevBuf<InnerCtl> ctls; DevBuf<InnerArgs> args;
+  if (!xs.resize(size_t(p->pl.total)) || !rows.resize(size_t(nb) * 56) || !seg.resize(size_t(std::max(p->pl.n_so3 - 1, 1)) * kSegDoubles) || !ctls.resize(size_t(std::max(ip.n_ctls, 1))) || !args.resize(1))
+    return INT32_MIN - OICC_ERR_HIP;
+  auto hip_ok = [&](hipError_t e) { if (e != hipSuccess) p->err = hipGetErrorString(e); return e == hipSuccess; };
+  if (!hip_ok(hipMemcpyAsync(xs.p, p->d_x.p, size_t(p->pl.total) * sizeof(double), hipMemcpyDeviceToDevice, st)) || !hip_ok(hipMemsetAsync(rows.p, 0, size_t(nb) * 56 * sizeof(double), st)))
+    return INT32_MIN - OICC_ERR_HIP;
+  if (p->opt["debug_poison_lds"] != 0.0) launch_lds_poison(st);   // (as the LM loop does in front of every step)
+  const InnerFirstEval fe{rows.p, seg.p, ctls.p, args.p};
+  rc = inner_sweep(p, xs.p, st, nullptr, nullptr, &fe);
+  if (rc == OICC_OK && (!hip_ok(hipMemcpyAsync(sums56, rows.p, size_t(nb) * 56 * sizeof(double), hipMemcpyDeviceToHost, st)) || !hip_ok(hipStreamSynchronize(st)))) rc = OICC_ERR_HIP;
+  else if (rc != OICC_OK) (void)hipStreamSynchronize(st);   // (the scratch buffers are freed on return)
+  if (rc) return INT32_MIN - rc;
+  for (size_t g = 0; g + 1 < ip.group_first.size(); ++g)
+    for (int b = ip.group_first[g]; b < ip.group_first[g + 1]; ++b) {
+      const InnerBlock& k = ip.blocks[size_t(b)];
+      int32_t* o8 = info8 + 8 * size_t(b); int np = 1;
+      o8[0] = int32_t(g); o8[1] = k.kind; o8[2] = k.idx; o8[3] = k.dim; o8[4] = k.n_items; o8[5] = k.n_slots; o8[6] = inner_block_route(ip, g, b, &np); o8[7] = np;
     }
   return nb;
 }

@@ -42,10 +42,10 @@ int launch_tile_pass(const TileStatic& hS, const TileStatic* dS, const TileDyn& 
 void launch_lds_poison(hipStream_t st);
 void launch_point_columns(const EvalCtx& ctx, const ViewData& vd, const uint8_t* view_rs, bool spline_active, hipStream_t st);   // kernels_points.hip
 void launch_inner_seg(const double* so3, int n_pairs, double* seg, hipStream_t st);
-void launch_inner_set(const InnerArgs* dA, double* xv, const InnerWg* wgs, long long* prof, int n_wgs, int mode, hipStream_t st);
-void launch_inner_wave(const InnerArgs* dA, double* xv, int b0, int n_blocks, bool r3_only, hipStream_t st);
+void launch_inner_set(const InnerArgs* dA, double* xv, const InnerWg* wgs, long long* prof, int n_wgs, int mode, hipStream_t st, bool read_out = false);   // read_out: the instantiations of the debug read-out (InnerArgs::first_eval)
+void launch_inner_wave(const InnerArgs* dA, double* xv, int b0, int n_blocks, bool r3_only, hipStream_t st, bool read_out = false);
 void launch_inner_shared_eval(const InnerArgs* dA, double* xv, const InnerWg* wgs, int n_wgs, double* partials, int max_parts, hipStream_t st);
-void launch_inner_shared_advance(const InnerArgs* dA, double* xv, const int32_t* block_ids, const int32_t* block_parts, int n_blocks, const double* partials, int max_parts, void* states, bool count_iterations, hipStream_t st);
+void launch_inner_shared_advance(const InnerArgs* dA, double* xv, const int32_t* block_ids, const int32_t* block_parts, int n_blocks, const double* partials, int max_parts, void* states, bool count_iterations, hipStream_t st, bool read_out = false);
 size_t inner_lm_state_bytes();
 void launch_inner_records(const ViewData& vd, const ImuData& ia, const ImuData& ig, InnerItemRec* rc, InnerItemRec* ra, InnerItemRec* rg, hipStream_t st);
 int inner_set_resident_capacity(int n_cu);
@@ -308,7 +308,10 @@ void build_inner_plan_host(oicc_problem* p, const InnerPlanOptions& o, double t_
 InnerPlanOptions inner_plan_options(oicc_problem* p, int flags, int64_t layout_gen);
 void start_inner_plan(oicc_problem* p, int flags, int64_t layout_gen);
 int build_inner_plan(oicc_problem* p, int flags);
-int inner_sweep(oicc_problem* p, double* xv, hipStream_t st, oicc_problem* shard = nullptr, bool* owner_computes = nullptr);
+// debug read-out of every block's first evaluation (oicc_debug_inner_first_evaluations): the sweep's own launches with InnerArgs::first_eval /
+// stop_first set, on scratch segment tables, control blocks and arguments, without the sweep and LM-iteration counters
+struct InnerFirstEval { double* rows; double* seg; InnerCtl* ctls; InnerArgs* d_args; };
+int inner_sweep(oicc_problem* p, double* xv, hipStream_t st, oicc_problem* shard = nullptr, bool* owner_computes = nullptr, const InnerFirstEval* fe = nullptr);
 // What one residual / Jacobian / cost pass is asked to do (eval_pass).  Everything but x has a default; the makers below fill the common shapes.
 struct PassRequest {
   const double* x = nullptr;          // parameter buffer (device)

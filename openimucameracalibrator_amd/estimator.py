@@ -426,6 +426,22 @@ class SplineTrajectoryEstimator:
             out.update(arr); out["fused"] = bool(info[0])
         return out
 
+    def DebugInnerFirstEvaluations(self, flags):
+        """Debug read-out (device library only): what every block of the inner-iteration plan sums at its FIRST evaluation, by the
+        launches of a sweep on a scratch copy of the parameters (every block's loop ends right behind that evaluation: nothing
+        moves, the problem stays as it is).  Returns (info [n, 8] = set, kind (_abi.INNER_KINDS), idx, dim, n_items, n_slots,
+        route (_abi.INNER_ROUTES), nparts; sums [n, 56] = upper triangle of H_b row by row | g_b | cost_b | zeros), plan order."""
+        fn = _abi.bind_inner_debug(self._b.lib, "oicc_debug_inner_first_evaluations")
+        cap = 1 << 12
+        while True:
+            info = np.zeros((cap, 8), np.int32); sums = np.zeros((cap, 56))
+            n = fn(self._h, int(flags), info.ctypes.data_as(_abi.c_i32p), _dp(sums), cap)
+            if n < -(1 << 30):
+                self._ck(-(1 << 31) - n)
+            if n >= 0:
+                return info[:n].copy(), sums[:n].copy()
+            cap = -n
+
     def TimeExchange(self, flags, repeats=10):
         """(ms per owner-computes exchange of the packed normal equations, bytes this rank moved); a collective: every rank calls it."""
         ms = C.c_double(0.0); nb = C.c_int64(0)
