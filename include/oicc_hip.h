@@ -432,6 +432,51 @@ int oicc_get_covariance_knot_arrow(const oicc_problem* p, int32_t kind, int64_t 
  * knot / cross block kernel behind it). */
 int oicc_get_covariance_timing(const oicc_problem* p, double ms[4]);
 
+/* ---- residual report and corner gating --------------------------------------
+ * Which corners and views fit badly, and whether the IMU residuals are at the sensors' noise level: two residual-only
+ * kernels at the current parameters (kernels_report.hip).  Everything is UNWEIGHTED:
+ *   corner error   e = pi(p_c) - z [px], through the functor the solve uses for that view (rolling-shutter views with
+ *                  quirk Q1 or option rs_time_in_seconds, global-shutter views without the line-delay shift), without
+ *                  1/sigma and without the quirk Q2 zeroing of global-shutter views
+ *   corner status  OICC_CORNER_USED; OICC_CORNER_PROJECTION_FAILED: the functor's (1e10, 1e10) case, kept as e, in no
+ *                  statistic; OICC_CORNER_GATED: weight 0 by oicc_gate_corners, its true error is still reported
+ *   view figures   n_used (status used), rms_px = sqrt(sum |e|^2 / n_used), max_px = max |e| over the used corners
+ *                  (0 for a view without a used corner)
+ *   accelerometer  R^T (a_w + g) - MS_a (a_m - b) [m/s^2];  gyroscope  omega - MS_g (omega_m - b) [rad/s]
+ * oicc_residual_info: counts by status; mean, rms, median and max of |e| over the used corners; sigma_px = median /
+ * 1.17741, the Rayleigh scale of |e| for a per-axis standard deviation sigma (robust against gross outliers); per-axis
+ * rms of both IMU families, unweighted and multiplied by the samples' weights (1 at the noise level the weights were
+ * derived from); ms_device: device time of the report's kernels.
+ * Every getter returns its data in the CALLER's order: corners, views (the accepted ones) and samples as they were
+ * added.  The getters return OICC_ERR_STATE unless a report exists for the current parameters and measurements: any
+ * setter, Add*Measurement, oicc_set_option, oicc_optimize and an oicc_gate_corners that changes a weight invalidate it.
+ *
+ * oicc_gate_corners, from the last report: a corner of status used or gated with |e| > threshold_px gets weight
+ * exactly 0, every other corner the weight it was added with (the original 1/sigma is kept, so gating never
+ * accumulates); threshold_px <= 0 lifts every gate and needs no report.  A view whose corners are all gated stays in
+ * the problem as a block of zero rows.  oicc_get_mean_reprojection_error skips gated corners (their weighted residual
+ * is zero).  The measurements count as changed: they travel again, tiles and the inner-iteration plan are rebuilt.
+ * The usual sequence is optimize, report, gate at 5 sigma_px, optimize again (the facades' OptimizeGated).
+ * oicc_residual_report and oicc_gate_corners return OICC_ERR_UNSUPPORTED on time-sharded problems (oicc_set_shard) and
+ * with a reduction across ranks installed: the median would be a collective. */
+enum { OICC_CORNER_USED = 0, OICC_CORNER_PROJECTION_FAILED = 1, OICC_CORNER_GATED = 2 };
+typedef struct oicc_residual_info {
+  int64_t num_corners, num_used, num_failed, num_gated, num_views, num_accl, num_gyro;
+  double mean_px, rms_px, median_px, sigma_px, max_px;
+  double accl_rms[3], accl_rms_weighted[3], gyro_rms[3], gyro_rms_weighted[3];
+  double ms_device;
+} oicc_residual_info;
+int oicc_residual_report(oicc_problem* p, oicc_residual_info* info);
+/* e_uv [n][2], status [n]; n = the number of corners of the accepted views; either pointer may be NULL */
+int oicc_get_corner_errors(oicc_problem* p, double* e_uv, uint8_t* status, int64_t n);
+/* [nv] each, nv = the number of accepted views; any pointer may be NULL */
+int oicc_get_view_errors(oicc_problem* p, double* rms_px, double* max_px, int32_t* n_used, int64_t nv);
+/* kind 1 accelerometer, 2 gyroscope (as oicc_evaluate_blocks); r_xyz [n][3], n = the number of accepted samples */
+int oicc_get_imu_residuals(oicc_problem* p, int32_t kind, double* r_xyz, int64_t n);
+int oicc_gate_corners(oicc_problem* p, double threshold_px, int64_t* n_gated);
+/* gated [n]: 1 where the corner is gated now; n as in oicc_get_corner_errors.  Needs no report. */
+int oicc_get_corner_gate(oicc_problem* p, uint8_t* gated, int64_t n);
+
 /* ---- read-back: mirrors the getters ------------------------------------- */
 int oicc_get_T_i_c(const oicc_problem* p, double q_xyzw_t_xyz[7]);  /* impl.h:1133 */
 int oicc_get_gravity(const oicc_problem* p, double g[3]);           /* impl.h:1128 */

@@ -58,6 +58,18 @@ class CovarianceInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ResidualInfo(C.Structure):
+    """oicc_residual_info (include/oicc_hip.h)."""
+    _fields_ = [("num_corners", C.c_int64), ("num_used", C.c_int64), ("num_failed", C.c_int64), ("num_gated", C.c_int64),
+                ("num_views", C.c_int64), ("num_accl", C.c_int64), ("num_gyro", C.c_int64),
+                ("mean_px", C.c_double), ("rms_px", C.c_double), ("median_px", C.c_double), ("sigma_px", C.c_double), ("max_px", C.c_double),
+                ("accl_rms", C.c_double * 3), ("accl_rms_weighted", C.c_double * 3), ("gyro_rms", C.c_double * 3), ("gyro_rms_weighted", C.c_double * 3),
+                ("ms_device", C.c_double)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k.endswith(("_rms", "_rms_weighted")) else getattr(self, k)) for k, _ in self._fields_}
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p)
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p)   # oicc_exchange_fn
 
@@ -135,6 +147,12 @@ DEVICE_ONLY = {
     "get_covariance_knots": (C.c_int, [H, c_dp, C.c_int64, c_dp, C.c_int64]),
     "get_covariance_knot_arrow": (C.c_int, [H, C.c_int32, C.c_int64, c_dp]),
     "get_covariance_timing": (C.c_int, [H, c_dp]),
+    "residual_report": (C.c_int, [H, C.POINTER(ResidualInfo)]),
+    "get_corner_errors": (C.c_int, [H, c_dp, c_u8p, C.c_int64]),
+    "get_view_errors": (C.c_int, [H, c_dp, c_dp, c_i32p, C.c_int64]),
+    "get_imu_residuals": (C.c_int, [H, C.c_int32, c_dp, C.c_int64]),
+    "gate_corners": (C.c_int, [H, C.c_double, c_i64p]),
+    "get_corner_gate": (C.c_int, [H, c_u8p, C.c_int64]),
     "sew_knot_spacing_and_variance": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, c_dp, c_dp, C.c_double, C.c_double, C.c_double,
                                                 c_dp, c_dp, c_i32p]),
 }

@@ -45,6 +45,7 @@ struct Flags {
   explicit Flags(std::map<std::string, std::string> table) : s(std::move(table)) {
     for (const auto& kv : s) is_bool_flag[kv.first] = kv.second == "true" || kv.second == "false";
   }
+  void define(const std::string& name, const std::string& def) { s[name] = def; is_bool_flag[name] = def == "true" || def == "false"; }   // one more flag, before parse()
   bool parse(int argc, char** argv) {
     for (int i = 1; i < argc; ++i) {
       std::string a = argv[i];

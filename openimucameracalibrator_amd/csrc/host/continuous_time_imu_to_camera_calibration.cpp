@@ -80,6 +80,9 @@ static int run_main(int argc, char* argv[]) {
            {"max_t", "1000."}, {"reestimate_biases", "false"}, {"gravity_const", "9.81"}, {"known_grav_dir_axis", "Z"},
            {"debug_video_path", ""}, {"dry_run", "false"}, {"device", "0"}, {"solver_partitions", "0"}, {"solver_algorithm", "0"},
            {"use_inner_iterations", "true"}});   // the reference's Optimize sets options.use_inner_iterations = true (impl.h:266)
+  // flags beyond the reference's command line for what it does not have: the residual report and the corner gate
+  F.define("gate_corners_sigmas", "0");       // > 0: stage 1 is OptimizeGated at this many sigma_px
+  F.define("residual_report_json", "");       // per-view pixel errors and IMU residual figures of the final parameters
   if (!F.parse(argc, argv)) return 2;
 
   // pose dataset, corners, camera (cc:93-105)
@@ -170,7 +173,8 @@ static int run_main(int argc, char* argv[]) {
     std::cout << "Setting a-priori gravity direction supplied by the user to: " << grav_dir[0] << " " << grav_dir[1] << " " << grav_dir[2] << "\n";
   } else flags |= SplineOptimFlags::GRAVITY_DIR;
 
-  const double reproj_error = imu_cam_calibrator.Optimize(50, flags);   // cc:215
+  const double gate_sigmas = F.d("gate_corners_sigmas");
+  const double reproj_error = gate_sigmas > 0.0 ? imu_cam_calibrator.OptimizeGated(50, flags, gate_sigmas) : imu_cam_calibrator.Optimize(50, flags);   // cc:215
   double reproj_error_after_ld = reproj_error;
   if (F.b("calibrate_cam_line_delay") && !F.b("global_shutter")) {     // cc:217-221
     flags = SplineOptimFlags::CAM_LINE_DELAY;
@@ -197,6 +201,30 @@ static int run_main(int argc, char* argv[]) {
   out["init_line_delay_us"] = Value(init_line_delay_us * S_TO_US);
   out["calib_line_delay_us"] = Value(calib_line_delay_us);
   out["time_offset_imu_to_cam_s"] = Value(time_offset_imu_to_cam);
+  if (gate_sigmas > 0.0) { out["gated_corners"] = Value(int64_t(imu_cam_calibrator.gated_corners_)); out["corner_sigma_px"] = Value(imu_cam_calibrator.gate_report_.sigma_px); }
+  if (!F.str("residual_report_json").empty()) {
+    const oicc_residual_info ri = tr.ResidualReport();
+    const ViewErrors ve = tr.GetViewErrors();
+    const std::vector<double>& vt = imu_cam_calibrator.GetAcceptedViewTimestamps();
+    CHECK_MSG(vt.size() == ve.n_used.size(), "residual report: " << ve.n_used.size() << " views for " << vt.size() << " accepted ones");
+    Value rep;
+    Value& c = rep["corners"];
+    c["num"] = Value(int64_t(ri.num_corners)); c["used"] = Value(int64_t(ri.num_used)); c["projection_failed"] = Value(int64_t(ri.num_failed)); c["gated"] = Value(int64_t(ri.num_gated));
+    c["mean_px"] = Value(ri.mean_px); c["rms_px"] = Value(ri.rms_px); c["median_px"] = Value(ri.median_px); c["sigma_px"] = Value(ri.sigma_px); c["max_px"] = Value(ri.max_px);
+    Value views; views.type = Value::Array;
+    for (size_t k = 0; k < vt.size(); ++k) {
+      Value e; e["timestamp"] = Value(vt[k]); e["n_used"] = Value(int64_t(ve.n_used[k])); e["rms_px"] = Value(ve.rms_px[k]); e["max_px"] = Value(ve.max_px[k]);
+      views.push_back(e);
+    }
+    rep["views"] = views;
+    Value& imu = rep["imu"];
+    imu["accl_rms"] = xyz(ri.accl_rms); imu["accl_rms_weighted"] = xyz(ri.accl_rms_weighted);
+    imu["gyro_rms"] = xyz(ri.gyro_rms); imu["gyro_rms_weighted"] = xyz(ri.gyro_rms_weighted);
+    imu["num_accl"] = Value(int64_t(ri.num_accl)); imu["num_gyro"] = Value(int64_t(ri.num_gyro));
+    std::ofstream f(F.str("residual_report_json"));
+    CHECK_MSG(f.is_open(), "cannot write " << F.str("residual_report_json"));
+    oicc_json::dump(rep, f, 4); f << std::endl;
+  }
 
   // trajectory dump (cc:274-327): one batched device evaluation instead of per-sample getters
   std::vector<int64_t> t_ns; std::vector<std::string> keys;

@@ -91,7 +91,22 @@ int oicc_get_covariance_arrow(const oicc_problem* p, double* cov, int32_t a_capa
 int oicc_get_covariance_knots(const oicc_problem* p, double* so3_blocks, int64_t n_so3, double* r3_blocks, int64_t n_r3) __attribute__((weak));
 }
 #endif
+// likewise the residual report and the corner gating
+#if defined(oicc_residual_report)
+#define OICC_FACADE_REPORT_OPTIONAL 1
+extern "C" {
+int oicc_residual_report(oicc_problem* p, oicc_residual_info* info) __attribute__((weak));
+int oicc_get_corner_errors(oicc_problem* p, double* e_uv, uint8_t* status, int64_t n) __attribute__((weak));
+int oicc_get_view_errors(oicc_problem* p, double* rms_px, double* max_px, int32_t* n_used, int64_t nv) __attribute__((weak));
+int oicc_get_imu_residuals(oicc_problem* p, int32_t kind, double* r_xyz, int64_t n) __attribute__((weak));
+int oicc_gate_corners(oicc_problem* p, double threshold_px, int64_t* n_gated) __attribute__((weak));
+}
+#endif
 namespace OpenICC {
+
+// SplineTrajectoryEstimator::GetCornerErrors / GetViewErrors: the last residual report, in the order the corners / views were added
+struct CornerErrors { std::vector<double> e_uv; std::vector<uint8_t> status; };                 // [n][2] px, oicc corner status
+struct ViewErrors { std::vector<double> rms_px, max_px; std::vector<int32_t> n_used; };         // one entry per accepted view
 
 // SplineTrajectoryEstimator::EstimateCovariance: (J^T J)^-1 in the tangent space of the active set (include/oicc_hip.h)
 struct CovarianceEstimate {
@@ -295,6 +310,29 @@ class SplineTrajectoryEstimator {
     }
     return c;
   }
+  // oicc_residual_report and its getters, oicc_gate_corners (include/oicc_hip.h): unweighted pixel error of every corner, per-view
+  // figures and IMU residuals at the current parameters; corners beyond threshold_px lose their weight (<= 0 lifts every gate)
+  oicc_residual_info ResidualReport() {
+    require_report();
+    ck(oicc_residual_report(h_, &last_report_)); return last_report_;
+  }
+  CornerErrors GetCornerErrors() {
+    require_report();
+    CornerErrors c; c.e_uv.resize(size_t(2 * last_report_.num_corners)); c.status.resize(size_t(last_report_.num_corners));
+    ck(oicc_get_corner_errors(h_, c.e_uv.data(), c.status.data(), last_report_.num_corners)); return c;
+  }
+  ViewErrors GetViewErrors() {
+    require_report();
+    const size_t nv = size_t(last_report_.num_views);
+    ViewErrors v; v.rms_px.resize(nv); v.max_px.resize(nv); v.n_used.resize(nv);
+    ck(oicc_get_view_errors(h_, v.rms_px.data(), v.max_px.data(), v.n_used.data(), int64_t(nv))); return v;
+  }
+  std::vector<double> GetImuResiduals(int kind) {   // 1 accelerometer [m/s^2], 2 gyroscope [rad/s]; [n][3]
+    require_report();
+    const int64_t n = kind == 1 ? last_report_.num_accl : last_report_.num_gyro;
+    std::vector<double> r(size_t(3 * n) + 1); ck(oicc_get_imu_residuals(h_, kind, r.data(), n)); r.resize(size_t(3 * n)); return r;
+  }
+  int64_t GateCorners(double threshold_px) { require_report(); int64_t n = 0; ck(oicc_gate_corners(h_, threshold_px, &n)); return n; }
   size_t GetNumSO3Knots() const { return size_t(oicc_get_num_so3_knots(h_)); }
   size_t GetNumR3Knots() const { return size_t(oicc_get_num_r3_knots(h_)); }
   int64_t GetMaxTimeNs() const { return oicc_get_max_time_ns(h_); }
@@ -308,6 +346,12 @@ class SplineTrajectoryEstimator {
 
  private:
   void ck(int rc) const { if (rc != OICC_OK) throw std::runtime_error(std::string("liboicc_hip: ") + oicc_last_error(h_)); }
+  void require_report() const {
+#ifdef OICC_FACADE_REPORT_OPTIONAL
+    if (!oicc_residual_report || !oicc_get_corner_errors || !oicc_get_view_errors || !oicc_get_imu_residuals || !oicc_gate_corners) throw std::runtime_error("liboicc_hip: this library has no residual report");
+#endif
+  }
+  oicc_residual_info last_report_{};
   bool add_view(const View* v, bool rs) {
     const int64_t t_ns = int64_t(v->timestamp_s * S_TO_NS);   // impl.h:481,541
     std::vector<double> uv; std::vector<int32_t> idx;
@@ -354,8 +398,10 @@ class ImuCameraCalibrator {
     trajectory_.BatchInitSO3R3VisPoses();
     trajectory_.InitBiasSplines(accl_intrinsics.bias, gyro_intrinsics.bias, int64_t(10 * 1e9), int64_t(10 * 1e9), 1.0, 1e-1);   // cc:80-85
     size_t views_added = 0;
-    for (const View& v : image_data_.views)   // cc:89-98
-      views_added += (initial_line_delay != 0.0) ? trajectory_.AddRSCameraMeasurement(&v, 0.0) : trajectory_.AddGSCameraMeasurement(&v, 0.0);
+    for (const View& v : image_data_.views) {   // cc:89-98
+      const bool added = (initial_line_delay != 0.0) ? trajectory_.AddRSCameraMeasurement(&v, 0.0) : trajectory_.AddGSCameraMeasurement(&v, 0.0);
+      if (added) { ++views_added; accepted_view_timestamps_.push_back(v.timestamp_s); }
+    }
     std::vector<int64_t> t_ns; std::vector<double> acc, gyr;
     for (size_t i = 0; i < telemetry_data.accelerometer.size(); ++i) {   // cc:102-120
       const double t = telemetry_data.accelerometer[i].t_s + time_offset_imu_to_cam;
@@ -396,6 +442,19 @@ class ImuCameraCalibrator {
     last_summary_ = trajectory_.Optimize(iterations, optim_flags);
     return trajectory_.GetMeanReprojectionError();
   }
+  // Optimize, residual report, gate the corners whose pixel error exceeds sigmas * sigma_px (the report's robust scale), Optimize again
+  // from the point reached.  The report between the solves, the threshold and the number of gated corners stay in gate_report_,
+  // gate_threshold_px_ and gated_corners_.
+  double OptimizeGated(int iterations, int optim_flags, double sigmas = 5.0) {
+    trajectory_.Optimize(iterations, optim_flags);
+    gate_report_ = trajectory_.ResidualReport();
+    gate_threshold_px_ = sigmas * gate_report_.sigma_px;
+    gated_corners_ = gate_threshold_px_ > 0.0 ? trajectory_.GateCorners(gate_threshold_px_) : 0;
+    std::cout << "Corner gate at " << gate_threshold_px_ << " px (" << sigmas << " x " << gate_report_.sigma_px << "): " << gated_corners_ << " of " << gate_report_.num_corners << " corners gated\n";
+    last_summary_ = trajectory_.Optimize(iterations, optim_flags);
+    return trajectory_.GetMeanReprojectionError();
+  }
+  const std::vector<double>& GetAcceptedViewTimestamps() const { return accepted_view_timestamps_; }   // the views of the residual report's per-view figures, in their order
   // Named standard deviations of the calibration from trajectory_.EstimateCovariance(flags)
   CalibrationStdDevs GetCalibrationStdDevs(int flags, bool scaled = true) {
     const CovarianceEstimate c = trajectory_.EstimateCovariance(flags);
@@ -449,8 +508,10 @@ class ImuCameraCalibrator {
 
   SplineTrajectoryEstimator<SPLINE_N> trajectory_;   // public in the reference too (imu_camera_calibrator.h:48)
   oicc_summary last_summary_{};
+  oicc_residual_info gate_report_{}; double gate_threshold_px_ = 0.0; int64_t gated_corners_ = 0;   // OptimizeGated
 
  private:
+  std::vector<double> accepted_view_timestamps_;
   CalibDataset image_data_;
   SE3 T_i_c_init_;
   std::vector<double> cam_timestamps_;

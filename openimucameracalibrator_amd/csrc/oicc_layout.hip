@@ -44,7 +44,7 @@ void rebuild_param_layout(oicc_problem* p, int64_t n_so3, int64_t n_r3, int64_t 
   keep(so3, pl.so3, 4 * n_so3); keep(r3, pl.r3, 3 * n_r3); keep(ab, pl.ab, 3 * n_ab); keep(gb, pl.gb, 3 * n_gb);
   std::memcpy(xs(p, pl.tic), T_i_c, sizeof(T_i_c)); std::memcpy(xs(p, pl.g), g, sizeof(g)); p->x[pl.ld] = ld;
   std::memcpy(xs(p, pl.ai), ai, sizeof(ai)); std::memcpy(xs(p, pl.gi), gi, sizeof(gi));
-  p->x_host_dirty = true; p->layout_flags = -1; p->cov.valid = false;
+  p->x_host_dirty = true; p->layout_flags = -1; p->invalidate_estimates();
 }
 
 int sync_params_to_device(oicc_problem* p) {
@@ -88,6 +88,7 @@ int sync_measurements(oicc_problem* p) {
   A.add(p->d_view_rs, p->view_rs);
   p->h_view_rs_all.assign(p->view_rs.size(), 1);
   A.add(p->d_view_rs_all, p->h_view_rs_all);
+  A.add(p->d_cgate, p->cgate);
   for (int k = 0; k < 2; ++k) {
     const ImuHost& h = k == 0 ? p->acc : p->gyr; ImuDev& d = k == 0 ? p->d_acc : p->d_gyr;
     A.add(d.s_so3, h.s_so3); A.add(d.s_r3, h.s_r3); A.add(d.s_b, h.s_b); A.add(d.u_so3, h.u_so3); A.add(d.u_r3, h.u_r3);
@@ -108,6 +109,9 @@ static void sort_views_by_time(oicc_problem* p) {
   std::vector<int64_t> c0(1, 0);
   for (size_t i = 0; i < nv; ++i) { const size_t v = vperm[i]; for (int64_t c = p->view_c0[v]; c < p->view_c0[v + 1]; ++c) cperm.push_back(size_t(c)); c0.push_back(int64_t(cperm.size())); }
   permute_vec(p->corner_pt, cperm); permute_vec(p->cu, cperm); permute_vec(p->cv, cperm); permute_vec(p->cisx, cperm); permute_vec(p->cisy, cperm); permute_vec(p->corner_orig, cperm);
+  permute_vec(p->cisx0, cperm); permute_vec(p->cisy0, cperm); permute_vec(p->cgate, cperm);
+  if (p->view_orig.empty()) { p->view_orig.resize(nv); for (size_t i = 0; i < nv; ++i) p->view_orig[i] = int32_t(i); }
+  permute_vec(p->view_orig, vperm);
   for (size_t i = 0; i < nv; ++i) for (int64_t c = c0[i]; c < c0[i + 1]; ++c) p->corner_view[size_t(c)] = int32_t(i);
   p->view_c0 = c0;
   permute_vec(p->view_s_so3, vperm); permute_vec(p->view_s_r3, vperm); permute_vec(p->view_u_so3, vperm); permute_vec(p->view_u_r3, vperm); permute_vec(p->view_rs, vperm);

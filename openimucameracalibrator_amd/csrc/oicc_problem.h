@@ -6,6 +6,7 @@
 //   oicc_tiles.hip      time tiles, chains and row formats of the Jacobian pass (tiles.h)
 //   oicc_inner.hip      plan and sweep of the inner iterations (inner_plan.h)
 //   oicc_exchange.hip   RCCL binding, rank consistency, owner-computes exchange of the normal equations
+//   oicc_report.hip     residual report (kernels_report.hip), corner gating
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>   // types and enums only: the entry points are bound with dlsym at run time
@@ -62,6 +63,10 @@ void launch_lm_retract(const double* x, double* xc, const ParamLayout& pl, const
                        const NormalEq& ne, double max_ab, double max_gb, hipStream_t st, double alpha = 1.0, int with_model = 1, double* seg_out = nullptr);
 void launch_lm_step_slope(const double* g, const SolveBuffers& sb, int P, double* out, hipStream_t st);
 void launch_lm_projected_gradient(const double* x, const ParamLayout& pl, const TangentLayout& tl, const NormalEq& ne, double max_ab, double max_gb, LmState* s, hipStream_t st);
+// kernels_report.hip
+void launch_report_views(const EvalCtx& ctx, const ViewData& vd, const uint8_t* gate, double* e_uv, uint8_t* status, int32_t* n_used,
+                         double* sum_sq, double* max_e, hipStream_t st);
+void launch_report_imu(const EvalCtx& ctx, const ImuData& id, int kind, double* r3, double* partials, hipStream_t st);
 void launch_lm_decide(LmCtl* out, const LmCtl* prev, const LmState* st, int64_t off_cost, hipStream_t stream);   // the trust-region decision on the device (kernels_solve.hip)
 }  // namespace oicc
 
@@ -116,6 +121,9 @@ struct oicc_problem {
   // measurements (host SoA)
   int32_t max_corner_pt = -1;
   std::vector<int32_t> corner_view, corner_pt; std::vector<double> cu, cv, cisx, cisy;
+  // corner gating (oicc_gate_corners): the 1/sigma every corner was added with next to the effective one above (0 where gated), so
+  // that a gate can be lifted and gating never accumulates; permuted wherever cisx is (sort_views_by_time)
+  std::vector<double> cisx0, cisy0; std::vector<uint8_t> cgate;
   std::vector<int64_t> view_c0{0}; std::vector<int32_t> view_s_so3, view_s_r3; std::vector<double> view_u_so3, view_u_r3;
   std::vector<uint8_t> view_rs;
   ImuHost acc, gyr;
@@ -128,6 +136,7 @@ struct oicc_problem {
   // dumps of oicc_evaluate_blocks, whose rows stay in the caller's order.
   bool views_unsorted = false, acc_unsorted = false, gyr_unsorted = false;
   std::vector<int64_t> corner_orig; std::vector<int32_t> acc_orig, gyr_orig;
+  std::vector<int32_t> view_orig;   // the same for the accepted views (the per-view figures of the residual report)
   // knot windows of measurements held by OTHER ranks (multi-GPU): only for layout/bandwidth
   std::vector<int32_t> remote_so3, remote_r3;   // pairs; r3 = -1 for gyro
   std::vector<int32_t> remote_owner;            // the rank that holds the remote measurement (-1: not told; owner-computes exchange needs it)
@@ -172,7 +181,7 @@ struct oicc_problem {
   bool seg_precomputed() const { const auto it = opt.find("debug_seg_precompute"); const int force = it == opt.end() ? 0 : int(it->second); return force == 1 || (force == 0 && tp.n_tiles > n_cu); }
   DevBuf<int32_t> d_corner_view, d_corner_pt, d_view_s_so3, d_view_s_r3;
   DevBuf<double> d_cu, d_cv, d_cisx, d_cisy, d_view_u_so3, d_view_u_r3;
-  DevBuf<int64_t> d_view_c0; DevBuf<uint8_t> d_view_rs, d_view_rs_all; std::vector<uint8_t> h_view_rs_all;
+  DevBuf<int64_t> d_view_c0; DevBuf<uint8_t> d_view_rs, d_view_rs_all, d_cgate; std::vector<uint8_t> h_view_rs_all;
   DevArena meas_arena, layout_arena, tile_arena, plan_arena;   // one device block + one copy per group of arrays
   ImuDev d_acc, d_gyr;
   DevBuf<int32_t> d_tl_so3, d_tl_r3, d_tl_ab, d_tl_gb, d_tl_pts, d_tl_rmap;
@@ -226,6 +235,14 @@ struct oicc_problem {
                DevBuf<double> d_s, d_Cs, d_Sc, d_Zaa, d_aa, d_zb, d_G, d_cov3, d_cross, d_zs; DevBuf<int32_t> d_flags;
                double ms[4] = {0, 0, 0, 0};                  // device time of the last estimate: build, forward factor, corner, backward sweep + finish
              } cov;
+  // residual report (oicc_report.hip): host copies in the layout's (time sorted) order, the getters hand them out in the caller's;
+  // valid = made at the current parameters and measurements (invalidate_estimates)
+  struct Report { bool valid = false;
+                  std::vector<double> e_uv, view_sum, view_max; std::vector<uint8_t> status; std::vector<int32_t> view_n;
+                  size_t n_acc = 0, n_gyr = 0;                  // samples behind d_acc_r / d_gyr_r (read back by oicc_get_imu_residuals)
+                  DevBuf<double> d_e, d_vsum, d_vmax, d_acc_r, d_gyr_r, d_part; DevBuf<uint8_t> d_status; DevBuf<int32_t> d_vn;
+                } report;
+  void invalidate_estimates() { cov.valid = false; report.valid = false; }   // parameters, measurements or options changed: what was derived from them is stale
   HostLayout L; TangentLayout tl{}; TangentLayout tl_tiles{}; NormalEq ne{}; NormalEq ne2{};   // tl_tiles: tl without the point columns (SplineOptimFlags::POINTS), what the tile pass sees
   Active act{};
 

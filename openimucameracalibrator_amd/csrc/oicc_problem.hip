@@ -300,7 +300,7 @@ int oicc_set_stream(oicc_problem* p, void* s) {
 int oicc_set_option(oicc_problem* p, const char* name, double value) {
   auto it = p->opt.find(name); ARG(p, it != p->opt.end(), std::string("unknown option ") + name);
   if (it->second != value) ++p->opt_gen;   // layout / tiles / inner plan are rebuilt at the next pass
-  if (it->second != value) p->cov.valid = false;
+  if (it->second != value) p->invalidate_estimates();
   it->second = value;
   return OICC_OK;
 }
@@ -326,9 +326,9 @@ int64_t oicc_get_num_r3_knots(const oicc_problem* p) { return p->pl.n_r3; }
 int64_t oicc_get_min_time_ns(const oicc_problem* p) { return p->start_ns; }
 int64_t oicc_get_max_time_ns(const oicc_problem* p) { return p->start_ns + (int64_t(p->pl.n_so3) - kN + 1) * p->dt_so3 - 1; }
 int oicc_set_so3_knots(oicc_problem* p, const double* q, int64_t n) {
-  ARG(p, n == p->pl.n_so3, "so3 knot count"); std::copy(q, q + 4 * n, xs(p, p->pl.so3)); p->x_host_dirty = true; p->cov.valid = false; return OICC_OK; }
+  ARG(p, n == p->pl.n_so3, "so3 knot count"); std::copy(q, q + 4 * n, xs(p, p->pl.so3)); p->x_host_dirty = true; p->invalidate_estimates(); return OICC_OK; }
 int oicc_set_r3_knots(oicc_problem* p, const double* v, int64_t n) {
-  ARG(p, n == p->pl.n_r3, "r3 knot count"); std::copy(v, v + 3 * n, xs(p, p->pl.r3)); p->x_host_dirty = true; p->cov.valid = false; return OICC_OK; }
+  ARG(p, n == p->pl.n_r3, "r3 knot count"); std::copy(v, v + 3 * n, xs(p, p->pl.r3)); p->x_host_dirty = true; p->invalidate_estimates(); return OICC_OK; }
 int oicc_get_so3_knots(const oicc_problem* p, double* q, int64_t n) { std::copy(p->x.begin() + p->pl.so3, p->x.begin() + p->pl.so3 + 4 * n, q); return OICC_OK; }
 int oicc_get_r3_knots(const oicc_problem* p, double* v, int64_t n) { std::copy(p->x.begin() + p->pl.r3, p->x.begin() + p->pl.r3 + 3 * n, v); return OICC_OK; }
 
@@ -344,16 +344,16 @@ int oicc_init_bias_splines(oicc_problem* p, const double ab[3], const double gb[
   p->ab_in.assign(na, 0); p->gb_in.assign(ng, 0);
   return OICC_OK;
 }
-int oicc_set_T_i_c(oicc_problem* p, const double v[7]) { std::memcpy(xs(p, p->pl.tic), v, 7 * sizeof(double)); p->x_host_dirty = true; p->cov.valid = false; return OICC_OK; }
-int oicc_set_gravity(oicc_problem* p, const double g[3]) { std::memcpy(xs(p, p->pl.g), g, 3 * sizeof(double)); p->x_host_dirty = true; p->cov.valid = false; return OICC_OK; }
-int oicc_set_camera_line_delay(oicc_problem* p, double s) { p->x[p->pl.ld] = s; p->x_host_dirty = true; p->cov.valid = false; p->layout_flags = -1; return OICC_OK; }
+int oicc_set_T_i_c(oicc_problem* p, const double v[7]) { std::memcpy(xs(p, p->pl.tic), v, 7 * sizeof(double)); p->x_host_dirty = true; p->invalidate_estimates(); return OICC_OK; }
+int oicc_set_gravity(oicc_problem* p, const double g[3]) { std::memcpy(xs(p, p->pl.g), g, 3 * sizeof(double)); p->x_host_dirty = true; p->invalidate_estimates(); return OICC_OK; }
+int oicc_set_camera_line_delay(oicc_problem* p, double s) { p->x[p->pl.ld] = s; p->x_host_dirty = true; p->invalidate_estimates(); p->layout_flags = -1; return OICC_OK; }
 int oicc_set_imu_intrinsics(oicc_problem* p, const double a[6], const double g[9]) {
-  std::memcpy(xs(p, p->pl.ai), a, 6 * sizeof(double)); std::memcpy(xs(p, p->pl.gi), g, 9 * sizeof(double)); p->x_host_dirty = true; p->cov.valid = false; return OICC_OK; }
+  std::memcpy(xs(p, p->pl.ai), a, 6 * sizeof(double)); std::memcpy(xs(p, p->pl.gi), g, 9 * sizeof(double)); p->x_host_dirty = true; p->invalidate_estimates(); return OICC_OK; }
 int oicc_set_camera(oicc_problem* p, int32_t model, const double* intr, int32_t n) {
   ARG(p, n >= 0 && n <= 10, "num_intrinsics");
   ARG(p, model == OICC_CAM_PINHOLE || model == OICC_CAM_PINHOLE_RADIAL_TANGENTIAL || model == OICC_CAM_FISHEYE ||
              model == OICC_CAM_DIVISION_UNDISTORTION || model == OICC_CAM_DOUBLE_SPHERE || model == OICC_CAM_EXTENDED_UNIFIED, "camera model");
-  p->cov.valid = false;
+  p->invalidate_estimates();
   p->cam_model = model; p->n_intr = n; std::fill(p->intr, p->intr + 10, 0.0); std::copy(intr, intr + n, p->intr); return OICC_OK; }
 int oicc_set_scene_points(oicc_problem* p, const double* xyzw, int64_t n) {
   ARG(p, n >= 0 && (xyzw != nullptr || n == 0), "scene points");
@@ -378,6 +378,7 @@ static int add_views(oicc_problem* p, bool rs, int64_t nv, const int64_t* t_ns, 
     if (accepted) accepted[v] = ok;
     if (!ok) continue;
     const int32_t vid = int32_t(p->view_rs.size());
+    if (!p->view_orig.empty()) p->view_orig.push_back(vid);
     if (vid > 0 && (s_so3 < p->view_s_so3.back() || (s_so3 == p->view_s_so3.back() && u_so3 < p->view_u_so3.back()))) p->views_unsorted = true;   // (sorted by sync_groups)
     for (int64_t c = coff[v]; c < coff[v + 1]; ++c) {
       if (!p->corner_orig.empty()) p->corner_orig.push_back(int64_t(p->corner_view.size()));
@@ -385,6 +386,7 @@ static int add_views(oicc_problem* p, bool rs, int64_t nv, const int64_t* t_ns, 
       p->corner_view.push_back(vid); p->corner_pt.push_back(pidx[c]); p->max_corner_pt = std::max(p->max_corner_pt, pidx[c]);
       p->cu.push_back(uv[2 * c]); p->cv.push_back(uv[2 * c + 1]);
       p->cisx.push_back(1.0 / std::sqrt(cov ? cov[2 * c] : 1.0)); p->cisy.push_back(1.0 / std::sqrt(cov ? cov[2 * c + 1] : 1.0));
+      p->cisx0.push_back(p->cisx.back()); p->cisy0.push_back(p->cisy.back()); p->cgate.push_back(0);
     }
     p->view_c0.push_back(int64_t(p->corner_view.size()));
     p->view_s_so3.push_back(int32_t(s_so3)); p->view_s_r3.push_back(int32_t(s_r3));
@@ -392,7 +394,7 @@ static int add_views(oicc_problem* p, bool rs, int64_t nv, const int64_t* t_ns, 
     for (int i = 0; i < kN; ++i) { p->so3_in[s_so3 + i] = 1; p->r3_in[s_r3 + i] = 1; }
     p->has_tic_block = true; if (rs) p->has_ld_block = true;
   }
-  p->meas_dirty = true; p->groups_dirty = true; p->layout_flags = -1; p->inner.flags = -2; p->cov.valid = false; ++p->meas_gen;
+  p->meas_dirty = true; p->groups_dirty = true; p->layout_flags = -1; p->inner.flags = -2; p->invalidate_estimates(); ++p->meas_gen;
   return OICC_OK;
 }
 int oicc_add_rs_camera_measurements(oicc_problem* p, int64_t nv, const int64_t* t, const int64_t* co, const double* uv, const double* cov,
@@ -420,7 +422,7 @@ int oicc_add_accelerometer_measurements(oicc_problem* p, int64_t n, const int64_
     for (int k = 0; k < kNb; ++k) p->ab_in[s_b + k] = 1;
     p->has_acc = true;
   }
-  p->meas_dirty = true; p->groups_dirty = true; p->layout_flags = -1; p->inner.flags = -2; p->cov.valid = false;
+  p->meas_dirty = true; p->groups_dirty = true; p->layout_flags = -1; p->inner.flags = -2; p->invalidate_estimates();
   return OICC_OK;
 }
 int oicc_add_gyroscope_measurements(oicc_problem* p, int64_t n, const int64_t* t_ns, const double* m, double w, uint8_t* accepted) {
@@ -442,7 +444,7 @@ int oicc_add_gyroscope_measurements(oicc_problem* p, int64_t n, const int64_t* t
     for (int k = 0; k < kNb; ++k) p->gb_in[s_b + k] = 1;
     p->has_gyr = true;
   }
-  p->meas_dirty = true; p->groups_dirty = true; p->layout_flags = -1; p->inner.flags = -2; p->cov.valid = false;
+  p->meas_dirty = true; p->groups_dirty = true; p->layout_flags = -1; p->inner.flags = -2; p->invalidate_estimates();
   return OICC_OK;
 }
 
@@ -569,7 +571,7 @@ int oicc_evaluate_blocks(oicc_problem* p, int32_t flags, int32_t kind, double* r
 // sequences kernels and reads one small struct per iteration.
 int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summary* sum) {
   const double t_start = now_s();
-  p->cov.valid = false;   // (the estimate belongs to the parameters it was made at)
+  p->invalidate_estimates();   // (the estimate belongs to the parameters it was made at)
   struct PlanJoin { oicc_problem* q; ~PlanJoin() { q->wait_plan(); } } plan_join{p};   // (no exit of this call leaves the second thread running)
   if (p->opt["inner_iterations"] != 0.0 && p->inner_src == nullptr && p->reduce == nullptr) p->plan_wanted_flags = flags;   // the plan's host part runs under the set-up (prepare)
   int rc = prepare(p, flags); if (rc) return rc;

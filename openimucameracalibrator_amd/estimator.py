@@ -497,6 +497,56 @@ class SplineTrajectoryEstimator:
         self._ck(self._b.get_covariance_timing(self._h, _dp(ms)))
         return dict(build=ms[0], forward=ms[1], corner=ms[2], backward=ms[3])
 
+    # ---- residual report and corner gating ---------------------------------
+    CORNER_USED, CORNER_PROJECTION_FAILED, CORNER_GATED = 0, 1, 2
+
+    def ResidualReport(self):
+        """oicc_residual_report at the current parameters: a dict of the counts by corner status, mean / rms / median / max of the
+        unweighted pixel error |e| over the used corners, sigma_px = median / 1.17741 (Rayleigh), the per-axis rms of the accelerometer
+        [m/s^2] and gyroscope [rad/s] residuals, unweighted and weighted, and ms_device.  Raises OiccError on time shards."""
+        info = _abi.ResidualInfo()
+        self._ck(self._b.residual_report(self._h, C.byref(info)))
+        self._last_report = info.as_dict()
+        return dict(self._last_report)
+
+    def _report_sizes(self):
+        r = getattr(self, "_last_report", None) or dict(num_corners=0, num_views=0, num_accl=0, num_gyro=0)
+        return r
+
+    def GetCornerErrors(self):
+        """(e_uv [n, 2] unweighted pixel errors pi(p_c) - z, status [n]) of the last report, corners in the order they were added."""
+        n = int(self._report_sizes()["num_corners"])
+        e = np.zeros((n, 2)); st = np.zeros(n, np.uint8)
+        self._ck(self._b.get_corner_errors(self._h, _dp(e), st.ctypes.data_as(_abi.c_u8p), n))
+        return e, st
+
+    def GetViewErrors(self):
+        """dict(rms_px, max_px, n_used) of the last report, one entry per accepted view in the order the views were added."""
+        nv = int(self._report_sizes()["num_views"])
+        rms = np.zeros(nv); mx = np.zeros(nv); nu = np.zeros(nv, np.int32)
+        self._ck(self._b.get_view_errors(self._h, _dp(rms), _dp(mx), nu.ctypes.data_as(_abi.c_i32p), nv))
+        return dict(rms_px=rms, max_px=mx, n_used=nu)
+
+    def GetImuResiduals(self, kind):
+        """[n, 3] unweighted residuals of the last report: kind 1 accelerometer [m/s^2], 2 gyroscope [rad/s], samples as added."""
+        n = int(self._report_sizes()["num_accl" if int(kind) == 1 else "num_gyro"])
+        r = np.zeros((n, 3))
+        self._ck(self._b.get_imu_residuals(self._h, int(kind), _dp(r), n))
+        return r
+
+    def GateCorners(self, threshold_px):
+        """oicc_gate_corners: corners of the last report with |e| > threshold_px get weight 0, all others their own weight back;
+        threshold_px <= 0 lifts every gate.  Returns the number of gated corners."""
+        n = C.c_int64(0)
+        self._ck(self._b.gate_corners(self._h, float(threshold_px), C.byref(n)))
+        return int(n.value)
+
+    def GetCornerGate(self, num_corners):
+        """[num_corners] bool: which corners are gated now, in the order they were added."""
+        g = np.zeros(int(num_corners), np.uint8)
+        self._ck(self._b.get_corner_gate(self._h, g.ctypes.data_as(_abi.c_u8p), len(g)))
+        return g.astype(bool)
+
     # ---- getters ------------------------------------------------------------
     def GetNumSO3Knots(self):
         return int(self._b.get_num_so3_knots(self._h))
@@ -756,6 +806,19 @@ class ImuCameraCalibrator:
         """imu_camera_calibrator.cc:163-168: returns the mean reprojection error."""
         self.summary = self.trajectory_.Optimize(iterations, optim_flags)
         return self.trajectory_.GetMeanReprojectionError()
+
+    def OptimizeGated(self, iterations, optim_flags, sigmas=5.0):
+        """Optimize, residual report, gate the corners whose pixel error exceeds sigmas * sigma_px (the report's robust scale),
+        Optimize again from the point reached.  Returns the mean reprojection error like Optimize; the first solve's summary, the
+        report between the solves, the threshold and the number of gated corners are left in summary_first, gate_report,
+        gate_threshold_px and gated_corners."""
+        tr = self.trajectory_
+        self.summary_first = tr.Optimize(iterations, optim_flags)
+        self.gate_report = tr.ResidualReport()
+        self.gate_threshold_px = float(sigmas) * self.gate_report["sigma_px"]
+        self.gated_corners = tr.GateCorners(self.gate_threshold_px) if self.gate_threshold_px > 0.0 else 0
+        self.summary = tr.Optimize(iterations, optim_flags)
+        return tr.GetMeanReprojectionError()
 
     def GetCalibrationStdDevs(self, flags, scaled=True):
         """Named standard deviations of the calibration from SplineTrajectoryEstimator.EstimateCovariance(flags): the square roots of
