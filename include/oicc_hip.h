@@ -645,6 +645,44 @@ int oicc_ba_optimize_views(oicc_ba* p, int32_t max_iters, int32_t flags, int32_t
  * point, robustified residuals as oicc_ba_evaluate), NaN for constant points; n = the number of scene points.
  * variance_factor (may be NULL) = 2 cost / (2 observations - 3 variable points); nothing is multiplied by it. */
 int oicc_ba_point_covariances(oicc_ba* p, double* cov9, int64_t n, double* variance_factor);
+/* Covariance of the intrinsics and the view poses, variable TOGETHER (no counterpart in the reference): (J^T J)^-1 at the
+ * current parameters for the J^T J that oicc_ba_evaluate returns for the same flags, intrinsics_mask and huber_width
+ * (robustified residuals), in its tangent order.  J^T J is a block diagonal (one d x d block per view, d = pose_dim = 3 or 6)
+ * with an intrinsics arrow of a <= 10 columns: once the intrinsics are eliminated the views are independent, so the device
+ * computes a view-parallel Schur complement -- never a dense P x P inverse -- on the matrix scaled to unit diagonal
+ * (S H S, s_i = H_ii^-1/2, no damping; cov_ij = s_i s_j Zs_ij).  A view without observations is left out of the system: it
+ * counts neither in P nor in views_used and its blocks are NaN.  d = 0 (poses constant) and a = 0 (intrinsics constant) are
+ * allowed.  Two estimates at the same parameters return the same bits in the arrays and in rcond, whatever the number of
+ * observations of a view (sums that the assembly forms with atomics in arrival order are formed again in a fixed order); cost
+ * and variance_factor come from the assembly pass and may differ in their last bits.
+ *   status           as oicc_covariance_status above; OICC_COV_RANK_DEFICIENT when a pivot is not positive or
+ *                    rcond < option covariance_min_rcond (oicc_ba_set_option, default 1e-12)
+ *   first_bad        -1, else the view -- or nv + intrinsics column -- of the first pivot (or diagonal entry) that failed
+ *   rcond            1 / max_i Zs_ii over every handed-out diagonal entry of the scaled inverse
+ *   variance_factor  2 cost / (num_residuals - P), num_residuals = 2 observations; nothing is multiplied by it
+ * oicc_ba_estimate_covariance returns OICC_OK for each status, OICC_ERR_INVALID_ARG for OICC_BA_POINTS in flags
+ * (oicc_ba_point_covariances is the entry for the board points) and for an empty active set.  The getters return
+ * OICC_ERR_STATE unless the last estimate has status OICC_COV_OK and still belongs to the current parameters: every setter,
+ * oicc_ba_set_option, oicc_ba_optimize and oicc_ba_optimize_views invalidate it. */
+typedef struct oicc_ba_covariance_info {
+  int32_t status;            /* oicc_covariance_status */
+  int32_t P, pose_dim, a;    /* P = pose_dim * views_used + a */
+  int32_t views_used;        /* views with at least one observation */
+  int32_t first_bad;
+  int64_t num_residuals;
+  double cost, variance_factor, rcond;
+} oicc_ba_covariance_info;
+int oicc_ba_estimate_covariance(oicc_ba* p, int32_t flags, int32_t intrinsics_mask, oicc_ba_covariance_info* info);
+/* cov [a][a] row major, ascending parameter index of the variable intrinsics; a_capacity >= a */
+int oicc_ba_get_covariance_intrinsics(const oicc_ba* p, double* cov, int32_t a_capacity);
+/* blocks [nv][d][d]: the full covariance of every view's pose in the tangent order of oicc_ba_evaluate */
+int oicc_ba_get_covariance_poses(const oicc_ba* p, double* blocks, int64_t nv);
+/* cross [nv][d][a]: the covariance of every view's pose with the intrinsics */
+int oicc_ba_get_covariance_pose_intrinsics(const oicc_ba* p, double* cross, int64_t nv);
+/* Device time of the last estimate in ms, whatever its status: [0] the assembly pass -- the device work of one oicc_ba_evaluate --,
+ * [1] the covariance kernels behind it.  Recorded (HIP events on the estimate's stream) only while option covariance_timing is 1
+ * (oicc_ba_set_option, default 0: an estimate records nothing); OICC_ERR_STATE when the last estimate was not timed. */
+int oicc_ba_get_covariance_timing(const oicc_ba* p, double ms[2]);
 /* GetReprojErrorOfView for every view: mean pixel distance of its observations, [nv] */
 int oicc_ba_view_reprojection_errors(oicc_ba* p, double* mean_px);
 

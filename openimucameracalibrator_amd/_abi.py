@@ -58,6 +58,16 @@ class CovarianceInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class BaCovarianceInfo(C.Structure):
+    """oicc_ba_covariance_info (include/oicc_hip.h)."""
+    _fields_ = [("status", C.c_int32), ("P", C.c_int32), ("pose_dim", C.c_int32), ("a", C.c_int32), ("views_used", C.c_int32),
+                ("first_bad", C.c_int32), ("num_residuals", C.c_int64), ("cost", C.c_double), ("variance_factor", C.c_double),
+                ("rcond", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class ResidualInfo(C.Structure):
     """oicc_residual_info (include/oicc_hip.h)."""
     _fields_ = [("num_corners", C.c_int64), ("num_used", C.c_int64), ("num_failed", C.c_int64), ("num_gated", C.c_int64),
@@ -180,9 +190,15 @@ BA_SIGNATURES = {
     "optimize_views": (C.c_int, [HB, C.c_int32, C.c_int32, c_i32p, c_dp]),
     "view_reprojection_errors": (C.c_int, [HB, c_dp]),
     "point_covariances": (C.c_int, [HB, c_dp, C.c_int64, c_dp]),
+    "estimate_covariance": (C.c_int, [HB, C.c_int32, C.c_int32, C.POINTER(BaCovarianceInfo)]),
+    "get_covariance_intrinsics": (C.c_int, [HB, c_dp, C.c_int32]),
+    "get_covariance_poses": (C.c_int, [HB, c_dp, C.c_int64]),
+    "get_covariance_pose_intrinsics": (C.c_int, [HB, c_dp, C.c_int64]),
+    "get_covariance_timing": (C.c_int, [HB, c_dp]),
 }
 # Entries of BA_SIGNATURES that only the device library has: the CPU checker, bound with the same table, has no counterpart.
-BA_DEVICE_ONLY = ("point_covariances",)
+BA_DEVICE_ONLY = ("point_covariances", "estimate_covariance", "get_covariance_intrinsics", "get_covariance_poses",
+                  "get_covariance_pose_intrinsics", "get_covariance_timing")
 
 
 class BoundBa:

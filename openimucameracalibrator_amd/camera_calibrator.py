@@ -25,6 +25,8 @@ from .synthetic import (CAM_PINHOLE, CAM_PINHOLE_RADIAL_TANGENTIAL, CAM_FISHEYE,
 BA_POSITION = 1
 BA_ORIENTATION = 2
 BA_POINTS = 4       # theia::BundleAdjustTracks: board points variable, cameras constant
+COV_OK, COV_RANK_DEFICIENT, COV_ZERO_COLUMN = 0, 1, 2   # oicc_covariance_status
+COV_STATUS_NAMES = {COV_OK: "ok", COV_RANK_DEFICIENT: "rank deficient", COV_ZERO_COLUMN: "zero column"}
 
 # theia::OptimizeIntrinsicsType [EXT, theia/sfm/types.h]
 NONE = 0x00
@@ -113,6 +115,7 @@ class ViewBundleAdjuster:
         self.h = h
         self.nv = 0
         self.n_intr = 0
+        self.cov_info_ = None      # info of the last EstimateCovariance
 
     def __del__(self):
         try:
@@ -202,6 +205,54 @@ class ViewBundleAdjuster:
         self._ck(self.b.point_covariances(self.h, _dp(cov), self.np_, C.byref(vf)))
         return cov, vf.value
 
+    def EstimateCovariance(self, flags, mask):
+        """oicc_ba_estimate_covariance: the covariance of the view poses and the intrinsics, variable together, at the current
+        parameters ((J^T J)^-1 of Evaluate(flags, mask); view-parallel Schur complement on the device).  Returns the info as a
+        dict (status COV_OK / COV_RANK_DEFICIENT / COV_ZERO_COLUMN, P, pose_dim, a, views_used, first_bad, num_residuals, cost,
+        variance_factor, rcond); the arrays come from the Covariance* getters, which raise unless the status is COV_OK and the
+        parameters are unchanged.  Nothing is multiplied by the variance factor."""
+        if not hasattr(self.b, "estimate_covariance"):
+            raise RuntimeError("this backend has no oicc_ba_estimate_covariance (device library only)")
+        info = _abi.BaCovarianceInfo()
+        self._ck(self.b.estimate_covariance(self.h, int(flags), int(mask), C.byref(info)))
+        self.cov_info_ = info.as_dict()
+        return dict(self.cov_info_)
+
+    def _cov_dims(self):
+        if self.cov_info_ is None:
+            raise RuntimeError("oicc_ba: no covariance estimate for the current parameters (EstimateCovariance has not run)")
+        return self.cov_info_["pose_dim"], self.cov_info_["a"]
+
+    def _cov_get(self, fn, shape, *args):
+        out = np.zeros(shape)
+        rc = fn(self.h, _dp(out), *args)
+        if rc != 0:
+            raise RuntimeError("oicc_ba: no covariance estimate for the current parameters (rc=%d)" % rc)
+        return out
+
+    def CovarianceIntrinsics(self):
+        """[a, a] in ascending parameter index of the variable intrinsics."""
+        _, a = self._cov_dims()
+        return self._cov_get(self.b.get_covariance_intrinsics, (a, a), a)
+
+    def CovariancePoses(self):
+        """[nv, d, d] in the tangent order of Evaluate; NaN for a view without observations."""
+        d, _ = self._cov_dims()
+        return self._cov_get(self.b.get_covariance_poses, (self.nv, d, d), self.nv)
+
+    def CovariancePoseIntrinsics(self):
+        """[nv, d, a]: every view's pose against the intrinsics."""
+        d, a = self._cov_dims()
+        return self._cov_get(self.b.get_covariance_pose_intrinsics, (self.nv, d, a), self.nv)
+
+    def CovarianceTiming(self):
+        """Device time of the last estimate in ms: (assembly pass = the device work of one Evaluate, covariance kernels).  Recorded only
+        with SetOption("covariance_timing", 1)."""
+        ms = np.zeros(2)
+        if self.b.get_covariance_timing(self.h, _dp(ms)) != 0:
+            raise RuntimeError("oicc_ba: the last estimate was not timed (option covariance_timing)")
+        return float(ms[0]), float(ms[1])
+
     def Iterations(self, cap=256):
         arr = (_abi.Iteration * cap)()
         n = self.b.get_iterations(self.h, arr, cap)
@@ -261,6 +312,8 @@ class CameraCalibrator:
         self.ba = ViewBundleAdjuster(device=device, backend=backend)
         self.max_num_iterations = 100  # theia::BundleAdjustmentOptions default [EXT]
         self.summaries = []
+        self.active_set_ = (BA_POSITION | BA_ORIENTATION, 0)   # flags, intrinsics mask of the last pose-variable BundleAdjustViews
+        self.covariance_ = None
 
     def SetVerbose(self):
         self.verbose_ = True
@@ -274,7 +327,8 @@ class CameraCalibrator:
         robust_init the start values use every corner and this has no effect."""
         self.ransac_error_thresh_ = float(error_thresh)
 
-    def CalibrateCameraFromJson(self, scene_json, output_path="", robust_init=False, ransac_backend=None, ransac_hypotheses=256):
+    def CalibrateCameraFromJson(self, scene_json, output_path="", robust_init=False, ransac_backend=None, ransac_hypotheses=256,
+                                estimate_covariance=False):
         """camera_calibrator.cc:221-377: views from the corner file (start pose and focal length per view, voxel filter),
         RunCalibration, outputs (`<out>.json`, `<out>.calibdata.json`, two PLY files).  robust_init=True: RANSAC over the
         corners of every view first (robust_init.py); start values from the inliers, ONLY the inliers become observations
@@ -329,10 +383,15 @@ class CameraCalibrator:
             return False
         total = self.TotalReprojectionError()
         print("Final camera calibration reprojection error: %s from %d view." % (total, self.NumViews()))
+        cov_obj = None
+        if estimate_covariance:   # a rank-deficient estimate is reported and writes nothing; the calibration stands
+            info = self.EstimateCovariance()
+            self.PrintCovariance(info)
+            cov_obj = self.GetIntrinsicsCovarianceObject() if info["status"] == COV_OK else None
         if output_path:
             io_files.write_pose_dataset(output_path + ".calibdata.json", self.views.t_s, self.views.pose, self.points, getattr(self, "point_ids_", None))
             io_files.write_camera_calibration(output_path + ".json", self.model, self.GetIntrinsics(), w, h, scene_json.get("camera_fps", 0.0),
-                                              self.NumViews(), total)
+                                              self.NumViews(), total, intrinsics_covariance=cov_obj)
             io_files.write_ply_cameras(output_path + "_final_poses.ply", self.views.pose, self.points)
         return True
 
@@ -384,7 +443,11 @@ class CameraCalibrator:
     def _bundle_adjust_views(self, constant_pose, intrinsics_to_optimize):
         self._upload()
         flags = 0 if constant_pose else (BA_POSITION | BA_ORIENTATION)
-        s = self.ba.Optimize(self.max_num_iterations, flags, intrinsics_mask(self.model, intrinsics_to_optimize))
+        mask = intrinsics_mask(self.model, intrinsics_to_optimize)
+        s = self.ba.Optimize(self.max_num_iterations, flags, mask)
+        if not constant_pose:
+            self.active_set_ = (flags, mask)   # what EstimateCovariance estimates
+        self.covariance_ = None
         self._download()
         self.summaries.append(s)
         if self.verbose_:
@@ -397,6 +460,8 @@ class CameraCalibrator:
         err = self.ba.ViewReprojectionErrors()
         bad = [i for i in range(len(err)) if not (err[i] <= max_reproj_error)]
         self.views.remove(bad)
+        if bad:
+            self.covariance_ = None    # it belonged to the views before the removal
         return bad
 
     def RunCalibration(self):
@@ -430,6 +495,7 @@ class CameraCalibrator:
         self._upload()
         s = self.ba.Optimize(self.max_num_iterations, BA_POINTS, 0)
         self.points = self.ba.GetScenePoints()
+        self.covariance_ = None
         self.summaries.append(s)
         if self.verbose_:
             print("BundleAdjustTracks: cost %.6f -> %.6f in %d iterations (%s)" % (s["initial_cost"], s["final_cost"], s["num_iterations"], s["message"]))
@@ -443,9 +509,79 @@ class CameraCalibrator:
     def GetIntrinsics(self):
         return np.array(self.intr)
 
+    # -- covariance of the result (oicc_ba_estimate_covariance; no counterpart in the reference) ------------
+    def EstimateCovariance(self):
+        """Covariance of the intrinsics and the poses on the active set of the last pose-variable BundleAdjustViews of
+        RunCalibration, at the current result.  Returns the info dict of ViewBundleAdjuster.EstimateCovariance; the arrays
+        are kept (status COV_OK) for GetIntrinsicsStdDevs / GetIntrinsicsCorrelation / GetPoseStdDevs and dropped otherwise."""
+        from . import io_files
+        flags, mask = self.active_set_
+        self._upload()
+        info = self.ba.EstimateCovariance(flags, mask)
+        self.covariance_ = None
+        if info["status"] == COV_OK:
+            idx = [k for k in range(NUM_INTRINSICS[self.model]) if (mask >> k) & 1]
+            self.covariance_ = dict(info=info, index=idx, parameters=[io_files._INTR_KEYS[self.model][k] for k in idx],
+                                    intrinsics=self.ba.CovarianceIntrinsics(), poses=self.ba.CovariancePoses(),
+                                    pose_intrinsics=self.ba.CovariancePoseIntrinsics())
+        return info
+
+    def _covariance(self):
+        if getattr(self, "covariance_", None) is None:
+            raise RuntimeError("no covariance estimate (EstimateCovariance has not run, or it was rank deficient)")
+        return self.covariance_
+
+    def GetIntrinsicsStdDevs(self):
+        """name -> sqrt(variance factor * variance) of every variable intrinsic (the convention of PrintBoardPointCovariances)."""
+        c = self._covariance()
+        sd = np.sqrt(c["info"]["variance_factor"] * np.diag(c["intrinsics"]))
+        return {n: float(x) for n, x in zip(c["parameters"], sd)}
+
+    def GetIntrinsicsCorrelation(self):
+        """(names, [a, a] correlation matrix of the variable intrinsics)."""
+        c = self._covariance()
+        sd = np.sqrt(np.diag(c["intrinsics"]))
+        return list(c["parameters"]), c["intrinsics"] / np.outer(sd, sd)
+
+    def GetPoseStdDevs(self):
+        """[nv, 6]: sqrt(variance factor * variance) of every view's position (m) and angle axis (rad)."""
+        c = self._covariance()
+        return np.sqrt(c["info"]["variance_factor"] * np.diagonal(c["poses"], axis1=1, axis2=2))
+
+    def GetIntrinsicsCovarianceObject(self):
+        """The `intrinsics_covariance` object of the calibration JSON."""
+        c = self._covariance()
+        names, corr = self.GetIntrinsicsCorrelation()
+        sd = self.GetIntrinsicsStdDevs()
+        return dict(parameters=names, std_dev=[sd[n] for n in names], correlation=[[float(x) for x in row] for row in corr],
+                    variance_factor=float(c["info"]["variance_factor"]), rcond=float(c["info"]["rcond"]))
+
+    def PrintCovariance(self, info, out=None):
+        """One line per variable intrinsic (value +- sigma) and the largest absolute correlation; for an estimate without a
+        covariance the status and rcond."""
+        import sys
+        out = out or sys.stdout
+        if info["status"] != COV_OK:
+            print("Covariance estimate: %s (rcond %.3e), no covariance written" % (COV_STATUS_NAMES.get(info["status"], info["status"]), info["rcond"]), file=out)
+            return
+        c = self._covariance()
+        sd = self.GetIntrinsicsStdDevs()
+        for k, n in zip(c["index"], c["parameters"]):
+            print("%s: %.9g +- %.3g" % (n, self.intr[k], sd[n]), file=out)
+        names, corr = self.GetIntrinsicsCorrelation()
+        if len(names) > 1:
+            off = np.abs(corr - np.diag(np.diag(corr)))
+            r, q = np.unravel_index(int(np.argmax(off)), off.shape)
+            print("Largest correlation: %.4f (%s, %s); variance factor %.6g, rcond %.3e" % (corr[r, q], names[r], names[q], c["info"]["variance_factor"], c["info"]["rcond"]), file=out)
+
     def PrintResult(self):
         i = self.intr
         pp = (i[2], i[3]) if self.model == CAM_DIVISION_UNDISTORTION else (i[3], i[4])
+        if getattr(self, "covariance_", None) is not None:
+            sd = self.GetIntrinsicsStdDevs()
+            pm = lambda n: (" +- %.3g" % sd[n]) if n in sd else ""
+            print("Focal Length:%s%spx Principal Point: %s%s/%s%spx." % (i[0], pm("focal_length"), pp[0], pm("principal_pt_x"), pp[1], pm("principal_pt_y")))
+            return
         print("Focal Length:%spx Principal Point: %s/%spx." % (i[0], pp[0], pp[1]))
 
 
@@ -509,6 +645,24 @@ class PoseEstimator:
         out = self.ba.GetPoses()
         self.views.pose = [out[i].copy() for i in range(len(out))]
         return it, fc
+
+    def EstimatePoseCovariances(self):
+        """Covariance of every frame's pose with the camera constant (the a = 0 case of oicc_ba_estimate_covariance, every
+        frame independent) at the current poses: [nv, 6, 6] (position | angle axis), not multiplied by the variance factor,
+        or None for an estimate without a covariance.  The info dict is kept in pose_covariance_info_."""
+        pose, off, uv, pid = self.views.flat()
+        self.ba.SetCamera(self.model, self.intr)
+        self.ba.SetScenePoints(self.points)
+        self.ba.SetViews(pose, off, uv, pid)
+        self.pose_covariance_info_ = self.ba.EstimateCovariance(BA_POSITION | BA_ORIENTATION, 0)
+        return self.ba.CovariancePoses() if self.pose_covariance_info_["status"] == COV_OK else None
+
+    def GetPoseStdDevs(self):
+        """[nv, 6] sqrt(variance factor * variance) from a fresh EstimatePoseCovariances, or None without a covariance."""
+        cov = self.EstimatePoseCovariances()
+        if cov is None:
+            return None
+        return np.sqrt(self.pose_covariance_info_["variance_factor"] * np.diagonal(cov, axis1=1, axis2=2))
 
     def EstimatePosesFromJson(self, scene_json, model, intrinsics, image_height, min_num_points=8, robust_init=False,
                               ransac_backend=None, ransac_hypotheses=256, ransac_threshold=None):

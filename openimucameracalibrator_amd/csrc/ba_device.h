@@ -38,6 +38,33 @@ struct BaLmOptions {
   int32_t jacobi_scaling, max_invalid, max_iters;
 };
 
+// oicc_ba_estimate_covariance (kernels_ba_covariance.hip): device buffers; D = pose_dim, a = variable intrinsics
+struct BaCovResult {
+  unsigned long long zmax_bits;   // bit pattern of the largest diagonal entry of the scaled inverse (positive doubles order as integers)
+  int32_t bad_diag;               // smallest tangent column whose diagonal of J^T J is not finite and positive (pose column v*D + r, intrinsics nv*D + q)
+  int32_t bad_pivot;              // smallest view, or nv + corner column, whose pivot failed
+};
+struct BaCovBuffers {
+  double* chunkC;    // [n_chunks][a][a] the intrinsics corner of every chunk of the assembly's work list
+  double* C;         // [a][a]         their sum in chunk order (the assembly's own corner is summed by atomics)
+  const int32_t* view_chunk0;   // [nv+1] first chunk of every view -- or null when no view has three or more chunks
+  double* chunkA;    // [n_chunks][D][D] upper triangle: the chunk's part of A_v, written for views of three or more chunks only
+  double* chunkE;    // [n_chunks][D][a] the chunk's part of E_v, likewise
+  double* Sv;        // [nv][D]        scale factors of the pose columns
+  double* Ainv;      // [nv][D(D+1)/2] inverse of the scaled pose block, upper triangle by rows; NaN where it failed
+  double* Wv;        // [nv*D][a]      W_v = A_v^-1 E_v (scaled)
+  double* part;      // [ceil(nv/16)][a][a] per-workgroup sums of E_v' W_v
+  double* Zth;       // [a][a]         scaled inverse of the Schur complement
+  double* cov_th;    // [a][a]         intrinsics covariance
+  double* cov_pose;  // [nv][D][D]
+  double* cross;     // [nv][D][a]
+  BaCovResult* res;
+};
+constexpr int kBaCovViewsPerGroup = 16;   // views of one workgroup of kernels_ba_covariance.hip (16 lanes each)
+// every launch of one estimate, stream ordered: the failure words, the front kernel (per-view step and chunk partials; two launches
+// of it when a view has three or more chunks), the corner, the per-view hand-out; x = the parameters the assembly pass ran at
+void launch_ba_covariance(const double* x, const NormalEq& ne, const BaData& d, const BaCovBuffers& cb, hipStream_t st);
+
 void launch_ba_blocks(const double* x, const BaData& d, const TangentLayout& tl, const NormalEq& ne, bool jac, hipStream_t st);
 void launch_ba_retract(const double* x, double* xc, const BaData& d, const TangentLayout& tl, const SolveBuffers& sb, const NormalEq& ne,
                        hipStream_t st);

@@ -48,7 +48,7 @@ inline bool load_scene(const std::string& path, Scene* sc) {
 // io::write_camera_calibration, src/io/write_camera_calibration.cc:34-140 (same keys; PINHOLE additionally carries its
 // two radial terms so that the file reproduces the calibrated camera)
 inline bool write_camera_calibration(const std::string& path, int model, const std::string& model_name, const std::vector<double>& in, int w, int h,
-                                     double fps, int nr_calib_images, double total_reproj_error) {
+                                     double fps, int nr_calib_images, double total_reproj_error, const Value* intrinsics_covariance = nullptr) {
   std::ofstream f(path); if (!f.is_open()) { std::cerr << "Could not open: " << path << "\n"; return false; }
   Value o, I;
   o["stabelized"] = Value(false); o["fps"] = Value(fps); o["nr_calib_images"] = Value(int64_t(nr_calib_images)); o["final_reproj_error"] = Value(total_reproj_error);
@@ -66,6 +66,7 @@ inline bool write_camera_calibration(const std::string& path, int model, const s
     case OICC_CAM_PINHOLE: I["radial_distortion_1"] = Value(in[5]); I["radial_distortion_2"] = Value(in[6]); break;
   }
   o["intrinsics"] = I;
+  if (intrinsics_covariance) o["intrinsics_covariance"] = *intrinsics_covariance;   // --estimate_covariance; without it the file is unchanged
   oicc_json::dump(o, f, 2); f << std::endl;
   return true;
 }
@@ -82,13 +83,18 @@ inline std::string pose_view_name(double t_s) {
 // JSON twin of theia::WriteReconstruction for a pose data set (read back by read_pose_dataset of cli_common.hpp); tracks carry the
 // corner file's point ids (`point_ids`, empty: 0 .. n-1)
 inline bool write_pose_dataset(const std::string& path, const OpenICC::core::BaViews& views, const std::vector<std::array<double, 4>>& points,
-                               const std::vector<int>& point_ids = {}) {
+                               const std::vector<int>& point_ids = {}, const std::vector<std::array<double, 6>>* pose_std_dev = nullptr) {
   std::ofstream f(path); if (!f.is_open()) return false;
   Value o, V, T;
   for (size_t v = 0; v < views.pose.size(); ++v) {
     Value e, aa, pos;
     for (int k = 0; k < 3; ++k) { pos.push_back(Value(views.pose[v][size_t(k)])); aa.push_back(Value(views.pose[v][size_t(3 + k)])); }
     e["orientation_angle_axis"] = aa; e["position"] = pos;
+    if (pose_std_dev && v < pose_std_dev->size()) {   // --estimate_covariance
+      Value sp, sa;
+      for (int k = 0; k < 3; ++k) { sp.push_back(Value((*pose_std_dev)[v][size_t(k)])); sa.push_back(Value((*pose_std_dev)[v][size_t(3 + k)])); }
+      e["position_std_dev"] = sp; e["angle_axis_std_dev"] = sa;
+    }
     V[pose_view_name(views.t_s[v])] = e;
   }
   for (size_t i = 0; i < points.size(); ++i) { Value p; for (double c : points[i]) p.push_back(Value(c)); T[std::to_string(i < point_ids.size() ? point_ids[i] : int(i))] = p; }

@@ -20,6 +20,7 @@ using namespace OpenICC::core;
 static int run_main(int argc, char* argv[]) {
   Flags F({{"input_corners", ""}, {"camera_model_to_calibrate", "DOUBLE_SPHERE"}, {"save_path_calib_dataset", ""}, {"grid_size", "0.04"},
            {"optimize_board_points", "false"}, {"verbose", "false"}, {"dry_run", "false"}});   // dry_run: print the start values, no device
+  F.define("estimate_covariance", "false");   // value +- sigma of every variable intrinsic, `intrinsics_covariance` in the calibration JSON
   if (!F.parse(argc, argv)) return 2;
   Scene sc;
   CHECK_MSG(load_scene(F.str("input_corners"), &sc), "Failed to load " << F.str("input_corners"));
@@ -74,9 +75,32 @@ static int run_main(int argc, char* argv[]) {
   if (!cal.RunCalibration()) { std::cerr << "Calibration failed.\n"; return 1; }
   const double total = cal.TotalReprojectionError();
   std::cout << "Final camera calibration reprojection error: " << total << " from " << cal.NumViews() << " view." << std::endl;
+  Value cov_obj; bool have_cov = false;
+  if (F.b("estimate_covariance")) {   // a rank-deficient estimate is reported and writes nothing; the calibration stands
+    const oicc_ba_covariance_info info = cal.EstimateCovariance();
+    if (!cal.HasCovariance()) {
+      std::cout << "Covariance estimate: " << (info.status == OICC_COV_RANK_DEFICIENT ? "rank deficient" : "zero column") << " (rcond " << info.rcond << "), no covariance written\n";
+    } else {
+      const auto sd = cal.GetIntrinsicsStdDevs();
+      const std::vector<double> corr = cal.GetIntrinsicsCorrelation();
+      const size_t a = sd.size();
+      Value names, sds, C;
+      double worst = 0.0; size_t wr = 0, wq = 0;
+      for (size_t r = 0; r < a; ++r) {
+        std::cout << sd[r].first << ": " << cal.Intrinsics()[size_t(cal.CovarianceParameterIndex()[r])] << " +- " << sd[r].second << "\n";
+        names.push_back(Value(sd[r].first)); sds.push_back(Value(sd[r].second));
+        Value row; for (size_t q = 0; q < a; ++q) { row.push_back(Value(corr[r * a + q])); if (q != r && std::fabs(corr[r * a + q]) > std::fabs(worst)) { worst = corr[r * a + q]; wr = r; wq = q; } }
+        C.push_back(row);
+      }
+      if (a > 1) std::cout << "Largest correlation: " << worst << " (" << sd[wr].first << ", " << sd[wq].first << "); variance factor " << info.variance_factor << ", rcond " << info.rcond << "\n";
+      cov_obj["parameters"] = names; cov_obj["std_dev"] = sds; cov_obj["correlation"] = C;
+      cov_obj["variance_factor"] = Value(info.variance_factor); cov_obj["rcond"] = Value(info.rcond);
+      have_cov = true;
+    }
+  }
   if (!out.empty()) {
     CHECK_MSG(write_pose_dataset(out + ".calibdata.json", cal.Views(), cal.Points(), sc.point_ids), "Could not write " << out << ".calibdata.json");
-    CHECK_MSG(write_camera_calibration(out + ".json", model, model_name, cal.Intrinsics(), sc.width, sc.height, sc.fps, cal.NumViews(), total),
+    CHECK_MSG(write_camera_calibration(out + ".json", model, model_name, cal.Intrinsics(), sc.width, sc.height, sc.fps, cal.NumViews(), total, have_cov ? &cov_obj : nullptr),
               "Could not write calibration file.");
     write_ply_cameras(out + "_final_poses.ply", cal.Views().pose, cal.Points());
   }

@@ -39,6 +39,20 @@ inline int32_t IntrinsicsMask(int model, int opt) {
   return m;
 }
 
+// names of the intrinsics in parameter order: the keys of the calibration JSON (write_camera_calibration)
+inline std::vector<std::string> IntrinsicsNames(int model) {
+  switch (model) {
+    case OICC_CAM_DIVISION_UNDISTORTION: return {"focal_length", "aspect_ratio", "principal_pt_x", "principal_pt_y", "div_undist_distortion"};
+    case OICC_CAM_PINHOLE_RADIAL_TANGENTIAL: return {"focal_length", "aspect_ratio", "skew", "principal_pt_x", "principal_pt_y", "radial_distortion_1",
+                                                     "radial_distortion_2", "radial_distortion_3", "tangential_distortion_1", "tangential_distortion_2"};
+    case OICC_CAM_FISHEYE: return {"focal_length", "aspect_ratio", "skew", "principal_pt_x", "principal_pt_y", "radial_distortion_1", "radial_distortion_2",
+                                   "radial_distortion_3", "radial_distortion_4"};
+    case OICC_CAM_DOUBLE_SPHERE: return {"focal_length", "aspect_ratio", "skew", "principal_pt_x", "principal_pt_y", "xi", "alpha"};
+    case OICC_CAM_EXTENDED_UNIFIED: return {"focal_length", "aspect_ratio", "skew", "principal_pt_x", "principal_pt_y", "alpha", "beta"};
+    default: return {"focal_length", "aspect_ratio", "skew", "principal_pt_x", "principal_pt_y", "radial_distortion_1", "radial_distortion_2"};
+  }
+}
+
 // ceres::RotationMatrixToAngleAxis [EXT] (theia::Camera::SetOrientationFromRotationMatrix); R row major, world -> camera
 inline std::array<double, 3> RotationMatrixToAngleAxis(const std::array<double, 9>& R) {
   const double c = std::min(1.0, std::max(-1.0, (R[0] + R[4] + R[8] - 1.0) * 0.5));
@@ -111,13 +125,29 @@ class ViewBundleAdjuster {   // theia::BundleAdjuster for one shared camera and 
     Check(oicc_ba_point_covariances(h_, cov.data(), int64_t(num_points), variance_factor));
     return cov;
   }
+  // oicc_ba_estimate_covariance: intrinsics and poses variable together; the arrays (not multiplied by the variance factor) come
+  // from the three getters, which end the program unless the status is OICC_COV_OK and the parameters are unchanged
+  oicc_ba_covariance_info EstimateCovariance(int flags, int mask) { Check(oicc_ba_estimate_covariance(h_, flags, mask, &cov_info_)); return cov_info_; }
+  std::vector<double> CovarianceIntrinsics() const {   // [a][a]
+    std::vector<double> c(size_t(cov_info_.a) * size_t(cov_info_.a), 0.0);
+    CheckCov(oicc_ba_get_covariance_intrinsics(h_, c.data(), cov_info_.a)); return c;
+  }
+  std::vector<double> CovariancePoses() const {   // [nv][d][d]
+    std::vector<double> c(size_t(nv_) * size_t(cov_info_.pose_dim) * size_t(cov_info_.pose_dim), 0.0);
+    CheckCov(oicc_ba_get_covariance_poses(h_, c.data(), nv_)); return c;
+  }
+  std::vector<double> CovariancePoseIntrinsics() const {   // [nv][d][a]
+    std::vector<double> c(size_t(nv_) * size_t(cov_info_.pose_dim) * size_t(cov_info_.a), 0.0);
+    CheckCov(oicc_ba_get_covariance_pose_intrinsics(h_, c.data(), nv_)); return c;
+  }
   void OptimizeViews(int max_iters, std::vector<int32_t>* it, std::vector<double>* cost) {
     it->resize(size_t(nv_)); cost->resize(size_t(nv_));
     Check(oicc_ba_optimize_views(h_, max_iters, OICC_BA_POSITION | OICC_BA_ORIENTATION, it->data(), cost->data()));
   }
   std::vector<double> ViewReprojectionErrors() { std::vector<double> e(static_cast<size_t>(nv_), 0.0); Check(oicc_ba_view_reprojection_errors(h_, e.data())); return e; }
  private:
-  oicc_ba* h_ = nullptr; int64_t nv_ = 0; int n_intr_ = 0;
+  void CheckCov(int rc) const { if (rc != OICC_OK) { std::cerr << "oicc_ba: no covariance estimate for the current parameters (rc=" << rc << ")\n"; std::exit(1); } }
+  oicc_ba* h_ = nullptr; int64_t nv_ = 0; int n_intr_ = 0; oicc_ba_covariance_info cov_info_{};
 };
 
 class CameraCalibrator {
@@ -154,6 +184,7 @@ class CameraCalibrator {
     std::vector<int> bad;
     for (size_t i = 0; i < err.size(); ++i) if (!(err[i] <= max_reproj_error)) bad.push_back(int(i));
     views_.remove(bad);
+    if (!bad.empty()) have_cov_ = false;   // it belonged to the views before the removal
   }
   bool RunCalibration() {   // camera_calibrator.cc:131-219
     if (NumViews() < min_num_view_) { std::cerr << "Not enough views for proper calibration!\n"; return false; }
@@ -172,6 +203,7 @@ class CameraCalibrator {
       ba_.Upload(model_, intr_, points_, views_);
       const oicc_summary s = ba_.Optimize(max_num_iterations_, OICC_BA_POINTS, 0);   // theia::BundleAdjustTracks
       ba_.DownloadPoints(&points_);
+      have_cov_ = false;
       if (verbose_) std::cout << "BundleAdjustTracks: cost " << s.initial_cost << " -> " << s.final_cost << " in " << s.num_iterations << " iterations (" << s.message << ")\n";
       BundleAdjustViews(false, opt);
     }
@@ -182,20 +214,67 @@ class CameraCalibrator {
     const std::vector<double> e = ba_.ViewReprojectionErrors();
     double s = 0; for (double v : e) s += v; return s / double(e.size());
   }
+  // Covariance of the intrinsics and the poses on the active set of the last pose-variable BundleAdjustViews of RunCalibration, at
+  // the current result (no counterpart in the reference).  The arrays are kept for the getters below when the status is OICC_COV_OK.
+  oicc_ba_covariance_info EstimateCovariance() {
+    ba_.Upload(model_, intr_, points_, views_);
+    cov_info_ = ba_.EstimateCovariance(active_flags_, active_mask_);
+    have_cov_ = cov_info_.status == OICC_COV_OK;
+    cov_index_.clear();
+    for (int k = 0; k < NumIntrinsics(model_); ++k) if ((active_mask_ >> k) & 1) cov_index_.push_back(k);
+    if (have_cov_) { cov_intr_ = ba_.CovarianceIntrinsics(); cov_pose_ = ba_.CovariancePoses(); }
+    return cov_info_;
+  }
+  bool HasCovariance() const { return have_cov_; }
+  const oicc_ba_covariance_info& CovarianceInfo() const { return cov_info_; }
+  const std::vector<int>& CovarianceParameterIndex() const { return cov_index_; }
+  // name -> sqrt(variance factor * variance) of every variable intrinsic, in parameter order
+  std::vector<std::pair<std::string, double>> GetIntrinsicsStdDevs() const {
+    std::vector<std::pair<std::string, double>> out;
+    if (!have_cov_) return out;
+    const std::vector<std::string> names = IntrinsicsNames(model_);
+    const size_t a = cov_index_.size();
+    for (size_t q = 0; q < a; ++q) out.emplace_back(names[size_t(cov_index_[q])], std::sqrt(cov_info_.variance_factor * cov_intr_[q * a + q]));
+    return out;
+  }
+  std::vector<double> GetIntrinsicsCorrelation() const {   // [a][a]
+    const size_t a = cov_index_.size();
+    std::vector<double> c(have_cov_ ? a * a : 0, 0.0);
+    for (size_t r = 0; r * a < c.size(); ++r) for (size_t q = 0; q < a; ++q) c[r * a + q] = cov_intr_[r * a + q] / std::sqrt(cov_intr_[r * a + r] * cov_intr_[q * a + q]);
+    return c;
+  }
+  std::vector<std::array<double, 6>> GetPoseStdDevs() const {   // position (m) | angle axis (rad)
+    std::vector<std::array<double, 6>> out;
+    if (!have_cov_ || cov_info_.pose_dim != 6) return out;
+    for (size_t v = 0; v * 36 < cov_pose_.size(); ++v) { std::array<double, 6> sd; for (size_t k = 0; k < 6; ++k) sd[k] = std::sqrt(cov_info_.variance_factor * cov_pose_[v * 36 + k * 7]); out.push_back(sd); }
+    return out;
+  }
   void PrintResult() const {
     const bool div = model_ == OICC_CAM_DIVISION_UNDISTORTION;
+    if (have_cov_) {
+      const auto sd = GetIntrinsicsStdDevs();
+      auto pm = [&](const char* n) { for (const auto& kv : sd) if (kv.first == n) return " +- " + std::to_string(kv.second); return std::string(); };
+      std::cout << "Focal Length:" << intr_[0] << pm("focal_length") << "px Principal Point: " << intr_[div ? 2 : 3] << pm("principal_pt_x") << "/" << intr_[div ? 3 : 4]
+                << pm("principal_pt_y") << "px.\n";
+      return;
+    }
     std::cout << "Focal Length:" << intr_[0] << "px Principal Point: " << intr_[div ? 2 : 3] << "/" << intr_[div ? 3 : 4] << "px.\n";
   }
  private:
   void BundleAdjustViews(bool constant_pose, int intrinsics_to_optimize) {
     ba_.Upload(model_, intr_, points_, views_);
-    const oicc_summary s = ba_.Optimize(max_num_iterations_, constant_pose ? 0 : (OICC_BA_POSITION | OICC_BA_ORIENTATION), IntrinsicsMask(model_, intrinsics_to_optimize));
+    const int flags = constant_pose ? 0 : (OICC_BA_POSITION | OICC_BA_ORIENTATION), mask = IntrinsicsMask(model_, intrinsics_to_optimize);
+    const oicc_summary s = ba_.Optimize(max_num_iterations_, flags, mask);
+    if (!constant_pose) { active_flags_ = flags; active_mask_ = mask; }
+    have_cov_ = false;
     ba_.Download(&intr_, &views_);
     if (verbose_) std::cout << "BundleAdjustViews: cost " << s.initial_cost << " -> " << s.final_cost << " in " << s.num_iterations << " iterations (" << s.message << ")\n";
   }
   std::string camera_model_; int model_; ViewBundleAdjuster ba_;
   BaViews views_; std::vector<std::array<double, 4>> points_; std::vector<double> intr_;
   int min_num_view_ = 10, max_num_iterations_ = 100; bool verbose_ = false, optimize_board_pts_ = false;
+  int active_flags_ = OICC_BA_POSITION | OICC_BA_ORIENTATION, active_mask_ = 0; bool have_cov_ = false;
+  oicc_ba_covariance_info cov_info_{}; std::vector<int> cov_index_; std::vector<double> cov_intr_, cov_pose_;
 };
 
 class PoseEstimator {   // bundle-adjustment half of pose_estimator.cc: poses of a calibrated camera, normalised PINHOLE f = 1
@@ -247,6 +326,23 @@ class PoseEstimator {   // bundle-adjustment half of pose_estimator.cc: poses of
     if (board_point_cov_.size() == 9 * points_.size() && !points_.empty()) { if (variance_factor) *variance_factor = board_point_variance_factor_; return board_point_cov_; }   // as OptimizeBoardPoints left them
     UploadBoardPointProblem(min_num_obs_for_optim);
     return ba_.PointCovariances(points_.size(), variance_factor);
+  }
+  // Covariance of every frame's pose with the camera constant (the a = 0 case of oicc_ba_estimate_covariance) at the current poses:
+  // 36 doubles per view, not multiplied by the variance factor; empty for an estimate without a covariance (info tells why).
+  std::vector<double> EstimatePoseCovariances(oicc_ba_covariance_info* info = nullptr) {
+    if (views_.pose.empty()) return {};
+    ba_.Upload(OICC_CAM_PINHOLE, {1.0, 1.0, 0.0, 0.0, 0.0, 0.0, 0.0}, points_, views_);
+    const oicc_ba_covariance_info i = ba_.EstimateCovariance(OICC_BA_POSITION | OICC_BA_ORIENTATION, 0);
+    if (info) *info = i;
+    return i.status == OICC_COV_OK ? ba_.CovariancePoses() : std::vector<double>();
+  }
+  std::vector<std::array<double, 6>> GetPoseStdDevs(oicc_ba_covariance_info* info = nullptr) {   // sqrt(variance factor * variance)
+    oicc_ba_covariance_info i{};
+    const std::vector<double> cov = EstimatePoseCovariances(&i);
+    if (info) *info = i;
+    std::vector<std::array<double, 6>> out;
+    for (size_t v = 0; v * 36 < cov.size(); ++v) { std::array<double, 6> sd; for (size_t k = 0; k < 6; ++k) sd[k] = std::sqrt(i.variance_factor * cov[v * 36 + k * 7]); out.push_back(sd); }
+    return out;
   }
   BaViews& Views() { return views_; }
   const std::vector<std::array<double, 4>>& Points() const { return points_; }

@@ -19,6 +19,7 @@ using namespace OpenICC::core;
 
 static int run_main(int argc, char* argv[]) {
   Flags F({{"input_corners", ""}, {"camera_calibration_json", ""}, {"output_pose_dataset", ""}, {"optimize_board_points", "false"}, {"dry_run", "false"}});   // dry_run: print the start poses, no device
+  F.define("estimate_covariance", "false");   // position_std_dev / angle_axis_std_dev per view in the pose data set
   if (!F.parse(argc, argv)) return 2;
   Scene sc;
   CHECK_MSG(load_scene(F.str("input_corners"), &sc), "Failed to load " << F.str("input_corners"));
@@ -85,7 +86,13 @@ static int run_main(int argc, char* argv[]) {
     V.remove(bad);
   }
   std::cout << "Estimated " << V.pose.size() << " camera poses, mean reprojection error " << (err_n ? err_sum / err_n : 0.0) << " px\n";
-  CHECK_MSG(write_pose_dataset(F.str("output_pose_dataset"), V, pe.Points(), sc.point_ids), "Could not write " << F.str("output_pose_dataset"));
+  std::vector<std::array<double, 6>> pose_sd;
+  if (F.b("estimate_covariance") && !V.pose.empty()) {   // a rank-deficient estimate is reported and writes nothing
+    oicc_ba_covariance_info info{};
+    pose_sd = pe.GetPoseStdDevs(&info);
+    if (pose_sd.empty()) std::cout << "Pose covariance estimate: " << (info.status == OICC_COV_RANK_DEFICIENT ? "rank deficient" : "zero column") << " (rcond " << info.rcond << "), no standard deviations written\n";
+  }
+  CHECK_MSG(write_pose_dataset(F.str("output_pose_dataset"), V, pe.Points(), sc.point_ids, pose_sd.empty() ? nullptr : &pose_sd), "Could not write " << F.str("output_pose_dataset"));
   write_ply_cameras(F.str("output_pose_dataset") + ".ply", V.pose, pe.Points());
   return 0;
 }

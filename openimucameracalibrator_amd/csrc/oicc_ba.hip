@@ -47,6 +47,14 @@ struct oicc_ba {
   DevBuf<LmState> d_state;
   struct HostPin { LmState st; double cost; };
   HostPin* pin = nullptr;
+  // oicc_ba_estimate_covariance: device buffers and the host copy the getters hand out (valid: status OICC_COV_OK at the current parameters)
+  // pin: ONE pinned block the results are copied into [BaCovResult | cost | intrinsics a a | poses nv d d | cross nv d a] (doubles)
+  struct Cov { bool valid = false, timed = false, layout_ok = false, big = false; int d = 0, a = 0; int64_t nv = 0; double* pin = nullptr; size_t pin_n = 0;
+               size_t o_intr = 0, o_poses = 0, o_cross = 0; double ms[2] = {0, 0}; std::vector<int32_t> view_chunk0; } cov;
+  hipEvent_t cov_ev[3] = {nullptr, nullptr, nullptr};   // option covariance_timing: around the assembly pass and the covariance kernels
+  DevBuf<int32_t> d_cvChunk0;
+  DevBuf<double> d_cvChunkA, d_cvChunkE, d_cvSv, d_cvChunkC, d_cvC, d_cvAinv, d_cvW, d_cvPart, d_cvZth, d_cvTh, d_cvPose, d_cvCross;
+  DevBuf<BaCovResult> d_cvRes;
   oicc_ba() {
     // theia::BundleAdjustmentOptions defaults [EXT]; the rest are the Ceres 2.1 defaults [EXT] Theia leaves alone
     opt["function_tolerance"] = 1e-6; opt["parameter_tolerance"] = 1e-8; opt["gradient_tolerance"] = 1e-10;
@@ -55,6 +63,8 @@ struct oicc_ba {
     opt["min_lm_diagonal"] = 1e-6; opt["max_lm_diagonal"] = 1e32; opt["jacobi_scaling"] = 1;
     opt["max_num_consecutive_invalid_steps"] = 5; opt["huber_width"] = 1.345; opt["verbose"] = 0;
     opt["solver_algorithm"] = 0; opt["num_threads"] = 0;
+    opt["covariance_timing"] = 0;          // 1: HIP events around the two parts of an estimate (oicc_ba_get_covariance_timing)
+    opt["covariance_min_rcond"] = 1e-12;   // oicc_ba_estimate_covariance: the value of the spline path (oicc_estimate_covariance)
   }
 };
 
@@ -204,24 +214,26 @@ void oicc_ba_destroy(oicc_ba* p) {
   if (!p) return;
   (void)hipSetDevice(p->device);
   if (p->stream) { (void)hipStreamSynchronize(p->stream); (void)hipStreamDestroy(p->stream); }
+  for (hipEvent_t e : p->cov_ev) if (e) (void)hipEventDestroy(e);
+  if (p->cov.pin) (void)hipHostFree(p->cov.pin);
   if (p->pin) (void)hipHostFree(p->pin);
   delete p;
 }
 const char* oicc_ba_last_error(const oicc_ba* p) { return p ? p->err.c_str() : "null problem"; }
 int oicc_ba_set_option(oicc_ba* p, const char* name, double value) {
-  auto it = p->opt.find(name); ARG(p, it != p->opt.end(), std::string("unknown option ") + name); it->second = value; return OICC_OK; }
+  auto it = p->opt.find(name); ARG(p, it != p->opt.end(), std::string("unknown option ") + name); it->second = value; p->cov.valid = false; return OICC_OK; }
 int oicc_ba_set_camera(oicc_ba* p, int32_t model, const double* intrinsics, int32_t n) {
   ARG(p, n > 0 && n <= kBaIntr && intrinsics, "bad intrinsics");
   p->model = model; p->n_intr = n; std::memset(p->intr, 0, sizeof(p->intr)); std::memcpy(p->intr, intrinsics, n * sizeof(double));
-  p->x_dirty = true; return OICC_OK; }
+  p->x_dirty = true; p->cov.valid = false; return OICC_OK; }
 int oicc_ba_get_camera(const oicc_ba* p, double* intrinsics, int32_t n) { std::memcpy(intrinsics, p->intr, std::min<int>(n, kBaIntr) * sizeof(double)); return OICC_OK; }
 int oicc_ba_set_scene_points(oicc_ba* p, const double* xyzw, int64_t n) {
   ARG(p, n >= 0, "bad count");
   for (size_t c = 0; c < p->pid.size(); ++c) ARG(p, p->pid[c] < n, "fewer points than the views reference");
-  p->pts.assign(xyzw, xyzw + 4 * n); p->var_pts.clear(); p->meas_dirty = true; p->x_dirty = true; return OICC_OK; }
+  p->pts.assign(xyzw, xyzw + 4 * n); p->var_pts.clear(); p->meas_dirty = true; p->x_dirty = true; p->cov.valid = false; return OICC_OK; }
 int oicc_ba_get_scene_points(const oicc_ba* p, double* xyzw, int64_t n) { std::copy(p->pts.begin(), p->pts.begin() + 4 * std::min<int64_t>(n, int64_t(p->pts.size() / 4)), xyzw); return OICC_OK; }
 int oicc_ba_set_variable_points(oicc_ba* p, const uint8_t* variable, int64_t n) {
-  ARG(p, n * 4 == int64_t(p->pts.size()), "point count mismatch"); p->var_pts.assign(variable, variable + n); return OICC_OK; }
+  ARG(p, n * 4 == int64_t(p->pts.size()), "point count mismatch"); p->var_pts.assign(variable, variable + n); p->cov.valid = false; return OICC_OK; }
 int oicc_ba_set_views(oicc_ba* p, int64_t nv, const double* pose6, const int64_t* coff, const double* uv, const int32_t* point_ids) {
   ARG(p, nv >= 0 && coff && coff[0] == 0, "bad view table");
   for (int64_t v = 0; v < nv; ++v) ARG(p, coff[v + 1] >= coff[v], "corner offsets must not decrease");
@@ -230,8 +242,8 @@ int oicc_ba_set_views(oicc_ba* p, int64_t nv, const double* pose6, const int64_t
   p->nv = nv; p->pose.assign(pose6, pose6 + 6 * nv);
   p->c0.assign(coff, coff + nv + 1); p->u.resize(nc); p->v.resize(nc); p->pid.assign(point_ids, point_ids + nc);
   for (int64_t c = 0; c < nc; ++c) { p->u[c] = uv[2 * c]; p->v[c] = uv[2 * c + 1]; }
-  p->meas_dirty = true; p->x_dirty = true; return OICC_OK; }
-int oicc_ba_set_poses(oicc_ba* p, const double* pose6, int64_t nv) { ARG(p, nv == p->nv, "view count mismatch"); p->pose.assign(pose6, pose6 + 6 * nv); p->x_dirty = true; return OICC_OK; }
+  p->meas_dirty = true; p->x_dirty = true; p->cov.valid = false; p->cov.layout_ok = false; return OICC_OK; }
+int oicc_ba_set_poses(oicc_ba* p, const double* pose6, int64_t nv) { ARG(p, nv == p->nv, "view count mismatch"); p->pose.assign(pose6, pose6 + 6 * nv); p->x_dirty = true; p->cov.valid = false; return OICC_OK; }
 int oicc_ba_get_poses(const oicc_ba* p, double* pose6, int64_t nv) { std::copy(p->pose.begin(), p->pose.begin() + 6 * std::min(nv, p->nv), pose6); return OICC_OK; }
 
 int oicc_ba_evaluate(oicc_ba* p, int32_t flags, int32_t mask, double* cost, double* H, double* g, int32_t Pcap) {
@@ -270,11 +282,134 @@ int oicc_ba_point_covariances(oicc_ba* p, double* cov9, int64_t n, double* varia
   return OICC_OK;
 }
 
+// Covariance of the intrinsics and the view poses at the current parameters: the inverse of J^T J of oicc_ba_evaluate for the same
+// flags and mask, by the view-parallel Schur complement of kernels_ba_covariance.hip.  The host sequences the launches, reads the
+// result back after ONE synchronisation and keeps the copy the getters hand out; it inverts and multiplies nothing.
+int oicc_ba_estimate_covariance(oicc_ba* p, int32_t flags, int32_t mask, oicc_ba_covariance_info* info) {
+  ARG(p, info != nullptr, "info");
+  std::memset(info, 0, sizeof(*info));
+  info->first_bad = -1;
+  p->cov.valid = false;
+  ARG(p, (flags & OICC_BA_POINTS) == 0, "OICC_BA_POINTS is not supported: oicc_ba_point_covariances handles the board points (cameras constant)");
+  Prepared P; int rc = prepare(p, flags, mask, &P); if (rc) return rc;
+  const int d = P.d.pose_dim, a = P.tl.a;
+  const int64_t nv = p->nv;
+  int64_t used = 0;
+  for (int64_t v = 0; v < nv; ++v) used += p->c0[size_t(v) + 1] > p->c0[size_t(v)] ? 1 : 0;
+  info->pose_dim = d; info->a = a; info->views_used = int32_t(used); info->P = int32_t(d * used + a);
+  info->num_residuals = 2 * int64_t(p->pid.size());
+  ARG(p, info->P > 0, "no active parameters");
+  hipStream_t st = p->stream;
+  oicc_ba::Cov& cv = p->cov;
+  if (!cv.layout_ok) {   // first chunk of every view (the chunks of sync(): 64 observations each); needed only with a view of three or more
+    cv.view_chunk0.assign(size_t(nv) + 1, 0); cv.big = false;
+    for (int64_t v = 0; v < nv; ++v) {
+      const int32_t n = int32_t((p->c0[size_t(v) + 1] - p->c0[size_t(v)] + 63) / 64);
+      cv.view_chunk0[size_t(v) + 1] = cv.view_chunk0[size_t(v)] + n; cv.big = cv.big || n >= 3;
+    }
+    if (cv.big && !p->d_cvChunk0.upload(cv.view_chunk0, st)) { p->err = "device upload failed"; return OICC_ERR_HIP; }
+    if (cv.big) HIPCK(p, hipStreamSynchronize(st));
+    cv.layout_ok = true;
+  }
+  const bool timed = p->opt["covariance_timing"] != 0;
+  cv.timed = false;
+  if (timed) { for (hipEvent_t& e : p->cov_ev) if (!e) HIPCK(p, hipEventCreate(&e)); HIPCK(p, hipEventRecord(p->cov_ev[0], st)); }
+  rc = eval_pass(p, P, p->d_x.p, true); if (rc) return rc;
+  if (timed) HIPCK(p, hipEventRecord(p->cov_ev[1], st));
+  const size_t groups = size_t((nv + kBaCovViewsPerGroup - 1) / kBaCovViewsPerGroup), nch = p->chunk_c0.size();
+  const size_t n_pose = size_t(nv) * d * d, n_cross = size_t(nv) * d * a, n_th = size_t(a) * a;
+  const bool big = cv.big && d > 0;
+  auto atl = [](size_t n) { return std::max<size_t>(n, 1); };
+  if (!p->d_cvChunkC.resize(atl(nch * n_th)) || !p->d_cvC.resize(atl(n_th)) || !p->d_cvChunkA.resize(atl(big ? nch * d * d : 0)) ||
+      !p->d_cvChunkE.resize(atl(big ? nch * d * a : 0)) || !p->d_cvSv.resize(atl(size_t(nv) * d)) ||
+      !p->d_cvAinv.resize(atl(size_t(nv) * d * (d + 1) / 2)) || !p->d_cvW.resize(atl(n_cross)) || !p->d_cvPart.resize(atl(groups * n_th)) ||
+      !p->d_cvZth.resize(atl(n_th)) || !p->d_cvTh.resize(atl(n_th)) || !p->d_cvPose.resize(atl(n_pose)) || !p->d_cvCross.resize(atl(n_cross)) ||
+      !p->d_cvRes.resize(1)) {
+    p->err = "hipMalloc covariance buffers"; return OICC_ERR_HIP; }
+  static_assert(sizeof(BaCovResult) == 2 * sizeof(double), "result words");
+  cv.o_intr = 3; cv.o_poses = cv.o_intr + n_th; cv.o_cross = cv.o_poses + n_pose;
+  const size_t pin_n = cv.o_cross + n_cross;
+  if (pin_n > cv.pin_n) {
+    if (cv.pin) (void)hipHostFree(cv.pin);
+    cv.pin = nullptr; cv.pin_n = 0;
+    HIPCK(p, hipHostMalloc(reinterpret_cast<void**>(&cv.pin), pin_n * sizeof(double), hipHostMallocDefault));
+    cv.pin_n = pin_n;
+  }
+  const BaCovBuffers cb{p->d_cvChunkC.p, p->d_cvC.p, big ? p->d_cvChunk0.p : nullptr, p->d_cvChunkA.p, p->d_cvChunkE.p, p->d_cvSv.p, p->d_cvAinv.p,
+                        p->d_cvW.p, p->d_cvPart.p, p->d_cvZth.p, p->d_cvTh.p, p->d_cvPose.p, p->d_cvCross.p, p->d_cvRes.p};
+  launch_ba_covariance(p->d_x.p, P.ne, P.d, cb, st);
+  HIPCK(p, hipGetLastError());
+  if (timed) HIPCK(p, hipEventRecord(p->cov_ev[2], st));
+  cv.d = d; cv.a = a; cv.nv = nv;
+  // read-backs into the pinned block (truly asynchronous), ONE synchronisation behind them
+  HIPCK(p, hipMemcpyAsync(cv.pin, p->d_cvRes.p, sizeof(BaCovResult), hipMemcpyDeviceToHost, st));
+  HIPCK(p, hipMemcpyAsync(cv.pin + 2, P.ne.cost(), sizeof(double), hipMemcpyDeviceToHost, st));
+  if (n_th) HIPCK(p, hipMemcpyAsync(cv.pin + cv.o_intr, p->d_cvTh.p, n_th * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (n_pose) HIPCK(p, hipMemcpyAsync(cv.pin + cv.o_poses, p->d_cvPose.p, n_pose * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (n_cross) HIPCK(p, hipMemcpyAsync(cv.pin + cv.o_cross, p->d_cvCross.p, n_cross * sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCK(p, hipStreamSynchronize(st));
+  if (timed) { for (int k = 0; k < 2; ++k) { float ms = 0; (void)hipEventElapsedTime(&ms, p->cov_ev[k], p->cov_ev[k + 1]); cv.ms[k] = ms; } cv.timed = true; }
+  BaCovResult res; std::memcpy(&res, cv.pin, sizeof(res));
+  const double cost = cv.pin[2];
+  info->cost = cost;
+  const double dof = double(info->num_residuals) - double(info->P);
+  info->variance_factor = dof > 0.0 ? 2.0 * cost / dof : std::nan("");
+  const int64_t Pb = nv * d;
+  char buf[200];
+  if (res.bad_diag < Pb + a) {
+    info->status = OICC_COV_ZERO_COLUMN;
+    info->first_bad = res.bad_diag < Pb ? int32_t(res.bad_diag / d) : int32_t(nv + (res.bad_diag - Pb));
+    std::snprintf(buf, sizeof(buf), "oicc_ba_estimate_covariance: the diagonal entry of J^T J at tangent column %d is not finite and positive", int(res.bad_diag));
+    p->err = buf; return OICC_OK;
+  }
+  const bool bad = res.bad_pivot < nv + a;
+  double zmax; std::memcpy(&zmax, &res.zmax_bits, sizeof(zmax));
+  info->rcond = (bad || !(zmax > 0.0)) ? 0.0 : 1.0 / zmax;
+  if (bad) info->first_bad = res.bad_pivot;
+  if (bad || info->rcond < p->opt["covariance_min_rcond"]) {
+    info->status = OICC_COV_RANK_DEFICIENT;
+    std::snprintf(buf, sizeof(buf), "oicc_ba_estimate_covariance: rank deficient (%s, rcond %.3e)", bad ? "a pivot is not positive" : "below covariance_min_rcond", info->rcond);
+    p->err = buf; return OICC_OK;
+  }
+  info->status = OICC_COV_OK;
+  cv.valid = true;
+  return OICC_OK;
+}
+int oicc_ba_get_covariance_intrinsics(const oicc_ba* p, double* cov, int32_t a_capacity) {
+  const oicc_ba::Cov& cv = p->cov;
+  if (!cv.valid) return OICC_ERR_STATE;
+  if (a_capacity < cv.a || (cov == nullptr && cv.a > 0)) return OICC_ERR_INVALID_ARG;
+  std::copy(cv.pin + cv.o_intr, cv.pin + cv.o_poses, cov);
+  return OICC_OK;
+}
+int oicc_ba_get_covariance_poses(const oicc_ba* p, double* blocks, int64_t nv) {
+  const oicc_ba::Cov& cv = p->cov;
+  if (!cv.valid) return OICC_ERR_STATE;
+  if (nv != cv.nv || (blocks == nullptr && cv.o_cross > cv.o_poses)) return OICC_ERR_INVALID_ARG;
+  std::copy(cv.pin + cv.o_poses, cv.pin + cv.o_cross, blocks);
+  return OICC_OK;
+}
+int oicc_ba_get_covariance_timing(const oicc_ba* p, double ms[2]) {
+  if (ms == nullptr) return OICC_ERR_INVALID_ARG;
+  if (!p->cov.timed) return OICC_ERR_STATE;   // option covariance_timing was not set for the last estimate
+  ms[0] = p->cov.ms[0]; ms[1] = p->cov.ms[1];
+  return OICC_OK;
+}
+int oicc_ba_get_covariance_pose_intrinsics(const oicc_ba* p, double* cross, int64_t nv) {
+  const oicc_ba::Cov& cv = p->cov;
+  if (!cv.valid) return OICC_ERR_STATE;
+  const size_t n_cross = size_t(cv.nv) * cv.d * cv.a;
+  if (nv != cv.nv || (cross == nullptr && n_cross > 0)) return OICC_ERR_INVALID_ARG;
+  std::copy(cv.pin + cv.o_cross, cv.pin + cv.o_cross + n_cross, cross);
+  return OICC_OK;
+}
+
 // Ceres 2.1 TrustRegionMinimizer + LevenbergMarquardtStrategy [EXT] as oicc_optimize drives it for the spline problem;
 // per LM iteration one read-back of the step state + candidate cost (problems of this path are small, the loop is not
 // pipelined).
 int oicc_ba_optimize(oicc_ba* p, int32_t max_iters, int32_t flags, int32_t mask, oicc_summary* sum) {
   const double t_start = now_s();
+  p->cov.valid = false;
   Prepared PR; int rc = prepare(p, flags, mask, &PR); if (rc) return rc;
   hipStream_t st = p->stream;
   const TangentLayout& tl = PR.tl; const NormalEq& ne = PR.ne;
@@ -380,6 +515,7 @@ int oicc_ba_get_iterations(const oicc_ba* p, oicc_iteration* out, int32_t cap) {
   const int n = std::min<int>(cap, int(p->trace.size())); std::copy(p->trace.begin(), p->trace.begin() + n, out); return n; }
 
 int oicc_ba_optimize_views(oicc_ba* p, int32_t max_iters, int32_t flags, int32_t* iterations, double* final_cost) {
+  p->cov.valid = false;
   Prepared PR; int rc = prepare(p, flags, 0, &PR); if (rc) return rc;
   ARG(p, !PR.points && PR.d.pose_dim > 0, "no pose component is variable");
   BaLmOptions o{p->opt["function_tolerance"], p->opt["parameter_tolerance"], p->opt["gradient_tolerance"], p->opt["initial_trust_region_radius"],

@@ -21,9 +21,11 @@ from . import io_files
 
 
 def estimate_poses_from_json(scene, model, intrinsics, image_height, device=0, backend=None, min_num_points=8, optimize_board_points=False,
-                             robust_init=False, ransac_backend=None, ransac_hypotheses=256):
+                             robust_init=False, ransac_backend=None, ransac_hypotheses=256, estimate_covariance=False):
     """applications/estimate_camera_poses_from_checkerboard.cc:55-70: EstimatePosesFromJson, optionally OptimizeBoardPoints +
-    OptimizeAllPoses, FilterBadPoses, GetPoseDataset.  Returns (t_s, pose6, points, per-view mean reprojection error [px])."""
+    OptimizeAllPoses, FilterBadPoses, GetPoseDataset.  Returns (t_s, pose6, points, per-view mean reprojection error [px]);
+    with estimate_covariance a fifth entry, the [n, 6] standard deviations of the kept poses (position | angle axis; None
+    when the estimate is rank deficient, which is reported and fails nothing)."""
     pe = CC.PoseEstimator(device=device, backend=backend)
     pe.EstimatePosesFromJson(scene, model, intrinsics, image_height, min_num_points=min_num_points, robust_init=robust_init,
                              ransac_backend=ransac_backend, ransac_hypotheses=ransac_hypotheses)
@@ -36,10 +38,16 @@ def estimate_poses_from_json(scene, model, intrinsics, image_height, device=0, b
         pe.OptimizeAllPoses()
     err = pe.FilterBadPoses()
     t_s, pose, points = pe.GetPoseDataset()
+    if estimate_covariance:
+        sd = pe.GetPoseStdDevs() if pe.views.pose else None
+        info = getattr(pe, "pose_covariance_info_", None)
+        if sd is None and info is not None:
+            print("Pose covariance estimate: %s (rcond %.3e), no standard deviations written" % (CC.COV_STATUS_NAMES.get(info["status"], info["status"]), info["rcond"]))
+        return t_s, pose, points, err, sd
     return t_s, pose, points, err
 
 
-def main(argv=None):
+def make_parser():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--input_corners", required=True)
     ap.add_argument("--camera_calibration_json", required=True)
@@ -47,15 +55,23 @@ def main(argv=None):
     ap.add_argument("--optimize_board_points", nargs="?", const="true", default="false")
     ap.add_argument("--robust_init", nargs="?", const="true", default="false")
     ap.add_argument("--ransac_hypotheses", type=int, default=256)
-    a = io_files.parse_reference_flags(ap, argv)
+    ap.add_argument("--estimate_covariance", nargs="?", const="true", default="false")
+    return ap
+
+
+def main(argv=None):
+    a = io_files.parse_reference_flags(make_parser(), argv)
     scene = io_files.read_scene_bson(a.input_corners)
     model, intr, w, h, _ = io_files.read_camera_calibration(a.camera_calibration_json)
-    t_s, pose, points, err = estimate_poses_from_json(scene, model, intr, h,
-                                                      optimize_board_points=str(a.optimize_board_points).lower() in ("1", "true", "yes", ""),
-                                                      robust_init=str(a.robust_init).lower() in ("1", "true", "yes", ""),
-                                                      ransac_hypotheses=a.ransac_hypotheses)
+    want_cov = str(a.estimate_covariance).lower() in ("1", "true", "yes", "")
+    res = estimate_poses_from_json(scene, model, intr, h,
+                                   optimize_board_points=str(a.optimize_board_points).lower() in ("1", "true", "yes", ""),
+                                   robust_init=str(a.robust_init).lower() in ("1", "true", "yes", ""),
+                                   ransac_hypotheses=a.ransac_hypotheses, estimate_covariance=want_cov)
+    t_s, pose, points, err = res[:4]
+    sd = res[4] if want_cov else None
     print("Estimated %d camera poses, mean reprojection error %.4f px" % (len(t_s), float(np.mean(err)) if len(err) else float("nan")))
-    io_files.write_pose_dataset(a.output_pose_dataset, t_s, pose, points, sorted(io_files.scene_points(scene)))
+    io_files.write_pose_dataset(a.output_pose_dataset, t_s, pose, points, sorted(io_files.scene_points(scene)), pose_std_dev=sd)
     io_files.write_ply_cameras(a.output_pose_dataset + ".ply", pose, points)
     return 0
 

@@ -185,15 +185,19 @@ _INTR_KEYS = {
 }
 
 
-def write_camera_calibration(path, model, intrinsics, image_width, image_height, fps, nr_calib_images, total_reproj_error):
+def write_camera_calibration(path, model, intrinsics, image_width, image_height, fps, nr_calib_images, total_reproj_error,
+                             intrinsics_covariance=None):
     """io::write_camera_calibration, src/io/write_camera_calibration.cc:34-140: same keys.  (The reference writes the
     PINHOLE model without its two radial terms and every model with skew 0; the radial terms are added here so that the
-    file reproduces the calibrated camera.)"""
+    file reproduces the calibrated camera.)  intrinsics_covariance (CameraCalibrator.GetIntrinsicsCovarianceObject:
+    parameters, std_dev, correlation, variance_factor, rcond) is added as one more object; without it the file is unchanged."""
     keys = _INTR_KEYS[model]
     intr = {k: float(v) for k, v in zip(keys, intrinsics)}
     intr["skew"] = 0.0
     obj = dict(stabelized=False, fps=float(fps), nr_calib_images=int(nr_calib_images), final_reproj_error=float(total_reproj_error),
                image_width=int(image_width), image_height=int(image_height), intrinsic_type=MODEL_NAMES[model], intrinsics=intr)
+    if intrinsics_covariance is not None:
+        obj["intrinsics_covariance"] = intrinsics_covariance
     json.dump(obj, open(path, "w"), indent=2)
     return True
 
@@ -215,11 +219,16 @@ def pose_view_name(t_s):
     return str(k + 1 if us - k > 1.0 - 1e-5 else k)
 
 
-def write_pose_dataset(path, t_s, pose6, points, point_ids=None):
+def write_pose_dataset(path, t_s, pose6, points, point_ids=None, pose_std_dev=None):
     """JSON twin of theia::WriteReconstruction for a pose data set (the file continuous_time_imu_to_camera_calibration
-    reads with --input_pose_dataset); tracks carry the corner file's point ids (TrackId = stoi(key), read_scene.cc:47-49)."""
+    reads with --input_pose_dataset); tracks carry the corner file's point ids (TrackId = stoi(key), read_scene.cc:47-49).
+    pose_std_dev ([n, 6], position | angle axis) adds position_std_dev and angle_axis_std_dev to every view; without it the
+    file is unchanged."""
     views = {pose_view_name(t): dict(orientation_angle_axis=[float(x) for x in p[3:]], position=[float(x) for x in p[:3]])
              for t, p in zip(t_s, pose6)}
+    if pose_std_dev is not None:
+        for t, sd in zip(t_s, pose_std_dev):
+            views[pose_view_name(t)].update(position_std_dev=[float(x) for x in sd[:3]], angle_axis_std_dev=[float(x) for x in sd[3:]])
     ids = list(range(len(points))) if point_ids is None else [int(i) for i in point_ids]
     json.dump(dict(views=views, tracks={str(ids[i]): [float(x) for x in points[i]] for i in range(len(points))}), open(path, "w"))
 
