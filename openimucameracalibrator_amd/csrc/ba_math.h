@@ -50,10 +50,10 @@ OICC_DEV void camera_intrinsics_jacobian(int model, const double* in, const doub
     double sc = 1.0, dsc_dr2 = 0.0, dsc_dk = 0.0;
     if (!(fabs(denom) < 2.220446049250313e-16 || inner < 0.0)) {
       const double sq = sqrt(inner);
-      sc = (1.0 - sq) / denom;
-      // sc = h(m), m = k r2:  h'(m) = (2 m / sq - (1 - sq)) / (2 m^2)
-      const double m = k * r2;
-      const double hp = (2.0 * m / sq - (1.0 - sq)) / (2.0 * m * m);
+      // sc = h(m) = 2 / (1 + sq), m = k r2 (the cancellation-free form of camera_project):  h'(m) = 4 / (sq (1 + sq)^2)
+      const double sp = 1.0 + sq;
+      sc = 2.0 / sp;
+      const double hp = 4.0 / (sq * sp * sp);
       dsc_dr2 = k * hp; dsc_dk = r2 * hp;
     }
     const double dr2_df = 2.0 * (ux * nx + uy * as * ny), dr2_da = 2.0 * uy * f * ny;

@@ -611,9 +611,10 @@ OICC_DEV bool camera_project(int model, const double* in, const double p[3], dou
       if (fabs(denom) < 2.220446049250313e-16 || inner < 0.0) { sc = 1.0; dsc = 0.0; }
       else {
         const double sq = sqrt(inner);
-        sc = (1.0 - sq) / denom;
-        // d/dr2 [(1 - sqrt(1-4k r2)) / (2k r2)] = (2k/sq * 2k r2 - (1-sq) 2k) / (2k r2)^2
-        dsc = ((2.0 * k / sq) * denom - (1.0 - sq) * 2.0 * k) / (denom * denom);
+        // (1 - sq) / (2 k r2) = 2 / (1 + sq): the reference's literal quotient cancels for small k r2 (camera models)
+        const double sp = 1.0 + sq;
+        sc = 2.0 / sp;
+        dsc = 4.0 * k / (sq * sp * sp);   // d sc / d r2
       }
       px[0] = ux * sc + in[2];
       px[1] = uy * sc + in[3];

@@ -148,7 +148,7 @@ def test_run_calibration_matches_oracle_and_truth(camera):
     assert g.TotalReprojectionError() < 0.4
 
 
-@pytest.mark.parametrize("flags", [POSE, CC.BA_POSITION])
+@pytest.mark.parametrize("flags", [POSE, CC.BA_POSITION, CC.BA_ORIENTATION])
 def test_optimize_views_one_launch_matches_per_view_oracle(flags):
     """PoseEstimator::OptimizeAllPoses: every view's own LM loop inside one kernel launch; iteration counts, final
     costs and poses as the oracle's per-view loops."""
