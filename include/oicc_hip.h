@@ -842,6 +842,15 @@ int oicc_planar_ransac(int32_t device_ordinal, int32_t num_views, const int64_t*
  * left at the end, the slot behind the last level's couplings, the slots the solver's workspace reserves.
  * Returns the number of levels (= inversions in sequence - 1), OICC_ERR_INVALID_ARG for n < 1 or too small a cap_levels. */
 int oicc_debug_bcr_plan(int32_t n, int32_t ghost, int32_t odd_only, int64_t* levels, int32_t cap_levels, int64_t info[3]);
+/* Which levels of that plan the solver runs as ONE launch -- every workgroup of a pivot inverts it itself and goes on with its Schur
+ * group -- instead of an inversion launch and a Schur launch (the solver's own rule, host arithmetic only).  joined [cap_levels] = 1 / 0
+ * per level.  A level is joined when join_levels != 0 (option bcr_join_levels), the solve is the whole band (ghost == 0, b0 == 0: the
+ * first block of a rank's range; no carried coupling), its inversions are not part of the build launch (level 0 when build_inverts
+ * != 0; build_inverts < 0: as the solver decides for n blocks) and pivots x (12 + 3 rtf) <= budget (rtf: 16-row tiles of the arrow
+ * rows + right-hand side, 1..4; budget: option bcr_join_max_workgroups, or the device's compute units).
+ * Returns the number of levels, OICC_ERR_INVALID_ARG as above or for rtf, budget, b0 out of range. */
+int oicc_debug_bcr_join_plan(int32_t n, int32_t ghost, int32_t odd_only, int32_t b0, int32_t rtf, int32_t join_levels, int32_t budget,
+                             int32_t build_inverts, int32_t* joined, int32_t cap_levels);
 
 #ifdef __cplusplus
 }

@@ -359,6 +359,7 @@ class BoundBoard:
 # its own like ALLAN_SIGNATURES.
 BCR_PLAN_SIGNATURES = {
     "plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_i64p, C.c_int32, c_i64p]),
+    "join_plan": (C.c_int, [C.c_int32] * 8 + [c_i32p, C.c_int32]),   # which levels run as one launch (oicc_debug_bcr_join_plan)
 }
 
 

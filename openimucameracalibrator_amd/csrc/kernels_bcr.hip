@@ -191,6 +191,8 @@ __device__ __forceinline__ void bcr_corner_solve(double* C, double* da, int* fai
 //                        the neighbours, their coupling, the arrow rows and the corner
 //   bcri_backward_kernel x_i = T_rhs - T_left^T x_il - T_right^T x_ir - T_arrow^T x_arrow: a matrix-vector product, no
 //                        triangular solve on the way back
+//   bcri_invert_schur_kernel   the first two in ONE launch where a level's Schur workgroups fit the chip at once (bcr_level_joined):
+//                        every workgroup of a pivot inverts D_i itself, Z_i stays in its LDS
 // Error: forward errors of B D^-1 B^T through the explicit inverse and through the Cholesky factor are both
 // O(cond(D_i) eps); the LM tests hold both to the oracle's steps.
 // =====================================================================================================================
@@ -219,8 +221,9 @@ __device__ __forceinline__ bcr_v4d bcri_z_tile(const double* W, int yt, int li, 
 }
 
 // What follows the factorisation of [D_i ; I] (all waves, after a workgroup barrier): Z = X X^T, and for the last block (LAST) the arrow
-// corner and the first back substitution.
-template <bool LAST>
+// corner and the first back substitution.  ZLDS: Z stays in LDS as it does for LAST (rows 0..63 of W) and is not stored -- the
+// workgroup goes on with a Schur group of its pivot (bcri_invert_schur_kernel).
+template <bool LAST, bool ZLDS>
 __device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* da, int* failp, const double* Fs, double* Zg, int tid, int wave, int lane, bool report,
                                           const double (&ttop)[16], const double ytop, double* x0s) {
   constexpr int LD = kInvLD, NW = kInvWaves, NT = 64 * NW, FLD = 65;
@@ -233,7 +236,7 @@ __device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* d
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int x = 16 * xt + li, y = 16 * yt + lq + 4 * r;
-      if (LAST) { W[y * LD + x] = g[r]; if (xt != yt) W[x * LD + y] = g[r]; }
+      if (LAST || ZLDS) { W[y * LD + x] = g[r]; if (xt != yt) W[x * LD + y] = g[r]; }
       else { Zg[y * 64 + x] = g[r]; if (xt != yt) Zg[x * 64 + y] = g[r]; }
     }
   }
@@ -328,8 +331,12 @@ __device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* d
 
 // LAST: the block left after the last level -- the inverse stays in LDS, T = F Z, the arrow corner minus T F^T, its solution and
 // x = T_rhs - T_arrow^T x_arrow, all in this workgroup
-template <bool LAST, bool PROF, class LoadD>
-__device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, LoadD load_d, const bool report = true) {
+// park (bcri_invert_schur_kernel): called once by every thread between the LDS fill of D_i and the first barrier -- the global loads
+// the caller issued before this function have landed with D_i's by then (one round trip for both), and what it writes behind `Fs`
+// is visible after the factorisation
+struct BcrNoPark { __device__ __forceinline__ void operator()(double*) const {} };
+template <bool LAST, bool PROF, bool ZLDS = false, class LoadD, class Park = BcrNoPark>
+__device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, LoadD load_d, const bool report = true, Park park = Park()) {
   constexpr int LD = kInvLD, NW = kInvWaves, NT = 64 * NW, NTILE = 20, SLOTS = (NTILE + NW - 1) / NW, RU = 128, NAW = 3, FLD = 65;
   static_assert(NW == 16, "the corner phases of block 0 take one tile per wave");
   extern __shared__ double lds[];
@@ -340,7 +347,7 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
   double* const da = W + 64 * LD;        // [64] arrow solution (LAST)
   int* const failp = reinterpret_cast<int*>(da + 64);
   double* const dg = da + 64 + 8;        // [16][16] copy of the current panel's diagonal tile (column major; see bcr_eliminate_kernel)
-  double* const Fs = dg + 256;           // LAST: [64][FLD] border rows of block 0, Fs[k * FLD + q]
+  double* const Fs = dg + 256;           // LAST: [64][FLD] border rows of block 0, Fs[k * FLD + q]; ZLDS: the caller's parked border tiles and Ts
   const int a1 = A.a + 1;
   double* Zg = A.Lf + (int64_t)i * (192 + a1) * 64;
   const double* Fg = A.F + (int64_t)i * 64 * a1;
@@ -387,6 +394,7 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
       W[c * LD + 64 + r] = r == c ? 1.0 : 0.0;
       if (LAST) Fs[c * FLD + r] = gf[k];
     }
+    park(Fs);
   }
   __syncthreads();
   // ---- static tile ownership: tiles 0..9 the lower triangle of D_i, 10..19 the upper triangle of X (X(r, c) = 0 for c < r)
@@ -475,7 +483,7 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
     BCR_MARK(4);
   }
   BCR_MARK(4);
-  bcri_tail<LAST>(A, W, da, failp, Fs, Zg, tid, wave, lane, report, ttop, ytop, dg);
+  bcri_tail<LAST, ZLDS>(A, W, da, failp, Fs, Zg, tid, wave, lane, report, ttop, ytop, dg);
   BCR_MARK(5);
   if (PROF && prof && lane == 0) for (int k = 0; k < 8; ++k) A.prof[k] = pc[k];
 #undef BCR_MARK
@@ -490,81 +498,97 @@ __global__ __launch_bounds__(64 * kInvWaves) void bcri_invert_kernel(BcrArgs A) 
   bcri_invert_body<LAST, PROF>(A, i, [Dg, Sd](int e) { double v = Dg[e]; if (LAST && Sd != nullptr && (e & 63) >= (e >> 6)) v += Sd[e]; return v; });
 }
 
-// one workgroup (4 waves) per (pivot, 16-row tile x of the border rows, group of up to four column tiles y)
-__global__ __launch_bounds__(256) void bcri_schur_kernel(BcrArgs A) {
-  BCR_RETURN_IF_DONE(A);
-  __shared__ double Ts[16][68];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+// ---- one Schur group of a pivot: (16-row tile x of the border rows, up to four column tiles y) ----
+// Run by bcri_schur_kernel (one workgroup of 4 waves per group, Z_i read from global memory, where bcri_invert_kernel left it) and by
+// bcri_invert_schur_kernel (every workgroup of a pivot inverts D_i itself and takes Z_i from its LDS): the same decoding, the same
+// MFMA sequence on the same operand values, the same stores and atomics -- only where the operands are read differs (`Ops` below).
+struct BcrSchurGroup {
+  int k, i, irs;                 // position among the active blocks, block, where the right neighbour's D / F live
+  bool hasL, hasR, ghostR;       // (a pivot at position 0 -- odd number of active blocks -- has no left neighbour; ghostR: the right neighbour is the next rank's first block)
+  int xk, xt, yk, ny;            // row tile (kind xk: 0 left, 1 right, 2 arrow rows / rhs; index xt), column tiles (kind yk, ny of them)
+  bool store_t;                  // this group stores its rows of T
+  bool leaves;                   // the pivot has no neighbour on a side the group works on
+};
+__device__ __forceinline__ BcrSchurGroup bcri_schur_group(const BcrArgs& A, int g, int piv) {
+  BcrSchurGroup G;
+  const int rtf = A.rtf;
+  G.k = 2 * piv + A.p;
+  G.i = A.o + G.k * A.s;
+  G.hasL = G.k > 0;
+  G.ghostR = A.ghost != 0 && G.k == A.m - 1;
+  G.hasR = G.k < A.m - 1 || G.ghostR;
+  G.irs = G.ghostR ? A.n : G.i + A.s;
+  if (g < 4) { G.xk = 0; G.xt = g; G.yk = 0; G.ny = g + 1; G.store_t = true; }
+  else if (g < 8) { G.xk = 1; G.xt = g - 4; G.yk = 0; G.ny = 4; G.store_t = false; }
+  else if (g < 12) { G.xk = 1; G.xt = g - 8; G.yk = 1; G.ny = G.xt + 1; G.store_t = true; }
+  else { g -= 12; G.yk = g / rtf; G.xt = g - G.yk * rtf; G.xk = 2; G.ny = G.yk < 2 ? 4 : G.xt + 1; G.store_t = G.yk == (G.hasL ? 0 : 1); }   // (the arrow rows of T: once per pivot)
+  G.leaves = ((G.xk == 1 || G.yk == 1) && !G.hasR) || ((G.xk == 0 || G.yk == 0) && !G.hasL);
+  return G;
+}
+// The three MFMA operands of a group, element kk of a lane's sixteen: B_x (row 16 xt + li, pivot variable 4 kk + lq), Z (column
+// 16 wave + li, the same variable), B_y (row 16 wave + li, the same variable).  From global memory ...
+struct BcrSchurGlobalOps {
+  static constexpr bool kLateY = false;   // (B_y is in flight with B_x and Z: one global round trip)
+  const double *px, *pz, *py; int sx, sy; bool okx, oky;
+  __device__ __forceinline__ double x(int kk) const { return px[4 * kk * sx]; }
+  __device__ __forceinline__ double z(int kk) const { return pz[4 * kk * 64]; }
+  __device__ __forceinline__ double y(int kk) const { return oky ? py[4 * kk * sy] : 0.0; }
+};
+// ... or from LDS: Z in rows 0..63 of the inversion's W (bcri_tail<., ZLDS>), the border tiles parked as [pivot variable][16 rows]
+// with zeros where a row lies beyond the arrow (bcri_invert_schur_kernel)
+struct BcrSchurLdsOps {
+  static constexpr bool kLateY = true;    // (an LDS read: B_y is loaded behind T, 32 registers fewer where 1024 threads leave 128)
+  const double *px, *pz, *py; bool okx;
+  __device__ __forceinline__ double x(int kk) const { return px[64 * kk]; }
+  __device__ __forceinline__ double z(int kk) const { return pz[4 * kk * kInvLD]; }
+  __device__ __forceinline__ double y(int kk) const { return py[64 * kk]; }
+};
+// Called by every thread of the workgroup (one barrier inside); `active`: this wave is one of the group's four, `wave` its index among them.
+template <class Ops>
+__device__ __forceinline__ void bcri_schur_body(const BcrArgs& A, const BcrSchurGroup& G, double (*Ts)[68], const Ops& ops, const bool active, const int wave, const int lane) {
   const int li = lane & 15, lq = lane >> 4;
-  const int a1 = A.a + 1, rtf = A.rtf, s = A.s;
-  if ((int)blockIdx.y == (int)gridDim.y - 1 && A.carry > 0) {
-    // distributed reduction, odd number of active blocks: the last one is no pivot at this level, its coupling to the ghost block
-    // moves on to the next level's table unchanged (the workgroups of this extra row of the grid copy it)
-    const int m = A.carry;
-    const double* src = A.S + (A.offS_in + (m - 1)) * 4096; double* dst = A.S + (A.offS_out + (m - 1) / 2) * 4096;
-    for (int e = (int)blockIdx.x * 256 + tid; e < 4096; e += (int)gridDim.x * 256) dst[e] = src[e];
-    return;
-  }
-  const int k = 2 * (int)blockIdx.y + A.p;          // position among the active blocks
-  const int i = A.o + k * s, il = i - s, ir = i + s;
-  const bool hasL = k > 0;                          // (a pivot at position 0 -- odd number of active blocks -- has no left neighbour)
-  const bool ghostR = A.ghost != 0 && k == A.m - 1; // the right neighbour is the next rank's first block
-  const bool hasR = k < A.m - 1 || ghostR;
-  const int irs = ghostR ? A.n : ir;                // where the right neighbour's D / F live
-  // group -> row tile (kind xk: 0 left, 1 right, 2 arrow rows / rhs; index xt), column tiles (kind yk, ny of them), and who stores T
-  int g = (int)blockIdx.x, xk, xt, yk, ny; bool store_t;
-  if (g < 4) { xk = 0; xt = g; yk = 0; ny = g + 1; store_t = true; }
-  else if (g < 8) { xk = 1; xt = g - 4; yk = 0; ny = 4; store_t = false; }
-  else if (g < 12) { xk = 1; xt = g - 8; yk = 1; ny = xt + 1; store_t = true; }
-  else { g -= 12; yk = g / rtf; xt = g - yk * rtf; xk = 2; ny = yk < 2 ? 4 : xt + 1; store_t = yk == (hasL ? 0 : 1); }   // (the arrow rows of T: once per pivot)
-  if ((xk == 1 || yk == 1) && !hasR) return;
-  if ((xk == 0 || yk == 0) && !hasL) return;
-  const double* SL = A.S + (A.offS_in + (hasL ? k - 1 : 0)) * 4096;
-  const double* SR = A.S + (A.offS_in + k) * 4096;
-  const double* Fg = A.F + (int64_t)i * 64 * a1;
-  double* Zg = A.Lf + (int64_t)i * (192 + a1) * 64;
-  double* Tg = Zg + 4096;
-  // border rows as MFMA operands: element (row 16 t + li, pivot variable k = 4 kk + lq)
-  auto border_ptr = [&](int kind, int t, int& stride, bool& ok) -> const double* {
-    if (kind == 0) { stride = 64; ok = true; return SL + lq * 64 + 16 * t + li; }
-    if (kind == 1) { stride = 64; ok = true; return SR + lq * 64 + 16 * t + li; }
-    const int q = 16 * t + li; ok = q < a1; stride = a1; return Fg + lq * a1 + (ok ? q : 0);
-  };
-  int sx, sy; bool okx, oky;
-  const double* px = border_ptr(xk, xt, sx, okx);
-  const double* py = border_ptr(yk, wave < ny ? wave : 0, sy, oky);
-  const double* pz = Zg + lq * 64 + 16 * wave + li;
+  const int a1 = A.a + 1, s = A.s;
+  const int k = G.k, i = G.i, il = i - s, irs = G.irs, xk = G.xk, xt = G.xt, yk = G.yk, ny = G.ny;
+  const bool hasL = G.hasL, ghostR = G.ghostR, store_t = G.store_t, okx = ops.okx;
+  double* Tg = A.Lf + (int64_t)i * (192 + a1) * 64 + 4096;
   double vx[16], vz[16], vy[16];
+  if (active) {
 #pragma unroll
-  for (int kk = 0; kk < 16; ++kk) { vx[kk] = px[4 * kk * sx]; vz[kk] = pz[4 * kk * 64]; }
+    for (int kk = 0; kk < 16; ++kk) { vx[kk] = ops.x(kk); vz[kk] = ops.z(kk); }
+    if (!Ops::kLateY) {
 #pragma unroll
-  for (int kk = 0; kk < 16; ++kk) vy[kk] = oky ? py[4 * kk * sy] : 0.0;
-  asm volatile("" ::: "memory");   // (every load above is issued before the first MFMA)
-  // T(x rows, columns 16 wave ..) = B_x Z: two accumulators, the dependent chain is 8 MFMAs
-  bcr_v4d tq = {0.0, 0.0, 0.0, 0.0}, tq2 = {0.0, 0.0, 0.0, 0.0};
+      for (int kk = 0; kk < 16; ++kk) vy[kk] = ops.y(kk);
+    }
+    asm volatile("" ::: "memory");   // (every load above is issued before the first MFMA)
+    // T(x rows, columns 16 wave ..) = B_x Z: two accumulators, the dependent chain is 8 MFMAs
+    bcr_v4d tq = {0.0, 0.0, 0.0, 0.0}, tq2 = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-  for (int kk = 0; kk < 16; kk += 2) {
-    tq = __builtin_amdgcn_mfma_f64_16x16x4f64(okx ? vx[kk] : 0.0, vz[kk], tq, 0, 0, 0);
-    tq2 = __builtin_amdgcn_mfma_f64_16x16x4f64(okx ? vx[kk + 1] : 0.0, vz[kk + 1], tq2, 0, 0, 0);
-  }
-  tq += tq2;
-  // tq[r] <-> (column 16 wave + li, row lq + 4 r of the tile)
-  const int trow0 = xk == 0 ? 16 * xt : (xk == 1 ? 64 + 16 * xt : 128 + 16 * xt);
+    for (int kk = 0; kk < 16; kk += 2) {
+      tq = __builtin_amdgcn_mfma_f64_16x16x4f64(okx ? vx[kk] : 0.0, vz[kk], tq, 0, 0, 0);
+      tq2 = __builtin_amdgcn_mfma_f64_16x16x4f64(okx ? vx[kk + 1] : 0.0, vz[kk + 1], tq2, 0, 0, 0);
+    }
+    tq += tq2;
+    // tq[r] <-> (column 16 wave + li, row lq + 4 r of the tile)
+    const int trow0 = xk == 0 ? 16 * xt : (xk == 1 ? 64 + 16 * xt : 128 + 16 * xt);
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int row = lq + 4 * r;
-    Ts[row][16 * wave + li] = tq[r];
-    if (store_t && (xk != 2 || 16 * xt + row < a1)) Tg[(int64_t)(trow0 + row) * 64 + 16 * wave + li] = tq[r];
+    for (int r = 0; r < 4; ++r) {
+      const int row = lq + 4 * r;
+      Ts[row][16 * wave + li] = tq[r];
+      if (store_t && (xk != 2 || 16 * xt + row < a1)) Tg[(int64_t)(trow0 + row) * 64 + 16 * wave + li] = tq[r];
+    }
   }
   __syncthreads();
-  if (wave >= ny) return;
+  if (!active || wave >= ny) return;
   const int yt = wave;
   // orientation of the new coupling (il, ir): il is at position kn of the next level, whose pivots have parity pn
   const int kn = hasL ? (k - 2 + A.p) / 2 : 0;
   const bool il_is_pivot = (kn & 1) == A.pn;
   const bool swap = xk == 1 && yk == 0 && !il_is_pivot && !ghostR;
   double vt[16];
+  if (Ops::kLateY) {
+#pragma unroll
+    for (int kk = 0; kk < 16; ++kk) vy[kk] = ops.y(kk);
+  }
 #pragma unroll
   for (int kk = 0; kk < 16; ++kk) vt[kk] = Ts[li][4 * kk + lq];
   asm volatile("" ::: "memory");   // (every load above is issued before the first MFMA)
@@ -614,6 +638,94 @@ __global__ __launch_bounds__(256) void bcri_schur_kernel(BcrArgs A) {
       }
     }
   }
+}
+
+// one workgroup (4 waves) per (pivot, group): Z_i from global memory
+__global__ __launch_bounds__(256) void bcri_schur_kernel(BcrArgs A) {
+  BCR_RETURN_IF_DONE(A);
+  __shared__ double Ts[16][68];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lq = lane >> 4;
+  const int a1 = A.a + 1;
+  if ((int)blockIdx.y == (int)gridDim.y - 1 && A.carry > 0) {
+    // distributed reduction, odd number of active blocks: the last one is no pivot at this level, its coupling to the ghost block
+    // moves on to the next level's table unchanged (the workgroups of this extra row of the grid copy it)
+    const int m = A.carry;
+    const double* src = A.S + (A.offS_in + (m - 1)) * 4096; double* dst = A.S + (A.offS_out + (m - 1) / 2) * 4096;
+    for (int e = (int)blockIdx.x * 256 + tid; e < 4096; e += (int)gridDim.x * 256) dst[e] = src[e];
+    return;
+  }
+  const BcrSchurGroup G = bcri_schur_group(A, (int)blockIdx.x, (int)blockIdx.y);
+  if (G.leaves) return;
+  const double* SL = A.S + (A.offS_in + (G.hasL ? G.k - 1 : 0)) * 4096;
+  const double* SR = A.S + (A.offS_in + G.k) * 4096;
+  const double* Fg = A.F + (int64_t)G.i * 64 * a1;
+  const double* Zg = A.Lf + (int64_t)G.i * (192 + a1) * 64;
+  // border rows as MFMA operands: element (row 16 t + li, pivot variable k = 4 kk + lq)
+  auto border_ptr = [&](int kind, int t, int& stride, bool& ok) -> const double* {
+    if (kind == 0) { stride = 64; ok = true; return SL + lq * 64 + 16 * t + li; }
+    if (kind == 1) { stride = 64; ok = true; return SR + lq * 64 + 16 * t + li; }
+    const int q = 16 * t + li; ok = q < a1; stride = a1; return Fg + lq * a1 + (ok ? q : 0);
+  };
+  BcrSchurGlobalOps ops;
+  ops.px = border_ptr(G.xk, G.xt, ops.sx, ops.okx);
+  ops.py = border_ptr(G.yk, wave < G.ny ? wave : 0, ops.sy, ops.oky);
+  ops.pz = Zg + lq * 64 + 16 * wave + li;
+  bcri_schur_body(A, G, Ts, ops, true, wave, lane);
+}
+
+// A level in ONE launch: grid (12 + 3 rtf groups, pivots of the level), 16 waves.  EVERY workgroup of a pivot inverts D_i itself --
+// the inversion is deterministic, all copies of Z_i are the same bits -- and then runs its Schur group with Z_i in its own LDS: no
+// store of Z, no second launch, nothing handed from one workgroup to another (no flag, no poll, no wait).  The group's border tiles
+// (one of B_x, up to four of B_y) do not depend on Z_i: their loads are issued with D_i's and parked in LDS behind the inversion's
+// arrays, so no global round trip stands behind the inversion.  Groups of a side the pivot has no neighbour on leave at once.  For
+// levels whose workgroups fit the chip at once (bcr_level_joined); level 0 is not among them while its inversions ride in the build
+// launch, whose workgroups still write the blocks the Schur updates land on.
+constexpr int kInvLdsDoubles = 64 * kInvLD + 64 + 8 + 256;                 // W, da, failp, dg of bcri_invert_body
+constexpr int kJoinLdsDoubles = kInvLdsDoubles + 5 * 1024 + 16 * 68;       // + B_x tile, four B_y tiles ([64][16] each), Ts
+__global__ __launch_bounds__(64 * kInvWaves) void bcri_invert_schur_kernel(BcrArgs A) {
+  BCR_RETURN_IF_DONE(A);
+  const BcrSchurGroup G = bcri_schur_group(A, (int)blockIdx.x, (int)blockIdx.y);
+  if (G.leaves) return;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int li = lane & 15, lq = lane >> 4;
+  const int a1 = A.a + 1;
+  const double* SL = A.S + (A.offS_in + (G.hasL ? G.k - 1 : 0)) * 4096;
+  const double* SR = A.S + (A.offS_in + G.k) * 4096;
+  const double* Fg = A.F + (int64_t)G.i * 64 * a1;
+  // thread -> element (pivot variable kv, row l of a 16-row tile) of each parked tile
+  const int kv = tid >> 4, l = tid & 15;
+  auto border_at = [&](int kind, int t) -> double {
+    if (kind == 0) return SL[kv * 64 + 16 * t + l];
+    if (kind == 1) return SR[kv * 64 + 16 * t + l];
+    const int q = 16 * t + l; return q < a1 ? Fg[kv * a1 + q] : 0.0;
+  };
+  double bx = border_at(G.xk, G.xt), by[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) by[t] = t < G.ny ? border_at(G.yk, t) : 0.0;
+  asm volatile("" ::: "memory");   // (issued here, with D_i's loads; parked in LDS before the first barrier of the inversion)
+  const double* Dg = A.D + (int64_t)G.i * 4096;
+  const bool report = (int)blockIdx.x == (G.hasL ? 0 : 8);   // the pivot's first group that does not leave (left x left, or right x right)
+  bcri_invert_body<false, false, true>(A, G.i, [Dg](int e) { return Dg[e]; }, report,
+    [&](double* P) {
+      P[tid] = bx;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) P[1024 * (1 + t) + tid] = by[t];
+    });
+  // (bcri_tail ended with a workgroup barrier: Z_i is in rows 0..63 of W, the parked tiles are visible)
+  extern __shared__ double lds[];
+  const double* W = lds;
+  const double* P = lds + kInvLdsDoubles;
+  double (*Ts)[68] = reinterpret_cast<double (*)[68]>(lds + kInvLdsDoubles + 5 * 1024);
+  const bool active = wave < 4;
+  BcrSchurLdsOps ops;
+  ops.okx = true;   // (rows beyond the arrow were parked as zeros)
+  ops.px = P + lq * 16 + li;
+  ops.py = P + 1024 * (1 + (active && wave < G.ny ? wave : 0)) + lq * 16 + li;
+  ops.pz = W + lq * kInvLD + 16 * (active ? wave : 0) + li;
+  bcri_schur_body(A, G, Ts, ops, active, wave, lane);
 }
 
 // ---- the retraction inside the LAST launch of a whole-band solve (lm_retract.h; used by the two-level back-substitution kernel) ----
@@ -1010,7 +1122,7 @@ static void bcr_allow_lds(const void* fn, size_t bytes) {
 
 
 static inline int bcr_blocks(int Pb) { return (Pb + 63) / 64; }
-static size_t bcr_lds_inv() { return ((size_t)64 * kInvLD + 64 + 8 + 256) * sizeof(double); }
+static size_t bcr_lds_inv() { return (size_t)kInvLdsDoubles * sizeof(double); }
 static int64_t bcr_coupling_slots(int nblk) { return 2 * (int64_t)nblk + 40; }   // the coupling tables of all levels (sum of active - 1 + ghost < 2 nblk) and of the one behind them
 static void bcr_carve(BcrArgs& A, double* w, int nblk, int a1) {   // nblk: blocks incl. a ghost
   A.D = w; w += (int64_t)nblk * 4096;
@@ -1081,22 +1193,42 @@ static bool bcr_launch_build(const NormalEq& ne, const TangentLayout& tl, const 
   }
   return fused_build;
 }
-// forward levels while more than one (local) block is active: inversions of the pivots, Schur complements onto their neighbours
-static void bcr_launch_forward(BcrArgs A, bool level0_inverted, const BcrLevels& L, hipStream_t st) {
+// Which levels run as ONE launch (bcri_invert_schur_kernel) instead of an inversion launch and a Schur launch: THE rule, host
+// arithmetic only (exported as oicc_debug_bcr_join_plan).  A level is joined when the option is on, no phase clocks are asked for,
+// the solve is the whole band (the distributed reduction -- ghost block, block offset, carried coupling -- keeps its launches), the
+// level's inversions are not already part of the build launch, and its pivots x groups fit the workgroup budget (default: one per
+// compute unit): every workgroup of a pivot repeats the inversion, which costs nothing on compute units that would idle and
+// everything on a level that is throughput bound.
+struct BcrJoin { int on = 0; int budget = 0; };
+static bool bcr_level_joined(const BcrJoin& J, bool prof, int ghost, int b0, bool carry, bool in_build, int npiv, int rtf) {
+  return J.on != 0 && !prof && ghost == 0 && b0 == 0 && !carry && !in_build && (int64_t)npiv * (12 + 3 * rtf) <= (int64_t)J.budget;
+}
+// forward levels while more than one (local) block is active: inversions of the pivots, Schur complements onto their neighbours;
+// returns the number of joined levels
+static int bcr_launch_forward(BcrArgs A, bool level0_inverted, const BcrLevels& L, hipStream_t st, const BcrJoin& J = BcrJoin()) {
   using KernelFn = void (*)(BcrArgs);
   KernelFn k_inv = A.prof ? bcri_invert_kernel<false, true> : bcri_invert_kernel<false, false>;
   bcr_allow_lds(reinterpret_cast<const void*>(k_inv), bcr_lds_inv());
   const int g = A.ghost != 0 ? 1 : 0;
+  int joined = 0;
   for (int l = 0; l < L.nlev; ++l) {
     const int m = L.active[l], npiv = L.npivs[l];
     bcr_set_level(A, L, l);
     A.side = (l == L.nlev - 1 && L.parity[l] == 0) ? 1 : 0;   // (the top level with two pivots)
     const bool carry = g != 0 && (m & 1) != 0;   // the last active block is no pivot: its coupling to the ghost block moves on unchanged
     A.carry = carry ? m : 0;
+    if (bcr_level_joined(J, A.prof != nullptr, A.ghost, A.b0, carry, level0_inverted && l == 0, npiv, A.rtf)) {
+      const size_t lds_join = (size_t)kJoinLdsDoubles * sizeof(double);
+      bcr_allow_lds(reinterpret_cast<const void*>(bcri_invert_schur_kernel), lds_join);
+      hipLaunchKernelGGL(bcri_invert_schur_kernel, dim3(12 + 3 * A.rtf, npiv), dim3(64 * kInvWaves), lds_join, st, A);
+      ++joined;
+      continue;
+    }
     BcrArgs Ai = A; if (l != 0) Ai.prof = nullptr;
     if (!(level0_inverted && l == 0)) hipLaunchKernelGGL(k_inv, dim3(npiv), dim3(64 * kInvWaves), bcr_lds_inv(), st, Ai);
     hipLaunchKernelGGL(bcri_schur_kernel, dim3(12 + 3 * A.rtf, npiv + (carry ? 1 : 0)), dim3(256), 0, st, A);
   }
+  return joined;
 }
 // the back substitution of the levels top, top - 1, ..., 0: two levels per launch from the bottom up (an odd count: the uppermost alone, first)
 // R (optional): the retraction request of a whole-band solve -- honoured by the two-level launch on the levels (1, 0), the last one of
@@ -1161,7 +1293,9 @@ int launch_bcr_solve(const NormalEq& ne, const TangentLayout& tl, const SolveBuf
   A.rtf = (a1 + 15) / 16; A.ctl = sb.ctl;
   const BcrLevels L = bcr_plan(n, 0, false);
   const bool inverted = bcr_launch_build(ne, tl, sb, reuse_diagonal, min_diag, max_diag, A, L, st);
-  bcr_launch_forward(A, inverted, L, st);
+  BcrJoin J; J.on = sb.bcr_join; J.budget = sb.bcr_join_budget;
+  const int joined = bcr_launch_forward(A, inverted, L, st, J);
+  if (sb.bcr_joined != nullptr) { sb.bcr_joined[0] = joined; sb.bcr_joined[1] += joined; }
   // the ONE place that decides: a request that is on, for the unscaled step, and a plan whose last launch is the two-level back
   // substitution on the levels (1, 0); this entry always solves the whole band (b0 = 0, no ghost block)
   const bool honour = retract != nullptr && retract->on != 0 && retract->rmap != nullptr && retract->alpha == 1.0 && L.nlev >= 3 && A.ghost == 0 && A.b0 == 0;
@@ -1321,5 +1455,19 @@ extern "C" int oicc_debug_bcr_plan(int32_t n, int32_t ghost, int32_t odd_only, i
     o[0] = L.origin[l]; o[1] = L.strides[l]; o[2] = L.parity[l]; o[3] = L.active[l]; o[4] = L.npivs[l]; o[5] = L.offS[l];
   }
   info[0] = L.last; info[1] = L.off_end; info[2] = oicc::bcr_coupling_slots(n + (ghost != 0 ? 1 : 0));
+  return L.nlev;
+}
+
+extern "C" int oicc_debug_bcr_join_plan(int32_t n, int32_t ghost, int32_t odd_only, int32_t b0, int32_t rtf, int32_t join_levels, int32_t budget,
+                                        int32_t build_inverts, int32_t* joined, int32_t cap_levels) {
+  if (n < 1 || joined == nullptr || rtf < 1 || rtf > 4 || budget < 0 || b0 < 0) return OICC_ERR_INVALID_ARG;
+  const oicc::BcrLevels L = oicc::bcr_plan(n, ghost, odd_only != 0);
+  if (L.nlev > cap_levels) return OICC_ERR_INVALID_ARG;
+  oicc::BcrJoin J; J.on = join_levels; J.budget = budget;
+  const bool in_build0 = build_inverts < 0 ? oicc::bcr_fused_build(n, nullptr) : build_inverts != 0;
+  for (int l = 0; l < L.nlev; ++l) {
+    const bool carry = ghost != 0 && (L.active[l] & 1) != 0;   // (as bcr_launch_forward)
+    joined[l] = oicc::bcr_level_joined(J, false, ghost, b0, carry, in_build0 && l == 0, L.npivs[l], rtf) ? 1 : 0;
+  }
   return L.nlev;
 }

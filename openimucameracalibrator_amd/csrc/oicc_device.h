@@ -147,6 +147,9 @@ struct SolveBuffers {
   double radius;   // trust-region radius of this step (kernel argument, no host->device copy)
   int bcr_max_border = 64;      // arrow + rhs rows the block cyclic reduction accepts (per problem: option bcr_max_border)
   int bcr_delay = 0;            // debug: panel waves other than wave 0 start every panel this many ~1000-cycle sleeps late (option debug_bcr_delay)
+  // cyclic reduction, levels as one launch (kernels_bcr.hip: bcr_level_joined; options bcr_join_levels, bcr_join_max_workgroups): on / off,
+  // the workgroup budget of a joined level, and (host memory, optional) where a whole-band solve leaves [its joined levels, += them]
+  int bcr_join = 0, bcr_join_budget = 0; int64_t* bcr_joined = nullptr;
   const LmCtl* ctl = nullptr;   // device-side LM control (round 5): the build kernels take the current normal equations, the radius and the
                                 // reuse-diagonal flag from it, every kernel of the solve returns at once when it says done
   // the decision of the PREVIOUS iteration folded into this iteration's build kernel (lm_decide.h): the state that iteration ran

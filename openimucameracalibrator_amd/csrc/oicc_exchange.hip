@@ -485,7 +485,14 @@ int oicc_debug_dist_solve_info(const oicc_problem* p, int64_t out4[4]) {
   out4[0] = p->dist.solves; out4[1] = p->dist.d.b0; out4[2] = p->dist.d.n_loc; out4[3] = dist_solve_usable(p) ? p->dist.d.nranks : 0;
   return OICC_OK;
 }
-
+// debug read-out (outside include/oicc_hip.h; tests): out4 = [levels of the last whole-band cyclic-reduction solve that ran as one launch
+// (bcri_invert_schur_kernel), such levels in all solves so far, the workgroup budget of a joined level, option bcr_join_levels]
+int oicc_debug_bcr_join_info(oicc_problem* p, int64_t out4[4]) {
+  if (!p || !out4) return OICC_ERR_INVALID_ARG;
+  const SolveBuffers sb = solve_buffers(p);
+  out4[0] = p->bcr_joined[0]; out4[1] = p->bcr_joined[1]; out4[2] = sb.bcr_join_budget; out4[3] = sb.bcr_join;
+  return OICC_OK;
+}
 
 int oicc_time_allreduce(oicc_problem* p, int32_t flags, int32_t repeats, double* ms_per_call, int64_t* bytes) {
   int rc = prepare(p, flags); if (rc) return rc;

@@ -380,6 +380,16 @@ class SplineTrajectoryEstimator:
         self._ck(fn(self._h, flags, nranks, float(radius), repeats, _dp(out)))
         return float(out[0]), bool(out[1]), out[2::2].copy(), out[3::2].copy()
 
+    def BcrJoinInfo(self):
+        """Debug read-out (device library only): levels of the last whole-band cyclic-reduction solve that ran as one launch
+        (inversion and Schur updates joined), such levels in all solves so far, the workgroup budget of a joined level, whether
+        option bcr_join_levels is on."""
+        fn = self._b.lib.oicc_debug_bcr_join_info
+        fn.restype = C.c_int; fn.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        out = (C.c_int64 * 4)()
+        self._ck(fn(self._h, out))
+        return dict(last=int(out[0]), total=int(out[1]), budget=int(out[2]), on=bool(out[3]))
+
     ROUTES = ("bcr_fused", "bcr_unfused", "sweep64", "sweep128", "partitioned", "global", "distributed")
 
     def DebugLmStep(self, flags, radius=1e4, reuse_diagonal=0, nranks=0, solve=True):
