@@ -851,6 +851,15 @@ int oicc_debug_bcr_plan(int32_t n, int32_t ghost, int32_t odd_only, int64_t* lev
  * Returns the number of levels, OICC_ERR_INVALID_ARG as above or for rtf, budget, b0 out of range. */
 int oicc_debug_bcr_join_plan(int32_t n, int32_t ghost, int32_t odd_only, int32_t b0, int32_t rtf, int32_t join_levels, int32_t budget,
                              int32_t build_inverts, int32_t* joined, int32_t cap_levels);
+/* Which level's back substitution the solver runs inside the last block's launch -- one workgroup per pivot of the level, each
+ * repeating the last block's work and taking its neighbours' solution from LDS -- instead of a launch of its own (the solver's own
+ * rule, host arithmetic only).  The back substitution pairs the levels from the bottom up; an even number of levels leaves level
+ * nlev - 2 alone.  It is folded when on != 0 (option bcr_fold_back), the solve is the whole band (ghost == 0, b0 == 0) and the plan
+ * has an even number of levels >= 2.  Returns that level, -1 when nothing folds, INT32_MIN for n < 1, b0 < 0 or a ghost other than 0 / 1. */
+int oicc_debug_bcr_fold_plan(int32_t n, int32_t ghost, int32_t odd_only, int32_t b0, int32_t on);
+/* out3 = [1 if the last whole-band cyclic-reduction solve of the problem folded a level that way, the solves that did so far, option
+ * bcr_fold_back].  OICC_ERR_INVALID_ARG for a null argument. */
+int oicc_debug_bcr_fold_info(oicc_problem* problem, int64_t out3[3]);
 
 #ifdef __cplusplus
 }

@@ -94,8 +94,10 @@ __device__ __forceinline__ void tri10(int t, int& xt, int& yt) {
 // substitution; the arrow part of the step lands in da[0..a).  ONE WAVE, lane = row (a + 1 <= 64): per column the pivot comes
 // by v_readlane, the rank-1 update of the remaining columns runs over LDS without a workgroup barrier (round 2 spent three
 // 1024-thread barriers per column here).  Called by all threads; ends with a workgroup barrier.
-template <int LD>
-__device__ __forceinline__ void bcr_corner_solve(double* C, double* da, int* failp, int a, int tid, int wave, int lane) {
+// idle: what the other waves do meanwhile (bcri_last_backward_kernel issues loads there: nothing they hold is live in wave 0's branch).
+struct BcrNoIdle { __device__ __forceinline__ void operator()() const {} };
+template <int LD, class Idle = BcrNoIdle>
+__device__ __forceinline__ void bcr_corner_solve(double* C, double* da, int* failp, int a, int tid, int wave, int lane, Idle idle = Idle()) {
   const int a1 = a + 1;
   if (a1 <= 16) {
     // up to 15 arrow columns (T_i_c, gravity, line delay: 9-10): the columns stay in registers -- per column the pivot chain of
@@ -143,7 +145,7 @@ __device__ __forceinline__ void bcr_corner_solve(double* C, double* da, int* fai
       }
       if (lane < a) da[lane] = xq_mine;
       if (bad && lane == 0) *failp = 1;
-    }
+    } else idle();
     __syncthreads();
     return;
   }
@@ -174,7 +176,7 @@ __device__ __forceinline__ void bcr_corner_solve(double* C, double* da, int* fai
       z = fma(-l, xq, z);
     }
     if (lane < a) da[lane] = xq_mine;
-  }
+  } else idle();
   __syncthreads();
 }
 
@@ -193,6 +195,9 @@ __device__ __forceinline__ void bcr_corner_solve(double* C, double* da, int* fai
 //                        triangular solve on the way back
 //   bcri_invert_schur_kernel   the first two in ONE launch where a level's Schur workgroups fit the chip at once (bcr_level_joined):
 //                        every workgroup of a pivot inverts D_i itself, Z_i stays in its LDS
+//   bcri_last_backward_kernel  the last block and the back substitution of the level below the top one in ONE launch where the
+//                        pairing of levels would leave that level alone (bcr_fold_level): one workgroup per pivot of the level
+//                        repeats the last block's work and finds its neighbours' x in its own LDS
 // Error: forward errors of B D^-1 B^T through the explicit inverse and through the Cholesky factor are both
 // O(cond(D_i) eps); the LM tests hold both to the oracle's steps.
 // =====================================================================================================================
@@ -220,15 +225,61 @@ __device__ __forceinline__ bcr_v4d bcri_z_tile(const double* W, int yt, int li, 
   return g;   // g[r] <-> (x row 16 XT + li, y row 16 yt + lq + 4 r)
 }
 
+// ---- the back substitution of ONE pivot of a level: x_i = T_rhs - T_left^T x_il - T_right^T x_ir - T_arrow^T x_arrow ----
+// Run by bcri_backward_kernel (a level alone in its launch) and by bcri_last_backward_kernel (the level below the top one, inside the
+// last block's launch): the same rows, the same eight partial sums over the rows w + 8 k in k order, added in the order w = 0..7 -- the
+// same bits from the same inputs.  Only where the neighbours' x and the arrow part are read differs (BcrBackX: LDS either way, staged
+// from A.x by the one, left there by the last block's own work in the other).
+constexpr int kBackRows = 192 / kBackWaves;   // rows of T per wave
+struct BcrBackX {
+  const double* xl; const double* xr; const double* xa;   // x of the left / right neighbour (64 each), of the arrow (a)
+  bool hasL, hasR;                                         // a missing side reads as zeros
+  __device__ __forceinline__ double at(int r, int a) const {
+    return r < 64 ? (hasL ? xl[r] : 0.0) : (r < 128 ? (hasR ? xr[r - 64] : 0.0) : (r < 128 + a ? xa[r - 128] : 0.0));
+  }
+};
+// wave w of eight issues its rows of T (Tg: the pivot's rows, behind its Z) and, w == 0, the rhs row
+__device__ __forceinline__ void bcri_back_rows(const double* Tg, int a, bool hasL, bool hasR, int w, int lane, double (&lv)[kBackRows], double& yv) {
+#pragma unroll
+  for (int k = 0; k < kBackRows; ++k) {
+    const int r = w + kBackWaves * k;
+    const bool ok = r < 128 + a && (hasL || r >= 64) && (hasR || r < 64 || r >= 128);
+    lv[k] = ok ? Tg[r * 64 + lane] : 0.0;
+  }
+  yv = w == 0 ? Tg[(128 + a) * 64 + lane] : 0.0;
+}
+// Called by every thread of the workgroup (one workgroup barrier inside); `active`: the eight waves w = 0..7 that hold the rows.
+// part: [kBackWaves][64] of LDS.  Wave w == 0 returns x_i of column `lane`.
+__device__ __forceinline__ double bcri_back_body(const double (&lv)[kBackRows], double yv, const BcrBackX& X, int a, double* part, bool active, int w, int lane) {
+  if (active) {
+    double sum = 0.0;
+#pragma unroll
+    for (int k = 0; k < kBackRows; ++k) { const int r = w + kBackWaves * k; sum = fma(lv[k], X.at(r, a), sum); }
+    part[w * 64 + lane] = sum;
+  }
+  __syncthreads();
+  double acc = 0.0;
+  if (active && w == 0) {
+#pragma unroll
+    for (int ww = 0; ww < kBackWaves; ++ww) acc += part[ww * 64 + lane];
+  }
+  return yv - acc;
+}
+
 // What follows the factorisation of [D_i ; I] (all waves, after a workgroup barrier): Z = X X^T, and for the last block (LAST) the arrow
 // corner and the first back substitution.  ZLDS: Z stays in LDS as it does for LAST (rows 0..63 of W) and is not stored -- the
 // workgroup goes on with a Schur group of its pivot (bcri_invert_schur_kernel).
-template <bool LAST, bool ZLDS>
-__device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* da, int* failp, const double* Fs, double* Zg, int tid, int wave, int lane, bool report,
+// FOLD (bcri_last_backward_kernel; with LAST): the launch has one workgroup per pivot of the level below the top one, whose plan
+// fields are A.o, A.s, A.p, A.m.  Every workgroup does the last block's work with identical bits and then the back substitution of
+// its own pivot from LDS; only workgroup 0 stores what they all share and raises A.fail.
+template <bool LAST, bool ZLDS, bool FOLD>
+__device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* da, int* failp, const double* Fs, const double* Cs, double* Zg, int tid, int wave, int lane, bool report,
                                           const double (&ttop)[16], const double ytop, double* x0s) {
+  static_assert(!FOLD || LAST, "the folded level follows the last block");
   constexpr int LD = kInvLD, NW = kInvWaves, NT = 64 * NW, FLD = 65;
   const int li = lane & 15, lq = lane >> 4;
   const int a = A.a, a1 = a + 1;
+  const bool shared_writer = !FOLD || blockIdx.x == 0;
   // ---- Z = X X^T (X = L^-T in rows 64..127): to global, or (LAST) into rows 0..63, where the factor is no longer needed
   for (int t = wave; t < 10; t += NW) {
     int xt, yt; tri10(t, xt, yt);
@@ -276,17 +327,31 @@ __device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* d
     bcr_v4d g = {0.0, 0.0, 0.0, 0.0};
 #pragma unroll
     for (int kk = 0; kk < 16; ++kk) g = __builtin_amdgcn_mfma_f64_16x16x4f64(vf[kk], vt[kk], g, 0, 0, 0);
-    // g[r] <-> (row q1 = 16 t1 + li, column q2 = 16 t2 + lq + 4 r)
-    const double* Sm = A.side != 0 ? A.Lf + (int64_t)A.last * (192 + a1) * 64 + 4096 + 64 * a1 : nullptr;   // (BcrArgs::side: the corner part)
-    double mc[4];
+    // g[r] <-> (row q1 = 16 t1 + li, column q2 = 16 t2 + lq + 4 r); Cs: the corner (+ the side buffer's corner part), parked when the kernel started
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { const int q1 = 16 * t1 + li, q2 = 16 * t2 + lq + 4 * r; mc[r] = (q1 < a1 && q2 < a1) ? A.Mc[q1 * a1 + q2] + (Sm != nullptr ? Sm[q1 * a1 + q2] : 0.0) : 0.0; }
+    for (int r = 0; r < 4; ++r) { const int q1 = 16 * t1 + li, q2 = 16 * t2 + lq + 4 * r; if (q1 < a1 && q2 < a1) W[q2 * LD + q1] = Cs[q1 * a1 + q2] - g[r]; }
+  }
+  // FOLD: this workgroup's pivot of the level below the top one.  Its rows of T (stored two launches ago) are issued when the corner
+  // solve starts, by the waves NW - 8 .. NW - 1, which idle through it: the corner solve, x_last and the top level stand between issue
+  // and use, and nothing of it is live in wave 0's branch (with the rows in the waves 0..7 the kernel went to scratch there: 24 doubles
+  // on top of the 16 of the top level and the corner's own 16 columns).  Wave NW - 8 + w does what wave w of bcri_backward_kernel does.
+  double lv[kBackRows], yv = 0.0;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { const int q1 = 16 * t1 + li, q2 = 16 * t2 + lq + 4 * r; if (q1 < a1 && q2 < a1) W[q2 * LD + q1] = mc[r] - g[r]; }
+  for (int k = 0; k < kBackRows; ++k) lv[k] = 0.0;
+  constexpr int BW0 = NW - kBackWaves;
+  int fi = 0; bool f_hasL = false, f_hasR = false;
+  if (FOLD) {
+    const int kp = 2 * (int)blockIdx.x + A.p;
+    fi = A.o + kp * A.s; f_hasL = kp > 0; f_hasR = kp < A.m - 1;
   }
   __syncthreads();
-  bcr_corner_solve<LD>(W, da, failp, a, tid, wave, lane);
-  for (int q = tid; q < a; q += NT) A.x[A.Pb + q] = da[q];
+  bcr_corner_solve<LD>(W, da, failp, a, tid, wave, lane, [&]() {
+    if (FOLD && wave >= BW0) {
+      bcri_back_rows(A.Lf + (int64_t)fi * (192 + a1) * 64 + 4096, a, f_hasL, f_hasR, wave - BW0, lane, lv, yv);
+      asm volatile("" ::: "memory");   // (issued here: the loads must not sink to their use)
+    }
+  });
+  if (shared_writer) for (int q = tid; q < a; q += NT) A.x[A.Pb + q] = da[q];
   if (wave == 0) {
     const double* tc = W + lane * LD + 64;
     double v = tc[a];
@@ -298,11 +363,11 @@ __device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* d
       for (int k = 0; k < 8; ++k) v = fma(-t8[k], d8[k], v);
     }
     const int gi = A.last * 64 + lane;
-    if (gi < A.Pb) A.x[gi] = v;
+    if (shared_writer && gi < A.Pb) A.x[gi] = v;
     x0s[lane] = gi < A.Pb ? v : 0.0;
   }
   __syncthreads();
-  if (tid == 0 && *failp) atomicOr(A.fail, 1);
+  if (shared_writer && tid == 0 && *failp) atomicOr(A.fail, 1);
   if (A.top_l >= 0 || A.top_r >= 0) {
     // the pivots of the top level (one: right of the last block; two: the ends of three active blocks), whose only neighbour is the
     // last block: x = T_rhs - T_nb^T x_last - T_arrow^T x_arrow; their rows of T were loaded when the kernel started
@@ -323,7 +388,19 @@ __device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* d
 #pragma unroll
       for (int w = 0; w < NW; ++w) acc += W[(wave * NW + w) * 64 + lane];
       const int gi = blk * 64 + lane;
-      if (blk >= 0 && gi < A.Pb) A.x[gi] = ytop - acc;
+      const bool ok = blk >= 0 && gi < A.Pb;
+      if (shared_writer && ok) A.x[gi] = ytop - acc;
+      if (FOLD) x0s[64 * (1 + wave) + lane] = ok ? ytop - acc : 0.0;   // (x0s has 256 doubles: x_last, x of top_r, x of top_l)
+    }
+    if (FOLD) {
+      // every neighbour of a pivot of this level is an active block of the top level: the last block or one of the top pivots
+      __syncthreads();
+      auto x_of = [&](int blk) -> const double* { return blk == A.last ? x0s : (blk == A.top_r ? x0s + 64 : x0s + 128); };
+      BcrBackX X;
+      X.hasL = f_hasL; X.hasR = f_hasR; X.xl = x_of(fi - A.s); X.xr = x_of(fi + A.s); X.xa = da;
+      const double xv = bcri_back_body(lv, yv, X, a, W + 2 * NW * 64, wave >= BW0, wave - BW0, lane);   // (W: behind the top level's partial sums)
+      const int gi = fi * 64 + lane;
+      if (wave == BW0 && gi < A.Pb) A.x[gi] = xv;
     }
   }
 }
@@ -335,7 +412,7 @@ __device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* d
 // the caller issued before this function have landed with D_i's by then (one round trip for both), and what it writes behind `Fs`
 // is visible after the factorisation
 struct BcrNoPark { __device__ __forceinline__ void operator()(double*) const {} };
-template <bool LAST, bool PROF, bool ZLDS = false, class LoadD, class Park = BcrNoPark>
+template <bool LAST, bool PROF, bool ZLDS = false, bool FOLD = false, class LoadD, class Park = BcrNoPark>
 __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, LoadD load_d, const bool report = true, Park park = Park()) {
   constexpr int LD = kInvLD, NW = kInvWaves, NT = 64 * NW, NTILE = 20, SLOTS = (NTILE + NW - 1) / NW, RU = 128, NAW = 3, FLD = 65;
   static_assert(NW == 16, "the corner phases of block 0 take one tile per wave");
@@ -348,10 +425,12 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
   int* const failp = reinterpret_cast<int*>(da + 64);
   double* const dg = da + 64 + 8;        // [16][16] copy of the current panel's diagonal tile (column major; see bcr_eliminate_kernel)
   double* const Fs = dg + 256;           // LAST: [64][FLD] border rows of block 0, Fs[k * FLD + q]; ZLDS: the caller's parked border tiles and Ts
+  double* const Cs = Fs + 64 * FLD;      // LAST: [a1][a1] the arrow corner (+ the side buffer's corner part), as A.Mc is laid out
   const int a1 = A.a + 1;
   double* Zg = A.Lf + (int64_t)i * (192 + a1) * 64;
   const double* Fg = A.F + (int64_t)i * 64 * a1;
   const double* Sf = (LAST && A.side != 0) ? Zg + 4096 : nullptr;   // (BcrArgs::side: the F part)
+  const double* Sm = (LAST && A.side != 0) ? Zg + 4096 + 64 * a1 : nullptr;   // (the corner part)
   const bool prof = PROF && A.prof != nullptr && blockIdx.x == 0 && wave == 0;
   long long pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   long long tprev = prof ? clock64() : 0;
@@ -378,12 +457,14 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
   }
   {
     constexpr int PER = 4096 / NT;
-    double gd[PER], gf[PER];
+    double gd[PER], gf[PER], gc[PER];
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
       const int e = tid + k * NT;
       gd[k] = load_d(e);
       if (LAST) { const int c = e >> 6, q = e & 63; gf[k] = q < a1 ? Fg[c * a1 + q] + (Sf != nullptr ? Sf[c * a1 + q] : 0.0) : 0.0; }
+      // the corner: final since the top level's launch ended, so it travels with D and F and no load stands behind the T F^T product
+      if (LAST) gc[k] = e < a1 * a1 ? A.Mc[e] + (Sm != nullptr ? Sm[e] : 0.0) : 0.0;
     }
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
@@ -393,6 +474,7 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
       if (c < 16 && r < 16) dg[c * 16 + r] = r >= c ? gd[k] : 0.0;
       W[c * LD + 64 + r] = r == c ? 1.0 : 0.0;
       if (LAST) Fs[c * FLD + r] = gf[k];
+      if (LAST && e < a1 * a1) Cs[e] = gc[k];
     }
     park(Fs);
   }
@@ -483,7 +565,7 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
     BCR_MARK(4);
   }
   BCR_MARK(4);
-  bcri_tail<LAST, ZLDS>(A, W, da, failp, Fs, Zg, tid, wave, lane, report, ttop, ytop, dg);
+  bcri_tail<LAST, ZLDS, FOLD>(A, W, da, failp, Fs, Cs, Zg, tid, wave, lane, report, ttop, ytop, dg);
   BCR_MARK(5);
   if (PROF && prof && lane == 0) for (int k = 0; k < 8; ++k) A.prof[k] = pc[k];
 #undef BCR_MARK
@@ -496,6 +578,20 @@ __global__ __launch_bounds__(64 * kInvWaves) void bcri_invert_kernel(BcrArgs A) 
   const double* Dg = A.D + (int64_t)i * 4096;
   const double* Sd = (LAST && A.side != 0) ? A.Lf + (int64_t)i * (192 + A.a + 1) * 64 : nullptr;   // (BcrArgs::side)
   bcri_invert_body<LAST, PROF>(A, i, [Dg, Sd](int e) { double v = Dg[e]; if (LAST && Sd != nullptr && (e & 63) >= (e >> 6)) v += Sd[e]; return v; });
+}
+
+// The last block AND the back substitution of the level below the top one in ONE launch (bcr_fold_level): one workgroup per pivot of
+// that level (2 to 4).  Every x such a pivot needs -- the last block's, the top pivots', the arrow part -- is produced by the last
+// block's workgroup and sits in its LDS, so every workgroup repeats that work on a compute unit that would idle (identical bits: the
+// same loads, the same arithmetic) and goes on with its own pivot.  Nothing is handed from one workgroup to another -- no flag, no
+// poll, no wait --, and every global word has one writer: workgroup 0 for what they share, workgroup b for x of pivot b.
+// A.o, A.s, A.p, A.m: the folded level; A.last, A.top_l, A.top_r, A.side as for bcri_invert_kernel<true, ...>.
+__global__ __launch_bounds__(64 * kInvWaves) void bcri_last_backward_kernel(BcrArgs A) {
+  BCR_RETURN_IF_DONE(A);
+  const int i = A.last;
+  const double* Dg = A.D + (int64_t)i * 4096;
+  const double* Sd = A.side != 0 ? A.Lf + (int64_t)i * (192 + A.a + 1) * 64 : nullptr;   // (BcrArgs::side)
+  bcri_invert_body<true, false, false, true>(A, i, [Dg, Sd](int e) { double v = Dg[e]; if (Sd != nullptr && (e & 63) >= (e >> 6)) v += Sd[e]; return v; });
 }
 
 // ---- one Schur group of a pivot: (16-row tile x of the border rows, up to four column tiles y) ----
@@ -824,34 +920,19 @@ __global__ __launch_bounds__(64 * kBackWaves) void bcri_backward_kernel(BcrArgs 
   const bool hasL = kp > 0;
   const bool hasR = kp < A.m - 1 || A.ghost != 0;
   const int ir = kp < A.m - 1 ? i + s : A.n;        // (distributed reduction: the ghost block's solution sits behind the local blocks)
-  const double* Tg = A.Lf + (int64_t)i * (192 + a1) * 64 + 4096;
-  constexpr int RW = 192 / kBackWaves;
-  double lv[RW];
-#pragma unroll
-  for (int k = 0; k < RW; ++k) {
-    const int r = wave + kBackWaves * k;
-    const bool ok = r < 128 + a && (hasL || r >= 64) && (hasR || r < 64 || r >= 128);
-    lv[k] = ok ? Tg[r * 64 + lane] : 0.0;
-  }
-  const double yv = wave == 0 ? Tg[(128 + a) * 64 + lane] : 0.0;
+  double lv[kBackRows], yv;
+  bcri_back_rows(A.Lf + (int64_t)i * (192 + a1) * 64 + 4096, a, hasL, hasR, wave, lane, lv, yv);
   double xin = 0.0;
   if (tid < 64) { const int gi = il * 64 + tid; xin = (hasL && gi < A.Pb) ? A.x[gi] : 0.0; }
   else if (tid < 128) { const int gi = ir * 64 + (tid - 64); xin = (hasR && gi < A.Pb) ? A.x[gi] : 0.0; }
   else if (tid < 128 + a) xin = A.x[A.Pb + (tid - 128)];
   if (tid < 192) xs[tid] = xin;
   __syncthreads();
-  double sum = 0.0;
-#pragma unroll
-  for (int k = 0; k < RW; ++k) { const int r = wave + kBackWaves * k; sum = fma(lv[k], r < 128 + a ? xs[r] : 0.0, sum); }
-  part[wave][lane] = sum;
-  __syncthreads();
-  if (wave == 0) {
-    double acc = 0.0;
-#pragma unroll
-    for (int w = 0; w < kBackWaves; ++w) acc += part[w][lane];
-    const int gi = i * 64 + lane;
-    if (gi < A.Pb) A.x[gi] = yv - acc;
-  }
+  BcrBackX X;
+  X.xl = xs; X.xr = xs + 64; X.xa = xs + 128; X.hasL = true; X.hasR = true;   // (a missing side was staged as zeros)
+  const double xv = bcri_back_body(lv, yv, X, a, &part[0][0], true, wave, lane);
+  const int gi = i * 64 + lane;
+  if (wave == 0 && gi < A.Pb) A.x[gi] = xv;
 }
 
 // Two levels of the back substitution in one launch: a workgroup takes a pivot j of the upper level (stride 2 s) and then, eight
@@ -1251,23 +1332,34 @@ static bool bcr_launch_back(BcrArgs A, const BcrLevels& L, int top, hipStream_t 
   }
   return fused;
 }
+// Which level's back substitution rides in the last block's launch (bcri_last_backward_kernel) instead of a launch of its own: THE
+// rule, host arithmetic only (exported as oicc_debug_bcr_fold_plan); -1: none.  The back substitution pairs the levels from the bottom
+// up, so an even number of levels leaves the uppermost one below the top level, nlev - 2, alone in a launch; its 2 to 4 pivots have
+// only the last block and the top pivots as neighbours.  It is folded when the option is on, no phase clocks are asked for and the
+// solve is the whole band (the distributed reduction -- ghost block, block offset -- keeps its launches).
+static int bcr_fold_level(int on, bool prof, int ghost, int b0, const BcrLevels& L) {
+  return (on != 0 && !prof && ghost == 0 && b0 == 0 && L.nlev >= 2 && (L.nlev & 1) == 0) ? L.nlev - 2 : -1;
+}
 // the last block with the arrow corner and the top level's back substitution (one or two pivots, whose only neighbour is the last
-// block), then the levels below
-static bool bcr_launch_last_and_back(BcrArgs A, const BcrLevels& L, hipStream_t st, const RetractReq* R = nullptr, const SolveBuffers* sb = nullptr) {
+// block), then the levels below.  fold: bcr_fold_level's answer (launch_bcr_solve alone hands one down) -- that level goes with the
+// last block and the launches below start under it.
+static bool bcr_launch_last_and_back(BcrArgs A, const BcrLevels& L, hipStream_t st, const RetractReq* R = nullptr, const SolveBuffers* sb = nullptr, int fold = -1) {
   using KernelFn = void (*)(BcrArgs);
-  KernelFn k_inv_last = bcri_invert_kernel<true, false>;
-  const size_t lds_inv_last = bcr_lds_inv() + (size_t)64 * 65 * sizeof(double);
-  bcr_allow_lds(reinterpret_cast<const void*>(k_inv_last), lds_inv_last);
+  KernelFn k_inv_last = fold >= 0 ? bcri_last_backward_kernel : bcri_invert_kernel<true, false>;
+  const int a1 = A.a + 1;
+  const size_t lds_inv_last = bcr_lds_inv() + (size_t)(64 * 65 + a1 * a1) * sizeof(double);           // + Fs, the parked corner
+  bcr_allow_lds(reinterpret_cast<const void*>(k_inv_last), bcr_lds_inv() + (size_t)(64 * 65 + 64 * 64) * sizeof(double));   // (set once per function: the widest arrow)
   const int nlev = L.nlev;
   A.o = 0; A.s = 0; A.p = 1; A.m = 1; A.pn = 1; A.offS_in = 0; A.offS_out = 0; A.carry = 0;
+  if (fold >= 0) bcr_set_level(A, L, fold);
   A.last = L.last; A.top_l = -1; A.top_r = -1; A.side = (nlev >= 1 && L.parity[nlev - 1] == 0) ? 1 : 0;
   if (nlev >= 1) {   // two active blocks: the pivot right of the last block; three: the two ends
     const int t = nlev - 1;
     A.top_r = L.last + L.strides[t];
     if (L.parity[t] == 0) A.top_l = L.last - L.strides[t];
   }
-  hipLaunchKernelGGL(k_inv_last, dim3(1), dim3(64 * kInvWaves), lds_inv_last, st, A);
-  return bcr_launch_back(A, L, nlev - 2, st, R, sb);        // (the top level went with the last block)
+  hipLaunchKernelGGL(k_inv_last, dim3(fold >= 0 ? L.npivs[fold] : 1), dim3(64 * kInvWaves), lds_inv_last, st, A);
+  return bcr_launch_back(A, L, fold >= 0 ? fold - 1 : nlev - 2, st, R, sb);        // (the top level went with the last block)
 }
 
 // the route of one cyclic-reduction solve (lm_solve_route): fused or separate build, or kRouteNone where it does not apply
@@ -1300,7 +1392,9 @@ int launch_bcr_solve(const NormalEq& ne, const TangentLayout& tl, const SolveBuf
   // substitution on the levels (1, 0); this entry always solves the whole band (b0 = 0, no ghost block)
   const bool honour = retract != nullptr && retract->on != 0 && retract->rmap != nullptr && retract->alpha == 1.0 && L.nlev >= 3 && A.ghost == 0 && A.b0 == 0;
   RetractReq R{}; if (honour) { R = *retract; R.ne = ne; }
-  const bool did = bcr_launch_last_and_back(A, L, st, honour ? &R : nullptr, &sb);
+  const int fold = bcr_fold_level(sb.bcr_fold, A.prof != nullptr, A.ghost, A.b0, L);
+  if (sb.bcr_folded != nullptr) { sb.bcr_folded[0] = fold >= 0 ? 1 : 0; sb.bcr_folded[1] += fold >= 0 ? 1 : 0; }
+  const bool did = bcr_launch_last_and_back(A, L, st, honour ? &R : nullptr, &sb, fold);
   if (fused) *fused = did;
   return 0;
 }
@@ -1470,4 +1564,10 @@ extern "C" int oicc_debug_bcr_join_plan(int32_t n, int32_t ghost, int32_t odd_on
     joined[l] = oicc::bcr_level_joined(J, false, ghost, b0, carry, in_build0 && l == 0, L.npivs[l], rtf) ? 1 : 0;
   }
   return L.nlev;
+}
+
+extern "C" int oicc_debug_bcr_fold_plan(int32_t n, int32_t ghost, int32_t odd_only, int32_t b0, int32_t on) {
+  if (n < 1 || b0 < 0 || ghost < 0 || ghost > 1) return INT32_MIN;   // (-1 is an answer here: no level folds)
+  const oicc::BcrLevels L = oicc::bcr_plan(n, ghost, odd_only != 0);
+  return oicc::bcr_fold_level(on, false, ghost, b0, L);
 }

@@ -150,6 +150,9 @@ struct SolveBuffers {
   // cyclic reduction, levels as one launch (kernels_bcr.hip: bcr_level_joined; options bcr_join_levels, bcr_join_max_workgroups): on / off,
   // the workgroup budget of a joined level, and (host memory, optional) where a whole-band solve leaves [its joined levels, += them]
   int bcr_join = 0, bcr_join_budget = 0; int64_t* bcr_joined = nullptr;
+  // cyclic reduction, the level below the top one inside the last block's launch (kernels_bcr.hip: bcr_fold_level; option bcr_fold_back):
+  // on / off, and (host memory, optional) where a whole-band solve leaves [1 if it folded, += that]
+  int bcr_fold = 0; int64_t* bcr_folded = nullptr;
   const LmCtl* ctl = nullptr;   // device-side LM control (round 5): the build kernels take the current normal equations, the radius and the
                                 // reuse-diagonal flag from it, every kernel of the solve returns at once when it says done
   // the decision of the PREVIOUS iteration folded into this iteration's build kernel (lm_decide.h): the state that iteration ran

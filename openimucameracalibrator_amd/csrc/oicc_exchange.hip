@@ -493,6 +493,14 @@ int oicc_debug_bcr_join_info(oicc_problem* p, int64_t out4[4]) {
   out4[0] = p->bcr_joined[0]; out4[1] = p->bcr_joined[1]; out4[2] = sb.bcr_join_budget; out4[3] = sb.bcr_join;
   return OICC_OK;
 }
+// debug read-out (tests): out3 = [1 if the last whole-band cyclic-reduction solve ran a back-substitution level inside the last block's
+// launch (bcri_last_backward_kernel), the solves that did so far, option bcr_fold_back]
+int oicc_debug_bcr_fold_info(oicc_problem* p, int64_t out3[3]) {
+  if (!p || !out3) return OICC_ERR_INVALID_ARG;
+  const SolveBuffers sb = solve_buffers(p);
+  out3[0] = p->bcr_folded[0]; out3[1] = p->bcr_folded[1]; out3[2] = sb.bcr_fold;
+  return OICC_OK;
+}
 
 int oicc_time_allreduce(oicc_problem* p, int32_t flags, int32_t repeats, double* ms_per_call, int64_t* bytes) {
   int rc = prepare(p, flags); if (rc) return rc;

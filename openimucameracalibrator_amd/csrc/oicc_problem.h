@@ -179,6 +179,7 @@ struct oicc_problem {
   // 1.2 us for them); on a one-round problem the dependent chain they add to the retraction kernel (+9 us at C2) costs more.
   int n_cu = 256;
   int64_t bcr_joined[2] = {0, 0};   // cyclic-reduction levels that ran as one launch: in the last whole-band solve, in all of them (oicc_debug_bcr_join_info)
+  int64_t bcr_folded[2] = {0, 0};   // whether the last whole-band cyclic-reduction solve folded a back-substitution level into the last block's launch; solves that did (oicc_debug_bcr_fold_info)
   bool seg_precomputed() const { const auto it = opt.find("debug_seg_precompute"); const int force = it == opt.end() ? 0 : int(it->second); return force == 1 || (force == 0 && tp.n_tiles > n_cu); }
   DevBuf<int32_t> d_corner_view, d_corner_pt, d_view_s_so3, d_view_s_r3;
   DevBuf<double> d_cu, d_cv, d_cisx, d_cisy, d_view_u_so3, d_view_u_r3;
@@ -284,6 +285,7 @@ struct oicc_problem {
     opt["bcr_max_border"] = 64;        // arrow + rhs rows the block cyclic reduction accepts (kernels_bcr.hip: up to 64 by construction; round 2 held it at 32 until the panel hazard was settled, test_bcr_wide_borders_and_the_panel_hazard)
     opt["bcr_join_levels"] = 1;        // 1: a level of the cyclic reduction above the build's whose pivots x Schur groups fit the workgroup budget runs as ONE launch, every workgroup of a pivot inverting it itself (kernels_bcr.hip: bcri_invert_schur_kernel); 0: an inversion launch and a Schur launch per level (A/B runs, tests)
     opt["bcr_join_max_workgroups"] = 0;   // the workgroup budget of a joined level; 0: the device's compute units
+    opt["bcr_fold_back"] = 1;          // 1: a whole-band solve of an even number of levels runs the back substitution of level nlev - 2 inside the last block's launch, one workgroup per pivot, each repeating the last block's work (kernels_bcr.hip: bcri_last_backward_kernel); 0: bcri_invert_kernel<true, false>, then bcri_backward_kernel on that level (A/B runs, tests)
     opt["debug_check_ne"] = 0;   // 1: before every linear solve compare the current normal equations with a host copy taken when they became current
     opt["debug_sync"] = 0;       // 1: drain the stream after every pass (debugging of inter-kernel hazards)
     opt["covariance_min_rcond"] = 1e-12;   // oicc_estimate_covariance: below this reciprocal condition estimate of the unit-diagonal normal equations no covariance is handed out (OICC_COV_RANK_DEFICIENT)

@@ -390,6 +390,15 @@ class SplineTrajectoryEstimator:
         self._ck(fn(self._h, out))
         return dict(last=int(out[0]), total=int(out[1]), budget=int(out[2]), on=bool(out[3]))
 
+    def BcrFoldInfo(self):
+        """Debug read-out (device library only): whether the last whole-band cyclic-reduction solve ran the back substitution of the
+        level below the top one inside the last block's launch, the solves that did so far, whether option bcr_fold_back is on."""
+        fn = self._b.lib.oicc_debug_bcr_fold_info
+        fn.restype = C.c_int; fn.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        out = (C.c_int64 * 3)()
+        self._ck(fn(self._h, out))
+        return dict(last=int(out[0]), total=int(out[1]), on=bool(out[2]))
+
     ROUTES = ("bcr_fused", "bcr_unfused", "sweep64", "sweep128", "partitioned", "global", "distributed")
 
     def DebugLmStep(self, flags, radius=1e4, reuse_diagonal=0, nranks=0, solve=True):
