@@ -152,7 +152,19 @@ void kabsch_from_cross_covariance(const double A[9], double R[9]) {
     const int c = order[k];
     for (int r = 0; r < 3; ++r) { Un[3 * r + k] = sv[c] > 1e-300 ? U[3 * r + c] / sv[c] : 0.0; Vn[3 * r + k] = V[3 * r + c]; }
   }
-  if (!(sv[order[2]] > 1e-12 * std::fmax(sv[order[0]], 1e-300))) {   // rank deficient: third left vector = u0 x u1 (sign fixed below by the determinant)
+  // rank deficient: the left vectors of the vanishing singular values are completed to an orthonormal basis (the reference's
+  // full-U JacobiSVD hands back one too; V is a product of rotations and is orthonormal whatever the rank), so that R is a
+  // rotation even for a cross-covariance of rank 1 or 0 (single-axis motion; every sample resampled to the same value)
+  const double sv_floor = 1e-12 * std::fmax(sv[order[0]], 1e-300);
+  if (!(sv[order[0]] > 1e-300)) { for (int k = 0; k < 9; ++k) Un[k] = (k % 4 == 0) ? 1.0 : 0.0; }
+  else if (!(sv[order[1]] > sv_floor)) {   // second left vector: the coordinate axis furthest from u0, made orthogonal to it
+    int j = 0; if (std::fabs(Un[3]) < std::fabs(Un[3 * j])) j = 1; if (std::fabs(Un[6]) < std::fabs(Un[3 * j])) j = 2;
+    double w[3], nw = 0.0;
+    for (int r = 0; r < 3; ++r) { w[r] = (r == j ? 1.0 : 0.0) - Un[3 * j] * Un[3 * r]; nw += w[r] * w[r]; }
+    nw = std::sqrt(nw);
+    for (int r = 0; r < 3; ++r) Un[3 * r + 1] = w[r] / nw;
+  }
+  if (!(sv[order[2]] > sv_floor)) {   // third left vector = u0 x u1 (sign fixed below by the determinant)
     Un[2] = Un[3] * Un[7] - Un[6] * Un[4]; Un[5] = Un[6] * Un[1] - Un[0] * Un[7]; Un[8] = Un[0] * Un[4] - Un[3] * Un[1];
   }
   auto det3 = [](const double* M) { return M[0] * (M[4] * M[8] - M[5] * M[7]) - M[1] * (M[3] * M[8] - M[5] * M[6]) + M[2] * (M[3] * M[7] - M[4] * M[6]); };
@@ -177,22 +189,18 @@ void quat_from_rotation(const double R[9], double q[4]) {
   q[0] = x; q[1] = y; q[2] = z; q[3] = w;
 }
 
-}  // namespace
-
-extern "C" int oicc_estimate_imu_to_camera_rotation(int32_t device_ordinal, int64_t n_vis, const double* t_vis_s, const double* q_vis_xyzw,
-                                                    int64_t n_imu, const double* t_imu_s, const double* gyro_xyz, double dt_imu,
-                                                    int32_t estimate_gyro_bias, double q_imu_to_cam_xyzw[4], double* time_offset_imu_to_cam,
-                                                    double gyro_bias[3], double* alignment_error, int32_t* iterations) {
-  if (!t_vis_s || !q_vis_xyzw || !t_imu_s || !gyro_xyz || !q_imu_to_cam_xyzw || !time_offset_imu_to_cam || !gyro_bias || n_vis < 2 || n_imu < 2 || !(dt_imu > 0.0))
-    return OICC_ERR_INVALID_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device_ordinal < 0 || device_ordinal >= ndev) return OICC_ERR_NO_DEVICE;   // no CPU fallback
-  if (hipSetDevice(device_ordinal) != hipSuccess) return OICC_ERR_NO_DEVICE;
+// ---- host: the O(n) preparation (cc:133-225) -----------------------------------------------------------------------
+struct RotationSeries { std::vector<double> tI, sImu, sVis; };   // IMU times of the common window (zero based), smoothed gyroscope and visual rates [n, 3]
+// common window, visual quaternions at the IMU times, difference rates with the over-360 deg/s hold, 15-tap moving averages.
+// No device call.  OICC_ERR_INVALID_ARG for unsorted times or a window of fewer than 16 IMU samples / 2 views.
+int prepare_rotation_series(int64_t n_vis, const double* t_vis_s, const double* q_vis_xyzw, int64_t n_imu, const double* t_imu_s,
+                            const double* gyro_xyz, double dt_imu, RotationSeries* out) {
   for (int64_t i = 1; i < n_vis; ++i) if (!(t_vis_s[i] > t_vis_s[i - 1])) return OICC_ERR_INVALID_ARG;   // the reference keeps both in time-ordered maps
   for (int64_t i = 1; i < n_imu; ++i) if (!(t_imu_s[i] > t_imu_s[i - 1])) return OICC_ERR_INVALID_ARG;
   // ---- common window, zero based (cc:133-165); the window end is the LATER end (:139)
   const double t0 = std::max(t_vis_s[0], t_imu_s[0]), tend = std::max(t_vis_s[n_vis - 1], t_imu_s[n_imu - 1]);
-  std::vector<double> tI, tV; std::vector<double> angImu; std::vector<Q> qV;
+  std::vector<double>& tI = out->tI; std::vector<double> tV; std::vector<double> angImu; std::vector<Q> qV;
+  tI.clear();
   for (int64_t i = 0; i < n_imu; ++i) if (t_imu_s[i] >= t0 && t_imu_s[i] <= tend) { tI.push_back(t_imu_s[i] - t0); angImu.insert(angImu.end(), gyro_xyz + 3 * i, gyro_xyz + 3 * i + 3); }
   for (int64_t i = 0; i < n_vis; ++i) if (t_vis_s[i] >= t0 && t_vis_s[i] <= tend) { tV.push_back(t_vis_s[i] - t0); qV.push_back(Q{q_vis_xyzw[4 * i], q_vis_xyzw[4 * i + 1], q_vis_xyzw[4 * i + 2], q_vis_xyzw[4 * i + 3]}); }
   const size_t n = tI.size();
@@ -217,7 +225,8 @@ extern "C" int oicc_estimate_imu_to_camera_rotation(int32_t device_ordinal, int6
     angVis[3 * i] = v[0]; angVis[3 * i + 1] = v[1]; angVis[3 * i + 2] = v[2];
   }
   // ---- 15-tap trailing moving averages (SimpleMovingAverage, cc:209-225)
-  std::vector<double> sImu(3 * n), sVis(3 * n);
+  std::vector<double>& sImu = out->sImu; std::vector<double>& sVis = out->sVis;
+  sImu.assign(3 * n, 0.0); sVis.assign(3 * n, 0.0);
   for (int c = 0; c < 3; ++c) {
     double ti = 0.0, tv = 0.0;
     for (size_t i = 0; i < n; ++i) {
@@ -227,21 +236,37 @@ extern "C" int oicc_estimate_imu_to_camera_rotation(int32_t device_ordinal, int6
       sImu[3 * i + c] = ti / cnt; sVis[3 * i + c] = tv / cnt;
     }
   }
-  // ---- device buffers
+  return OICC_OK;
+}
+
+constexpr int kRotGridCap = 512;   // workgroups of the two probe kernels; longer series go round their grid-stride loops
+
+// ---- one probe of the golden-section search on the device: SolveClosedForm (cc:39-124) ----------------------------------
+// Holds the prepared series on the device; the calibration entry and the debug entry below both drive this one object.
+struct RotationProbe {
   double *d_t = nullptr, *d_imu = nullptr, *d_vis = nullptr, *d_acc = nullptr, *d_Rb = nullptr; hipStream_t st = nullptr;
-  auto cleanup = [&]() { if (d_t) (void)hipFree(d_t); if (d_imu) (void)hipFree(d_imu); if (d_vis) (void)hipFree(d_vis); if (d_acc) (void)hipFree(d_acc); if (d_Rb) (void)hipFree(d_Rb); if (st) (void)hipStreamDestroy(st); };
-  if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess || hipMalloc(&d_t, n * 8) != hipSuccess || hipMalloc(&d_imu, 3 * n * 8) != hipSuccess ||
-      hipMalloc(&d_vis, 3 * n * 8) != hipSuccess || hipMalloc(&d_acc, 16 * 8) != hipSuccess || hipMalloc(&d_Rb, 12 * 8) != hipSuccess) { cleanup(); return OICC_ERR_HIP; }
-  if (hipMemcpyAsync(d_t, tI.data(), n * 8, hipMemcpyHostToDevice, st) != hipSuccess || hipMemcpyAsync(d_imu, sImu.data(), 3 * n * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipMemcpyAsync(d_vis, sVis.data(), 3 * n * 8, hipMemcpyHostToDevice, st) != hipSuccess) { cleanup(); return OICC_ERR_HIP; }
-  const int grid = int(std::min<size_t>((n + 255) / 256, 512));
-  bool ok = true;
-  // SolveClosedForm (cc:39-124): returns the error, fills R (row major) and the bias
-  auto solve_closed_form = [&](double td, double R[9], double b[3]) -> double {
+  size_t n = 0; int grid = 0; int estimate_gyro_bias = 0; bool ok = true;
+  void cleanup() {
+    if (d_t) (void)hipFree(d_t); if (d_imu) (void)hipFree(d_imu); if (d_vis) (void)hipFree(d_vis); if (d_acc) (void)hipFree(d_acc); if (d_Rb) (void)hipFree(d_Rb); if (st) (void)hipStreamDestroy(st);
+    d_t = d_imu = d_vis = d_acc = d_Rb = nullptr; st = nullptr;
+  }
+  // times [n], smoothed gyroscope and visual rates [n, 3] (host) -> device
+  int upload(size_t n_, const double* tI, const double* sImu, const double* sVis, int grid_cap, int estimate_bias) {
+    n = n_; estimate_gyro_bias = estimate_bias;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess || hipMalloc(&d_t, n * 8) != hipSuccess || hipMalloc(&d_imu, 3 * n * 8) != hipSuccess ||
+        hipMalloc(&d_vis, 3 * n * 8) != hipSuccess || hipMalloc(&d_acc, 16 * 8) != hipSuccess || hipMalloc(&d_Rb, 12 * 8) != hipSuccess) { cleanup(); return OICC_ERR_HIP; }
+    if (hipMemcpyAsync(d_t, tI, n * 8, hipMemcpyHostToDevice, st) != hipSuccess || hipMemcpyAsync(d_imu, sImu, 3 * n * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(d_vis, sVis, 3 * n * 8, hipMemcpyHostToDevice, st) != hipSuccess) { cleanup(); return OICC_ERR_HIP; }
+    grid = int(std::min<size_t>((n + 255) / 256, size_t(grid_cap)));
+    return OICC_OK;
+  }
+  // returns the error, fills R (row major) and the bias; moments (optional): the 15 sums of rot_moments_kernel
+  double solve_closed_form(double td, double R[9], double b[3], double* moments = nullptr) {
     double h[16];
     if (hipMemsetAsync(d_acc, 0, 16 * 8, st) != hipSuccess) { ok = false; return 0.0; }
     hipLaunchKernelGGL(rot_moments_kernel, dim3(grid), dim3(256), 0, st, d_t, d_imu, d_vis, int(n), td, d_acc);
     if (hipMemcpyAsync(h, d_acc, 15 * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { ok = false; return 0.0; }
+    if (moments) std::memcpy(moments, h, 15 * sizeof(double));
     const double N = double(n);
     const double mi[3] = {h[0] / N, h[1] / N, h[2] / N}, mv[3] = {h[3] / N, h[4] / N, h[5] / N};
     double A[9];                                                       // P^T Q with centred P (imu), Q (vis)
@@ -255,26 +280,88 @@ extern "C" int oicc_estimate_imu_to_camera_rotation(int32_t device_ordinal, int6
     double e = 0.0;
     if (hipMemcpyAsync(&e, d_acc, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { ok = false; return 0.0; }
     return e;
-  };
+  }
+};
+
+int rot_select_device(int32_t device_ordinal) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device_ordinal < 0 || device_ordinal >= ndev) return OICC_ERR_NO_DEVICE;   // no CPU fallback
+  if (hipSetDevice(device_ordinal) != hipSuccess) return OICC_ERR_NO_DEVICE;
+  return OICC_OK;
+}
+
+}  // namespace
+
+extern "C" int oicc_estimate_imu_to_camera_rotation(int32_t device_ordinal, int64_t n_vis, const double* t_vis_s, const double* q_vis_xyzw,
+                                                    int64_t n_imu, const double* t_imu_s, const double* gyro_xyz, double dt_imu,
+                                                    int32_t estimate_gyro_bias, double q_imu_to_cam_xyzw[4], double* time_offset_imu_to_cam,
+                                                    double gyro_bias[3], double* alignment_error, int32_t* iterations) {
+  if (!t_vis_s || !q_vis_xyzw || !t_imu_s || !gyro_xyz || !q_imu_to_cam_xyzw || !time_offset_imu_to_cam || !gyro_bias || n_vis < 2 || n_imu < 2 || !(dt_imu > 0.0))
+    return OICC_ERR_INVALID_ARG;
+  if (int rc = rot_select_device(device_ordinal)) return rc;
+  RotationSeries S;
+  if (int rc = prepare_rotation_series(n_vis, t_vis_s, q_vis_xyzw, n_imu, t_imu_s, gyro_xyz, dt_imu, &S)) return rc;
+  RotationProbe P;
+  if (int rc = P.upload(S.tI.size(), S.tI.data(), S.sImu.data(), S.sVis.data(), kRotGridCap, estimate_gyro_bias)) return rc;
   // ---- golden-section search (cc:227-257)
   const double gRatio = (1.0 + std::sqrt(5.0)) / 2.0, tolerance = 1e-4, maxOffset = 1.0;
   double a = -maxOffset, b = maxOffset, c = b - (b - a) / gRatio, d = a + (b - a) / gRatio;
   double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, bias[3] = {0, 0, 0}, error = 0.0; int iter = 0;
-  while (ok && std::fabs(c - d) > tolerance) {
+  while (P.ok && std::fabs(c - d) > tolerance) {
     double Rc[9], Rd[9], bc[3], bd[3];
-    const double fc = solve_closed_form(c, Rc, bc);
-    const double fd = solve_closed_form(d, Rd, bd);
+    const double fc = P.solve_closed_form(c, Rc, bc);
+    const double fd = P.solve_closed_form(d, Rd, bd);
     if (fc < fd) { b = d; std::memcpy(R, Rc, sizeof(R)); if (estimate_gyro_bias) std::memcpy(bias, bc, sizeof(bias)); error = fc; }
     else { a = c; std::memcpy(R, Rd, sizeof(R)); if (estimate_gyro_bias) std::memcpy(bias, bd, sizeof(bias)); error = fd; }
     c = b - (b - a) / gRatio; d = a + (b - a) / gRatio;
     ++iter;
   }
-  cleanup();
-  if (!ok) return OICC_ERR_HIP;
+  P.cleanup();
+  if (!P.ok) return OICC_ERR_HIP;
   quat_from_rotation(R, q_imu_to_cam_xyzw);
   *time_offset_imu_to_cam = (b + a) / 2.0;
   if (estimate_gyro_bias) { gyro_bias[0] = bias[0]; gyro_bias[1] = bias[1]; gyro_bias[2] = bias[2]; }
   if (alignment_error) *alignment_error = error;
   if (iterations) *iterations = iter;
+  return OICC_OK;
+}
+
+// Debug exports (outside include/oicc_hip.h).
+// One SolveClosedForm per offset on a prepared series (times ts [n] ascending, smoothed rates imu / vis [n, 3]) through the
+// RotationProbe the calibration entry drives: the 15 moments, R (row major), the bias and the error of every offset.
+// grid_cap 0: the production cap of the probe kernels' grid; a positive value replaces it.
+extern "C" int oicc_debug_rotation_probe(int32_t device_ordinal, int64_t n, const double* ts, const double* imu, const double* vis, int32_t num_td,
+                                         const double* tds, int32_t estimate_bias, int32_t grid_cap, double* moments_out, double* R_out, double* b_out,
+                                         double* err_out) {
+  if (!ts || !imu || !vis || !tds || !moments_out || !R_out || !b_out || !err_out || n < 2 || n > INT32_MAX || num_td < 1 || grid_cap < 0) return OICC_ERR_INVALID_ARG;
+  for (int64_t i = 0; i < n; ++i) if (!std::isfinite(ts[i]) || (i > 0 && !(ts[i] > ts[i - 1]))) return OICC_ERR_INVALID_ARG;
+  for (int32_t i = 0; i < num_td; ++i) if (!std::isfinite(tds[i])) return OICC_ERR_INVALID_ARG;
+  if (int rc = rot_select_device(device_ordinal)) return rc;
+  RotationProbe P;
+  if (int rc = P.upload(size_t(n), ts, imu, vis, grid_cap > 0 ? grid_cap : kRotGridCap, estimate_bias)) return rc;
+  for (int32_t i = 0; i < num_td && P.ok; ++i) err_out[i] = P.solve_closed_form(tds[i], R_out + 9 * i, b_out + 3 * i, moments_out + 15 * i);
+  P.cleanup();
+  return P.ok ? OICC_OK : OICC_ERR_HIP;
+}
+
+// The host preparation alone (no device call): the IMU times of the common window, the smoothed gyroscope and visual rates.
+// *n_out: the number of samples; cap: the room (samples) of tI [cap], sImu, sVis [cap, 3].
+extern "C" int oicc_debug_rotation_prepare(int64_t n_vis, const double* t_vis_s, const double* q_vis_xyzw, int64_t n_imu, const double* t_imu_s,
+                                           const double* gyro_xyz, double dt_imu, int64_t cap, int64_t* n_out, double* tI, double* sImu, double* sVis) {
+  if (!t_vis_s || !q_vis_xyzw || !t_imu_s || !gyro_xyz || !n_out || !tI || !sImu || !sVis || n_vis < 2 || n_imu < 2 || !(dt_imu > 0.0) || cap < 0) return OICC_ERR_INVALID_ARG;
+  RotationSeries S;
+  if (int rc = prepare_rotation_series(n_vis, t_vis_s, q_vis_xyzw, n_imu, t_imu_s, gyro_xyz, dt_imu, &S)) return rc;
+  const int64_t n = int64_t(S.tI.size());
+  *n_out = n;
+  if (n > cap) return OICC_ERR_INVALID_ARG;
+  std::memcpy(tI, S.tI.data(), sizeof(double) * n); std::memcpy(sImu, S.sImu.data(), sizeof(double) * 3 * n); std::memcpy(sVis, S.sVis.data(), sizeof(double) * 3 * n);
+  return OICC_OK;
+}
+
+// The host Kabsch step alone (no device call): R (row major) from a 3x3 cross-covariance A (row major) of any rank.
+extern "C" int oicc_debug_rotation_kabsch(const double* A, double* R) {
+  if (!A || !R) return OICC_ERR_INVALID_ARG;
+  for (int k = 0; k < 9; ++k) if (!std::isfinite(A[k])) return OICC_ERR_INVALID_ARG;
+  kabsch_from_cross_covariance(A, R);
   return OICC_OK;
 }

@@ -48,19 +48,74 @@ __global__ void sew_reduce_kernel(const double* pw, int64_t nh, double bin_hz, d
   if (threadIdx.x == 0) { unsafeAtomicAdd(out, sm[0][0]); unsafeAtomicAdd(out + 1, sm[1][0]); }
 }
 
-struct SewDevice {
-  double* pw = nullptr; double* acc = nullptr; int64_t n = 0, nh = 0; double bin_hz = 0.0; hipStream_t st = nullptr; int evals = 0;
+constexpr int kSewGridCap = 1024;   // workgroups of the spectral reduction; longer spectra go round its grid-stride loop
+
+// The spectrum of one series on the device: buffers, stream and hipFFT plan for a (device, dims, n), the transform
+// (upload -> hipfftExecD2Z -> power kernel) and the two spectral sums for a trial knot spacing.  The calibration entry and the
+// debug entry below both drive this one object.
+// Buffers and plan are kept for the next call with the same (device, dims, n): get_sew_for_dataset.py calls the entry twice
+// per data set (accelerometer, gyroscope) and plan creation costs milliseconds.
+struct SewSpectrum {
+  int device = -1, dims = 0; int64_t n = 0, nh = 0;
+  double* d_sig = nullptr; hipfftDoubleComplex* d_spec = nullptr; double* pw = nullptr; double* acc = nullptr;
+  hipStream_t st = nullptr; hipfftHandle plan = 0; bool have_plan = false;
+  double bin_hz = 0.0; int evals = 0; int grid_cap = kSewGridCap;   // of the series loaded last
+  void release() {
+    if (have_plan) (void)hipfftDestroy(plan);
+    if (d_sig) (void)hipFree(d_sig); if (d_spec) (void)hipFree(d_spec); if (pw) (void)hipFree(pw); if (acc) (void)hipFree(acc);
+    if (st) (void)hipStreamDestroy(st);
+    *this = SewSpectrum();
+  }
+  // buffers and plan for (device, dims, n): kept when they fit, rebuilt when they do not
+  int bind(int device_ordinal, int dims_, int64_t n_) {
+    if (device == device_ordinal && dims == dims_ && n == n_) return OICC_OK;
+    release();
+    const int64_t nh_ = n_ / 2 + 1;
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess ||
+        hipMalloc(&d_sig, sizeof(double) * dims_ * n_) != hipSuccess || hipMalloc(&d_spec, sizeof(hipfftDoubleComplex) * dims_ * nh_) != hipSuccess ||
+        hipMalloc(&pw, sizeof(double) * nh_) != hipSuccess || hipMalloc(&acc, 2 * sizeof(double)) != hipSuccess) { release(); return OICC_ERR_HIP; }
+    int len = int(n_);
+    if (hipfftPlanMany(&plan, 1, &len, nullptr, 1, len, nullptr, 1, int(nh_), HIPFFT_D2Z, dims_) != HIPFFT_SUCCESS) { release(); return OICC_ERR_HIP; }
+    have_plan = true;
+    if (hipfftSetStream(plan, st) != HIPFFT_SUCCESS) { release(); return OICC_ERR_HIP; }
+    device = device_ordinal; dims = dims_; n = n_; nh = nh_;
+    return OICC_OK;
+  }
+  // signal [dims, n] (host) -> pw[0 .. n/2] on the device
+  int transform(const double* signal, double sample_rate, int cap) {
+    bin_hz = sample_rate / double(n); evals = 0; grid_cap = cap;
+    if (hipMemcpyAsync(d_sig, signal, sizeof(double) * dims * n, hipMemcpyHostToDevice, st) != hipSuccess) { release(); return OICC_ERR_HIP; }
+    if (hipfftExecD2Z(plan, d_sig, d_spec) != HIPFFT_SUCCESS) { release(); return OICC_ERR_HIP; }
+    hipLaunchKernelGGL(sew_power_kernel, dim3(int((nh + 255) / 256)), dim3(256), 0, st, d_spec, dims, n, nh, pw);
+    return OICC_OK;
+  }
+  // h[0] = sum_k pw[k], h[1] = sum_k pw[k] (1 - H(f_k, dt))^2
+  bool sums(double dt, double h[2]) {
+    if (hipMemsetAsync(acc, 0, 2 * sizeof(double), st) != hipSuccess) return false;
+    int grid = int((nh + 255) / 256); if (grid > grid_cap) grid = grid_cap;
+    hipLaunchKernelGGL(sew_reduce_kernel, dim3(grid), dim3(256), 0, st, pw, nh, bin_hz, dt, acc);
+    if (hipMemcpyAsync(h, acc, 2 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return false;
+    ++evals;
+    return true;
+  }
   // (signal energy, removed energy) for a knot spacing, both as sew.py's signal_energy (sum |.|^2 / n)
   bool energies(double dt, double* energy, double* removed) {
-    if (hipMemsetAsync(acc, 0, 2 * sizeof(double), st) != hipSuccess) return false;
-    int grid = int((nh + 255) / 256); if (grid > 1024) grid = 1024;
-    hipLaunchKernelGGL(sew_reduce_kernel, dim3(grid), dim3(256), 0, st, pw, nh, bin_hz, dt, acc);
     double h[2];
-    if (hipMemcpyAsync(h, acc, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return false;
-    *energy = h[0] / double(n); *removed = h[1] / double(n); ++evals;
+    if (!sums(dt, h)) return false;
+    *energy = h[0] / double(n); *removed = h[1] / double(n);
     return true;
   }
 };
+
+SewSpectrum g_sew;
+std::mutex g_sew_mutex;   // one call at a time: concurrent callers (other devices, other sizes) would rebuild each other's plan mid-use
+
+int sew_select_device(int32_t device_ordinal) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device_ordinal < 0 || device_ordinal >= ndev) return OICC_ERR_NO_DEVICE;   // no CPU fallback
+  if (hipSetDevice(device_ordinal) != hipSuccess) return OICC_ERR_NO_DEVICE;
+  return OICC_OK;
+}
 
 }  // namespace
 
@@ -68,9 +123,7 @@ extern "C" int oicc_sew_knot_spacing_and_variance(int32_t device_ordinal, int32_
                                                   const double* times, double quality, double min_dt, double max_dt,
                                                   double* dt_out, double* var_out, int32_t* num_evaluations) {
   if (!signal || !times || !dt_out || !var_out || dims < 1 || n < 8 || !(quality > 0.0 && quality < 1.0)) return OICC_ERR_INVALID_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device_ordinal < 0 || device_ordinal >= ndev) return OICC_ERR_NO_DEVICE;   // no CPU fallback
-  if (hipSetDevice(device_ordinal) != hipSuccess) return OICC_ERR_NO_DEVICE;
+  if (int rc = sew_select_device(device_ordinal)) return rc;
   // sample rate = 1 / mean(diff(times))  (sew.py:144)
   const double span = times[n - 1] - times[0];
   if (!(span > 0.0)) return OICC_ERR_INVALID_ARG;
@@ -78,36 +131,12 @@ extern "C" int oicc_sew_knot_spacing_and_variance(int32_t device_ordinal, int32_
   if (!(min_dt > 0.0)) min_dt = 1.0 / sample_rate;                       // sew.py:153-154
   if (!(max_dt > 0.0)) max_dt = (double(n) / 4.0) / sample_rate;         // sew.py:156-157
 
-  const int64_t nh = n / 2 + 1;
-  // device buffers, stream and the hipFFT plan are kept for the next call with the same (device, dims, n):
-  // get_sew_for_dataset.py calls this twice per data set (accelerometer, gyroscope) and plan creation costs milliseconds
-  struct Cache { int device = -1, dims = 0; int64_t n = 0; double* d_sig = nullptr; hipfftDoubleComplex* d_spec = nullptr;
-                 double* pw = nullptr; double* acc = nullptr; hipStream_t st = nullptr; hipfftHandle plan = 0; bool have_plan = false; };
-  static Cache C;
-  static std::mutex cache_mutex;   // one call at a time: concurrent callers (other devices, other sizes) would rebuild each other's plan mid-use
-  std::lock_guard<std::mutex> cache_lock(cache_mutex);
-  auto release = [&]() {
-    if (C.have_plan) (void)hipfftDestroy(C.plan);
-    if (C.d_sig) (void)hipFree(C.d_sig); if (C.d_spec) (void)hipFree(C.d_spec); if (C.pw) (void)hipFree(C.pw); if (C.acc) (void)hipFree(C.acc);
-    if (C.st) (void)hipStreamDestroy(C.st);
-    C = Cache();
-  };
-  if (C.device != device_ordinal || C.dims != dims || C.n != n) {
-    release();
-    if (hipStreamCreateWithFlags(&C.st, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&C.d_sig, sizeof(double) * dims * n) != hipSuccess || hipMalloc(&C.d_spec, sizeof(hipfftDoubleComplex) * dims * nh) != hipSuccess ||
-        hipMalloc(&C.pw, sizeof(double) * nh) != hipSuccess || hipMalloc(&C.acc, 2 * sizeof(double)) != hipSuccess) { release(); return OICC_ERR_HIP; }
-    int len = int(n);
-    if (hipfftPlanMany(&C.plan, 1, &len, nullptr, 1, len, nullptr, 1, int(nh), HIPFFT_D2Z, dims) != HIPFFT_SUCCESS) { release(); return OICC_ERR_HIP; }
-    C.have_plan = true;
-    if (hipfftSetStream(C.plan, C.st) != HIPFFT_SUCCESS) { release(); return OICC_ERR_HIP; }
-    C.device = device_ordinal; C.dims = dims; C.n = n;
-  }
-  SewDevice D; D.n = n; D.nh = nh; D.bin_hz = sample_rate / double(n); D.pw = C.pw; D.acc = C.acc; D.st = C.st;
-  int rc = OICC_OK;
-  if (hipMemcpyAsync(C.d_sig, signal, sizeof(double) * dims * n, hipMemcpyHostToDevice, D.st) != hipSuccess) { release(); return OICC_ERR_HIP; }
-  if (hipfftExecD2Z(C.plan, C.d_sig, C.d_spec) != HIPFFT_SUCCESS) { release(); return OICC_ERR_HIP; }
-  hipLaunchKernelGGL(sew_power_kernel, dim3(int((nh + 255) / 256)), dim3(256), 0, D.st, C.d_spec, dims, n, nh, D.pw);
+  std::lock_guard<std::mutex> lock(g_sew_mutex);
+  SewSpectrum& D = g_sew;
+  int rc = D.bind(device_ordinal, dims, n);
+  if (rc != OICC_OK) return rc;
+  rc = D.transform(signal, sample_rate, kSewGridCap);
+  if (rc != OICC_OK) return rc;
 
   // quality_func(dt) = max_remove / removed(dt), max_remove = signal_energy(Xhat) (1 - quality)  (sew.py:146-151)
   bool ok = true;
@@ -172,4 +201,24 @@ extern "C" int oicc_sew_knot_spacing_and_variance(int32_t device_ordinal, int32_
   if (num_evaluations) *num_evaluations = D.evals;
   if (!ok) rc = OICC_ERR_HIP;
   return rc;
+}
+
+// Debug export (outside include/oicc_hip.h): the power spectrum and the raw sums of the spectral reduction (not divided by n)
+// for a list of knot spacings, through the SewSpectrum the calibration entry drives.  grid_cap 0: the production cap of the
+// reduction's grid; a positive value replaces it (the grid-stride loop at a test-sized spectrum).
+extern "C" int oicc_debug_sew_spectrum(int32_t device_ordinal, int32_t dims, int64_t n, const double* signal, double sample_rate,
+                                       int32_t num_dt, const double* dts, int32_t grid_cap, double* pw_out, double* sums_out) {
+  if (!signal || !pw_out || dims < 1 || n < 8 || n > INT32_MAX || !(sample_rate > 0.0) || !std::isfinite(sample_rate) || num_dt < 0 || grid_cap < 0 ||
+      (num_dt > 0 && (!dts || !sums_out))) return OICC_ERR_INVALID_ARG;
+  for (int32_t i = 0; i < num_dt; ++i) if (!(dts[i] > 0.0) || !std::isfinite(dts[i])) return OICC_ERR_INVALID_ARG;
+  if (int rc = sew_select_device(device_ordinal)) return rc;
+  std::lock_guard<std::mutex> lock(g_sew_mutex);
+  SewSpectrum& D = g_sew;
+  int rc = D.bind(device_ordinal, dims, n);
+  if (rc != OICC_OK) return rc;
+  rc = D.transform(signal, sample_rate, grid_cap > 0 ? grid_cap : kSewGridCap);
+  if (rc != OICC_OK) return rc;
+  if (hipMemcpyAsync(pw_out, D.pw, sizeof(double) * D.nh, hipMemcpyDeviceToHost, D.st) != hipSuccess || hipStreamSynchronize(D.st) != hipSuccess) return OICC_ERR_HIP;
+  for (int32_t i = 0; i < num_dt; ++i) if (!D.sums(dts[i], sums_out + 2 * i)) return OICC_ERR_HIP;
+  return OICC_OK;
 }

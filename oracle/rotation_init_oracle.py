@@ -3,9 +3,12 @@
 numpy restatement of the reference's gyroscope-to-camera rotation / time-offset initialisation:
 ImuToCameraRotationEstimator::EstimateCameraImuRotation and SolveClosedForm
 (src/core/imu_to_camera_rotation_estimator.cc:39-274) with the helpers of src/utils/utils.cc:194-261.
-PARITY UNPINNED: the reference is C++ on Eigen / glog and cannot be built in this container, and it has no tests;
-this restatement is checked by recovering planted rotations / offsets (tests/test_rotation_init.py) and is written
-independently of the device path (vectorised numpy, numpy's SVD) so that the two can check each other.
+PINNED (solve_closed_form, prepare): the reference is C++ on Eigen / glog, cannot be built here and has no tests, so there is no
+golden of its own; tests/rotation_probe_restatement.py restates both functions from the reference's text in mpmath at 50 digits
+and tests/test_rotation_probe_restatement.py holds them to it at float64 rounding (the yardstick tables of that module), at exact
+ties, held and extrapolated samples, the Huber switch, the over-360 deg/s hold and both slerp branches.  The golden-section driver
+below is checked by recovering planted rotations / offsets (tests/test_rotation_init.py).  Written independently of the device
+path (vectorised numpy, numpy's SVD) so that the two can check each other.
 Reference quirks kept: blend towards sample idx+1 from the NEAREST sample (utils.cc:228-236,246-256), later window
 end (:139), Huber switch on the squared error (:113-118), rotation of the last better probe with the midpoint offset
 (:232-257).  Deviation (also in the device path): where the reference reads one element past the end the last sample is used.

@@ -35,6 +35,10 @@ def cases():
     out["handheld_endpoint"] = (s, t, 0.5, 0.005, 0.02)              # quality reached at max_dt: end-point return (sew.py:95-99)
     s, t = _handheld(3000, 100.0, 13, dims=1)
     out["single_axis_unreachable"] = (s[0], t, 0.999999, 0.05, 0.4)  # no dt satisfies: best dt of the back-off (sew.py:133-137)
+    # the shortest series the entry accepts (n = 8), the shortest odd one, and 16: default min/max dt, so that max_dt = n / 4 samples
+    for n, seed, dims in ((8, 17, 3), (9, 19, 1), (16, 23, 3)):
+        s, t = _handheld(n, 200.0, seed, dims=dims)
+        out["short_n%d_defaults" % n] = (s if dims > 1 else s[0], t, 0.9, None, None)
     return out
 
 

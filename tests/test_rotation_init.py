@@ -1,6 +1,6 @@
 """Gyroscope-to-camera rotation / time-offset initialisation (src/core/imu_to_camera_rotation_estimator.cc).
 
-* not gpu: the numpy oracle (oracle/rotation_init_oracle.py, parity unpinned -- the reference is unbuildable here) recovers
+* not gpu: the numpy oracle (oracle/rotation_init_oracle.py; its probe and preparation are pinned by tests/rotation_probe_restatement.py) recovers
   planted rotations, gyro biases and time offsets from synthetic data and has the properties the algorithm implies;
 * gpu: the device path (oicc_estimate_imu_to_camera_rotation) against the oracle: rotation 1e-9, offset identical
   (same golden-section path), bias 1e-9, error 1e-9 relative.
