@@ -19,6 +19,7 @@ SCALE = np.array([1.0, 1.0, 1.0, A.GYRO_SCALE, A.GYRO_SCALE, A.GYRO_SCALE])
 
 def channels(duration, rate, seed, **kw):
     # gravity left out: a 9.8 m/s^2 mean makes the restatement's own running sum too coarse for a 1e-8 comparison
+    # (gravity, and larger means, are tested against the exact reference in tests/test_gpu_allan_edges.py)
     tel, truth = synthetic.make_stationary_imu(duration=duration, rate=rate, seed=seed, gravity=(0.0, 0.0, 0.0), **kw)
     w = np.concatenate([tel["accelerometer"].T, tel["gyroscope"].T], axis=0)
     return w, tel["timestamps_ns"] * 1e-9, truth
