@@ -281,6 +281,8 @@ __device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* d
   const int a = A.a, a1 = a + 1;
   const bool shared_writer = !FOLD || blockIdx.x == 0;
   // ---- Z = X X^T (X = L^-T in rows 64..127): to global, or (LAST) into rows 0..63, where the factor is no longer needed
+  // (tile t on wave t puts 28 / 24 / 16 / 12 of the 80 MFMAs on the four SIMDs -- the waves w, w + 4, w + 8, w + 12 share one -- and a
+  // table that puts 20 on each was measured without gain: DESIGN §8-1)
   for (int t = wave; t < 10; t += NW) {
     int xt, yt; tri10(t, xt, yt);
     const bcr_v4d g = xt == 0 ? bcri_z_tile<0>(W, yt, li, lq) : (xt == 1 ? bcri_z_tile<1>(W, yt, li, lq) : (xt == 2 ? bcri_z_tile<2>(W, yt, li, lq) : bcri_z_tile<3>(W, yt, li, lq)));
@@ -509,11 +511,14 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
       for (int c = 0; c < 16; ++c) { const double v = colp[c * cstride]; av[c] = (act && (lane >= 16 || lane >= c)) ? v : 0.0; }
       if (PROF && prof) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
       BCR_MARK(6);
+      // ONE failure test per panel: a pivot that is not positive makes rsq NaN (negative, NaN) or inf (zero), so g0 = piv * y0, h1 and
+      // with them l are NaN in every lane; every later column of the panel takes an update with l and is NaN as well, its pivot
+      // included.  So !(pivot of column 15 > 0) is true exactly for the panels in which !(pivot > 0) holds at some column.
       bool bad = false;
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
         const double piv = bcr_readlane(av[c], c);
-        bad |= !(piv > 0.0);
+        if (c == 15) bad = !(piv > 0.0);
         const double y0 = __builtin_amdgcn_rsq(piv);
         const double g0 = piv * y0, h0 = 0.5 * y0;
         const double r0 = fma(-g0, h0, 0.5);

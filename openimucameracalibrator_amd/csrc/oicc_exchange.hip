@@ -415,6 +415,16 @@ int oicc_debug_lm_step(oicc_problem* p, int32_t flags, double radius, int32_t re
   hipStream_t st = p->stream;
   rc = system_at_current_point(p, local_pass(p->d_x.p, true), sb.scale, p->opt["jacobi_scaling"] != 0, 0.0); if (rc) return rc;
   if (p->opt["debug_poison_lds"] != 0.0) launch_lds_poison(st);
+  // (tests: a negative pivot at a chosen column -- the band diagonal there is -1 for this solve and its read-out, and put back behind them)
+  const int64_t plant = int64_t(p->opt["debug_plant_pivot"]);
+  double* const planted = plant >= 0 && plant < Pb ? p->ne.band() + plant * tl.W : nullptr;
+  double planted_was = 0.0;
+  if (planted != nullptr) {
+    const double neg = -1.0;
+    HIPCK(p, hipMemcpyAsync(&planted_was, planted, sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(p, hipMemcpyAsync(planted, &neg, sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCK(p, hipStreamSynchronize(st));
+  }
   const double min_diag = p->opt["min_lm_diagonal"], max_diag = p->opt["max_lm_diagonal"];
   if (nranks == 0) {
     if (launch_lm_solve(p->ne, tl, sb, radius, reuse_diagonal ? 1 : 0, min_diag, max_diag, st) != 0) { p->err = "solver geometry unsupported"; return OICC_ERR_UNSUPPORTED; }
@@ -427,6 +437,7 @@ int oicc_debug_lm_step(oicc_problem* p, int32_t flags, double radius, int32_t re
   HIPCK(p, d2h(scale, sb.scale, P)); HIPCK(p, d2h(diag, sb.diag, P)); HIPCK(p, d2h(D2, sb.D2, P)); HIPCK(p, d2h(step_s, sb.step_s, P));
   LmState hs;
   HIPCK(p, hipMemcpyAsync(&hs, p->d_state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
+  if (planted != nullptr) HIPCK(p, hipMemcpyAsync(planted, &planted_was, sizeof(double), hipMemcpyHostToDevice, st));
   HIPCK(p, hipStreamSynchronize(st));
   *chol_failed = hs.chol_failed;
   return OICC_OK;
