@@ -77,12 +77,20 @@ struct BcrArgs {
 #define BCR_RETURN_IF_DONE(A) do { if ((A).ctl != nullptr && (A).ctl->done != 0) return; } while (0)
 
 __device__ __forceinline__ void bcr_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// The LDS stores of this wave's lanes are visible to the loads of its other lanes behind this: LDS operations of ONE wave execute in
+// issue order, so this orders the compiler (wavefront-scope fences) and issues nothing -- no workgroup barrier, no wait.
+__device__ __forceinline__ void bcr_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 __device__ __forceinline__ double bcr_readlane(double v, int lane) {
   const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
   return __hiloint2double(hi, lo);
 }
 typedef double bcr_v4d __attribute__((ext_vector_type(4)));
+typedef double bcr_v2d __attribute__((ext_vector_type(2)));
 
 // lower-triangular tile index 0..9 -> (xt >= yt) in a 4x4 tile grid
 __device__ __forceinline__ void tri10(int t, int& xt, int& yt) {
@@ -203,7 +211,9 @@ __device__ __forceinline__ void bcr_corner_solve(double* C, double* da, int* fai
 // =====================================================================================================================
 constexpr int kBackWaves = 8;   // waves of a back-substitution workgroup (one level alone: bcri_backward_kernel)
 constexpr int kInvWaves = 16;   // (measured: 13.3 us per pivot against 14.5 with 8 waves, 17 with 4)
-constexpr int kInvLD = 145;   // 128 rows, + 16 (two panels' rows of one wave land in different banks), + 1
+constexpr int kInvLD = 145;   // 128 rows, + 16 (two panels' rows of one wave land in different banks; they hold kInvDgRow's copy), + 1
+constexpr int kInvMsDoubles = 384;   // multiplier strips of the three panel waves, 128 doubles each (bcri_invert_body); the tail's x0s (256)
+constexpr int kInvDgRow = 128;   // rows 128..143 of the columns j0..j0 + 15: the copy of a panel's diagonal tile the panel waves read (bcri_invert_body)
 
 // Z tile (xt, yt), xt >= yt, of X X^T: X(r, k) = 0 for k < r, the sum starts at the tile of the later rows
 template <int XT>
@@ -418,15 +428,16 @@ template <bool LAST, bool PROF, bool ZLDS = false, bool FOLD = false, class Load
 __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, LoadD load_d, const bool report = true, Park park = Park()) {
   constexpr int LD = kInvLD, NW = kInvWaves, NT = 64 * NW, NTILE = 20, SLOTS = (NTILE + NW - 1) / NW, RU = 128, NAW = 3, FLD = 65;
   static_assert(NW == 16, "the corner phases of block 0 take one tile per wave");
-  extern __shared__ double lds[];
+  extern __shared__ __attribute__((aligned(16))) double lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 15, lq = lane >> 4;
   double* const W = lds;                 // [64][LD] column major: rows 0..63 D_i -> L, rows 64..127 I -> L^-T
   double* const da = W + 64 * LD;        // [64] arrow solution (LAST)
   int* const failp = reinterpret_cast<int*>(da + 64);
-  double* const dg = da + 64 + 8;        // [16][16] copy of the current panel's diagonal tile (column major; see bcr_eliminate_kernel)
-  double* const Fs = dg + 256;           // LAST: [64][FLD] border rows of block 0, Fs[k * FLD + q]; ZLDS: the caller's parked border tiles and Ts
+  double* const ms = da + 64 + 8;        // [NAW][128] multiplier strips of the panel waves (below); the tail's x0s (256 doubles); 16-byte aligned
+  static_assert(kInvMsDoubles >= NAW * 128 && kInvMsDoubles >= 256 && ((64 * LD + 64 + 8) * 8) % 16 == 0, "ms");
+  double* const Fs = ms + kInvMsDoubles;           // LAST: [64][FLD] border rows of block 0, Fs[k * FLD + q]; ZLDS: the caller's parked border tiles and Ts
   double* const Cs = Fs + 64 * FLD;      // LAST: [a1][a1] the arrow corner (+ the side buffer's corner part), as A.Mc is laid out
   const int a1 = A.a + 1;
   double* Zg = A.Lf + (int64_t)i * (192 + a1) * 64;
@@ -473,7 +484,7 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
       const int e = tid + k * NT;
       const int c = e >> 6, r = e & 63;
       W[c * LD + r] = r >= c ? gd[k] : 0.0;
-      if (c < 16 && r < 16) dg[c * 16 + r] = r >= c ? gd[k] : 0.0;
+      if (c < 16 && r < 16) W[c * LD + kInvDgRow + r] = r >= c ? gd[k] : 0.0;
       W[c * LD + 64 + r] = r == c ? 1.0 : 0.0;
       if (LAST) Fs[c * FLD + r] = gf[k];
       if (LAST && e < a1 * a1) Cs[e] = gc[k];
@@ -495,7 +506,12 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
   }
   BCR_MARK(0);
   // Panels of 16 columns = one tile column (four LDS round trips and eight barriers per block instead of eight and sixteen).
-  // Panel waves: lanes 0..15 the panel's diagonal rows (from `dg`, redundantly in every panel wave), lanes 16..63 one row each.
+  // Panel waves: lanes 0..15 the panel's diagonal rows (redundantly in every panel wave), lanes 16..63 one row each.
+  // The diagonal rows are read from a COPY of the diagonal tile (wave 0 overwrites the tile in W while the waves 1, 2 may still read),
+  // which lives in the padding rows of the panel's own columns -- DG(c, r) = W[(j0 + c) * LD + kInvDgRow + r] -- so that all lanes
+  // load with ONE stride and the sixteen loads take immediate offsets.  Its upper triangle is a zero IN LDS (the fill; the write-back
+  // of the trailing update), and the rows of the lanes that are not active are loaded as they are: nothing reads what those lanes
+  // compute -- v_readlane takes lanes 0..15 only and the store leaves them out --, so the chain carries no select at all.
   const int prow = 16 + wave * 48 + (lane - 16);
   for (int p = 0; p < 4; ++p) {
     const int j0 = 16 * p;
@@ -504,16 +520,27 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
       // rows of X below the panel's last column are still zero
       const bool act = lane < 16 || (rho >= j0 + 16 && rho < RU && !(rho >= 64 && rho - 64 > j0 + 15));
       if (A.delay > 0 && wave > 0) for (int k = 0; k < A.delay; ++k) __builtin_amdgcn_s_sleep(16);
-      const double* colp = lane < 16 ? dg + lane : W + j0 * LD + (act ? rho : 0);
-      const int cstride = lane < 16 ? 16 : LD;
+      // (the compiler pairs the sixteen loads into eight ds_read2_b64, whose 8-bit offsets take a base address per pair)
+      const double* colp = W + j0 * LD + (lane < 16 ? kInvDgRow + lane : (act ? rho : 0));
       double av[16];
 #pragma unroll
-      for (int c = 0; c < 16; ++c) { const double v = colp[c * cstride]; av[c] = (act && (lane >= 16 || lane >= c)) ? v : 0.0; }
+      for (int c = 0; c < 16; ++c) av[c] = colp[c * LD];
       if (PROF && prof) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
       BCR_MARK(6);
       // ONE failure test per panel: a pivot that is not positive makes rsq NaN (negative, NaN) or inf (zero), so g0 = piv * y0, h1 and
       // with them l are NaN in every lane; every later column of the panel takes an update with l and is NaN as well, its pivot
       // included.  So !(pivot of column 15 > 0) is true exactly for the panels in which !(pivot > 0) holds at some column.
+      // The multipliers l(c2) of column c's updates: the one of column c + 1 -- the hop the next pivot waits for -- comes by
+      // v_readlane; those of the columns c + 2 .. 15 are read back from a 16-double strip of LDS private to the wave, into which
+      // lanes 0..15 store l: every lane reads the same address (a broadcast), two multipliers per ds_read_b128.  A v_readlane pair
+      // and the wait states behind it occupy the wave's issue slot, the LDS reads run beside the next column's rsq sequence
+      // (scripts/micro/chain_issue.hip).  Three strips in turn: the reads of column c are issued before the store of column c + 3.
+      // Every lane stores -- lanes 16..63 into 48 doubles behind the strips that nobody reads --: a store under `lane < 16` is a
+      // branch per column, and the updates then sink into the block of their use with every multiplier live until there (spills).
+      // A wave's 128 doubles: strip s at [16 s, 16 s + 16), the unread stores at [48 + 16 s, 96 + 16 s).
+      // The arithmetic and its order per entry are unchanged: av[c2] takes the updates of the columns 0 .. c2 - 1 in that order.
+      double* const strip_w = ms + wave * 128 + (lane < 16 ? lane : 32 + lane);
+      const double* const strip_r = ms + wave * 128;
       bool bad = false;
 #pragma unroll
       for (int c = 0; c < 16; ++c) {
@@ -527,10 +554,20 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
         const double u = (av[c] + av[c]) * h1;
         const double l = fma(u, r1, u);
         av[c] = l;
+        if (c < 14) {
+          strip_w[(c % 3) * 16] = l;
+          bcr_wave_sync();
+        }
+        if (c < 15) av[c + 1] = fma(-l, bcr_readlane(l, c + 1), av[c + 1]);
+        if (c < 14) {
+          double m[16];
 #pragma unroll
-        for (int c2 = c + 1; c2 < 16; ++c2) {
-          const double lc2 = bcr_readlane(l, c2);
-          av[c2] = fma(-l, lc2, av[c2]);
+          for (int c2 = c + 2; c2 < 16; ++c2) {   // (an odd c2 behind the first came with the pair before it)
+            if ((c2 & 1) == 0) { const bcr_v2d v = *reinterpret_cast<const bcr_v2d*>(strip_r + (c % 3) * 16 + c2); m[c2] = v[0]; m[c2 + 1] = v[1]; }
+            else if (c2 == c + 2) m[c2] = strip_r[(c % 3) * 16 + c2];
+          }
+#pragma unroll
+          for (int c2 = c + 2; c2 < 16; ++c2) av[c2] = fma(-l, m[c2], av[c2]);
         }
       }
       if (PROF && prof) { asm volatile("s_nop 0" :: "v"(av[15])); }
@@ -560,7 +597,10 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
           if (t_ct[k] == p + 1) {   // the next panel's columns go back to LDS
             double* dst = W + (16 * t_ct[k] + lq) * LD + 16 * t_rt[k] + li;
             dst[0] = acc[k][0]; dst[4 * LD] = acc[k][1]; dst[8 * LD] = acc[k][2]; dst[12 * LD] = acc[k][3];
-            if (t_rt[k] == t_ct[k]) { dg[lq * 16 + li] = acc[k][0]; dg[(lq + 4) * 16 + li] = acc[k][1]; dg[(lq + 8) * 16 + li] = acc[k][2]; dg[(lq + 12) * 16 + li] = acc[k][3]; }
+            if (t_rt[k] == t_ct[k]) {   // the panel waves' copy of the diagonal tile: its lower triangle, zeros above (column lq + 4 r, row li)
+              double* dd = W + (16 * t_ct[k] + lq) * LD + kInvDgRow + li;
+              dd[0] = li >= lq ? acc[k][0] : 0.0; dd[4 * LD] = li >= lq + 4 ? acc[k][1] : 0.0; dd[8 * LD] = li >= lq + 8 ? acc[k][2] : 0.0; dd[12 * LD] = li >= lq + 12 ? acc[k][3] : 0.0;
+            }
           }
         }
       }
@@ -570,7 +610,7 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
     BCR_MARK(4);
   }
   BCR_MARK(4);
-  bcri_tail<LAST, ZLDS, FOLD>(A, W, da, failp, Fs, Cs, Zg, tid, wave, lane, report, ttop, ytop, dg);
+  bcri_tail<LAST, ZLDS, FOLD>(A, W, da, failp, Fs, Cs, Zg, tid, wave, lane, report, ttop, ytop, ms);
   BCR_MARK(5);
   if (PROF && prof && lane == 0) for (int k = 0; k < 8; ++k) A.prof[k] = pc[k];
 #undef BCR_MARK
@@ -783,7 +823,7 @@ __global__ __launch_bounds__(256) void bcri_schur_kernel(BcrArgs A) {
 // arrays, so no global round trip stands behind the inversion.  Groups of a side the pivot has no neighbour on leave at once.  For
 // levels whose workgroups fit the chip at once (bcr_level_joined); level 0 is not among them while its inversions ride in the build
 // launch, whose workgroups still write the blocks the Schur updates land on.
-constexpr int kInvLdsDoubles = 64 * kInvLD + 64 + 8 + 256;                 // W, da, failp, dg of bcri_invert_body
+constexpr int kInvLdsDoubles = 64 * kInvLD + 64 + 8 + kInvMsDoubles;                 // W, da, failp, ms of bcri_invert_body
 constexpr int kJoinLdsDoubles = kInvLdsDoubles + 5 * 1024 + 16 * 68;       // + B_x tile, four B_y tiles ([64][16] each), Ts
 __global__ __launch_bounds__(64 * kInvWaves) void bcri_invert_schur_kernel(BcrArgs A) {
   BCR_RETURN_IF_DONE(A);
@@ -816,7 +856,7 @@ __global__ __launch_bounds__(64 * kInvWaves) void bcri_invert_schur_kernel(BcrAr
       for (int t = 0; t < 4; ++t) P[1024 * (1 + t) + tid] = by[t];
     });
   // (bcri_tail ended with a workgroup barrier: Z_i is in rows 0..63 of W, the parked tiles are visible)
-  extern __shared__ double lds[];
+  extern __shared__ __attribute__((aligned(16))) double lds[];
   const double* W = lds;
   const double* P = lds + kInvLdsDoubles;
   double (*Ts)[68] = reinterpret_cast<double (*)[68]>(lds + kInvLdsDoubles + 5 * 1024);
@@ -1220,7 +1260,7 @@ static int64_t bcr_carve_doubles(int nblk, int a1) { return (int64_t)nblk * 4096
 // Arrow limit: the kernels take up to 63 arrow columns (four 16-row border tiles).  Round 2 saw sporadic NaN pivots with more than
 // two border tiles; the cause was the in-place read of the panel's diagonal block by waves that start a panel late (see the panel
 // factorisation and tests/test_gpu_parity.py::test_bcr_wide_borders_and_the_panel_hazard, which makes it deterministic); with the
-// `dg` copy the limit is the kernels' own.
+// copy of the diagonal tile (kInvDgRow) the limit is the kernels' own.
 // (the limit travels with the problem: SolveBuffers::bcr_max_border, option bcr_max_border; the workspace is sized for the kernels' own limit)
 bool bcr_applicable(const TangentLayout& tl) { return tl.Pb >= 1 && tl.hb <= 64 && tl.a + 1 <= 64; }
 int64_t bcr_workspace_doubles(const TangentLayout& tl) {

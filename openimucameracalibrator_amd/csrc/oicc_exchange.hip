@@ -425,6 +425,28 @@ int oicc_debug_lm_step(oicc_problem* p, int32_t flags, double radius, int32_t re
     HIPCK(p, hipMemcpyAsync(planted, &neg, sizeof(double), hipMemcpyHostToDevice, st));
     HIPCK(p, hipStreamSynchronize(st));
   }
+  // (tests: option debug_plant_tile = a band column `col`.  The sixteen variables of col's 16-aligned tile are cut off from every other
+  // variable for this solve and its read-out -- their band couplings and arrow rows are zero, the diagonal stays -- and the tile's one
+  // off-diagonal entry is H(col + 2, col) = 0.875 sqrt(H(col, col) H(col + 2, col + 2)): the system stays positive definite, and of the
+  // tile's Cholesky multipliers only l(col + 2, col) is not zero.  Put back behind the read-out.)
+  const int64_t tcol = int64_t(p->opt["debug_plant_tile"]), W = tl.W;
+  std::vector<double> band_was, et_was;
+  if (tcol >= 0 && (tcol & 15) <= 13 && (tcol | 15) < Pb && W > 2) {
+    band_was.resize(size_t(Pb * W)); et_was.resize(size_t(a * Pb));
+    HIPCK(p, hipMemcpyAsync(band_was.data(), p->ne.band(), band_was.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (a > 0) HIPCK(p, hipMemcpyAsync(et_was.data(), p->ne.Et(), et_was.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCK(p, hipStreamSynchronize(st));
+    std::vector<double> b = band_was, e = et_was;
+    const int64_t t0 = tcol & ~int64_t(15), t1 = t0 + 16;
+    for (int64_t j = std::max<int64_t>(0, t0 - W + 1); j < t1; ++j)
+      for (int64_t k = 1; k < W && j + k < Pb; ++k)
+        if ((j >= t0 && j < t1) || (j + k >= t0 && j + k < t1)) b[size_t(j * W + k)] = 0.0;
+    b[size_t(tcol * W + 2)] = 0.875 * std::sqrt(b[size_t(tcol * W)] * b[size_t((tcol + 2) * W)]);
+    for (int64_t q = 0; q < a; ++q) for (int64_t j = t0; j < t1; ++j) e[size_t(q * Pb + j)] = 0.0;
+    HIPCK(p, hipMemcpyAsync(p->ne.band(), b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    if (a > 0) HIPCK(p, hipMemcpyAsync(p->ne.Et(), e.data(), e.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    HIPCK(p, hipStreamSynchronize(st));
+  }
   const double min_diag = p->opt["min_lm_diagonal"], max_diag = p->opt["max_lm_diagonal"];
   if (nranks == 0) {
     if (launch_lm_solve(p->ne, tl, sb, radius, reuse_diagonal ? 1 : 0, min_diag, max_diag, st) != 0) { p->err = "solver geometry unsupported"; return OICC_ERR_UNSUPPORTED; }
@@ -438,6 +460,10 @@ int oicc_debug_lm_step(oicc_problem* p, int32_t flags, double radius, int32_t re
   LmState hs;
   HIPCK(p, hipMemcpyAsync(&hs, p->d_state.p, sizeof(hs), hipMemcpyDeviceToHost, st));
   if (planted != nullptr) HIPCK(p, hipMemcpyAsync(planted, &planted_was, sizeof(double), hipMemcpyHostToDevice, st));
+  if (!band_was.empty()) {
+    HIPCK(p, hipMemcpyAsync(p->ne.band(), band_was.data(), band_was.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    if (a > 0) HIPCK(p, hipMemcpyAsync(p->ne.Et(), et_was.data(), et_was.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  }
   HIPCK(p, hipStreamSynchronize(st));
   *chol_failed = hs.chol_failed;
   return OICC_OK;
