@@ -857,6 +857,12 @@ int oicc_debug_bcr_join_plan(int32_t n, int32_t ghost, int32_t odd_only, int32_t
  * nlev - 2 alone.  It is folded when on != 0 (option bcr_fold_back), the solve is the whole band (ghost == 0, b0 == 0) and the plan
  * has an even number of levels >= 2.  Returns that level, -1 when nothing folds, INT32_MIN for n < 1, b0 < 0 or a ghost other than 0 / 1. */
 int oicc_debug_bcr_fold_plan(int32_t n, int32_t ghost, int32_t odd_only, int32_t b0, int32_t on);
+/* The 16-column panel chain of the 64 x 64 inversions as its events in program order (host arithmetic only; the table the kernels
+ * expand): rows of six int32 {type, column, gap, k, c2, aux} -- type 0 pivot read of `column`; 1 strip store of column k = `column`,
+ * every lane, the doubles [aux, c2) of the wave's strips; 2 LDS read of the multiplier m(k, c2) at double aux; 3 deferred update
+ * av[c2] -= l(k) m(k, c2) issued in gap `gap` of `column`; 4 the v_readlane hop (column, column + 1).  Returns the number of events;
+ * rows beyond cap are not written. */
+int oicc_debug_bcr_chain_schedule(int32_t* rows, int32_t cap);
 /* out3 = [1 if the last whole-band cyclic-reduction solve of the problem folded a level that way, the solves that did so far, option
  * bcr_fold_back].  OICC_ERR_INVALID_ARG for a null argument. */
 int oicc_debug_bcr_fold_info(oicc_problem* problem, int64_t out3[3]);

@@ -36,6 +36,7 @@
 #include "lm_decide.h"
 #include "lm_launch.h"
 #include "lm_retract.h"
+#include "bcr_chain_body.h"
 #include "../../include/oicc_hip.h"
 
 namespace oicc {
@@ -77,18 +78,7 @@ struct BcrArgs {
 #define BCR_RETURN_IF_DONE(A) do { if ((A).ctl != nullptr && (A).ctl->done != 0) return; } while (0)
 
 __device__ __forceinline__ void bcr_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// The LDS stores of this wave's lanes are visible to the loads of its other lanes behind this: LDS operations of ONE wave execute in
-// issue order, so this orders the compiler (wavefront-scope fences) and issues nothing -- no workgroup barrier, no wait.
-__device__ __forceinline__ void bcr_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-__device__ __forceinline__ double bcr_readlane(double v, int lane) {
-  const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);
-  const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
-  return __hiloint2double(hi, lo);
-}
+// (bcr_wave_sync, bcr_readlane: bcr_chain_body.h)
 typedef double bcr_v4d __attribute__((ext_vector_type(4)));
 typedef double bcr_v2d __attribute__((ext_vector_type(2)));
 
@@ -212,7 +202,7 @@ __device__ __forceinline__ void bcr_corner_solve(double* C, double* da, int* fai
 constexpr int kBackWaves = 8;   // waves of a back-substitution workgroup (one level alone: bcri_backward_kernel)
 constexpr int kInvWaves = 16;   // (measured: 13.3 us per pivot against 14.5 with 8 waves, 17 with 4)
 constexpr int kInvLD = 145;   // 128 rows, + 16 (two panels' rows of one wave land in different banks; they hold kInvDgRow's copy), + 1
-constexpr int kInvMsDoubles = 384;   // multiplier strips of the three panel waves, 128 doubles each (bcri_invert_body); the tail's x0s (256)
+constexpr int kInvMsDoubles = 3 * kChainStripDoubles;   // multiplier strips of the three panel waves, a strip per column of a panel (bcr_chain_body.h); the tail's x0s (256)
 constexpr int kInvDgRow = 128;   // rows 128..143 of the columns j0..j0 + 15: the copy of a panel's diagonal tile the panel waves read (bcri_invert_body)
 
 // Z tile (xt, yt), xt >= yt, of X X^T: X(r, k) = 0 for k < r, the sum starts at the tile of the later rows
@@ -283,13 +273,33 @@ __device__ __forceinline__ double bcri_back_body(const double (&lv)[kBackRows], 
 // fields are A.o, A.s, A.p, A.m.  Every workgroup does the last block's work with identical bits and then the back substitution of
 // its own pivot from LDS; only workgroup 0 stores what they all share and raises A.fail.
 template <bool LAST, bool ZLDS, bool FOLD>
-__device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* da, int* failp, const double* Fs, const double* Cs, double* Zg, int tid, int wave, int lane, bool report,
-                                          const double (&ttop)[16], const double ytop, double* x0s) {
+__device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* da, int* failp, const double* Fs, const double* Cs, double* Zg, int tid, int wave, int lane, bool report, double* x0s) {
   static_assert(!FOLD || LAST, "the folded level follows the last block");
   constexpr int LD = kInvLD, NW = kInvWaves, NT = 64 * NW, FLD = 65;
   const int li = lane & 15, lq = lane >> 4;
   const int a = A.a, a1 = a + 1;
   const bool shared_writer = !FOLD || blockIdx.x == 0;
+  // rows of T of the top level's pivots: [0..4) the rows against the last block and [4..8) the arrow rows of the pivot right of it
+  // (whose left neighbour it is: rows 0..63 of T), [8..16) the same of the pivot left of it (rows 64..127); wave 0 / 1 their rhs row.
+  // Final since the top level's launch ended.  Issued HERE, ahead of Z = X X^T, which is longer than a global round trip, and not at
+  // the head of the kernel: they are 34 registers, which the panel chain needs for the multipliers of its deferred updates.
+  double ttop[16], ytop = 0.0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) ttop[k] = 0.0;
+  if (LAST && (A.top_l >= 0 || A.top_r >= 0)) {
+    const int64_t ru64 = (int64_t)(192 + a1) * 64;
+    const double* Tr = A.Lf + (A.top_r >= 0 ? A.top_r : 0) * ru64 + 4096;
+    const double* Tl = A.Lf + (A.top_l >= 0 ? A.top_l : 0) * ru64 + 4096;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int r = wave + NW * k;
+      if (A.top_r >= 0) { ttop[k] = Tr[r * 64 + lane]; if (r < A.a) ttop[4 + k] = Tr[(128 + r) * 64 + lane]; }
+      if (A.top_l >= 0) { ttop[8 + k] = Tl[(64 + r) * 64 + lane]; if (r < A.a) ttop[12 + k] = Tl[(128 + r) * 64 + lane]; }
+    }
+    if (wave == 0 && A.top_r >= 0) ytop = Tr[(128 + A.a) * 64 + lane];
+    if (wave == 1 && A.top_l >= 0) ytop = Tl[(128 + A.a) * 64 + lane];
+    asm volatile("" ::: "memory");   // (issued here, used after the corner: the loads must not sink to their use)
+  }
   // ---- Z = X X^T (X = L^-T in rows 64..127): to global, or (LAST) into rows 0..63, where the factor is no longer needed
   // (tile t on wave t puts 28 / 24 / 16 / 12 of the 80 MFMAs on the four SIMDs -- the waves w, w + 4, w + 8, w + 12 share one -- and a
   // table that puts 20 on each was measured without gain: DESIGN §8-1)
@@ -435,8 +445,8 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
   double* const W = lds;                 // [64][LD] column major: rows 0..63 D_i -> L, rows 64..127 I -> L^-T
   double* const da = W + 64 * LD;        // [64] arrow solution (LAST)
   int* const failp = reinterpret_cast<int*>(da + 64);
-  double* const ms = da + 64 + 8;        // [NAW][128] multiplier strips of the panel waves (below); the tail's x0s (256 doubles); 16-byte aligned
-  static_assert(kInvMsDoubles >= NAW * 128 && kInvMsDoubles >= 256 && ((64 * LD + 64 + 8) * 8) % 16 == 0, "ms");
+  double* const ms = da + 64 + 8;        // [NAW][kChainStripDoubles] multiplier strips of the panel waves (below); the tail's x0s (256 doubles); 16-byte aligned
+  static_assert(kInvMsDoubles >= NAW * kChainStripDoubles && (kChainStripDoubles * 8) % 16 == 0 && kInvMsDoubles >= 256 && ((64 * LD + 64 + 8) * 8) % 16 == 0, "ms");
   double* const Fs = ms + kInvMsDoubles;           // LAST: [64][FLD] border rows of block 0, Fs[k * FLD + q]; ZLDS: the caller's parked border tiles and Ts
   double* const Cs = Fs + 64 * FLD;      // LAST: [a1][a1] the arrow corner (+ the side buffer's corner part), as A.Mc is laid out
   const int a1 = A.a + 1;
@@ -449,25 +459,6 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
   long long tprev = prof ? clock64() : 0;
 #define BCR_MARK(k) do { if (PROF && prof) { const long long tn_ = clock64(); pc[k] += tn_ - tprev; tprev = tn_; } } while (0)
   if (tid == 0) *failp = 0;
-  // rows of T of the top level's pivots: [0..4) the rows against the last block and [4..8) the arrow rows of the pivot right of it
-  // (whose left neighbour it is: rows 0..63 of T), [8..16) the same of the pivot left of it (rows 64..127); wave 0 / 1 their rhs row
-  double ttop[16], ytop = 0.0;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) ttop[k] = 0.0;
-  if (LAST && (A.top_l >= 0 || A.top_r >= 0)) {
-    const int64_t ru64 = (int64_t)(192 + a1) * 64;
-    const double* Tr = A.Lf + (A.top_r >= 0 ? A.top_r : 0) * ru64 + 4096;
-    const double* Tl = A.Lf + (A.top_l >= 0 ? A.top_l : 0) * ru64 + 4096;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int r = wave + NW * k;
-      if (A.top_r >= 0) { ttop[k] = Tr[r * 64 + lane]; if (r < A.a) ttop[4 + k] = Tr[(128 + r) * 64 + lane]; }
-      if (A.top_l >= 0) { ttop[8 + k] = Tl[(64 + r) * 64 + lane]; if (r < A.a) ttop[12 + k] = Tl[(128 + r) * 64 + lane]; }
-    }
-    if (wave == 0 && A.top_r >= 0) ytop = Tr[(128 + A.a) * 64 + lane];
-    if (wave == 1 && A.top_l >= 0) ytop = Tl[(128 + A.a) * 64 + lane];
-    asm volatile("" ::: "memory");   // (issued here, used after the corner: the loads must not sink to their use)
-  }
   {
     constexpr int PER = 4096 / NT;
     double gd[PER], gf[PER], gc[PER];
@@ -527,49 +518,15 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
       for (int c = 0; c < 16; ++c) av[c] = colp[c * LD];
       if (PROF && prof) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
       BCR_MARK(6);
+      // The chain: bcr_chain_panel (bcr_chain_body.h) under the table kChainSchedule (bcr_chain_schedule.h).  Per column the dependent
+      // sequence pivot -> rsq -> two Goldschmidt steps -> l -> v_readlane hop onto the next column, and in the gaps between its steps
+      // seven or eight of the panel's 105 deferred updates av[c2] = fma(-l(k), m(k, c2), av[c2]), whose multipliers m(k, c2) are read
+      // back as LDS broadcasts from column k's strip -- every column of a panel has a strip of its own, every lane stores.
       // ONE failure test per panel: a pivot that is not positive makes rsq NaN (negative, NaN) or inf (zero), so g0 = piv * y0, h1 and
       // with them l are NaN in every lane; every later column of the panel takes an update with l and is NaN as well, its pivot
       // included.  So !(pivot of column 15 > 0) is true exactly for the panels in which !(pivot > 0) holds at some column.
-      // The multipliers l(c2) of column c's updates: the one of column c + 1 -- the hop the next pivot waits for -- comes by
-      // v_readlane; those of the columns c + 2 .. 15 are read back from a 16-double strip of LDS private to the wave, into which
-      // lanes 0..15 store l: every lane reads the same address (a broadcast), two multipliers per ds_read_b128.  A v_readlane pair
-      // and the wait states behind it occupy the wave's issue slot, the LDS reads run beside the next column's rsq sequence
-      // (scripts/micro/chain_issue.hip).  Three strips in turn: the reads of column c are issued before the store of column c + 3.
-      // Every lane stores -- lanes 16..63 into 48 doubles behind the strips that nobody reads --: a store under `lane < 16` is a
-      // branch per column, and the updates then sink into the block of their use with every multiplier live until there (spills).
-      // A wave's 128 doubles: strip s at [16 s, 16 s + 16), the unread stores at [48 + 16 s, 96 + 16 s).
       // The arithmetic and its order per entry are unchanged: av[c2] takes the updates of the columns 0 .. c2 - 1 in that order.
-      double* const strip_w = ms + wave * 128 + (lane < 16 ? lane : 32 + lane);
-      const double* const strip_r = ms + wave * 128;
-      bool bad = false;
-#pragma unroll
-      for (int c = 0; c < 16; ++c) {
-        const double piv = bcr_readlane(av[c], c);
-        if (c == 15) bad = !(piv > 0.0);
-        const double y0 = __builtin_amdgcn_rsq(piv);
-        const double g0 = piv * y0, h0 = 0.5 * y0;
-        const double r0 = fma(-g0, h0, 0.5);
-        const double g1 = fma(g0, r0, g0), h1 = fma(h0, r0, h0);
-        const double r1 = fma(-g1, h1, 0.5);
-        const double u = (av[c] + av[c]) * h1;
-        const double l = fma(u, r1, u);
-        av[c] = l;
-        if (c < 14) {
-          strip_w[(c % 3) * 16] = l;
-          bcr_wave_sync();
-        }
-        if (c < 15) av[c + 1] = fma(-l, bcr_readlane(l, c + 1), av[c + 1]);
-        if (c < 14) {
-          double m[16];
-#pragma unroll
-          for (int c2 = c + 2; c2 < 16; ++c2) {   // (an odd c2 behind the first came with the pair before it)
-            if ((c2 & 1) == 0) { const bcr_v2d v = *reinterpret_cast<const bcr_v2d*>(strip_r + (c % 3) * 16 + c2); m[c2] = v[0]; m[c2 + 1] = v[1]; }
-            else if (c2 == c + 2) m[c2] = strip_r[(c % 3) * 16 + c2];
-          }
-#pragma unroll
-          for (int c2 = c + 2; c2 < 16; ++c2) av[c2] = fma(-l, m[c2], av[c2]);
-        }
-      }
+      const bool bad = bcr_chain_panel<kChainSchedule>(av, ms + wave * kChainStripDoubles + lane, ms + wave * kChainStripDoubles);
       if (PROF && prof) { asm volatile("s_nop 0" :: "v"(av[15])); }
       BCR_MARK(7);
       if (act && (lane >= 16 || wave == 0)) {
@@ -610,7 +567,7 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
     BCR_MARK(4);
   }
   BCR_MARK(4);
-  bcri_tail<LAST, ZLDS, FOLD>(A, W, da, failp, Fs, Cs, Zg, tid, wave, lane, report, ttop, ytop, ms);
+  bcri_tail<LAST, ZLDS, FOLD>(A, W, da, failp, Fs, Cs, Zg, tid, wave, lane, report, ms);
   BCR_MARK(5);
   if (PROF && prof && lane == 0) for (int k = 0; k < 8; ++k) A.prof[k] = pc[k];
 #undef BCR_MARK
@@ -1615,4 +1572,42 @@ extern "C" int oicc_debug_bcr_fold_plan(int32_t n, int32_t ghost, int32_t odd_on
   if (n < 1 || b0 < 0 || ghost < 0 || ghost > 1) return INT32_MIN;   // (-1 is an answer here: no level folds)
   const oicc::BcrLevels L = oicc::bcr_plan(n, ghost, odd_only != 0);
   return oicc::bcr_fold_level(on, false, ghost, b0, L);
+}
+
+// The panel chain of bcri_invert_body as a list of events in PROGRAM order (host arithmetic only; tests): what bcr_chain_column
+// (bcr_chain_body.h) expands from the table kChainSchedule, restated step by step.  One row of six per event:
+//   {type, column, gap, k, c2, aux}
+//   type 0  pivot read of `column` (v_readlane)                         type 3  deferred update av[c2] = fma(-l(k), m(k, c2), av[c2])
+//   type 1  strip store of `column` = k; every lane stores: the doubles  type 4  the v_readlane hop: update (column, column + 1)
+//           [aux, c2) of the wave's strips, of which [aux, aux + 16) are strip k
+//   type 2  LDS read of m(k, c2) = double aux of the wave's strips, issued in `column` for an update of column + 1
+// gap: where in the column (bcr_chain_schedule.h); -1 for the types 0, 1, 4.  Returns the number of events; rows beyond `cap` are
+// not written.
+extern "C" int oicc_debug_bcr_chain_schedule(int32_t* rows, int32_t cap) {
+  const oicc::BcrChainSchedule& S = oicc::kChainSchedule;
+  int n = 0;
+  auto put = [&](int type, int column, int gap, int k, int c2, int aux) {
+    if (rows != nullptr && n < cap) { int32_t* r = rows + 6 * (int64_t)n; r[0] = type; r[1] = column; r[2] = gap; r[3] = k; r[4] = c2; r[5] = aux; }
+    ++n;
+  };
+  auto gap = [&](int c, int g) {
+    const int first = oicc::bcr_chain_gap_first(S, c, g);
+    for (int q = 0; q < S.gap_n[c][g]; ++q) put(3, c, g, S.k[c][first + q], S.c2[c][first + q], 0);
+  };
+  auto loads = [&](int c, bool fresh) {   // issued in column c for the updates of column c + 1
+    for (int u = 0; u < S.total[c + 1]; ++u)
+      if ((S.k[c + 1][u] == c) == fresh) put(2, c, fresh ? 7 : 1, S.k[c + 1][u], S.c2[c + 1][u], 16 * S.k[c + 1][u] + S.c2[c + 1][u]);
+  };
+  for (int c = 0; c < 16; ++c) {
+    put(0, c, -1, c, c, 0);
+    gap(c, 0);
+    if (c < 14) loads(c, false);
+    for (int g = 1; g <= 6; ++g) gap(c, g);
+    if (c < 15) {
+      if (c < 14) { put(1, c, -1, c, 16 * c + 64, 16 * c); loads(c, true); }
+      gap(c, 7);
+      put(4, c, -1, c, c + 1, 0);
+    }
+  }
+  return n;
 }

@@ -427,11 +427,12 @@ int oicc_debug_lm_step(oicc_problem* p, int32_t flags, double radius, int32_t re
   }
   // (tests: option debug_plant_tile = a band column `col`.  The sixteen variables of col's 16-aligned tile are cut off from every other
   // variable for this solve and its read-out -- their band couplings and arrow rows are zero, the diagonal stays -- and the tile's one
-  // off-diagonal entry is H(col + 2, col) = 0.875 sqrt(H(col, col) H(col + 2, col + 2)): the system stays positive definite, and of the
-  // tile's Cholesky multipliers only l(col + 2, col) is not zero.  Put back behind the read-out.)
-  const int64_t tcol = int64_t(p->opt["debug_plant_tile"]), W = tl.W;
+  // off-diagonal entry is H(col + d, col) = 0.875 sqrt(H(col, col) H(col + d, col + d)): the system stays positive definite, and of the
+  // tile's Cholesky multipliers only l(col + d, col) is not zero.  d = option debug_plant_tile_dist, 2 <= d <= 15 - (col & 15); 2 unless
+  // set.  Put back behind the read-out.)
+  const int64_t tcol = int64_t(p->opt["debug_plant_tile"]), tdist = int64_t(p->opt["debug_plant_tile_dist"]), W = tl.W;
   std::vector<double> band_was, et_was;
-  if (tcol >= 0 && (tcol & 15) <= 13 && (tcol | 15) < Pb && W > 2) {
+  if (tcol >= 0 && tdist >= 2 && tdist <= 15 - (tcol & 15) && (tcol | 15) < Pb && W > tdist) {
     band_was.resize(size_t(Pb * W)); et_was.resize(size_t(a * Pb));
     HIPCK(p, hipMemcpyAsync(band_was.data(), p->ne.band(), band_was.size() * sizeof(double), hipMemcpyDeviceToHost, st));
     if (a > 0) HIPCK(p, hipMemcpyAsync(et_was.data(), p->ne.Et(), et_was.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -441,7 +442,7 @@ int oicc_debug_lm_step(oicc_problem* p, int32_t flags, double radius, int32_t re
     for (int64_t j = std::max<int64_t>(0, t0 - W + 1); j < t1; ++j)
       for (int64_t k = 1; k < W && j + k < Pb; ++k)
         if ((j >= t0 && j < t1) || (j + k >= t0 && j + k < t1)) b[size_t(j * W + k)] = 0.0;
-    b[size_t(tcol * W + 2)] = 0.875 * std::sqrt(b[size_t(tcol * W)] * b[size_t((tcol + 2) * W)]);
+    b[size_t(tcol * W + tdist)] = 0.875 * std::sqrt(b[size_t(tcol * W)] * b[size_t((tcol + tdist) * W)]);
     for (int64_t q = 0; q < a; ++q) for (int64_t j = t0; j < t1; ++j) e[size_t(q * Pb + j)] = 0.0;
     HIPCK(p, hipMemcpyAsync(p->ne.band(), b.data(), b.size() * sizeof(double), hipMemcpyHostToDevice, st));
     if (a > 0) HIPCK(p, hipMemcpyAsync(p->ne.Et(), e.data(), e.size() * sizeof(double), hipMemcpyHostToDevice, st));

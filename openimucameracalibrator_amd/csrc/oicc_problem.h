@@ -287,6 +287,7 @@ struct oicc_problem {
     opt["bcr_join_max_workgroups"] = 0;   // the workgroup budget of a joined level; 0: the device's compute units
     opt["bcr_fold_back"] = 1;          // 1: a whole-band solve of an even number of levels runs the back substitution of level nlev - 2 inside the last block's launch, one workgroup per pivot, each repeating the last block's work (kernels_bcr.hip: bcri_last_backward_kernel); 0: bcri_invert_kernel<true, false>, then bcri_backward_kernel on that level (A/B runs, tests)
     opt["debug_plant_tile"] = -1;    // oicc_debug_lm_step only (tests): >= 0: a band column; its 16-aligned diagonal tile is diagonal but for the entry (column + 2, column) and cut off from every other variable for that solve and its read-out
+    opt["debug_plant_tile_dist"] = 2;   // with debug_plant_tile (tests): the planted entry is (column + d, column), 2 <= d <= 15 - (column & 15); another value plants nothing
     opt["debug_plant_pivot"] = -1;  // oicc_debug_lm_step only (tests): >= 0: the band diagonal of this column is -1 for that solve and its read-out, which makes the pivot there negative whatever the damping
     opt["debug_check_ne"] = 0;   // 1: before every linear solve compare the current normal equations with a host copy taken when they became current
     opt["debug_sync"] = 0;       // 1: drain the stream after every pass (debugging of inter-kernel hazards)
