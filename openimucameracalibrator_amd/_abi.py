@@ -243,10 +243,23 @@ INNER_ROUTES = ("set_kernel<0>", "set_kernel<1>", "set_kernel<2>", "wave_kernel"
 INNER_KINDS = ("so3", "r3", "T_i_c", "gravity", "line_delay", "accl_bias", "gyro_bias", "accl_intrinsics", "gyro_intrinsics", "point")   # InnerKind, csrc/inner_plan.h
 
 
-def bind_inner_debug(lib, name):
+def bind_inner_debug(lib, name, table=INNER_DEBUG_SIGNATURES):
     fn = getattr(lib, name)  # AttributeError = missing symbol: fail loudly
-    fn.restype, fn.argtypes = INNER_DEBUG_SIGNATURES[name]
+    fn.restype, fn.argtypes = table[name]
     return fn
+
+
+# The option tables of the two problem objects (csrc/oicc_options.def, csrc/oicc_ba_options.def) and what an option holds (device
+# library only, outside include/oicc_hip.h: csrc/oicc_problem.hip, csrc/oicc_ba.hip); bound on first use (bind_option_debug).
+OPTION_DEBUG_SIGNATURES = {
+    "oicc_debug_option_table": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_char_p), c_dp]),   # (which: 0 oicc_problem, 1 oicc_ba; index) -> number of options
+    "oicc_debug_get_option": (C.c_int, [H, C.c_char_p, c_dp]),
+    "oicc_debug_ba_get_option": (C.c_int, [HB, C.c_char_p, c_dp]),
+}
+
+
+def bind_option_debug(lib, name):
+    return bind_inner_debug(lib, name, OPTION_DEBUG_SIGNATURES)
 
 
 # IMU noise characterisation (oicc_allan_* in include/oicc_hip.h): name -> (restype, argtypes).  A table of its own:

@@ -13,7 +13,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <string>
 #include <vector>
 
@@ -22,6 +21,7 @@
 #include "lm_launch.h"
 #include "ba_device.h"
 #include "covariance.h"
+#include "oicc_options.h"
 
 using namespace oicc;
 
@@ -39,7 +39,7 @@ struct oicc_ba {
   std::vector<int64_t> chunk_c0; std::vector<int32_t> chunk_n, chunk_view;
   double intr[kBaIntr] = {0};
   bool meas_dirty = true, x_dirty = true;
-  std::map<std::string, double> opt;
+  OiccBaOptions opt;   // oicc_ba_options.def
   std::vector<oicc_iteration> trace;
   DevBuf<double> d_x, d_xc, d_u, d_v, d_ne, d_Mb, d_Mt, d_Mc, d_scale, d_diag, d_D2, d_step, d_ws, d_out;
   DevBuf<int32_t> d_pid, d_chunk_n, d_chunk_view, d_iters, d_corner_view, d_pobs, d_pchunk_n, d_pchunk_point, d_point_tangent;
@@ -55,17 +55,6 @@ struct oicc_ba {
   DevBuf<int32_t> d_cvChunk0;
   DevBuf<double> d_cvChunkA, d_cvChunkE, d_cvSv, d_cvChunkC, d_cvC, d_cvAinv, d_cvW, d_cvPart, d_cvZth, d_cvTh, d_cvPose, d_cvCross;
   DevBuf<BaCovResult> d_cvRes;
-  oicc_ba() {
-    // theia::BundleAdjustmentOptions defaults [EXT]; the rest are the Ceres 2.1 defaults [EXT] Theia leaves alone
-    opt["function_tolerance"] = 1e-6; opt["parameter_tolerance"] = 1e-8; opt["gradient_tolerance"] = 1e-10;
-    opt["initial_trust_region_radius"] = 1e4; opt["max_trust_region_radius"] = 1e12;
-    opt["min_trust_region_radius"] = 1e-32; opt["min_relative_decrease"] = 1e-3;
-    opt["min_lm_diagonal"] = 1e-6; opt["max_lm_diagonal"] = 1e32; opt["jacobi_scaling"] = 1;
-    opt["max_num_consecutive_invalid_steps"] = 5; opt["huber_width"] = 1.345; opt["verbose"] = 0;
-    opt["solver_algorithm"] = 0; opt["num_threads"] = 0;
-    opt["covariance_timing"] = 0;          // 1: HIP events around the two parts of an estimate (oicc_ba_get_covariance_timing)
-    opt["covariance_min_rcond"] = 1e-12;   // oicc_ba_estimate_covariance: the value of the spline path (oicc_estimate_covariance)
-  }
 };
 
 namespace {
@@ -153,7 +142,7 @@ int prepare(oicc_ba* p, int flags, int mask, Prepared* out) {
   int a = 0;
   for (int k = 0; k < kBaIntr; ++k) d.intr_col[k] = (k < p->n_intr && ((mask >> k) & 1)) ? a++ : -1;
   d.n_arrow = a;
-  d.huber = p->opt["huber_width"];
+  d.huber = p->opt.huber_width;
   d.dbg_res = nullptr;
   d.corner_view = p->d_corner_view.p; d.pobs = p->d_pobs.p; d.pchunk_c0 = p->d_pchunk_c0.p; d.pchunk_n = p->d_pchunk_n.p;
   d.pchunk_point = p->d_pchunk_point.p; d.n_pchunks = int32_t(p->pchunk_c0.size()); d.n_points = int64_t(p->pts.size() / 4);
@@ -221,7 +210,9 @@ void oicc_ba_destroy(oicc_ba* p) {
 }
 const char* oicc_ba_last_error(const oicc_ba* p) { return p ? p->err.c_str() : "null problem"; }
 int oicc_ba_set_option(oicc_ba* p, const char* name, double value) {
-  auto it = p->opt.find(name); ARG(p, it != p->opt.end(), std::string("unknown option ") + name); it->second = value; p->cov.valid = false; return OICC_OK; }
+  double* v = find_option(p->opt, name); ARG(p, v, std::string("unknown option ") + name); *v = value; p->cov.valid = false; return OICC_OK; }
+int oicc_debug_ba_get_option(oicc_ba* p, const char* name, double* value) {   // outside include/oicc_hip.h (tests/test_options_table.py)
+  const double* v = find_option(p->opt, name); ARG(p, v, std::string("unknown option ") + name); *value = *v; return OICC_OK; }
 int oicc_ba_set_camera(oicc_ba* p, int32_t model, const double* intrinsics, int32_t n) {
   ARG(p, n > 0 && n <= kBaIntr && intrinsics, "bad intrinsics");
   p->model = model; p->n_intr = n; std::memset(p->intr, 0, sizeof(p->intr)); std::memcpy(p->intr, intrinsics, n * sizeof(double));
@@ -311,7 +302,7 @@ int oicc_ba_estimate_covariance(oicc_ba* p, int32_t flags, int32_t mask, oicc_ba
     if (cv.big) HIPCK(p, hipStreamSynchronize(st));
     cv.layout_ok = true;
   }
-  const bool timed = p->opt["covariance_timing"] != 0;
+  const bool timed = p->opt.covariance_timing != 0;
   cv.timed = false;
   if (timed) { for (hipEvent_t& e : p->cov_ev) if (!e) HIPCK(p, hipEventCreate(&e)); HIPCK(p, hipEventRecord(p->cov_ev[0], st)); }
   rc = eval_pass(p, P, p->d_x.p, true); if (rc) return rc;
@@ -366,7 +357,7 @@ int oicc_ba_estimate_covariance(oicc_ba* p, int32_t flags, int32_t mask, oicc_ba
   double zmax; std::memcpy(&zmax, &res.zmax_bits, sizeof(zmax));
   info->rcond = (bad || !(zmax > 0.0)) ? 0.0 : 1.0 / zmax;
   if (bad) info->first_bad = res.bad_pivot;
-  if (bad || info->rcond < p->opt["covariance_min_rcond"]) {
+  if (bad || info->rcond < p->opt.covariance_min_rcond) {
     info->status = OICC_COV_RANK_DEFICIENT;
     std::snprintf(buf, sizeof(buf), "oicc_ba_estimate_covariance: rank deficient (%s, rcond %.3e)", bad ? "a pivot is not positive" : "below covariance_min_rcond", info->rcond);
     p->err = buf; return OICC_OK;
@@ -418,12 +409,12 @@ int oicc_ba_optimize(oicc_ba* p, int32_t max_iters, int32_t flags, int32_t mask,
   S.num_parameters_tangent = P; S.band_dim = tl.Pb; S.arrow_dim = tl.a; S.half_bandwidth = tl.hb;
   S.num_residual_blocks = int64_t(p->pid.size()); S.num_residuals = 2 * S.num_residual_blocks;   // constant points keep their blocks (cost)
   p->trace.clear();
-  const double ftol = p->opt["function_tolerance"], ptol = p->opt["parameter_tolerance"], gtol = p->opt["gradient_tolerance"];
-  double radius = p->opt["initial_trust_region_radius"]; const double max_radius = p->opt["max_trust_region_radius"];
-  const double min_radius = p->opt["min_trust_region_radius"], min_rel_dec = p->opt["min_relative_decrease"];
-  const double min_diag = p->opt["min_lm_diagonal"], max_diag = p->opt["max_lm_diagonal"];
-  const int max_invalid = int(p->opt["max_num_consecutive_invalid_steps"]);
-  const bool verbose = p->opt["verbose"] != 0;
+  const double ftol = p->opt.function_tolerance, ptol = p->opt.parameter_tolerance, gtol = p->opt.gradient_tolerance;
+  double radius = p->opt.initial_trust_region_radius; const double max_radius = p->opt.max_trust_region_radius;
+  const double min_radius = p->opt.min_trust_region_radius, min_rel_dec = p->opt.min_relative_decrease;
+  const double min_diag = p->opt.min_lm_diagonal, max_diag = p->opt.max_lm_diagonal;
+  const int max_invalid = int(p->opt.max_num_consecutive_invalid_steps);
+  const bool verbose = p->opt.verbose != 0;
   double decrease_factor = 2.0; bool reuse_diagonal = false;
   double cost = 0.0, gmax = 0.0;
   auto finish = [&](int term, const char* msg) {
@@ -438,9 +429,9 @@ int oicc_ba_optimize(oicc_ba* p, int32_t max_iters, int32_t flags, int32_t mask,
     HIPCK(p, hipStreamSynchronize(st)); return OICC_OK; };
   double t0 = now_s();
   rc = eval_pass(p, PR, p->d_x.p, true); if (rc) return rc;
-  SolveBuffers sb{p->d_Mb.p, p->d_Mt.p, p->d_Mc.p, p->d_scale.p, p->d_diag.p, p->d_D2.p, p->d_step.p, p->d_state.p, nullptr, p->d_ws.p, (int64_t)p->d_ws.n, 0, int(p->opt["solver_algorithm"])};
+  SolveBuffers sb{p->d_Mb.p, p->d_Mt.p, p->d_Mc.p, p->d_scale.p, p->d_diag.p, p->d_D2.p, p->d_step.p, p->d_state.p, nullptr, p->d_ws.p, (int64_t)p->d_ws.n, 0, int(p->opt.solver_algorithm)};
   HIPCK(p, hipMemsetAsync(p->d_state.p, 0, sizeof(LmState), st));
-  if (P > 0) { launch_lm_scale(ne, tl, sb.scale, p->opt["jacobi_scaling"] != 0, st); launch_lm_gradmax(ne, P, p->d_state.p, st); }
+  if (P > 0) { launch_lm_scale(ne, tl, sb.scale, p->opt.jacobi_scaling != 0, st); launch_lm_gradmax(ne, P, p->d_state.p, st); }
   rc = read_back(); if (rc) return rc;
   cost = pin->cost; gmax = pin->st.gradient_max_norm;
   S.seconds_jacobian += now_s() - t0;
@@ -518,9 +509,9 @@ int oicc_ba_optimize_views(oicc_ba* p, int32_t max_iters, int32_t flags, int32_t
   p->cov.valid = false;
   Prepared PR; int rc = prepare(p, flags, 0, &PR); if (rc) return rc;
   ARG(p, !PR.points && PR.d.pose_dim > 0, "no pose component is variable");
-  BaLmOptions o{p->opt["function_tolerance"], p->opt["parameter_tolerance"], p->opt["gradient_tolerance"], p->opt["initial_trust_region_radius"],
-                p->opt["max_trust_region_radius"], p->opt["min_trust_region_radius"], p->opt["min_relative_decrease"], p->opt["min_lm_diagonal"],
-                p->opt["max_lm_diagonal"], p->opt["jacobi_scaling"] != 0 ? 1 : 0, int32_t(p->opt["max_num_consecutive_invalid_steps"]), max_iters};
+  BaLmOptions o{p->opt.function_tolerance, p->opt.parameter_tolerance, p->opt.gradient_tolerance, p->opt.initial_trust_region_radius,
+                p->opt.max_trust_region_radius, p->opt.min_trust_region_radius, p->opt.min_relative_decrease, p->opt.min_lm_diagonal,
+                p->opt.max_lm_diagonal, p->opt.jacobi_scaling != 0 ? 1 : 0, int32_t(p->opt.max_num_consecutive_invalid_steps), max_iters};
   if (!p->d_iters.resize(std::max<int64_t>(p->nv, 1)) || !p->d_out.resize(std::max<int64_t>(p->nv, 1))) { p->err = "hipMalloc"; return OICC_ERR_HIP; }
   launch_ba_optimize_views(p->d_x.p, PR.d, o, p->d_iters.p, p->d_out.p, p->stream);
   HIPCK(p, hipGetLastError());

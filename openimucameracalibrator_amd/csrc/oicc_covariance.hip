@@ -61,7 +61,7 @@ int oicc_estimate_covariance(oicc_problem* p, int32_t flags, oicc_covariance_inf
   const CovBuffers cb{cv.d_s.p, cv.d_Cs.p, cv.d_Sc.p, cv.d_Zaa.p, cv.d_aa.p, cv.d_zb.p, cv.d_G.p, cv.d_cov3.p, cv.d_cross.p, cv.d_zs.p, cv.d_flags.p};
   SolveBuffers sb = solve_buffers(p);
   sb.force_p = 1; sb.algo = 1;   // the single-workgroup sweep (window 64 / 128), or the global-memory factorisation where its LDS does not fit
-  const bool poison = p->opt["debug_poison_lds"] != 0.0;
+  const bool poison = p->opt.debug_poison_lds != 0.0;
   struct Events { hipEvent_t e[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } events;   // (released on every return)
   hipEvent_t* const ev = events.e;
   for (int k = 0; k < 5; ++k) HIPCK(p, hipEventCreate(&ev[k]));
@@ -106,7 +106,7 @@ int oicc_estimate_covariance(oicc_problem* p, int32_t flags, oicc_covariance_inf
   double zmax = 0.0; bool bad = hs.chol_failed != 0 || hflags[1] != 0;
   for (int i = 0; i < P; ++i) { if (!(zs[i] > 0.0) || !std::isfinite(zs[i])) bad = true; else zmax = std::max(zmax, zs[i]); }
   info->rcond = (bad || zmax <= 0.0) ? 0.0 : 1.0 / zmax;
-  if (bad || info->rcond < p->opt["covariance_min_rcond"]) {
+  if (bad || info->rcond < p->opt.covariance_min_rcond) {
     info->status = OICC_COV_RANK_DEFICIENT;
     char buf[160]; std::snprintf(buf, sizeof(buf), "oicc_estimate_covariance: rank deficient (%s, rcond %.3e)", bad ? "a pivot is not positive" : "below covariance_min_rcond", info->rcond);
     p->err = buf; cv.info = *info; return OICC_OK;

@@ -101,7 +101,7 @@ int owner_exchange_agree(oicc_problem* p, hipStream_t st, bool* use) {
   bool dist_applies = false;
   const bool dist_ok = dist_solve_prepare(p, &dist_applies);
   uint32_t hm = op.hash;
-  for (const char* name : {"distributed_solve", "solver_algorithm", "bcr_max_border"}) hm = hash_mix(hm, p->opt[name]);   // (the choice of solve is part of what the ranks must agree on)
+  for (const double v : {p->opt.distributed_solve, p->opt.solver_algorithm, p->opt.bcr_max_border}) hm = hash_mix(hm, v);   // (the choice of solve is part of what the ranks must agree on)
   const double h = double(op.valid ? (hm & 0xfffffu) : 0u);
   double v[4] = {owner_exchange_ready(p) && dist_ok ? 1.0 : 0.0, 1.0, h, h * h};
   if (!p->d_xagree.resize(4)) { p->err = "hipMalloc exchange agreement"; return OICC_ERR_HIP; }
@@ -112,7 +112,7 @@ int owner_exchange_agree(oicc_problem* p, hipStream_t st, bool* use) {
   op.agreed = v[0] == v[1] && v[1] == double(p->shard_n) && v[1] * v[3] == v[2] * v[2];
   op.agreed_gen = p->layout_gen;
   p->dist.usable = op.agreed && dist_applies; p->dist.gen = p->layout_gen;
-  if (!op.agreed && p->opt["verbose"] != 0.0) std::printf("[oicc] rank %d: owner-computes exchange not agreed on by all ranks (ready %g of %g, shard size %d): all-reduce of the packed buffer\n", p->shard_rank, v[0], v[1], p->shard_n);
+  if (!op.agreed && p->opt.verbose != 0.0) std::printf("[oicc] rank %d: owner-computes exchange not agreed on by all ranks (ready %g of %g, shard size %d): all-reduce of the packed buffer\n", p->shard_rank, v[0], v[1], p->shard_n);
   *use = op.agreed;
   return OICC_OK;
 }
@@ -164,9 +164,9 @@ static bool dist_solve_prepare(oicc_problem* p, bool* applies) {
   const oicc_problem::OwnerPlan& op = p->owner;
   const TangentLayout& tl = p->tl;
   const int n = p->shard_n;
-  if (n < 2 || n > 64 || !op.valid || p->opt["distributed_solve"] == 0.0) return true;
-  const int algo = int(p->opt["solver_algorithm"]);
-  if (!bcr_applicable(tl) || tl.a + 1 > int(p->opt["bcr_max_border"]) || (algo != 0 && algo != 4)) return true;
+  if (n < 2 || n > 64 || !op.valid || p->opt.distributed_solve == 0.0) return true;
+  const int algo = int(p->opt.solver_algorithm);
+  if (!bcr_applicable(tl) || tl.a + 1 > int(p->opt.bcr_max_border) || (algo != 0 && algo != 4)) return true;
   const int nblk = (tl.Pb + 63) / 64;
   ds.b0.assign(size_t(n) + 1, 0);
   for (int k = 0; k <= n; ++k) ds.b0[size_t(k)] = k == n ? nblk : op.cut[size_t(k)] / 64;
@@ -298,7 +298,7 @@ namespace oicc {
 static bool dist_emulated_applies(const oicc_problem* p, int nranks) {
   const TangentLayout& tl = p->tl;
   const int nblk = (tl.Pb + 63) / 64;
-  return nranks >= 2 && nranks <= 64 && nranks <= nblk && bcr_applicable(tl) && tl.a + 1 <= int(p->opt.at("bcr_max_border"));
+  return nranks >= 2 && nranks <= 64 && nranks <= nblk && bcr_applicable(tl) && tl.a + 1 <= int(p->opt.bcr_max_border);
 }
 // Runs it on `sb` (scale and LmState set by the caller; the solution lands in sb.step_s): every rank's forward part in turn (into its
 // slot of the gather buffer: the "all-gather" is a no-op in one address space), then every rank's top system + local back
@@ -324,7 +324,7 @@ static int dist_solve_emulated(oicc_problem* p, const SolveBuffers& sb, int nran
   }
   EventPair ev;
   if (ms) { HIPCK(p, hipEventCreate(&ev.a)); HIPCK(p, hipEventCreate(&ev.b)); }
-  const double min_diag = p->opt["min_lm_diagonal"], max_diag = p->opt["max_lm_diagonal"];
+  const double min_diag = p->opt.min_lm_diagonal, max_diag = p->opt.max_lm_diagonal;
   const int runs = ms ? reps + 1 : 1;
   for (int phase = 0; phase < 2; ++phase)
     for (int k = 0; k < nranks; ++k) {
@@ -387,7 +387,7 @@ int oicc_debug_dist_solve_emulated(oicc_problem* p, int32_t flags, int32_t nrank
   int rc = prepare(p, flags); if (rc) return rc;
   ARG(p, out != nullptr && dist_emulated_applies(p, nranks), "distributed solve: ranks / geometry");
   SolveBuffers sb = solve_buffers(p); sb.radius = radius;
-  rc = system_at_current_point(p, local_pass(p->d_x.p, true), sb.scale, p->opt["jacobi_scaling"] != 0, 0.0); if (rc) return rc;
+  rc = system_at_current_point(p, local_pass(p->d_x.p, true), sb.scale, p->opt.jacobi_scaling != 0, 0.0); if (rc) return rc;
   rc = dist_solve_emulated(p, sb, nranks, 0, std::max<int>(repeats, 1), out + 2); if (rc) return rc;
   return read_solve_residual(p, sb, &out[0], nullptr, &out[1]);
 }
@@ -413,10 +413,10 @@ int oicc_debug_lm_step(oicc_problem* p, int32_t flags, double radius, int32_t re
   if (!solve) return OICC_OK;
   ARG(p, route.route != kRouteNone, "debug_lm_step: solver geometry unsupported");
   hipStream_t st = p->stream;
-  rc = system_at_current_point(p, local_pass(p->d_x.p, true), sb.scale, p->opt["jacobi_scaling"] != 0, 0.0); if (rc) return rc;
-  if (p->opt["debug_poison_lds"] != 0.0) launch_lds_poison(st);
+  rc = system_at_current_point(p, local_pass(p->d_x.p, true), sb.scale, p->opt.jacobi_scaling != 0, 0.0); if (rc) return rc;
+  if (p->opt.debug_poison_lds != 0.0) launch_lds_poison(st);
   // (tests: a negative pivot at a chosen column -- the band diagonal there is -1 for this solve and its read-out, and put back behind them)
-  const int64_t plant = int64_t(p->opt["debug_plant_pivot"]);
+  const int64_t plant = int64_t(p->opt.debug_plant_pivot);
   double* const planted = plant >= 0 && plant < Pb ? p->ne.band() + plant * tl.W : nullptr;
   double planted_was = 0.0;
   if (planted != nullptr) {
@@ -430,7 +430,7 @@ int oicc_debug_lm_step(oicc_problem* p, int32_t flags, double radius, int32_t re
   // off-diagonal entry is H(col + d, col) = 0.875 sqrt(H(col, col) H(col + d, col + d)): the system stays positive definite, and of the
   // tile's Cholesky multipliers only l(col + d, col) is not zero.  d = option debug_plant_tile_dist, 2 <= d <= 15 - (col & 15); 2 unless
   // set.  Put back behind the read-out.)
-  const int64_t tcol = int64_t(p->opt["debug_plant_tile"]), tdist = int64_t(p->opt["debug_plant_tile_dist"]), W = tl.W;
+  const int64_t tcol = int64_t(p->opt.debug_plant_tile), tdist = int64_t(p->opt.debug_plant_tile_dist), W = tl.W;
   std::vector<double> band_was, et_was;
   if (tcol >= 0 && tdist >= 2 && tdist <= 15 - (tcol & 15) && (tcol | 15) < Pb && W > tdist) {
     band_was.resize(size_t(Pb * W)); et_was.resize(size_t(a * Pb));
@@ -448,7 +448,7 @@ int oicc_debug_lm_step(oicc_problem* p, int32_t flags, double radius, int32_t re
     if (a > 0) HIPCK(p, hipMemcpyAsync(p->ne.Et(), e.data(), e.size() * sizeof(double), hipMemcpyHostToDevice, st));
     HIPCK(p, hipStreamSynchronize(st));
   }
-  const double min_diag = p->opt["min_lm_diagonal"], max_diag = p->opt["max_lm_diagonal"];
+  const double min_diag = p->opt.min_lm_diagonal, max_diag = p->opt.max_lm_diagonal;
   if (nranks == 0) {
     if (launch_lm_solve(p->ne, tl, sb, radius, reuse_diagonal ? 1 : 0, min_diag, max_diag, st) != 0) { p->err = "solver geometry unsupported"; return OICC_ERR_UNSUPPORTED; }
   } else {
@@ -489,12 +489,12 @@ int oicc_debug_lm_retract(oicc_problem* p, int32_t flags, double radius, int64_t
   if (!run) return OICC_OK;
   hipStream_t st = p->stream;
   SolveBuffers sb = solve_buffers(p);
-  rc = system_at_current_point(p, local_pass(p->d_x.p, true), sb.scale, p->opt["jacobi_scaling"] != 0, 0.0); if (rc) return rc;
+  rc = system_at_current_point(p, local_pass(p->d_x.p, true), sb.scale, p->opt.jacobi_scaling != 0, 0.0); if (rc) return rc;
   auto d2h = [&](double* dst, const double* src, int64_t count) { return count <= 0 ? hipSuccess : hipMemcpyAsync(dst, src, size_t(count) * sizeof(double), hipMemcpyDeviceToHost, st); };
   LmState hs;
   HIPCK(p, hipMemsetAsync(p->d_xc.p, 0xff, size_t(N) * sizeof(double), st));
   bool fused = false;
-  rc = lm_solve_and_retract(p, sb, radius, 0, p->opt["min_lm_diagonal"], p->opt["max_lm_diagonal"], st, &fused, /*local=*/true); if (rc) return rc;
+  rc = lm_solve_and_retract(p, sb, radius, 0, p->opt.min_lm_diagonal, p->opt.max_lm_diagonal, st, &fused, /*local=*/true); if (rc) return rc;
   HIPCK(p, hipGetLastError());
   HIPCK(p, d2h(xc_loop, p->d_xc.p, N));
   HIPCK(p, hipMemcpyAsync(&hs, p->d_state.p, sizeof(hs), hipMemcpyDeviceToHost, st));

@@ -307,15 +307,15 @@ void build_inner_plan_host(oicc_problem* p, const InnerPlanOptions& o, double t_
 }
 InnerPlanOptions inner_plan_options(oicc_problem* p, int flags, int64_t layout_gen) {   // (main thread: reads the option map, asks the runtime)
   InnerPlanOptions o;
-  o.flags = flags; o.gs_unit = p->opt["gs_unit_loss"] != 0.0; o.general_kernel = p->opt["debug_inner_general_kernel"] != 0.0;
-  o.resident_wgs = inner_set_resident_capacity(p->n_cu); o.shared_share = std::min(1.0, std::max(0.0, p->opt["inner_shared_residency"])); o.layout_gen = layout_gen;
-  o.wave_blocks = int(p->opt["inner_wave_blocks"]); o.n_cu = p->n_cu; o.big_slots = int(p->opt["inner_shared_launch_slots"]);
+  o.flags = flags; o.gs_unit = p->opt.gs_unit_loss != 0.0; o.general_kernel = p->opt.debug_inner_general_kernel != 0.0;
+  o.resident_wgs = inner_set_resident_capacity(p->n_cu); o.shared_share = std::min(1.0, std::max(0.0, p->opt.inner_shared_residency)); o.layout_gen = layout_gen;
+  o.wave_blocks = int(p->opt.inner_wave_blocks); o.n_cu = p->n_cu; o.big_slots = int(p->opt.inner_shared_launch_slots);
   return o;
 }
 void start_inner_plan(oicc_problem* p, int flags, int64_t layout_gen) {
   oicc_problem::InnerPlan& ip = p->inner;
   if (p->plan_thread.joinable()) p->plan_thread.join();
-  const bool gs_unit = p->opt["gs_unit_loss"] != 0.0;
+  const bool gs_unit = p->opt.gs_unit_loss != 0.0;
   if (ip.flags == flags && ip.layout_gen == layout_gen && ip.gs_unit == gs_unit && !ip.blocks.empty()) return;   // current
   p->plan_job = inner_plan_options(p, flags, layout_gen);
   p->plan_job_valid = true;
@@ -323,7 +323,7 @@ void start_inner_plan(oicc_problem* p, int flags, int64_t layout_gen) {
 }
 int build_inner_plan(oicc_problem* p, int flags) {
   oicc_problem::InnerPlan& ip = p->inner;
-  const bool gs_unit = p->opt["gs_unit_loss"] != 0.0;
+  const bool gs_unit = p->opt.gs_unit_loss != 0.0;
   const double t0 = now_s();
   if (p->plan_thread.joinable()) p->plan_thread.join();
   const bool prebuilt = p->plan_job_valid && p->plan_job.flags == flags && p->plan_job.layout_gen == p->layout_gen && p->plan_job.gs_unit == gs_unit;
@@ -348,7 +348,7 @@ int build_inner_plan(oicc_problem* p, int flags) {
   if (any_wave) launch_inner_records(view_data(p), imu_data(p->acc, p->d_acc), imu_data(p->gyr, p->d_gyr), ip.d_rec[0].p, ip.d_rec[1].p, ip.d_rec[2].p, st);   // (the measurements are on the device: prepare() ran)
   HIPCK(p, hipMemsetAsync(ip.d_lm_iterations.p, 0, sizeof(unsigned long long), st));
   ip.lm_iterations = 0;                 // host mirror of the device counter that was just cleared (oicc_optimize reports the difference)
-  if (p->opt["verbose"] >= 2.0) std::printf("[oicc] inner plan: %zu blocks, %zu sets, %zu workgroups; host ms: blocks + neighbourhoods %.3f, independent sets %.3f, runs + workgroups %.3f (%s: waited %.3f), device buffers %.3f\n",
+  if (p->opt.verbose >= 2.0) std::printf("[oicc] inner plan: %zu blocks, %zu sets, %zu workgroups; host ms: blocks + neighbourhoods %.3f, independent sets %.3f, runs + workgroups %.3f (%s: waited %.3f), device buffers %.3f\n",
                                            ip.blocks.size(), ip.group_first.size() - 1, ip.wgs.size(), p->plan_ms[0], p->plan_ms[1], p->plan_ms[2], prebuilt ? "second thread under the set-up" : "inline", 1e3 * (t1 - t0), 1e3 * (now_s() - t1));
   ip.flags = flags; ip.layout_gen = p->layout_gen; ip.gs_unit = gs_unit;
   return OICC_OK;
@@ -398,7 +398,7 @@ static int build_rank_part(oicc_problem* p, oicc_problem* shard) {
 int inner_sweep(oicc_problem* p, double* xv, hipStream_t st, oicc_problem* shard, bool* owner_computes, const InnerFirstEval* fe) {   // p: the problem whose measurements and plan are used (xv may belong to another problem with the same spline)
   oicc_problem::InnerPlan& ip = p->inner;
   const bool owned = shard != nullptr && shard != p && shard->shard_n > 1 && shard->owner.valid && shard->owner.agreed && shard->owner.agreed_gen == shard->layout_gen &&
-                     shard->opt["owner_computes_sweeps"] != 0.0;
+                     shard->opt.owner_computes_sweeps != 0.0;
   if (owner_computes) *owner_computes = owned;
   if (owned) { const int rc = build_rank_part(p, shard); if (rc) return rc; }
   static_assert(std::is_trivially_copyable<InnerArgs>::value, "InnerArgs is copied bytewise");
@@ -424,7 +424,7 @@ int inner_sweep(oicc_problem* p, double* xv, hipStream_t st, oicc_problem* shard
   }
   if (fe == nullptr) { dA = ip.d_args.p; ++ip.sweeps; }
   // debug_inner_set_costs: the total cost before the sweep and behind every independent set (one cost pass + one read-back each)
-  const bool trace_sets = p->opt["debug_inner_set_costs"] != 0.0 && (shard == nullptr || shard == p) && fe == nullptr;
+  const bool trace_sets = p->opt.debug_inner_set_costs != 0.0 && (shard == nullptr || shard == p) && fe == nullptr;
   auto trace_cost = [&](double nblocks) -> int {
     if (!p->d_dbg_cost.resize(1)) { p->err = "hipMalloc debug cost"; return OICC_ERR_HIP; }
     HIPCK(p, hipMemsetAsync(p->d_dbg_cost.p, 0, sizeof(double), st));
@@ -437,7 +437,7 @@ int inner_sweep(oicc_problem* p, double* xv, hipStream_t st, oicc_problem* shard
   if (trace_sets) { const int rc = trace_cost(-1.0); if (rc) return rc; }
   launch_inner_seg(xv + p->pl.so3, std::max(p->pl.n_so3 - 1, 0), A.seg, st);
   if (ip.n_ctls > 0) HIPCK(p, hipMemsetAsync(A.ctls, 0, size_t(ip.n_ctls) * sizeof(InnerCtl), st));
-  const int prof_set = fe != nullptr ? -1 : int(p->opt["debug_inner_profile"]) - 1;   // debug: phase clocks of workgroup 0 of this set
+  const int prof_set = fe != nullptr ? -1 : int(p->opt.debug_inner_profile) - 1;   // debug: phase clocks of workgroup 0 of this set
   DevBuf<long long> d_prof;
   for (size_t g = 0; g + 1 < ip.group_wg0.size(); ++g) {
     long long* prof = nullptr;
@@ -524,11 +524,11 @@ int oicc_debug_host_inner_plan(oicc_problem* p, int32_t flags, int32_t* out8, in
   const double t1 = now_s();
   make_layout_host(p, flags);
   const double t2 = now_s();
-  InnerPlanOptions o; o.flags = flags; o.gs_unit = p->opt["gs_unit_loss"] != 0.0; o.general_kernel = false; o.resident_wgs = 256; o.shared_share = 0.5; o.layout_gen = 0;
-  o.wave_blocks = int(p->opt["inner_wave_blocks"]); o.n_cu = 256; o.big_slots = int(p->opt["inner_shared_launch_slots"]);   // (an MI355X's compute units: there is no device to ask)
+  InnerPlanOptions o; o.flags = flags; o.gs_unit = p->opt.gs_unit_loss != 0.0; o.general_kernel = false; o.resident_wgs = 256; o.shared_share = 0.5; o.layout_gen = 0;
+  o.wave_blocks = int(p->opt.inner_wave_blocks); o.n_cu = 256; o.big_slots = int(p->opt.inner_shared_launch_slots);   // (an MI355X's compute units: there is no device to ask)
   double ms[3];
   build_inner_plan_host(p, o, ms);
-  if (p->opt["verbose"] >= 2.0) std::printf("[oicc] host only: runs of samples %.3f ms, host layout %.3f ms, plan: blocks + neighbourhoods %.3f, independent sets %.3f, runs + workgroups %.3f ms\n", 1e3 * (t1 - t0), 1e3 * (t2 - t1), ms[0], ms[1], ms[2]);
+  if (p->opt.verbose >= 2.0) std::printf("[oicc] host only: runs of samples %.3f ms, host layout %.3f ms, plan: blocks + neighbourhoods %.3f, independent sets %.3f, runs + workgroups %.3f ms\n", 1e3 * (t1 - t0), 1e3 * (t2 - t1), ms[0], ms[1], ms[2]);
   const oicc_problem::InnerPlan& ip = p->inner;
   if (n_sets) *n_sets = int32_t(ip.group_first.size()) - 1;
   if (n_wgs) *n_wgs = int32_t(ip.wgs.size());
@@ -578,7 +578,7 @@ int oicc_debug_inner_first_evaluations(oicc_problem* p, int32_t flags, int32_t* 
   auto hip_ok = [&](hipError_t e) { if (e != hipSuccess) p->err = hipGetErrorString(e); return e == hipSuccess; };
   if (!hip_ok(hipMemcpyAsync(xs.p, p->d_x.p, size_t(p->pl.total) * sizeof(double), hipMemcpyDeviceToDevice, st)) || !hip_ok(hipMemsetAsync(rows.p, 0, size_t(nb) * 56 * sizeof(double), st)))
     return INT32_MIN - OICC_ERR_HIP;
-  if (p->opt["debug_poison_lds"] != 0.0) launch_lds_poison(st);   // (as the LM loop does in front of every step)
+  if (p->opt.debug_poison_lds != 0.0) launch_lds_poison(st);   // (as the LM loop does in front of every step)
   const InnerFirstEval fe{rows.p, seg.p, ctls.p, args.p};
   rc = inner_sweep(p, xs.p, st, nullptr, nullptr, &fe);
   if (rc == OICC_OK && (!hip_ok(hipMemcpyAsync(sums56, rows.p, size_t(nb) * 56 * sizeof(double), hipMemcpyDeviceToHost, st)) || !hip_ok(hipStreamSynchronize(st)))) rc = OICC_ERR_HIP;

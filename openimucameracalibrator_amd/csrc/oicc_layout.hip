@@ -306,7 +306,7 @@ void layout_scalars(oicc_problem* p) {
 }
 int make_layout_device(oicc_problem* p, int flags, std::thread* tiles_thread, int* tiles_rc) {
   HostLayout& L = p->L;
-  const bool timing = p->opt["verbose"] >= 2.0; const double tl0 = now_s();
+  const bool timing = p->opt.verbose >= 2.0; const double tl0 = now_s();
   // device copies
   hipStream_t st = p->stream;
   DevArena& LA = p->layout_arena;   // tangent offsets + every buffer of the normal equations and the solve: one block, one copy
@@ -350,7 +350,7 @@ int prepare(oicc_problem* p, int flags) {
   ARG(p, p->pl.n_so3 > 0, "oicc_set_times has not been called");
   ARG(p, p->max_corner_pt < p->pl.n_pts, "a corner refers to a board point beyond those of oicc_set_scene_points");
   HIPCK(p, hipSetDevice(p->device));
-  const bool timing = p->opt["verbose"] >= 2.0;
+  const bool timing = p->opt.verbose >= 2.0;
   const double t00 = now_s();
   if (plan_wanted != flags) p->wait_plan();   // (a plan job of an earlier call reads what this call may rebuild)
   sync_groups(p);
@@ -383,7 +383,7 @@ int prepare(oicc_problem* p, int flags) {
   if (!current) {
     layout_scalars(p);
     int n_cu = 256; (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, p->device); p->n_cu = n_cu < 1 ? 256 : n_cu;
-    if (p->corner_view.size() + p->acc.size() + p->gyr.size() >= 100000 && p->opt["debug_sync"] == 0.0 && p->opt["setup_threads"] != 0.0) tiles_thread = std::thread([p, &tiles_rc]() { tiles_rc = build_tiles_host(p); });
+    if (p->corner_view.size() + p->acc.size() + p->gyr.size() >= 100000 && p->opt.debug_sync == 0.0 && p->opt.setup_threads != 0.0) tiles_thread = std::thread([p, &tiles_rc]() { tiles_rc = build_tiles_host(p); });
     else tiles_rc = build_tiles_host(p);
   }
   int rc = sync_measurements(p); if (rc) return rc;
@@ -401,7 +401,7 @@ EvalCtx make_ctx(oicc_problem* p, const double* x) {
   c.x = x; c.pl = p->pl; c.tl = p->tl; c.ne = p->ne; c.pts = x + p->pl.pts;   // (the board points are part of the parameter vector)
   c.inv_so3_dt = p->inv_so3_dt; c.inv_r3_dt = p->inv_r3_dt;
   std::memcpy(c.intr, p->intr, sizeof(c.intr)); c.cam_model = p->cam_model;
-  c.gs_unit_loss = p->opt["gs_unit_loss"] != 0.0; c.rs_time_in_seconds = p->opt["rs_time_in_seconds"] != 0.0;
+  c.gs_unit_loss = p->opt.gs_unit_loss != 0.0; c.rs_time_in_seconds = p->opt.rs_time_in_seconds != 0.0;
   c.dbg_res = nullptr; c.dbg_jac = nullptr; c.prof = nullptr; c.prof_repeat = 0; c.only_kind = -1;
   return c;
 }

@@ -17,7 +17,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <thread>
 #include <memory>
 #include <type_traits>
@@ -31,6 +30,7 @@
 #include "inner_plan.h"
 #include "line_search.h"
 #include "covariance.h"
+#include "oicc_options.h"
 
 
 namespace oicc {
@@ -161,7 +161,7 @@ struct oicc_problem {
   std::thread plan_thread; InnerPlanOptions plan_job{}; bool plan_job_valid = false; double plan_ms[3] = {0, 0, 0};   // the plan's host part on a second thread (start_inner_plan)
   void wait_plan() { if (plan_thread.joinable()) plan_thread.join(); }
   int plan_wanted_flags = -2;   // oicc_optimize -> prepare: build the inner-iteration plan for these flags under the set-up
-  std::map<std::string, double> opt;
+  OiccOptions opt;   // oicc_options.def
   std::vector<oicc_iteration> trace;
   std::vector<double> inner_set_costs; DevBuf<double> d_dbg_cost;   // option debug_inner_set_costs: per sweep [-1, cost before], then per independent set [blocks, cost behind it] (oicc_get_inner_set_costs)
   oicc_allreduce_fn reduce = nullptr; void* reduce_user = nullptr;
@@ -180,7 +180,7 @@ struct oicc_problem {
   int n_cu = 256;
   int64_t bcr_joined[2] = {0, 0};   // cyclic-reduction levels that ran as one launch: in the last whole-band solve, in all of them (oicc_debug_bcr_join_info)
   int64_t bcr_folded[2] = {0, 0};   // whether the last whole-band cyclic-reduction solve folded a back-substitution level into the last block's launch; solves that did (oicc_debug_bcr_fold_info)
-  bool seg_precomputed() const { const auto it = opt.find("debug_seg_precompute"); const int force = it == opt.end() ? 0 : int(it->second); return force == 1 || (force == 0 && tp.n_tiles > n_cu); }
+  bool seg_precomputed() const { const int force = int(opt.debug_seg_precompute); return force == 1 || (force == 0 && tp.n_tiles > n_cu); }
   DevBuf<int32_t> d_corner_view, d_corner_pt, d_view_s_so3, d_view_s_r3;
   DevBuf<double> d_cu, d_cv, d_cisx, d_cisy, d_view_u_so3, d_view_u_r3;
   DevBuf<int64_t> d_view_c0; DevBuf<uint8_t> d_view_rs, d_view_rs_all, d_cgate; std::vector<uint8_t> h_view_rs_all;
@@ -247,53 +247,6 @@ struct oicc_problem {
   void invalidate_estimates() { cov.valid = false; report.valid = false; }   // parameters, measurements or options changed: what was derived from them is stale
   HostLayout L; TangentLayout tl{}; TangentLayout tl_tiles{}; NormalEq ne{}; NormalEq ne2{};   // tl_tiles: tl without the point columns (SplineOptimFlags::POINTS), what the tile pass sees
   Active act{};
-
-  oicc_problem() {
-    opt["function_tolerance"] = 1e-4; opt["parameter_tolerance"] = 1e-7; opt["gradient_tolerance"] = 1e-10;
-    opt["initial_trust_region_radius"] = 1e4; opt["max_trust_region_radius"] = 1e16;
-    opt["min_trust_region_radius"] = 1e-32; opt["min_relative_decrease"] = 1e-3;
-    opt["min_lm_diagonal"] = 1e-6; opt["max_lm_diagonal"] = 1e32; opt["jacobi_scaling"] = 1;
-    opt["max_num_consecutive_invalid_steps"] = 5; opt["gs_unit_loss"] = 0; opt["rs_time_in_seconds"] = 0;
-    opt["verbose"] = 0; opt["num_threads"] = 0; opt["solver_partitions"] = 0; opt["solver_algorithm"] = 0; opt["imu_chunk_cells"] = 0;
-    opt["inner_iterations"] = 0;   // 1: Ceres' use_inner_iterations = true as the reference sets it (impl.h:266): a block coordinate descent sweep after every
-                                   //    trust-region candidate (inner_iterations.hip); the applications switch it on, the bare C-ABI default is off
-    opt["inner_iteration_tolerance"] = 1e-3;
-    opt["setup_threads"] = 1;           // 1: large problems build the host part of the tiles on a thread of its own under the measurement copies (prepare); 0: inline
-    opt["distributed_solve"] = 1;       // time-sharded ranks with the owner-computes exchange: every rank eliminates the blocks of its own band range, only the ranks' separator blocks and the step travel (0: the band is gathered and every rank solves the whole system)
-    opt["owner_computes_sweeps"] = 1;   // time-sharded ranks with the owner-computes exchange: a rank sweeps only the knot blocks it owns, owners broadcast after every set (0: replicated sweeps)
-    opt["inner_shared_launch_slots"] = 65536;   // a block every view / sample depends on with at least this many item slots is minimised by a sequence of launches over the whole device instead of resident workgroups that wait for each other (0: never)
-    opt["inner_wave_blocks"] = 0;   // inner sweeps, which sets run one WAVE per block (inner_wave_kernel) instead of one workgroup: 0 = sets of at least 4 x compute units knot blocks (throughput bound), 1 = every eligible set, 2 = none
-    opt["fused_retract"] = 1;   // 1: the last launch of the cyclic-reduction solve also retracts (kernels_bcr.hip) where that applies; 0: always lm_retract_kernel, a launch of its own (A/B runs, tests)
-    opt["device_lm"] = 1;   // 1: plain Levenberg-Marquardt (no inner iterations / line search / collective) takes its trust-region decisions on the device
-                            //    (LmCtl, lm_decide_kernel): the host enqueues iterations and polls a pinned word one iteration behind.  0: the host-driven loop
-    opt["inner_shared_residency"] = 0.5;     // share of the device's resident workgroups the parts of a set's shared blocks (T_i_c, gravity, line delay, IMU intrinsics) may take together
-    opt["debug_inner_general_kernel"] = 0;   // 1: sets of R^3 knots run on the general 4-wave build of the inner kernel too (tests: both builds give the same sweep)
-    opt["debug_inner_set_costs"] = 0;   // 1: a cost pass behind every independent set of every sweep (tests: a mismatch with the checker names the set); oicc_get_inner_set_costs
-    opt["debug_inner_profile"] = 0;   // g + 1: print the phase clocks of workgroup 0 of independent set g after every sweep
-    opt["projected_gradient_norm"] = 0;   // 1: gradient_max_norm of a bounds-constrained program as Ceres reports it (ambient max norm of Plus(x, -g) - x; only the 1e-10 gradient tolerance and the iteration trace see it)
-    opt["bounds_line_search"] = 0;   // 1: Ceres' Armijo search along the projected path before every candidate evaluation when bias knots (box bounded, impl.h:206-240) are active
-    opt["assembly"] = 0;        // 0: time tiles (LDS accumulators + slab merge), 2: tiles in direct mode (fp64 atomics on the packed buffer: the independent accumulation path of the tests)
-    opt["tile_windows"] = 0;    // knot windows per tile; 0: automatic
-    opt["chain_tiles"] = 0;     // consecutive tiles one workgroup walks with its ring accumulator (tiles.h); 0: automatic = ceil(tiles / compute units)
-    opt["accumulation"] = 0;    // 1 = deterministic: one wave per chain, every sum of the Jacobian pass in a fixed order (bit-identical runs; slower)
-    opt["view_unit_items"] = 0; opt["accel_unit_items"] = 0; opt["gyro_unit_items"] = 0;   // items per unit of the tile pass (0: as many as fit the wave's row buffer); smaller units = more waves per tile busy on one-round problems
-    opt["wide_cells"] = 1;      // IMU samples of several consecutive SO(3) windows share one Gram product (as many as fit the 16-column blocks)
-    opt["debug_unit_order"] = 0;  // 1: units of a tile ordered views, accelerometer, gyroscope instead of by expected duration
-    opt["debug_no_direct_rows"] = 0;   // 1: every accumulator row goes through its tile's slab (tests: both routes give the same sums)
-    opt["debug_seg_precompute"] = 0;   // 1 / 2: segment tables always / never precomputed per parameter vector (default: by problem size)
-    opt["debug_bcr_delay"] = 0;        // panel waves other than wave 0 of the BCR elimination start every panel this many ~1000-cycle sleeps late (tests)
-    opt["bcr_max_border"] = 64;        // arrow + rhs rows the block cyclic reduction accepts (kernels_bcr.hip: up to 64 by construction; round 2 held it at 32 until the panel hazard was settled, test_bcr_wide_borders_and_the_panel_hazard)
-    opt["bcr_join_levels"] = 1;        // 1: a level of the cyclic reduction above the build's whose pivots x Schur groups fit the workgroup budget runs as ONE launch, every workgroup of a pivot inverting it itself (kernels_bcr.hip: bcri_invert_schur_kernel); 0: an inversion launch and a Schur launch per level (A/B runs, tests)
-    opt["bcr_join_max_workgroups"] = 0;   // the workgroup budget of a joined level; 0: the device's compute units
-    opt["bcr_fold_back"] = 1;          // 1: a whole-band solve of an even number of levels runs the back substitution of level nlev - 2 inside the last block's launch, one workgroup per pivot, each repeating the last block's work (kernels_bcr.hip: bcri_last_backward_kernel); 0: bcri_invert_kernel<true, false>, then bcri_backward_kernel on that level (A/B runs, tests)
-    opt["debug_plant_tile"] = -1;    // oicc_debug_lm_step only (tests): >= 0: a band column; its 16-aligned diagonal tile is diagonal but for the entry (column + 2, column) and cut off from every other variable for that solve and its read-out
-    opt["debug_plant_tile_dist"] = 2;   // with debug_plant_tile (tests): the planted entry is (column + d, column), 2 <= d <= 15 - (column & 15); another value plants nothing
-    opt["debug_plant_pivot"] = -1;  // oicc_debug_lm_step only (tests): >= 0: the band diagonal of this column is -1 for that solve and its read-out, which makes the pivot there negative whatever the damping
-    opt["debug_check_ne"] = 0;   // 1: before every linear solve compare the current normal equations with a host copy taken when they became current
-    opt["debug_sync"] = 0;       // 1: drain the stream after every pass (debugging of inter-kernel hazards)
-    opt["covariance_min_rcond"] = 1e-12;   // oicc_estimate_covariance: below this reciprocal condition estimate of the unit-diagonal normal equations no covariance is handed out (OICC_COV_RANK_DEFICIENT)
-    opt["debug_poison_lds"] = 0; // 1: fill every CU's LDS with NaNs before each Jacobian / cost pass and each linear solve (tests)
-  }
 };
 
 #define HIPCK(p, call)                                                                 \

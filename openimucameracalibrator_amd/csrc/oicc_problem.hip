@@ -19,7 +19,7 @@ int eval_pass(oicc_problem* p, const PassRequest& rq) {
   const oicc_allreduce_fn reduce = rq.local ? nullptr : p->reduce;
   hipStream_t st = p->stream;
   const NormalEq ne = rq.target ? *rq.target : p->ne;   // where this pass accumulates
-  if (p->opt["debug_poison_lds"] != 0.0) launch_lds_poison(st);
+  if (p->opt.debug_poison_lds != 0.0) launch_lds_poison(st);
   {                                     // time tiles (kernels_tiles.hip): the slab merge writes every entry of the packed buffer
     const bool with_points = jac && p->tl.a_pts > 0 && (only_kind < 0 || only_kind == 0);   // SplineOptimFlags::POINTS
     if (jac && (p->tp.direct || p->tp.n_tiles == 0)) HIPCK(p, hipMemsetAsync(ne.base, 0, ne.total * sizeof(double), st));
@@ -69,7 +69,7 @@ int eval_pass(oicc_problem* p, const PassRequest& rq) {
     }
   }
   HIPCK(p, hipGetLastError());
-  if (p->opt["debug_sync"] != 0.0) HIPCK(p, hipStreamSynchronize(st));
+  if (p->opt.debug_sync != 0.0) HIPCK(p, hipStreamSynchronize(st));
   if (reduce) {
     double* cdst = (!jac && rq.cost_out) ? rq.cost_out : ne.cost();
     int rc;
@@ -84,11 +84,11 @@ int eval_pass(oicc_problem* p, const PassRequest& rq) {
 }
 
 SolveBuffers solve_buffers(oicc_problem* p, long long* prof) {
-  SolveBuffers sb{p->d_Mb.p, p->d_Mt.p, p->d_Mc.p, p->d_scale.p, p->d_diag.p, p->d_D2.p, p->d_step.p, p->d_state.p, prof, p->d_ws.p, (int64_t)p->d_ws.n, int(p->opt["solver_partitions"]), int(p->opt["solver_algorithm"])};
-  sb.radius = 0.0; sb.bcr_max_border = int(p->opt["bcr_max_border"]); sb.bcr_delay = int(p->opt["debug_bcr_delay"]);
-  const int join_max = int(p->opt["bcr_join_max_workgroups"]);
-  sb.bcr_join = p->opt["bcr_join_levels"] != 0.0 ? 1 : 0; sb.bcr_join_budget = join_max > 0 ? join_max : p->n_cu; sb.bcr_joined = p->bcr_joined;
-  sb.bcr_fold = p->opt["bcr_fold_back"] != 0.0 ? 1 : 0; sb.bcr_folded = p->bcr_folded;
+  SolveBuffers sb{p->d_Mb.p, p->d_Mt.p, p->d_Mc.p, p->d_scale.p, p->d_diag.p, p->d_D2.p, p->d_step.p, p->d_state.p, prof, p->d_ws.p, (int64_t)p->d_ws.n, int(p->opt.solver_partitions), int(p->opt.solver_algorithm)};
+  sb.radius = 0.0; sb.bcr_max_border = int(p->opt.bcr_max_border); sb.bcr_delay = int(p->opt.debug_bcr_delay);
+  const int join_max = int(p->opt.bcr_join_max_workgroups);
+  sb.bcr_join = p->opt.bcr_join_levels != 0.0 ? 1 : 0; sb.bcr_join_budget = join_max > 0 ? join_max : p->n_cu; sb.bcr_joined = p->bcr_joined;
+  sb.bcr_fold = p->opt.bcr_fold_back != 0.0 ? 1 : 0; sb.bcr_folded = p->bcr_folded;
   return sb;
 }
 
@@ -101,7 +101,7 @@ int read_cost(oicc_problem* p, double* cost) {
 
 RetractReq retract_request(oicc_problem* p) {
   RetractReq R{};
-  R.on = (p->opt["fused_retract"] != 0.0 && !p->seg_precomputed() && p->d_tl_rmap.p != nullptr && p->pl.total < kRmapMaxParams) ? 1 : 0;
+  R.on = (p->opt.fused_retract != 0.0 && !p->seg_precomputed() && p->d_tl_rmap.p != nullptr && p->pl.total < kRmapMaxParams) ? 1 : 0;
   R.x = p->d_x.p; R.xc = p->d_xc.p; R.rmap = p->d_tl_rmap.p; R.ne = p->ne;
   R.max_ab = p->max_ab; R.max_gb = p->max_gb; R.alpha = 1.0;
   return R;
@@ -123,9 +123,9 @@ static_assert(sizeof(LmIterRec) == sizeof(oicc_iteration) && offsetof(LmIterRec,
 
 // Can this solve run under device-side control?  Plain LM on one rank with the tile assembly (the merge leaves max |g| in LmState).
 bool device_lm_applicable(oicc_problem* p, bool inner, bool line_search, bool projected_gmax) {
-  if (p->opt["device_lm"] == 0.0 || p->hmsg == nullptr || inner || line_search || projected_gmax || p->reduce != nullptr) return false;
+  if (p->opt.device_lm == 0.0 || p->hmsg == nullptr || inner || line_search || projected_gmax || p->reduce != nullptr) return false;
   if (p->tp.direct || p->tp.n_tiles == 0 || p->tl.a_pts != 0 || p->tl.P == 0) return false;
-  for (const char* name : {"debug_sync", "debug_check_ne", "debug_poison_lds"}) if (p->opt[name] != 0.0) return false;
+  if (p->opt.debug_sync != 0.0 || p->opt.debug_check_ne != 0.0 || p->opt.debug_poison_lds != 0.0) return false;
   return true;
 }
 // Upload the control block: current = d_x / ne, candidate = d_xc / ne2.
@@ -208,16 +208,16 @@ int device_lm_end(oicc_problem* p, int k_last, LmCtl* out, std::vector<LmIterRec
 LmCtl device_lm_control(oicc_problem* p, double radius, double cost, double gmax, int max_iters, int hold) {
   LmCtl h; std::memset(&h, 0, sizeof(h));
   h.radius = radius; h.decrease_factor = 2.0; h.cost = cost; h.gmax = gmax;
-  h.ftol = p->opt["function_tolerance"]; h.ptol = p->opt["parameter_tolerance"]; h.gtol = p->opt["gradient_tolerance"];
-  h.min_radius = p->opt["min_trust_region_radius"]; h.max_radius = p->opt["max_trust_region_radius"]; h.min_rel_dec = p->opt["min_relative_decrease"];
-  h.reuse_diagonal = 0; h.max_iters = max_iters; h.max_invalid = int(p->opt["max_num_consecutive_invalid_steps"]); h.hold = hold;
+  h.ftol = p->opt.function_tolerance; h.ptol = p->opt.parameter_tolerance; h.gtol = p->opt.gradient_tolerance;
+  h.min_radius = p->opt.min_trust_region_radius; h.max_radius = p->opt.max_trust_region_radius; h.min_rel_dec = p->opt.min_relative_decrease;
+  h.reuse_diagonal = 0; h.max_iters = max_iters; h.max_invalid = int(p->opt.max_num_consecutive_invalid_steps); h.hold = hold;
   return h;
 }
 // The loop under device-side control, from *h (h->max_iters >= 1) to the control block the device ends with, also in *h: per iteration
 // the host enqueues solve -> retraction -> Jacobian pass at the candidate and looks at the pinned word two iterations behind what it
 // has enqueued; iterations enqueued past the end return at their first instruction (LmCtl::done).
 int device_lm_run(oicc_problem* p, const SolveBuffers& sb, LmCtl* h, std::vector<LmIterRec>* recs, std::vector<long long>* stamps) {
-  const int max_iters = h->max_iters; const double min_diag = p->opt["min_lm_diagonal"], max_diag = p->opt["max_lm_diagonal"];
+  const int max_iters = h->max_iters; const double min_diag = p->opt.min_lm_diagonal, max_diag = p->opt.max_lm_diagonal;
   int rc = device_lm_begin(p, *h, max_iters); if (rc) return rc;
   int done = 0, k_last = -1;
   for (int k = 0; k < max_iters && done == 0; ++k) {
@@ -301,11 +301,23 @@ int oicc_set_stream(oicc_problem* p, void* s) {
   p->stream = reinterpret_cast<hipStream_t>(s); p->own_stream = false; return OICC_OK;
 }
 int oicc_set_option(oicc_problem* p, const char* name, double value) {
-  auto it = p->opt.find(name); ARG(p, it != p->opt.end(), std::string("unknown option ") + name);
-  if (it->second != value) ++p->opt_gen;   // layout / tiles / inner plan are rebuilt at the next pass
-  if (it->second != value) p->invalidate_estimates();
-  it->second = value;
+  double* v = find_option(p->opt, name); ARG(p, v, std::string("unknown option ") + name);
+  if (*v != value) ++p->opt_gen;   // layout / tiles / inner plan are rebuilt at the next pass
+  if (*v != value) p->invalidate_estimates();
+  *v = value;
   return OICC_OK;
+}
+// Test hooks (outside include/oicc_hip.h; tests/test_options_table.py): what an option holds, and the tables of oicc_options.h
+// themselves -- which 0: oicc_problem, 1: oicc_ba; returns the table's length, fills name / default of entry `index` where there is one
+// (host arithmetic, no problem object).
+int oicc_debug_get_option(oicc_problem* p, const char* name, double* value) {
+  const double* v = find_option(p->opt, name); ARG(p, v, std::string("unknown option ") + name); *value = *v; return OICC_OK; }
+int oicc_debug_option_table(int32_t which, int32_t index, const char** name, double* default_value) {
+  auto entry = [&](const auto& table) {
+    const int32_t n = int32_t(sizeof(table) / sizeof(table[0]));
+    if (index >= 0 && index < n) { if (name) *name = table[index].name; if (default_value) *default_value = table[index].default_value; }
+    return n; };
+  return which == 0 ? entry(kOptionTable) : which == 1 ? entry(kBaOptionTable) : 0;
 }
 int oicc_set_allreduce(oicc_problem* p, oicc_allreduce_fn fn, void* user) { p->reduce = fn; p->reduce_user = user; return OICC_OK; }
 int oicc_set_inner_iteration_source(oicc_problem* p, oicc_problem* whole) { ARG(p, whole != p, "a problem cannot be its own inner iteration source"); p->inner_src = whole; return OICC_OK; }
@@ -576,7 +588,7 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
   const double t_start = now_s();
   p->invalidate_estimates();   // (the estimate belongs to the parameters it was made at)
   struct PlanJoin { oicc_problem* q; ~PlanJoin() { q->wait_plan(); } } plan_join{p};   // (no exit of this call leaves the second thread running)
-  if (p->opt["inner_iterations"] != 0.0 && p->inner_src == nullptr && p->reduce == nullptr) p->plan_wanted_flags = flags;   // the plan's host part runs under the set-up (prepare)
+  if (p->opt.inner_iterations != 0.0 && p->inner_src == nullptr && p->reduce == nullptr) p->plan_wanted_flags = flags;   // the plan's host part runs under the set-up (prepare)
   int rc = prepare(p, flags); if (rc) return rc;
   hipStream_t st = p->stream;
   const TangentLayout& tl = p->tl;
@@ -587,12 +599,12 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
   S.num_residual_blocks = int64_t(p->view_rs.size() + p->acc.size() + p->gyr.size());
   S.num_residuals = int64_t(2 * p->corner_view.size() + 3 * p->acc.size() + 3 * p->gyr.size());
   p->trace.clear(); p->line_search_steps = 0; p->inner_set_costs.clear();
-  const double ftol = p->opt["function_tolerance"], ptol = p->opt["parameter_tolerance"], gtol = p->opt["gradient_tolerance"];
-  double radius = p->opt["initial_trust_region_radius"]; const double max_radius = p->opt["max_trust_region_radius"];
-  const double min_radius = p->opt["min_trust_region_radius"], min_rel_dec = p->opt["min_relative_decrease"];
-  const double min_diag = p->opt["min_lm_diagonal"], max_diag = p->opt["max_lm_diagonal"];
-  const int max_invalid = int(p->opt["max_num_consecutive_invalid_steps"]);
-  const bool verbose = p->opt["verbose"] != 0;
+  const double ftol = p->opt.function_tolerance, ptol = p->opt.parameter_tolerance, gtol = p->opt.gradient_tolerance;
+  double radius = p->opt.initial_trust_region_radius; const double max_radius = p->opt.max_trust_region_radius;
+  const double min_radius = p->opt.min_trust_region_radius, min_rel_dec = p->opt.min_relative_decrease;
+  const double min_diag = p->opt.min_lm_diagonal, max_diag = p->opt.max_lm_diagonal;
+  const int max_invalid = int(p->opt.max_num_consecutive_invalid_steps);
+  const bool verbose = p->opt.verbose != 0;
   double decrease_factor = 2.0; bool reuse_diagonal = false;
   double cost = 0.0, gmax = 0.0;
   const int inner_sweeps0 = (p->inner_src ? p->inner_src : p)->inner.sweeps; int64_t inner_lm0 = (p->inner_src ? p->inner_src : p)->inner.lm_iterations;
@@ -638,7 +650,7 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
 
   double t0 = now_s();
   HIPCK(p, hipMemsetAsync(p->d_state.p, 0, sizeof(LmState), st));
-  const bool projected_gmax = p->opt["projected_gradient_norm"] != 0.0 && (p->act.ab || p->act.gb);   // Ceres: is_constrained
+  const bool projected_gmax = p->opt.projected_gradient_norm != 0.0 && (p->act.ab || p->act.gb);   // Ceres: is_constrained
   bool gmax_folded = false;   // the last Jacobian pass already left max |g| in LmState (slab merge): no lm_gradmax launch
   auto jacobian_at = [&](const double* xbuf, const NormalEq* nq) {   // the Jacobian pass of the loop: max |g| rides in the merge where it can
     PassRequest rq = jacobian_pass(xbuf, nq); rq.gmax_into = projected_gmax ? nullptr : p->d_state.p; rq.gmax_folded = &gmax_folded;
@@ -648,7 +660,7 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
     else if (!gmax_folded) launch_lm_gradmax(nq, P, p->d_state.p, st); };
   rc = jacobian_at(p->d_x.p, nullptr); if (rc) return rc;
   SolveBuffers sb = solve_buffers(p);
-  if (P > 0) { launch_lm_scale(p->ne, tl, sb.scale, p->opt["jacobi_scaling"] != 0, st); gradient_norm(p->d_x.p, p->ne); }
+  if (P > 0) { launch_lm_scale(p->ne, tl, sb.scale, p->opt.jacobi_scaling != 0, st); gradient_norm(p->d_x.p, p->ne); }
   rc = read_back(true); if (rc) return rc;
   cost = pin->cost; gmax = pin->st.gradient_max_norm;
   S.seconds_jacobian += now_s() - t0;
@@ -662,14 +674,16 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
   int iter = 0, invalid = 0;
   bool inner_enabled = false, plan_pending = false;
   oicc_problem* const q = p->inner_src ? p->inner_src : p;   // whose measurements the sweeps run over (a time-sharded rank: the problem with every rank's measurements)
-  if (p->opt["inner_iterations"] != 0.0) {
+  if (p->opt.inner_iterations != 0.0) {
     if (p->reduce && q == p) { p->err = "inner iterations on a time-sharded problem need oicc_set_inner_iteration_source (a sweep minimises a block over ALL its residual blocks)"; return OICC_ERR_UNSUPPORTED; }
     if (q != p) {
       if (q->device != p->device || q->pl.total != p->pl.total || q->pl.n_so3 != p->pl.n_so3 || q->pl.n_r3 != p->pl.n_r3 || q->dt_so3 != p->dt_so3 || q->dt_r3 != p->dt_r3 || q->start_ns != p->start_ns) {
         p->err = "inner iteration source: different device or spline"; return OICC_ERR_INVALID_ARG; }
-      for (const char* name : {"gs_unit_loss", "rs_time_in_seconds", "inner_iteration_tolerance", "inner_shared_residency"}) q->opt[name] = p->opt[name];
-      for (const char* name : {"inner_wave_blocks", "inner_shared_launch_slots"})   // plan options set on the shard (as oicc_hip.h documents): a change rebuilds the source's plan
-        if (q->opt[name] != p->opt[name]) { q->opt[name] = p->opt[name]; ++q->opt_gen; }
+      q->opt.gs_unit_loss = p->opt.gs_unit_loss; q->opt.rs_time_in_seconds = p->opt.rs_time_in_seconds;
+      q->opt.inner_iteration_tolerance = p->opt.inner_iteration_tolerance; q->opt.inner_shared_residency = p->opt.inner_shared_residency;
+      // plan options set on the shard (as oicc_hip.h documents): a change rebuilds the source's plan
+      if (q->opt.inner_wave_blocks != p->opt.inner_wave_blocks) { q->opt.inner_wave_blocks = p->opt.inner_wave_blocks; ++q->opt_gen; }
+      if (q->opt.inner_shared_launch_slots != p->opt.inner_shared_launch_slots) { q->opt.inner_shared_launch_slots = p->opt.inner_shared_launch_slots; ++q->opt_gen; }
       q->max_ab = p->max_ab; q->max_gb = p->max_gb;   // the box of the bias knots the sweeps project onto
       q->cam_model = p->cam_model; q->n_intr = p->n_intr; std::memcpy(q->intr, p->intr, sizeof(q->intr));
       q->x[q->pl.ld] = p->x[p->pl.ld];   // (active_set looks at the zero-ness of the line delay)
@@ -686,13 +700,13 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
     inner_lm0 = q->inner.lm_iterations;   // (a rebuilt plan restarts the device counter)
     inner_enabled = q->inner.blocks.size() >= 2;   // Ceres: "Reduced problem only contains one parameter block. Disabling inner iterations."
     return OICC_OK; };
-  const bool line_search = p->opt["bounds_line_search"] != 0.0 && (p->act.ab || p->act.gb);   // Ceres: the program is bounds constrained
+  const bool line_search = p->opt.bounds_line_search != 0.0 && (p->act.ab || p->act.gb);   // Ceres: the program is bounds constrained
   // ---- plain LM: the trust-region logic runs ON THE DEVICE (LmCtl, lm_decide.h).  Per iteration the host enqueues
   // solve -> retraction -> Jacobian pass at the candidate (cost, gradient, normal equations in one pass: no separate cost pass); the
   // decision of an iteration is taken inside the NEXT iteration's build kernel (a kernel of its own only behind the last one), and the
   // host looks at a pinned word that kernel wrote, two iterations behind what it has enqueued: no copy, no event, no synchronisation
   // inside the loop; iterations enqueued past the end return at their first instruction (LmCtl::done).
-  if (device_lm_applicable(p, inner_enabled || p->opt["inner_iterations"] != 0.0, line_search, projected_gmax)) {
+  if (device_lm_applicable(p, inner_enabled || p->opt.inner_iterations != 0.0, line_search, projected_gmax)) {
     if (max_iters <= 0) return finish(OICC_NO_CONVERGENCE, "Maximum number of iterations reached.");
     if (radius <= min_radius) return finish(OICC_CONVERGENCE, "Minimum trust region radius reached.");
     LmCtl h = device_lm_control(p, radius, cost, gmax, max_iters, 0);
@@ -725,7 +739,7 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
     if (radius <= min_radius) { rc = settle_gmax(); if (rc) return rc; return finish(OICC_CONVERGENCE, "Minimum trust region radius reached."); }
     // --- trust-region step: damped solve on the device, retraction, candidate cost
 #ifdef OICC_DEBUG_SOLVER   // host copies / comparisons before every solve (make HIPFLAGS+=-DOICC_DEBUG_SOLVER): not in the shipped library
-    if (p->opt["debug_check_ne"] != 0.0) {
+    if (p->opt.debug_check_ne != 0.0) {
       static std::vector<double> keep; static const double* keep_base = nullptr;
       std::vector<double> now(p->ne.total), aux(size_t(3) * std::max(P, 1));
       HIPCK(p, hipMemcpyAsync(now.data(), p->ne.base, now.size() * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -739,9 +753,9 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
       std::printf("[check_ne] iter %d base %p changed %zu nonfinite %zu min scale %.3e min diag %.3e radius %.4e reuse %d\n", iter, (void*)p->ne.base, nbad, nnan, smin, dmin, radius, int(reuse_diagonal));
       keep = now; keep_base = p->ne.base;
     }
-    if (p->opt["debug_sync"] == 2.0) HIPCK(p, hipStreamSynchronize(st));
-    if (p->opt["debug_sync"] >= 4.0) {   // D2H copy of one buffer before the solve: 4 scene points (unrelated), 5 normal equations, 6 scale + diag, 7 solver workspace
-      static std::vector<double> sink; const int w = int(p->opt["debug_sync"]);
+    if (p->opt.debug_sync == 2.0) HIPCK(p, hipStreamSynchronize(st));
+    if (p->opt.debug_sync >= 4.0) {   // D2H copy of one buffer before the solve: 4 scene points (unrelated), 5 normal equations, 6 scale + diag, 7 solver workspace
+      static std::vector<double> sink; const int w = int(p->opt.debug_sync);
       const double* src = w == 4 ? p->d_x.p + p->pl.pts : (w == 5 ? p->ne.base : (w == 6 || w == 8 ? sb.scale : (w == 9 ? sb.diag : (w == 10 ? sb.D2 : (w == 11 ? reinterpret_cast<const double*>(p->d_state.p) : p->d_ws.p)))));
       const size_t cnt = w == 4 ? p->pts.size() : (w == 5 ? size_t(p->ne.total) : (w == 6 || w == 8 || w == 9 || w == 10 ? size_t(P) : (w == 11 ? size_t(7) : p->d_ws.n)));
       sink.resize(cnt);
@@ -751,7 +765,7 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
     }
 #endif
     HIPCK(p, hipEventRecord(ev[0], st));
-    if (p->opt["debug_poison_lds"] != 0.0) launch_lds_poison(st);
+    if (p->opt.debug_poison_lds != 0.0) launch_lds_poison(st);
     // (agreed shards: the distributed cyclic reduction, oicc_exchange.hip.)  The retraction rides in the solve's last launch where the
     // route allows; the separate launch also leaves the candidate's segment tables (one kernel fewer per cost pass)
     rc = lm_solve_and_retract(p, sb, radius, reuse_diagonal ? 1 : 0, min_diag, max_diag, st); if (rc) return rc;
@@ -843,7 +857,7 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
     // Jacobian pass + gradient norm at the CANDIDATE into the second buffer, before the host knows whether the step is
     // accepted (it is, on 4 of 4 iterations of the C2 calibration): the read-back latency hides behind it.  A rejected
     // step simply leaves the second buffer unused.
-    const bool speculate = p->opt["debug_sync"] != 3.0;
+    const bool speculate = p->opt.debug_sync != 3.0;
     HIPCK(p, hipEventRecord(ev[3], st));
     if (speculate) {
       rc = jacobian_at(p->d_xc.p, &p->ne2); if (rc) return rc;
@@ -857,7 +871,7 @@ int oicc_optimize(oicc_problem* p, int32_t max_iters, int32_t flags, oicc_summar
     if (inner_ran) {
       hs.model_cost_change += cand_before_inner - cand_cost;
       inner_useful = cand_cost < cost;
-      inner_enabled = 1.0 - cand_cost / cand_before_inner > p->opt["inner_iteration_tolerance"];
+      inner_enabled = 1.0 - cand_cost / cand_before_inner > p->opt.inner_iteration_tolerance;
       if (verbose) std::printf("[oicc] iter %d inner iterations: %.12e -> %.12e (%s)\n", iter + 1, cand_before_inner, cand_cost, inner_enabled ? "stay on" : "switched off");
     }
     S.seconds_linear_solver += elapsed_s(ev[0], ev[1]); S.seconds_residual += elapsed_s(ev[1], ev[2]);
@@ -938,19 +952,19 @@ int oicc_run_lm_iterations(oicc_problem* p, int32_t flags, int32_t steps) {
   bool gmax_folded = false;
   auto jacobian_at_x = [&](const NormalEq* nq) { PassRequest rq = jacobian_pass(p->d_x.p, nq); rq.gmax_into = p->d_state.p; rq.gmax_folded = &gmax_folded; return eval_pass(p, rq); };
   rc = jacobian_at_x(nullptr); if (rc) return rc;
-  launch_lm_scale(p->ne, tl, sb.scale, p->opt["jacobi_scaling"] != 0, st);
+  launch_lm_scale(p->ne, tl, sb.scale, p->opt.jacobi_scaling != 0, st);
   if (!gmax_folded) launch_lm_gradmax(p->ne, tl.P, p->d_state.p, st);
-  if (device_lm_applicable(p, p->opt["inner_iterations"] != 0.0, p->opt["bounds_line_search"] != 0.0 && (p->act.ab || p->act.gb), p->opt["projected_gradient_norm"] != 0.0 && (p->act.ab || p->act.gb))) {
+  if (device_lm_applicable(p, p->opt.inner_iterations != 0.0, p->opt.bounds_line_search != 0.0 && (p->act.ab || p->act.gb), p->opt.projected_gradient_norm != 0.0 && (p->act.ab || p->act.gb))) {
     // the loop of oicc_optimize under device-side control, in its benchmark mode: every iteration solves the system at x, retracts,
     // runs the Jacobian pass at the candidate and takes the decision -- which is recorded but not applied (LmCtl::hold)
     double c0 = 0.0; rc = read_cost(p, &c0); if (rc) return rc;
-    LmCtl h = device_lm_control(p, p->opt["initial_trust_region_radius"], c0, 0.0, steps, 1);
+    LmCtl h = device_lm_control(p, p->opt.initial_trust_region_radius, c0, 0.0, steps, 1);
     rc = device_lm_run(p, sb, &h, nullptr, nullptr); if (rc) return rc;
     if (h.done != 0 || h.seq != steps) { p->err = "Cholesky failed in benchmark iteration"; return OICC_ERR_STATE; }
     return OICC_OK;
   }
   for (int it = 0; it < steps; ++it) {
-    rc = lm_solve_and_retract(p, sb, p->opt["initial_trust_region_radius"], 0, p->opt["min_lm_diagonal"], p->opt["max_lm_diagonal"], st); if (rc) return rc;
+    rc = lm_solve_and_retract(p, sb, p->opt.initial_trust_region_radius, 0, p->opt.min_lm_diagonal, p->opt.max_lm_diagonal, st); if (rc) return rc;
     if (p->reduce != nullptr && !(p->rccl_comm != nullptr && p->rccl_nranks <= 1)) {
       const bool same = p->dist.last_step_gathered;
       rc = make_rank_consistent(p, p->d_xc.p, true, st, same); if (rc) return rc;
@@ -994,10 +1008,10 @@ int oicc_time_linear_solve(oicc_problem* p, int32_t flags, int32_t repeats, doub
   // time-sharded ranks (oicc_set_shard + a reduction): the pass runs with its exchange and the solve is the one oicc_optimize
   // uses there -- the distributed cyclic reduction where the ranks agreed on it -- so every rank must make this call
   const bool sharded = p->shard_n > 1 && p->reduce != nullptr;
-  const double radius = p->opt["initial_trust_region_radius"], min_diag = p->opt["min_lm_diagonal"], max_diag = p->opt["max_lm_diagonal"];
+  const double radius = p->opt.initial_trust_region_radius, min_diag = p->opt.min_lm_diagonal, max_diag = p->opt.max_lm_diagonal;
   SolveBuffers sb = solve_buffers(p);
   PassRequest rq = jacobian_pass(p->d_x.p); rq.local = !sharded;
-  rc = system_at_current_point(p, rq, sb.scale, p->opt["jacobi_scaling"] != 0, radius); if (rc) return rc;
+  rc = system_at_current_point(p, rq, sb.scale, p->opt.jacobi_scaling != 0, radius); if (rc) return rc;
   if (p->tl.P == 0) { if (ms_per_solve) *ms_per_solve = 0; return OICC_OK; }
   EventPair ev; HIPCK(p, hipEventCreate(&ev.a)); HIPCK(p, hipEventCreate(&ev.b));
   rc = lm_solve_any(p, p->ne, sb, radius, 0, min_diag, max_diag, st); if (rc) return rc;
@@ -1016,9 +1030,9 @@ int oicc_time_linear_solve(oicc_problem* p, int32_t flags, int32_t repeats, doub
 int oicc_solve_residual(oicc_problem* p, int32_t flags, double radius, double out[3]) {
   int rc = prepare(p, flags); if (rc) return rc;
   SolveBuffers sb = solve_buffers(p);
-  rc = system_at_current_point(p, local_pass(p->d_x.p, true), sb.scale, p->opt["jacobi_scaling"] != 0, 0.0); if (rc) return rc;
+  rc = system_at_current_point(p, local_pass(p->d_x.p, true), sb.scale, p->opt.jacobi_scaling != 0, 0.0); if (rc) return rc;
   if (p->tl.P == 0) { out[0] = out[1] = out[2] = 0.0; return OICC_OK; }
-  if (launch_lm_solve(p->ne, p->tl, sb, radius, 0, p->opt["min_lm_diagonal"], p->opt["max_lm_diagonal"], p->stream) != 0) { p->err = "solver geometry unsupported"; return OICC_ERR_UNSUPPORTED; }
+  if (launch_lm_solve(p->ne, p->tl, sb, radius, 0, p->opt.min_lm_diagonal, p->opt.max_lm_diagonal, p->stream) != 0) { p->err = "solver geometry unsupported"; return OICC_ERR_UNSUPPORTED; }
   return read_solve_residual(p, sb, &out[0], &out[1], &out[2]);
 }
 

@@ -103,7 +103,7 @@ void make_tiles(const oicc_problem* p, int T, TileBuild* out) {
   // order by (tile, expected duration): the waves of a tile pull units from a queue, longest first packs them best.  Measured on
   // C5 (prof_tile.py): an accelerometer unit (evaluation + ~4 cells) ~46k cycles, a view ~40k, a gyroscope unit ~35k.
   // (a three-way merge: every family's units already ascend in time)
-  const int unit_order = int(p->opt.count("debug_unit_order") ? p->opt.at("debug_unit_order") : 0.0);
+  const int unit_order = int(p->opt.debug_unit_order);
   const int order[3] = {unit_order == 1 ? 1 : 0, unit_order == 1 ? 0 : 1, 2};   // families in the order they are queued inside a tile
   std::vector<UnitDesc>& U = out->units; std::vector<int32_t>& UT = out->unit_tile;
   U.clear(); UT.clear(); out->tiles.clear();
@@ -138,7 +138,7 @@ void make_tiles(const oicc_problem* p, int T, TileBuild* out) {
 int build_tiles_host(oicc_problem* p) {
   const TangentLayout& tl = p->tl_tiles; const Active& a = p->act;   // (without the board-point columns: kernels_points.hip adds those)
   p->fv = view_row_fmt(tl, a.spline);
-  const int wide_max = p->opt["wide_cells"] != 0.0 ? 8 : 0;
+  const int wide_max = p->opt.wide_cells != 0.0 ? 8 : 0;
   p->fa = imu_row_fmt(tl, true, a.spline, a.ab, wide_max);
   p->fg = imu_row_fmt(tl, false, a.spline, a.gb, wide_max);
   TileParams& tp = p->tp; tp = TileParams{};
@@ -153,18 +153,18 @@ int build_tiles_host(oicc_problem* p) {
   int rb = std::max(need(p->fv, max_nc), std::max(need(p->fa, 32), need(p->fg, 32)));
   rb = std::min(rb, 3456);   // 27 KB per wave: a 50-corner view in one piece
   rb = std::max(rb, 512);
-  auto unit_cap = [&](const char* name) { const int v = int(p->opt[name]); return v > 0 ? std::min(v, 64) : 64; };
-  row_fmt_capacity(p->fv, rb, unit_cap("view_unit_items")); row_fmt_capacity(p->fa, rb, unit_cap("accel_unit_items")); row_fmt_capacity(p->fg, rb, unit_cap("gyro_unit_items"));
+  auto unit_cap = [](double items) { const int v = int(items); return v > 0 ? std::min(v, 64) : 64; };
+  row_fmt_capacity(p->fv, rb, unit_cap(p->opt.view_unit_items)); row_fmt_capacity(p->fa, rb, unit_cap(p->opt.accel_unit_items)); row_fmt_capacity(p->fg, rb, unit_cap(p->opt.gyro_unit_items));
   if (p->fv.cap < 1 || p->fa.cap < 1 || p->fg.cap < 1) { p->err = "row buffer too small for this parameter set"; return OICC_ERR_UNSUPPORTED; }
   tp.rb_doubles = rb; tp.wave_doubles = 96 + rb;
   const int64_t dt_fine = std::min(p->dt_so3, p->dt_r3);
   const int64_t n_windows = (p->end_ns - p->start_ns) / dt_fine + 1;
-  const int mode = int(p->opt["assembly"]);
+  const int mode = int(p->opt.assembly);
   // Tile length T (fine knot windows): small problems want many tiles (latency: ~200 workgroups), large ones the longest tile
   // whose accumulator fits LDS (the halo rows of a tile are summed by the merge kernel: their share falls with T); a multiple
   // of the window ratio of the two splines keeps the R^3 windows (and with them the views and IMU cells) whole.
   const int ratio = int(std::max<int64_t>(1, std::min<int64_t>(8, std::max(p->dt_so3, p->dt_r3) / dt_fine)));
-  const int T_user = int(p->opt["tile_windows"]);
+  const int T_user = int(p->opt.tile_windows);
   int T = T_user > 0 ? T_user : int(std::max<int64_t>(ratio, std::min<int64_t>(64, n_windows / 200)));
   auto carve = [&](int nks, int nkr, int nunits, int acc_doubles) {   // returns total doubles
     int o = 0;
@@ -177,12 +177,12 @@ int build_tiles_host(oicc_problem* p) {
   // waves per workgroup: one per SIMD; option accumulation = 1 ("deterministic"): ONE wave per chain takes the units in their fixed
   // order, so the LDS additions (and with the fixed chain order of the merge every sum of the pass) happen in one order: two runs
   // give the same bits (for bisecting a parity failure; slower)
-  tp.n_waves = p->opt["accumulation"] != 0.0 ? 1 : 4;
+  tp.n_waves = p->opt.accumulation != 0.0 ? 1 : 4;
   auto try_T = [&](int t) {   // builds the tiles for t windows; true if they fit
     make_tiles(p, t, &tb);
     if (tb.max_nks > kMaxTileKnots || tb.max_nkr > kMaxTileKnots) return false;
     const int need_d = carve(tb.max_nks, tb.max_nkr, tb.max_units, tp.direct ? 0 : tb.max_rows * tp.Wl + tp.corner);
-    if (p->opt["verbose"] >= 3.0) std::printf("[oicc] tile length %d: %zu tiles, rows %d, knots %d / %d, units %d, LDS %d of %d doubles (direct %d)\n", t, tb.tiles.size(), tb.max_rows, tb.max_nks, tb.max_nkr, tb.max_units, need_d, budget, tp.direct);
+    if (p->opt.verbose >= 3.0) std::printf("[oicc] tile length %d: %zu tiles, rows %d, knots %d / %d, units %d, LDS %d of %d doubles (direct %d)\n", t, tb.tiles.size(), tb.max_rows, tb.max_nks, tb.max_nkr, tb.max_units, need_d, budget, tp.direct);
     return need_d <= budget;
   };
   // Automatic tile length.  Measured (scripts/time_tile_windows.py, prof_tile.py; C2 ... C5): pass time ~ 8 us (launch) +
@@ -222,7 +222,7 @@ int build_tiles_host(oicc_problem* p) {
   p->h_tiles.swap(tb.tiles); p->h_units.swap(tb.units);
   tp.n_tiles = int32_t(p->h_tiles.size()); tp.n_units = int32_t(p->h_units.size());
   // Chains: workgroup c walks tiles [c L, (c + 1) L), L = the number of rounds the tiles would need as workgroups of their own.
-  tp.chain_len = std::max(1, int(p->opt["chain_tiles"]) > 0 ? int(p->opt["chain_tiles"]) : (tp.n_tiles + n_cu - 1) / n_cu);
+  tp.chain_len = std::max(1, int(p->opt.chain_tiles) > 0 ? int(p->opt.chain_tiles) : (tp.n_tiles + n_cu - 1) / n_cu);
   tp.n_chains = (tp.n_tiles + tp.chain_len - 1) / tp.chain_len;
   // Which chains touch which knot (a knot = 3 consecutive tangent rows): a knot of exactly one chain is stored by that chain (final),
   // every other knot goes through the slabs of its chains and the merge.  Inside a chain a knot lives in one ring slot from the first
@@ -235,7 +235,7 @@ int build_tiles_host(oicc_problem* p) {
     const TileDesc& td = p->h_tiles[t]; const int32_t c = t / tp.chain_len;
     for (int k = 0; k < td.nks + td.nkr; ++k) { const int id = knot_id(td, k); if (first_chain[id] < 0) first_chain[id] = c; last_chain[id] = c; }
   }
-  const bool all_slab = p->opt["debug_no_direct_rows"] != 0.0;
+  const bool all_slab = p->opt.debug_no_direct_rows != 0.0;
   p->h_row_direct.assign(std::max(tl.Pb, 1), 0);
   struct Held { int32_t row, chain, slab_row; };
   std::vector<Held> held;                                              // rows that go through slabs, generated in chain order
@@ -327,7 +327,7 @@ int build_tiles_device(oicc_problem* p) {
   TA.add(p->d_merge_ptr, p->h_merge_ptr); TA.add(p->d_merge_src, p->h_merge_src); TA.add(p->d_merge_tab, p->h_merge_tab); TA.add(p->d_row_direct, p->h_row_direct);
   if (!TA.commit(st) ||
       !p->d_slabs.resize(size_t(std::max<int64_t>(1, tp.direct ? 1 : int64_t(tp.n_chains) * tp.slab_stride)))) { p->err = "hipMalloc tiles"; return OICC_ERR_HIP; }
-  if (p->opt["verbose"] >= 2.0) std::printf("[oicc] tiles: %d tiles of %d windows in %d chains of %d, %d waves, %d units, accumulator %d rows x %d (+%d), slab %d rows, %d of %d rows merged, row buffer %d doubles, items per unit view %d accel %d gyro %d (wide +%d / +%d), LDS %d B, direct %d\n",
+  if (p->opt.verbose >= 2.0) std::printf("[oicc] tiles: %d tiles of %d windows in %d chains of %d, %d waves, %d units, accumulator %d rows x %d (+%d), slab %d rows, %d of %d rows merged, row buffer %d doubles, items per unit view %d accel %d gyro %d (wide +%d / +%d), LDS %d B, direct %d\n",
                                            tp.n_tiles, p->tile_T, tp.n_chains, tp.chain_len, tp.n_waves, tp.n_units, tp.acc_rows, tp.Wl, tp.corner, tp.slab_rows, tp.n_merge_rows, tl.Pb, tp.rb_doubles, p->fv.cap, p->fa.cap, p->fg.cap, p->fa.ks_extra, p->fg.ks_extra, tp.lds_bytes, tp.direct);
   tp.tiles = p->d_tiles.p; tp.units = p->d_units.p; tp.tile_rows = p->d_tile_rows.p; tp.slabs = p->d_slabs.p; tp.merge_rows = p->d_merge_rows.p; tp.merge_ptr = p->d_merge_ptr.p; tp.merge_src = p->d_merge_src.p; tp.merge_tab = p->d_merge_tab.p; tp.row_direct = p->d_row_direct.p;
   return OICC_OK;
