@@ -833,6 +833,61 @@ int oicc_planar_ransac(int32_t device_ordinal, int32_t num_views, const int64_t*
                        int32_t mode, double threshold, int32_t num_hypotheses, uint64_t seed, uint8_t* inlier,
                        int32_t* num_inliers, double* q, double* pose, int32_t* hypothesis_counts, double* device_ms);
 
+/* ---- camera maps: pixel -> ray, rectification maps, model discrepancy and image resampling (camera_maps.hip) ---------------
+ * The device has the forward projection of the six camera models (camera_project, spline_math.h); these entries add its
+ * inverse and what users build on it: undistorted frames and the same camera expressed in another model.  Specified step by
+ * step by tests/camera_maps_restatement.py and DESIGN.md ("Camera maps").  Models and intrinsics as in oicc_set_camera; the
+ * intrinsics arrays hold the model's own count (PINHOLE 7, PINHOLE_RADIAL_TANGENTIAL 10, FISHEYE 9, DIVISION_UNDISTORTION 5,
+ * DOUBLE_SPHERE 7, EXTENDED_UNIFIED 7).
+ *
+ * oicc_camera_unproject: one lane per pixel; Newton on project(x, y, 1) = uv with the analytic Jacobian, from the pinhole start
+ *   x0 = (u - cx) / f, y0 = (v - cy) / (f aspect), at most 20 steps, stop at max|step| <= 1e-13 (1 + max|xy|).
+ *   uv [n][2] pixels, xy [n][2] rays (x, y, 1), status [n]: 0 a ray, 1 no ray on the principal branch (xy = NaN).
+ *   Status 0 needs finite values, a projection that did not fail, max|project(x, y, 1) - uv| <= 1e-9 (1 + max|uv|) and, for
+ *   A = d(px)/d(x, y) at the solution, det A > 0 and A00 / f + A11 / (f aspect) > 0: beyond the fold of a camera whose radial
+ *   map turns back, Newton converges onto rays that reproject exactly but are not the ones the lens imaged.
+ *   Limitations: rays are (x, y, 1), so fields of view of 180 degrees and more are out of scope; a model whose radial map
+ *   folds twice can still offer a second branch on which both signs are positive.
+ *   n_intr must be the model's count; device_ms (may be NULL): kernel time by device events.
+ * oicc_camera_rectify_map: for every pixel of a destination camera the coordinates of the same ray in a source camera.
+ *   Unproject through the destination camera (closed form for a PINHOLE without distortion, else the Newton above), rotate by
+ *   R9 (row-major 3 x 3, destination camera -> source camera; NULL = identity), project through the source camera.
+ *   map [dst_h][dst_w][2] float32 (x, y) source coordinates, the layout of OpenCV's CV_32FC2 maps; valid [dst_h][dst_w]: 1 iff
+ *   the pixel has a ray, the rotated ray has z > 0, the projection succeeded and the coordinates lie in
+ *   [0, src_w - 1] x [0, src_h - 1]; invalid pixels get NaN coordinates.  num_valid (may be NULL): the number of ones.
+ * oicc_camera_discrepancy: every pixel of a w x h image is unprojected through camera A and projected through camera B;
+ *   stats[3] = number of pixels with a ray and a projection, rms and maximum of the distance |px_B - px| over them (0 without
+ *   one).  One partial row per wave by a fixed butterfly, added on the host in order: bit-identical between runs.
+ * oicc_camera_remap: bilinear resampling of num_frames u8 frames [src_h][src_w][channels] (channels 1 or 3) through one map
+ *   [dst_h][dst_w][2] float32, out [num_frames][dst_h][dst_w][channels].  Host pointers; frames travel in batches of `batch`
+ *   through pinned staging, two batches in flight on two streams.  Value: ((1-a)(1-b) p00 + a(1-b) p01) + ((1-a) b p10 + a b p11)
+ *   in double, (a, b) the fractions of the float32 coordinates, then floor(v + 0.5) clamped to 0..255; a neighbour of weight
+ *   exactly 0 is not read, so coordinates on the last row or column are legal.  A map entry that is NaN or outside
+ *   [0, src_w - 1] x [0, src_h - 1] gives border_value.  report (may be NULL): milliseconds by device events, summed over
+ *   the batches, and the wall time of the call.
+ * oicc_camera_remap_device: the same kernel on device pointers, asynchronous on hip_stream (a hipStream_t; NULL = the
+ *   default stream), no copies, on the current device: frames that already live on the GPU stay there.  The stream and the
+ *   three arrays must belong to the current device (OICC_ERR_INVALID_ARG otherwise).  oicc_camera_remap runs every batch
+ *   through this entry.
+ * OICC_ERR_INVALID_ARG for an unknown model, a wrong intrinsics count, non-finite intrinsics or R9, sizes < 1, channels
+ * other than 1 or 3, a batch < 1, a null array or more than (2^31 - 1) * 256 pixels in one call; OICC_ERR_NO_DEVICE without a usable HIP device (no CPU fallback). */
+typedef struct oicc_camera_remap_report {
+  double ms_upload, ms_kernel, ms_download, ms_total;
+} oicc_camera_remap_report;
+int oicc_camera_unproject(int32_t device_ordinal, int32_t model, const double* intrinsics, int32_t n_intr, int64_t n, const double* uv,
+                          double* xy, uint8_t* status, double* device_ms);
+int oicc_camera_rectify_map(int32_t device_ordinal, int32_t src_model, const double* src_intr, int32_t src_w, int32_t src_h,
+                            int32_t dst_model, const double* dst_intr, int32_t dst_w, int32_t dst_h, const double* R9, float* map,
+                            uint8_t* valid, int64_t* num_valid, double* device_ms);
+int oicc_camera_discrepancy(int32_t device_ordinal, int32_t model_a, const double* intr_a, int32_t model_b, const double* intr_b,
+                            int32_t w, int32_t h, double stats[3], double* device_ms);
+int oicc_camera_remap(int32_t device_ordinal, int32_t num_frames, int32_t src_w, int32_t src_h, int32_t channels, const uint8_t* frames,
+                      const float* map, int32_t dst_w, int32_t dst_h, int32_t border_value, int32_t batch, uint8_t* out,
+                      oicc_camera_remap_report* report);
+int oicc_camera_remap_device(void* hip_stream, int32_t num_frames, int32_t src_w, int32_t src_h, int32_t channels,
+                             const uint8_t* frames_dev, const float* map_dev, int32_t dst_w, int32_t dst_h, int32_t border_value,
+                             uint8_t* out_dev);
+
 /* ---- the elimination plan of the block cyclic reduction (kernels_bcr.hip), host arithmetic only: needs no device ----------
  * The damped LM system of n 64-column blocks is reduced level by level.  Level l: the active blocks are origin + k stride,
  * k < active; those with k mod 2 == parity are its pivots (parity 0 when `active` is odd -- both ends are pivots --, else 1;

@@ -431,3 +431,40 @@ class BoundPlanarRansac:
             fn.restype = res
             fn.argtypes = args
             setattr(self, name, fn)
+
+
+class CameraRemapReport(C.Structure):
+    """oicc_camera_remap_report (include/oicc_hip.h)."""
+    _fields_ = [("ms_upload", C.c_double), ("ms_kernel", C.c_double), ("ms_download", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+c_fp = C.POINTER(C.c_float)
+
+# Camera maps (oicc_camera_* in include/oicc_hip.h), a table of its own like ALLAN_SIGNATURES: SIGNATURES is also bound against
+# the CPU checker, which has no counterpart of these entries.
+CAMERA_MAPS_SIGNATURES = {
+    "unproject": (C.c_int, [C.c_int32, C.c_int32, c_dp, C.c_int32, C.c_int64, c_dp, c_dp, c_u8p, c_dp]),
+    "rectify_map": (C.c_int, [C.c_int32, C.c_int32, c_dp, C.c_int32, C.c_int32, C.c_int32, c_dp, C.c_int32, C.c_int32, c_dp, c_fp,
+                              c_u8p, c_i64p, c_dp]),
+    "discrepancy": (C.c_int, [C.c_int32, C.c_int32, c_dp, C.c_int32, c_dp, C.c_int32, C.c_int32, c_dp, c_dp]),
+    "remap": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_u8p, c_fp, C.c_int32, C.c_int32, C.c_int32,
+                        C.c_int32, c_u8p, C.POINTER(CameraRemapReport)]),
+    "remap_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, c_u8p, c_fp, C.c_int32, C.c_int32, C.c_int32,
+                               c_u8p]),
+}
+
+
+class BoundCameraMaps:
+    """Bound oicc_camera_* entry points of one library + prefix (``oicc_camera_`` for liboicc_hip.so)."""
+
+    def __init__(self, lib, prefix):
+        self.lib = lib
+        self.prefix = prefix
+        for name, (res, args) in CAMERA_MAPS_SIGNATURES.items():
+            fn = getattr(lib, prefix + name)  # AttributeError = missing symbol: fail loudly
+            fn.restype = res
+            fn.argtypes = args
+            setattr(self, name, fn)

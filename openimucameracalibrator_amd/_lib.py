@@ -7,7 +7,7 @@ fails when no HIP device is usable.
 import ctypes
 import os
 
-from ._abi import Bound, BoundAllan, BoundBa, BoundBcrPlan, BoundBoard, BoundLmRetract, BoundPlanarRansac, BoundStaticImu
+from ._abi import Bound, BoundAllan, BoundBa, BoundBcrPlan, BoundBoard, BoundCameraMaps, BoundLmRetract, BoundPlanarRansac, BoundStaticImu
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OICC_DEV_LIB") or os.path.join(_HERE, "csrc", "liboicc_hip.so")   # OICC_DEV_LIB: another BUILD of the same library (developer A/B timing, scripts/build_variant.sh)
@@ -17,6 +17,7 @@ _bound_allan = None
 _bound_static_imu = None
 _bound_board = None
 _bound_planar_ransac = None
+_bound_camera_maps = None
 _bound_bcr_plan = None
 _bound_lm_retract = None
 
@@ -71,6 +72,14 @@ def load_planar_ransac():
     if _bound_planar_ransac is None:
         _bound_planar_ransac = BoundPlanarRansac(load().lib, "oicc_planar_")
     return _bound_planar_ransac
+
+
+def load_camera_maps():
+    """oicc_camera_* entry points (pixel -> ray, rectification maps, discrepancy, remap) of the same library."""
+    global _bound_camera_maps
+    if _bound_camera_maps is None:
+        _bound_camera_maps = BoundCameraMaps(load().lib, "oicc_camera_")
+    return _bound_camera_maps
 
 
 def load_bcr_plan():

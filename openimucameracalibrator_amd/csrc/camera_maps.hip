@@ -1,0 +1,463 @@
+// Camera maps: pixel -> ray for the six camera models, rectification maps, the discrepancy between two models and bilinear
+// resampling of u8 frames (include/oicc_hip.h, "camera maps"; DESIGN.md section 3, "Camera maps").
+//
+//   unproject    one lane per pixel: Newton on camera_project<true>(x, y, 1) = uv with columns 0 and 1 of the analytic 2 x 3
+//                Jacobian, Cramer's rule, pinhole start.  A solution counts only on the principal branch: det A > 0 and
+//                A00 / f + A11 / (f aspect) > 0 (beyond the fold of a folding camera Newton converges onto rays that reproject
+//                exactly).
+//   map          one lane per destination pixel: unproject (destination camera), rotate, project (source camera); float2
+//                coordinates and one validity byte.
+//   discrepancy  one lane per pixel, unproject through A, project through B; per wave one xor butterfly over (count, sum d^2,
+//                max d), one row per wave, added by the host in order.
+//   remap        one lane per destination pixel: the map entry and the four weights once, then all frames of the batch and all
+//                channels.
+//
+// Limitations: rays are (x, y, 1), so fields of view of 180 degrees and more are out of scope; a model whose radial map folds
+// twice can still offer a second branch on which both signs of the branch test are positive.
+//
+// tests/camera_maps_restatement.py restates every step in numpy.  This unit is compiled with -ffp-contract=off
+// (csrc/Makefile): without fused multiply-adds the bilinear sum rounds as the restatement's and the u8 results agree byte
+// for byte.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+#include "../../include/oicc_hip.h"
+#include "spline_math.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kNewtonSteps = 20;
+constexpr double kStepTol = 1e-13;
+constexpr double kReprojectionTol = 1e-9;
+constexpr int kMaxIntr = 10;
+
+struct Camera { int model; double in[kMaxIntr]; };
+
+__host__ __device__ inline int intrinsics_count(int model) {
+  switch (model) {
+    case oicc::CAM_PINHOLE: return 7;
+    case oicc::CAM_PINHOLE_RADIAL_TANGENTIAL: return 10;
+    case oicc::CAM_FISHEYE: return 9;
+    case oicc::CAM_DIVISION_UNDISTORTION: return 5;
+    case oicc::CAM_DOUBLE_SPHERE: return 7;
+    case oicc::CAM_EXTENDED_UNIFIED: return 7;
+    default: return 0;
+  }
+}
+
+__device__ __forceinline__ double max_abs2(double a, double b) { return fmax(fabs(a), fabs(b)); }
+
+// The ray (x, y, 1) of pixel (u, v) on the principal branch; false (and NaN) where there is none.
+__device__ bool unproject(const Camera& cam, double u, double v, double& x, double& y) {
+  const bool division = cam.model == oicc::CAM_DIVISION_UNDISTORTION;
+  const double f = cam.in[0], fa = cam.in[0] * cam.in[1];
+  const double cx = division ? cam.in[2] : cam.in[3], cy = division ? cam.in[3] : cam.in[4];
+  x = (u - cx) / f;
+  y = (v - cy) / fa;
+  double px[2], J[6];
+  bool ok = true;
+  for (int it = 0; it < kNewtonSteps; ++it) {
+    const double p[3] = {x, y, 1.0};
+    ok = oicc::camera_project<true>(cam.model, cam.in, p, px, J);
+    if (!ok) break;
+    const double ex = px[0] - u, ey = px[1] - v;
+    const double det = J[0] * J[4] - J[1] * J[3];
+    const double dx = (J[4] * ex - J[1] * ey) / det;
+    const double dy = (J[0] * ey - J[3] * ex) / det;
+    x -= dx;
+    y -= dy;
+    if (!(max_abs2(dx, dy) > kStepTol * (1.0 + max_abs2(x, y)))) break;    // also leaves on NaN
+  }
+  if (ok) {
+    const double p[3] = {x, y, 1.0};
+    ok = oicc::camera_project<true>(cam.model, cam.in, p, px, J);
+    const double err = max_abs2(px[0] - u, px[1] - v);
+    const double det = J[0] * J[4] - J[1] * J[3];
+    const double tr = J[0] / f + J[4] / fa;
+    ok = ok && isfinite(x) && isfinite(y) && isfinite(err) && isfinite(det) && isfinite(tr) &&
+         err <= kReprojectionTol * (1.0 + max_abs2(u, v)) && det > 0.0 && tr > 0.0;
+  }
+  if (!ok) { x = nan(""); y = nan(""); }
+  return ok;
+}
+
+__global__ __launch_bounds__(kThreads) void camera_unproject_kernel(Camera cam, int64_t n, const double* __restrict__ uv,
+                                                                    double* __restrict__ xy, uint8_t* __restrict__ status) {
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const double2 p = *reinterpret_cast<const double2*>(uv + 2 * i);
+  double x, y;
+  const bool ok = unproject(cam, p.x, p.y, x, y);
+  *reinterpret_cast<double2*>(xy + 2 * i) = make_double2(x, y);
+  status[i] = ok ? 0 : 1;
+}
+
+struct Rotation { double r[9]; };
+
+__global__ __launch_bounds__(kThreads) void camera_map_kernel(Camera src, int src_w, int src_h, Camera dst, int closed_form, int dst_w,
+                                                              int dst_h, Rotation R, float2* __restrict__ map,
+                                                              uint8_t* __restrict__ valid) {
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= int64_t(dst_w) * dst_h) return;
+  const double u = double(i % dst_w), v = double(i / dst_w);
+  double x, y;
+  bool ok = true;
+  if (closed_form) {
+    y = (v - dst.in[4]) / (dst.in[0] * dst.in[1]);
+    x = (u - dst.in[3] - dst.in[2] * y) / dst.in[0];
+  } else {
+    ok = unproject(dst, u, v, x, y);
+  }
+  const double p[3] = {(R.r[0] * x + R.r[1] * y) + R.r[2], (R.r[3] * x + R.r[4] * y) + R.r[5], (R.r[6] * x + R.r[7] * y) + R.r[8]};
+  double px[2] = {0.0, 0.0};
+  ok = ok && p[2] > 0.0;
+  if (ok) ok = oicc::camera_project<false>(src.model, src.in, p, px, nullptr);
+  ok = ok && px[0] >= 0.0 && px[0] <= double(src_w - 1) && px[1] >= 0.0 && px[1] <= double(src_h - 1);
+  const float qnan = __builtin_nanf("");
+  map[i] = ok ? make_float2(float(px[0]), float(px[1])) : make_float2(qnan, qnan);
+  valid[i] = ok ? 1 : 0;
+}
+
+// rows [waves][3] = count, sum d^2, max d of the wave's pixels, every lane of a wave holding the same values after the butterfly
+__global__ __launch_bounds__(kThreads) void camera_discrepancy_kernel(Camera a, Camera b, int w, int h, double* __restrict__ rows) {
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  double cnt = 0.0, sum = 0.0, mx = 0.0;
+  if (i < int64_t(w) * h) {
+    const double u = double(i % w), v = double(i / w);
+    double x, y;
+    if (unproject(a, u, v, x, y)) {
+      const double p[3] = {x, y, 1.0};
+      double px[2];
+      if (oicc::camera_project<false>(b.model, b.in, p, px, nullptr)) {
+        const double ex = px[0] - u, ey = px[1] - v;
+        const double d2 = ex * ex + ey * ey;
+        if (isfinite(d2)) { cnt = 1.0; sum = d2; mx = sqrt(d2); }
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    cnt += __shfl_xor(cnt, o, 64);
+    sum += __shfl_xor(sum, o, 64);
+    mx = fmax(mx, __shfl_xor(mx, o, 64));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    double* row = rows + 3 * (int64_t(blockIdx.x) * kWaves + (threadIdx.x >> 6));
+    row[0] = cnt; row[1] = sum; row[2] = mx;
+  }
+}
+
+template <int CH>
+__global__ __launch_bounds__(kThreads) void camera_remap_kernel(const uint8_t* __restrict__ frames, int num_frames, int src_w, int src_h,
+                                                                const float2* __restrict__ map, int64_t dst_pixels, int border,
+                                                                uint8_t* __restrict__ out) {
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= dst_pixels) return;
+  const float2 m = map[i];
+  const int64_t src_frame = int64_t(src_w) * src_h * CH, dst_frame = dst_pixels * CH;
+  uint8_t* o = out + i * CH;
+  // NaN fails every comparison
+  const bool inside = m.x >= 0.0f && m.x <= float(src_w - 1) && m.y >= 0.0f && m.y <= float(src_h - 1);
+  if (!inside) {
+    for (int f = 0; f < num_frames; ++f, o += dst_frame)
+#pragma unroll
+      for (int c = 0; c < CH; ++c) o[c] = uint8_t(border);
+    return;
+  }
+  const double xf = double(m.x), yf = double(m.y);
+  const double x0 = floor(xf), y0 = floor(yf);
+  const double a = xf - x0, b = yf - y0;
+  const double w00 = (1.0 - a) * (1.0 - b), w01 = a * (1.0 - b), w10 = (1.0 - a) * b, w11 = a * b;
+  const bool right = a != 0.0, down = b != 0.0;       // a weight of exactly 0: the neighbour is not read (last row / column)
+  const int64_t o00 = (int64_t(y0) * src_w + int64_t(x0)) * CH;
+  const int64_t o01 = right ? o00 + CH : o00, o10 = down ? o00 + int64_t(src_w) * CH : o00;
+  const int64_t o11 = o10 + (right ? CH : 0);
+  const uint8_t* s = frames;
+  for (int f = 0; f < num_frames; ++f, s += src_frame, o += dst_frame) {
+#pragma unroll
+    for (int c = 0; c < CH; ++c) {
+      const double p00 = double(s[o00 + c]), p01 = double(s[o01 + c]), p10 = double(s[o10 + c]), p11 = double(s[o11 + c]);
+      const double val = (w00 * p00 + w01 * p01) + (w10 * p10 + w11 * p11);
+      const double r = floor(val + 0.5);
+      o[c] = uint8_t(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
+    }
+  }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------
+
+bool make_camera(int32_t model, const double* intr, Camera* cam) {
+  const int n = intrinsics_count(model);
+  if (n == 0 || !intr) return false;
+  cam->model = model;
+  for (int k = 0; k < kMaxIntr; ++k) cam->in[k] = 0.0;
+  for (int k = 0; k < n; ++k) {
+    if (!std::isfinite(intr[k])) return false;
+    cam->in[k] = intr[k];
+  }
+  return true;
+}
+
+int select_device(int32_t device_ordinal) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device_ordinal < 0 || device_ordinal >= ndev) return OICC_ERR_NO_DEVICE;   // no CPU fallback
+  if (hipSetDevice(device_ordinal) != hipSuccess) return OICC_ERR_NO_DEVICE;
+  return OICC_OK;
+}
+
+constexpr int64_t kMaxLanes = ((int64_t(1) << 31) - 1) * kThreads;   // one lane per pixel: the grid's x dimension stays below 2^31 blocks
+
+inline unsigned blocks_for(int64_t n) { return unsigned((n + kThreads - 1) / kThreads); }
+
+bool remap_args_ok(int32_t num_frames, int32_t src_w, int32_t src_h, int32_t channels, int32_t dst_w, int32_t dst_h, int32_t border_value) {
+  return num_frames >= 1 && src_w >= 1 && src_h >= 1 && dst_w >= 1 && dst_h >= 1 && (channels == 1 || channels == 3) &&
+         border_value >= 0 && border_value <= 255 && int64_t(dst_w) * dst_h <= kMaxLanes;
+}
+
+int launch_remap(hipStream_t st, int num_frames, int src_w, int src_h, int channels, const uint8_t* frames, const float* map, int dst_w,
+                 int dst_h, int border, uint8_t* out) {
+  const int64_t pixels = int64_t(dst_w) * dst_h;
+  const float2* m = reinterpret_cast<const float2*>(map);
+  if (channels == 1)
+    hipLaunchKernelGGL(camera_remap_kernel<1>, dim3(blocks_for(pixels)), dim3(kThreads), 0, st, frames, num_frames, src_w, src_h, m, pixels, border, out);
+  else
+    hipLaunchKernelGGL(camera_remap_kernel<3>, dim3(blocks_for(pixels)), dim3(kThreads), 0, st, frames, num_frames, src_w, src_h, m, pixels, border, out);
+  return hipGetLastError() == hipSuccess ? OICC_OK : OICC_ERR_HIP;
+}
+
+}  // namespace
+
+#define CAMERA_TRY(expr) do { if ((expr) != hipSuccess) { rc = OICC_ERR_HIP; goto done; } } while (0)
+
+extern "C" int oicc_camera_unproject(int32_t device_ordinal, int32_t model, const double* intrinsics, int32_t n_intr, int64_t n,
+                                     const double* uv, double* xy, uint8_t* status, double* device_ms) {
+  Camera cam;
+  if (n_intr != intrinsics_count(model) || !make_camera(model, intrinsics, &cam) || n < 1 || n > kMaxLanes || !uv || !xy || !status) return OICC_ERR_INVALID_ARG;
+  if (int rc = select_device(device_ordinal)) return rc;
+  int rc = OICC_OK;
+  double *d_uv = nullptr, *d_xy = nullptr; uint8_t* d_st = nullptr;
+  hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
+  float ms = 0.0f;
+  CAMERA_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  CAMERA_TRY(hipEventCreate(&e0)); CAMERA_TRY(hipEventCreate(&e1));
+  CAMERA_TRY(hipMalloc(&d_uv, sizeof(double) * 2 * size_t(n)));
+  CAMERA_TRY(hipMalloc(&d_xy, sizeof(double) * 2 * size_t(n)));
+  CAMERA_TRY(hipMalloc(&d_st, size_t(n)));
+  CAMERA_TRY(hipMemcpyAsync(d_uv, uv, sizeof(double) * 2 * size_t(n), hipMemcpyHostToDevice, st));
+  CAMERA_TRY(hipEventRecord(e0, st));
+  hipLaunchKernelGGL(camera_unproject_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, cam, n, d_uv, d_xy, d_st);
+  CAMERA_TRY(hipGetLastError());
+  CAMERA_TRY(hipEventRecord(e1, st));
+  CAMERA_TRY(hipMemcpyAsync(xy, d_xy, sizeof(double) * 2 * size_t(n), hipMemcpyDeviceToHost, st));
+  CAMERA_TRY(hipMemcpyAsync(status, d_st, size_t(n), hipMemcpyDeviceToHost, st));
+  CAMERA_TRY(hipStreamSynchronize(st));
+  CAMERA_TRY(hipEventElapsedTime(&ms, e0, e1));
+  if (device_ms) *device_ms = double(ms);
+done:
+  if (rc != OICC_OK && st) (void)hipStreamSynchronize(st);
+  for (void* p : {(void*)d_uv, (void*)d_xy, (void*)d_st}) if (p) (void)hipFree(p);
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (st) (void)hipStreamDestroy(st);
+  return rc;
+}
+
+extern "C" int oicc_camera_rectify_map(int32_t device_ordinal, int32_t src_model, const double* src_intr, int32_t src_w, int32_t src_h,
+                                       int32_t dst_model, const double* dst_intr, int32_t dst_w, int32_t dst_h, const double* R9,
+                                       float* map, uint8_t* valid, int64_t* num_valid, double* device_ms) {
+  Camera src, dst;
+  if (!make_camera(src_model, src_intr, &src) || !make_camera(dst_model, dst_intr, &dst) || src_w < 1 || src_h < 1 || dst_w < 1 ||
+      dst_h < 1 || int64_t(dst_w) * dst_h > kMaxLanes || !map || !valid) return OICC_ERR_INVALID_ARG;
+  Rotation R = {{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}};
+  if (R9)
+    for (int k = 0; k < 9; ++k) {
+      if (!std::isfinite(R9[k])) return OICC_ERR_INVALID_ARG;
+      R.r[k] = R9[k];
+    }
+  if (int rc = select_device(device_ordinal)) return rc;
+  const int closed_form = dst.model == oicc::CAM_PINHOLE && dst.in[5] == 0.0 && dst.in[6] == 0.0;
+  const int64_t pixels = int64_t(dst_w) * dst_h;
+  int rc = OICC_OK;
+  float2* d_map = nullptr; uint8_t* d_valid = nullptr;
+  hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
+  float ms = 0.0f;
+  CAMERA_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  CAMERA_TRY(hipEventCreate(&e0)); CAMERA_TRY(hipEventCreate(&e1));
+  CAMERA_TRY(hipMalloc(&d_map, sizeof(float2) * size_t(pixels)));
+  CAMERA_TRY(hipMalloc(&d_valid, size_t(pixels)));
+  CAMERA_TRY(hipEventRecord(e0, st));
+  hipLaunchKernelGGL(camera_map_kernel, dim3(blocks_for(pixels)), dim3(kThreads), 0, st, src, int(src_w), int(src_h), dst, closed_form,
+                     int(dst_w), int(dst_h), R, d_map, d_valid);
+  CAMERA_TRY(hipGetLastError());
+  CAMERA_TRY(hipEventRecord(e1, st));
+  CAMERA_TRY(hipMemcpyAsync(map, d_map, sizeof(float2) * size_t(pixels), hipMemcpyDeviceToHost, st));
+  CAMERA_TRY(hipMemcpyAsync(valid, d_valid, size_t(pixels), hipMemcpyDeviceToHost, st));
+  CAMERA_TRY(hipStreamSynchronize(st));
+  CAMERA_TRY(hipEventElapsedTime(&ms, e0, e1));
+  if (device_ms) *device_ms = double(ms);
+  if (num_valid) {
+    int64_t c = 0;
+    for (int64_t i = 0; i < pixels; ++i) c += valid[i];
+    *num_valid = c;
+  }
+done:
+  if (rc != OICC_OK && st) (void)hipStreamSynchronize(st);
+  if (d_map) (void)hipFree(d_map);
+  if (d_valid) (void)hipFree(d_valid);
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (st) (void)hipStreamDestroy(st);
+  return rc;
+}
+
+extern "C" int oicc_camera_discrepancy(int32_t device_ordinal, int32_t model_a, const double* intr_a, int32_t model_b,
+                                       const double* intr_b, int32_t w, int32_t h, double stats[3], double* device_ms) {
+  Camera a, b;
+  if (!make_camera(model_a, intr_a, &a) || !make_camera(model_b, intr_b, &b) || w < 1 || h < 1 || int64_t(w) * h > kMaxLanes || !stats) return OICC_ERR_INVALID_ARG;
+  if (int rc = select_device(device_ordinal)) return rc;
+  const int64_t pixels = int64_t(w) * h;
+  const unsigned blocks = blocks_for(pixels);
+  std::vector<double> rows(size_t(blocks) * kWaves * 3);
+  int rc = OICC_OK;
+  double* d_rows = nullptr;
+  hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
+  float ms = 0.0f;
+  CAMERA_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  CAMERA_TRY(hipEventCreate(&e0)); CAMERA_TRY(hipEventCreate(&e1));
+  CAMERA_TRY(hipMalloc(&d_rows, sizeof(double) * rows.size()));
+  CAMERA_TRY(hipEventRecord(e0, st));
+  hipLaunchKernelGGL(camera_discrepancy_kernel, dim3(blocks), dim3(kThreads), 0, st, a, b, int(w), int(h), d_rows);
+  CAMERA_TRY(hipGetLastError());
+  CAMERA_TRY(hipEventRecord(e1, st));
+  CAMERA_TRY(hipMemcpyAsync(rows.data(), d_rows, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, st));
+  CAMERA_TRY(hipStreamSynchronize(st));
+  CAMERA_TRY(hipEventElapsedTime(&ms, e0, e1));
+  if (device_ms) *device_ms = double(ms);
+  {
+    double cnt = 0.0, sum = 0.0, mx = 0.0;
+    for (size_t r = 0; r < rows.size() / 3; ++r) { cnt += rows[3 * r]; sum += rows[3 * r + 1]; mx = std::max(mx, rows[3 * r + 2]); }
+    stats[0] = cnt; stats[1] = cnt > 0.0 ? std::sqrt(sum / cnt) : 0.0; stats[2] = mx;
+  }
+done:
+  if (rc != OICC_OK && st) (void)hipStreamSynchronize(st);
+  if (d_rows) (void)hipFree(d_rows);
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (st) (void)hipStreamDestroy(st);
+  return rc;
+}
+
+extern "C" int oicc_camera_remap_device(void* hip_stream, int32_t num_frames, int32_t src_w, int32_t src_h, int32_t channels,
+                                        const uint8_t* frames_dev, const float* map_dev, int32_t dst_w, int32_t dst_h,
+                                        int32_t border_value, uint8_t* out_dev) {
+  if (!remap_args_ok(num_frames, src_w, src_h, channels, dst_w, dst_h, border_value) || !frames_dev || !map_dev || !out_dev)
+    return OICC_ERR_INVALID_ARG;
+  int ndev = 0, cur = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || hipGetDevice(&cur) != hipSuccess) return OICC_ERR_NO_DEVICE;   // no CPU fallback
+  // the launch goes to the current device: the stream and the three arrays have to live there
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (stream) {
+    hipDevice_t of_stream = 0, of_current = 0;
+    if (hipStreamGetDevice(stream, &of_stream) != hipSuccess || hipDeviceGet(&of_current, cur) != hipSuccess || of_stream != of_current) {
+      (void)hipGetLastError();
+      return OICC_ERR_INVALID_ARG;
+    }
+  }
+  for (const void* p : {(const void*)frames_dev, (const void*)map_dev, (const void*)out_dev}) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type == hipMemoryTypeUnregistered || (a.type == hipMemoryTypeDevice && a.device != cur)) {
+      (void)hipGetLastError();
+      return OICC_ERR_INVALID_ARG;
+    }
+  }
+  return launch_remap(stream, num_frames, src_w, src_h, channels, frames_dev, map_dev, dst_w, dst_h,
+                      border_value, out_dev);
+}
+
+namespace {
+struct RemapSlot {
+  uint8_t *pin_in = nullptr, *pin_out = nullptr, *d_in = nullptr, *d_out = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};    // upload start, upload end, kernel end, download end
+  int first = 0, num = 0;
+};
+}  // namespace
+
+extern "C" int oicc_camera_remap(int32_t device_ordinal, int32_t num_frames, int32_t src_w, int32_t src_h, int32_t channels,
+                                 const uint8_t* frames, const float* map, int32_t dst_w, int32_t dst_h, int32_t border_value,
+                                 int32_t batch, uint8_t* out, oicc_camera_remap_report* report) {
+  if (!remap_args_ok(num_frames, src_w, src_h, channels, dst_w, dst_h, border_value) || batch < 1 || !frames || !map || !out)
+    return OICC_ERR_INVALID_ARG;
+  if (int rc = select_device(device_ordinal)) return rc;
+  const auto t_start = std::chrono::steady_clock::now();
+  oicc_camera_remap_report rep = {0.0, 0.0, 0.0, 0.0};
+  const int64_t in_frame = int64_t(src_w) * src_h * channels, out_frame = int64_t(dst_w) * dst_h * channels;
+  const int64_t nbatch = std::min<int64_t>(batch, num_frames);
+  const int nslots = num_frames > nbatch ? 2 : 1;     // a second staging slot only when a second batch exists
+  const size_t map_bytes = sizeof(float) * 2 * size_t(dst_w) * size_t(dst_h);
+  int rc = OICC_OK;
+  float* d_map = nullptr;
+  hipStream_t st[2] = {nullptr, nullptr};
+  RemapSlot slot[2];
+  CAMERA_TRY(hipMalloc(&d_map, map_bytes));
+  CAMERA_TRY(hipMemcpy(d_map, map, map_bytes, hipMemcpyHostToDevice));
+  for (int q = 0; q < nslots; ++q) {
+    RemapSlot& s = slot[q];
+    CAMERA_TRY(hipStreamCreateWithFlags(&st[q], hipStreamNonBlocking));
+    CAMERA_TRY(hipHostMalloc(&s.pin_in, size_t(nbatch * in_frame), hipHostMallocDefault));
+    CAMERA_TRY(hipHostMalloc(&s.pin_out, size_t(nbatch * out_frame), hipHostMallocDefault));
+    CAMERA_TRY(hipMalloc(&s.d_in, size_t(nbatch * in_frame)));
+    CAMERA_TRY(hipMalloc(&s.d_out, size_t(nbatch * out_frame)));
+    for (auto& e : s.ev) CAMERA_TRY(hipEventCreate(&e));
+  }
+  {
+    // one batch per slot and stream: host copy into pinned memory, upload, kernel, download; the other slot's batch overlaps
+    auto enqueue = [&](int q, int first) -> int {
+      RemapSlot& s = slot[q];
+      s.first = first; s.num = int(std::min<int64_t>(nbatch, num_frames - first));
+      if (s.num <= 0) return OICC_OK;
+      std::memcpy(s.pin_in, frames + int64_t(first) * in_frame, size_t(s.num * in_frame));
+      if (hipEventRecord(s.ev[0], st[q]) != hipSuccess ||
+          hipMemcpyAsync(s.d_in, s.pin_in, size_t(s.num * in_frame), hipMemcpyHostToDevice, st[q]) != hipSuccess ||
+          hipEventRecord(s.ev[1], st[q]) != hipSuccess) return OICC_ERR_HIP;
+      if (oicc_camera_remap_device(st[q], s.num, src_w, src_h, channels, s.d_in, d_map, dst_w, dst_h, border_value, s.d_out) != OICC_OK) return OICC_ERR_HIP;
+      if (hipEventRecord(s.ev[2], st[q]) != hipSuccess ||
+          hipMemcpyAsync(s.pin_out, s.d_out, size_t(s.num * out_frame), hipMemcpyDeviceToHost, st[q]) != hipSuccess ||
+          hipEventRecord(s.ev[3], st[q]) != hipSuccess) return OICC_ERR_HIP;
+      return OICC_OK;
+    };
+    int next = 0;
+    for (int q = 0; q < nslots && next < num_frames; ++q) { if ((rc = enqueue(q, next)) != OICC_OK) goto done; next += slot[q].num; }
+    for (int k = 0; slot[k % nslots].num > 0; ++k) {        // batches complete in order, alternating between the slots
+      const int q = k % nslots;
+      RemapSlot& s = slot[q];
+      CAMERA_TRY(hipStreamSynchronize(st[q]));
+      float ms = 0.0f;
+      double* acc[3] = {&rep.ms_upload, &rep.ms_kernel, &rep.ms_download};
+      for (int j = 0; j < 3; ++j) { CAMERA_TRY(hipEventElapsedTime(&ms, s.ev[j], s.ev[j + 1])); *acc[j] += ms; }
+      std::memcpy(out + int64_t(s.first) * out_frame, s.pin_out, size_t(s.num * out_frame));
+      s.num = 0;
+      if (next < num_frames) { if ((rc = enqueue(q, next)) != OICC_OK) goto done; next += s.num; }
+    }
+  }
+  rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+  if (report) *report = rep;
+done:
+  for (int q = 0; q < 2; ++q) if (st[q]) (void)hipStreamSynchronize(st[q]);
+  for (int q = 0; q < 2; ++q) {
+    RemapSlot& s = slot[q];
+    if (s.pin_in) (void)hipHostFree(s.pin_in);
+    if (s.pin_out) (void)hipHostFree(s.pin_out);
+    if (s.d_in) (void)hipFree(s.d_in);
+    if (s.d_out) (void)hipFree(s.d_out);
+    for (auto& e : s.ev) if (e) (void)hipEventDestroy(e);
+    if (st[q]) (void)hipStreamDestroy(st[q]);
+  }
+  if (d_map) (void)hipFree(d_map);
+  return rc;
+}

@@ -117,6 +117,7 @@ class ViewBundleAdjuster {   // theia::BundleAdjuster for one shared camera and 
     Check(oicc_ba_get_scene_points(h_, flat.data(), int64_t(points->size())));
     for (size_t i = 0; i < points->size(); ++i) std::copy(flat.begin() + 4 * i, flat.begin() + 4 * i + 4, (*points)[i].begin());
   }
+  void SetOption(const char* name, double value) { Check(oicc_ba_set_option(h_, name, value)); }
   void SetVariablePoints(const std::vector<uint8_t>& mask) { Check(oicc_ba_set_variable_points(h_, mask.data(), int64_t(mask.size()))); }
   oicc_summary Optimize(int max_iters, int flags, int mask) { oicc_summary s; Check(oicc_ba_optimize(h_, max_iters, flags, mask, &s)); return s; }
   // oicc_ba_point_covariances: 9 doubles per scene point (NaN for constant points), not multiplied by the variance factor

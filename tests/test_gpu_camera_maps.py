@@ -1,0 +1,361 @@
+"""The camera maps on the device (csrc/camera_maps.hip) against their numpy specification tests/camera_maps_restatement.py.
+
+Rays: the yardstick is the distance of the float64 restatement from its numpy.longdouble run on the same pixels; the device may
+be ten times that away from the float64 restatement (only libm and the order of the sums differ).  Both figures are printed
+("Camera maps", holds the measured ones).  Remap results are byte-identical: fixed order, no contraction."""
+import functools
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import camera_maps_cases as K
+import camera_maps_restatement as R
+from openimucameracalibrator_amd import camera_maps as cm
+from openimucameracalibrator_amd import io_files
+from openimucameracalibrator_amd import synthetic as S
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "openimucameracalibrator_amd", "csrc")
+
+
+def _rays_project_back(model, intr, xy, uv):
+    px, ok = S.project(model, np.asarray(intr, dtype=np.float64), np.concatenate([xy, np.ones((len(xy), 1))], 1))
+    assert np.all(ok)
+    return np.abs(px - uv).max(axis=1)
+
+
+# ---------------------------------------------------------------- unproject
+@pytest.mark.parametrize("n", K.UNPROJECT_SIZES)
+@pytest.mark.parametrize("name", K.PRESETS + ("folding",))
+def test_unproject_against_restatement(name, n):
+    model, intr, w, h = K.camera(name)
+    uv = K.unproject_pixels(name)[:n]
+    ref, ref_status = R.unproject(model, intr, uv)
+    ext, ext_status = R.unproject(model, intr, uv, dtype=np.longdouble)
+    xy, status = cm.unproject(model, intr, uv)
+    assert np.array_equal(status, ref_status)
+    assert np.array_equal(ext_status, ref_status)
+    if n > 1:
+        assert status[1] == 1 and np.all(np.isnan(xy[1]))              # the NaN pixel
+    good = status == 0
+    assert np.all(np.isnan(xy[~good]))
+    if name != "folding":
+        assert np.all(status[np.isfinite(uv[:, 0])] == 0)
+    if not good.any():
+        return
+    yardstick = float(np.abs(ext[good] - ref[good]).max())
+    distance = float(np.abs(xy[good] - ref[good]).max())
+    print("unproject %s n=%d: yardstick (float64 vs longdouble) %.3e, device vs float64 %.3e" % (name, n, yardstick, distance))
+    assert distance <= 10.0 * yardstick
+    back = _rays_project_back(model, intr, xy[good], uv[good])
+    assert np.all(back <= 1e-9 * (1.0 + np.abs(uv[good]).max(axis=1)))
+
+
+def test_unproject_folding_camera_accepts_exactly_the_pixels_inside_the_fold():
+    model, intr, w, h = R.FOLDING_CAMERA
+    uv = R.pixel_grid(w, h, 3)
+    xy, status = cm.unproject(model, intr, uv)
+    radius = np.hypot(uv[:, 0] - 480.0, uv[:, 1] - 270.0)
+    assert np.array_equal(status == 0, radius < R.FOLD_RADIUS_PX)
+    assert int((status == 0).sum()) == 32618
+
+
+def test_unproject_rejects_bad_arguments():
+    model, intr, w, h = S.CAMERAS["pinhole"]
+    with pytest.raises(ValueError):
+        cm.unproject(model, intr[:-1], [[1.0, 2.0]])
+    with pytest.raises(ValueError):
+        cm.unproject(3, intr, [[1.0, 2.0]])
+    with pytest.raises(ValueError):
+        cm.unproject(model, [np.nan] + list(intr[1:]), [[1.0, 2.0]])
+
+
+# ---------------------------------------------------------------- map
+@functools.lru_cache(maxsize=None)
+def _ray_yardstick_px(case, size):
+    """The double yardstick of the map coordinates: float64 against longdouble restatement, in pixels."""
+    (sm, si, sw, sh), dm, di, Rm, _ = K.MAP_CASES[case]
+    sw, sh = K.map_reference(case, size)[4]
+    dw, dh = size
+    a = R.rectify_map(sm, si, sw, sh, dm, di, dw, dh, R=Rm)[2]
+    b = R.rectify_map(sm, si, sw, sh, dm, di, dw, dh, R=Rm, dtype=np.longdouble)[2]
+    both = np.isfinite(a[..., 0]) & np.isfinite(np.asarray(b[..., 0], dtype=np.float64))
+    return float(np.abs(a[both] - b[both]).max()) if both.any() else 0.0
+
+
+@pytest.mark.parametrize("size", K.MAP_SIZES, ids=lambda s: "%dx%d" % s)
+@pytest.mark.parametrize("case", list(K.MAP_CASES))
+def test_map_against_restatement(case, size):
+    (sm, si, _, _), dm, di, Rm, all_valid = K.MAP_CASES[case]
+    ref_map, ref_valid, _, raw, (sw, sh) = K.map_reference(case, size)
+    dw, dh = size
+    mapxy, valid, num_valid = cm.rectify_map(sm, si, sw, sh, dm, di, dw, dh, R=Rm)
+    assert mapxy.shape == (dh, dw, 2) and mapxy.dtype == np.float32 and valid.shape == (dh, dw)
+    assert num_valid == int(valid.sum())
+    flagged = K.near_border(raw, sw, sh)
+    assert flagged.sum() <= 1e-3 * dw * dh
+    assert np.array_equal(valid[~flagged], ref_valid[~flagged])
+    assert np.all(np.isnan(mapxy[valid == 0]))
+    if all_valid:
+        assert num_valid == dw * dh
+    both = (valid == 1) & (ref_valid == 1)
+    if both.any():
+        yardstick = _ray_yardstick_px(case, size)
+        diff = np.abs(mapxy[both].astype(np.float64) - ref_map[both].astype(np.float64))
+        ulp = np.spacing(np.abs(ref_map[both])).astype(np.float64)
+        print("map %s %dx%d: valid %d, worst |device - restatement| %.3e px, double yardstick %.3e px" % (case, dw, dh, num_valid, diff.max(), yardstick))
+        assert np.all(diff <= ulp + yardstick)
+    if case.startswith("identity"):
+        uu, vv = np.meshgrid(np.arange(dw), np.arange(dh))
+        assert np.abs(mapxy - np.stack([uu + 1.0, vv + 1.0], -1)).max() <= 1e-3
+
+
+@pytest.mark.parametrize("size", K.MAP_SIZES, ids=lambda s: "%dx%d" % s)
+@pytest.mark.parametrize("name", K.PRESETS)
+def test_map_of_a_camera_onto_itself_is_the_identity(name, size):
+    """Source = destination, literally: the same camera and the same size.  Every border pixel then maps onto the image border,
+    where the last bit of the Newton decides the validity (the whole border, 0.58 % of 960 x 540, would be flagged: more than the
+    0.1 % cap of the test above), so validity is compared in the interior only.  On the border a pixel is either valid with its own
+    coordinates, src_w - 1 and src_h - 1 included, or invalid with NaN."""
+    model, intr, _, _ = S.CAMERAS[name]
+    w, h = size
+    mapxy, valid, num_valid = cm.rectify_map(model, intr, w, h, model, intr, w, h)
+    uu, vv = np.meshgrid(np.arange(w), np.arange(h))
+    own = np.stack([uu, vv], -1).astype(np.float64)
+    border = (uu == 0) | (uu == w - 1) | (vv == 0) | (vv == h - 1)
+    assert np.all(valid[~border] == 1)
+    assert num_valid == int(valid.sum())
+    ok = valid == 1
+    assert np.all(np.isnan(mapxy[~ok]))
+    if ok.any():
+        assert np.abs(mapxy[ok] - own[ok]).max() <= 1e-3
+        assert mapxy[ok][:, 0].max() <= w - 1 and mapxy[ok][:, 1].max() <= h - 1 and mapxy[ok].min() >= 0
+    print("identity %s %dx%d: %d of %d border pixels valid" % (name, w, h, int((ok & border).sum()), int(border.sum())))
+    # the restatement agrees wherever its own coordinate is not within 1e-6 px of the border
+    ref_map, ref_valid, _, raw = R.rectify_map(model, intr, w, h, model, intr, w, h)
+    flagged = K.near_border(raw, w, h)
+    assert np.array_equal(valid[~flagged], ref_valid[~flagged])
+
+
+def test_rectified_pinhole_equals_restatement_and_balance_one_loses_pixels():
+    for name in K.PRESETS:
+        model, intr, w, h = S.CAMERAS[name]
+        for balance in (0.0, 1.0):
+            dev = cm.rectified_pinhole(model, intr, w, h, balance)
+            ref = R.rectified_pinhole(model, intr, w, h, balance)
+            assert np.allclose(dev, ref, rtol=1e-12, atol=0)
+        _, _, n1 = cm.rectify_map(model, intr, w, h, S.CAM_PINHOLE, cm.rectified_pinhole(model, intr, w, h, 1.0), w, h)
+        assert n1 < w * h
+
+
+# ---------------------------------------------------------------- remap
+@pytest.mark.parametrize("border", (0, 255))
+@pytest.mark.parametrize("num_frames", (1, 5))
+@pytest.mark.parametrize("channels", (1, 3))
+def test_remap_is_byte_identical_to_restatement(channels, num_frames, border):
+    for name, ((w, h), m) in K.REMAP_MAPS.items():
+        F = K.remap_frames(name, num_frames, channels)
+        ref = R.remap(F, m, border)
+        rep = {}
+        out = cm.remap(F, m, border_value=border, batch=2, report=rep)          # 5 frames: three batches, the last one short
+        assert out.shape == ref.shape and out.dtype == np.uint8
+        assert np.array_equal(out, ref), name
+        assert rep["ms_total"] > 0 and rep["ms_kernel"] > 0
+    # the ties of the half-pixel shift round up: (0 + 255 + 255 + 0) / 4 = 127.5 -> 128
+    F = K.remap_frames("half-pixel-shift", num_frames, channels)
+    out = cm.remap(F, K.REMAP_MAPS["half-pixel-shift"][1], border_value=border, batch=2)
+    assert np.all(out[0] == 128)
+
+
+def test_remap_on_a_cuda_tensor_equals_the_host_route():
+    import torch
+    for channels in (1, 3):
+        for name, ((w, h), m) in K.REMAP_MAPS.items():
+            F = K.remap_frames(name, 5, channels)
+            host = cm.remap(F, m, border_value=17, batch=2)
+            t = torch.from_numpy(F).cuda()
+            out = cm.remap(t, m, border_value=17)
+            assert isinstance(out, torch.Tensor) and out.is_cuda and out.device == t.device and out.dtype == torch.uint8
+            assert np.array_equal(out.cpu().numpy(), host), name
+            out2 = cm.remap(t, torch.from_numpy(m).cuda(), border_value=17)
+            assert np.array_equal(out2.cpu().numpy(), host), name
+
+
+def test_remap_device_rejects_arrays_that_are_not_on_the_device():
+    import ctypes as C
+    from openimucameracalibrator_amd import _abi, _lib
+    import torch
+    b = _lib.load_camera_maps()
+    F = np.zeros((1, 4, 4), np.uint8); m = np.zeros((2, 2, 2), np.float32); out = np.zeros((1, 2, 2), np.uint8)
+    t = torch.zeros((1, 4, 4), dtype=torch.uint8, device="cuda"); o = torch.zeros((1, 2, 2), dtype=torch.uint8, device="cuda")
+    mt = torch.zeros((2, 2, 2), dtype=torch.float32, device="cuda")
+    u8 = lambda x: C.cast(x.data_ptr(), _abi.c_u8p)
+    assert b.remap_device(None, 1, 4, 4, 1, u8(t), C.cast(mt.data_ptr(), _abi.c_fp), 2, 2, 0, u8(o)) == 0
+    torch.cuda.synchronize()
+    assert b.remap_device(None, 1, 4, 4, 1, F.ctypes.data_as(_abi.c_u8p), C.cast(mt.data_ptr(), _abi.c_fp), 2, 2, 0, u8(o)) == -1
+    assert b.remap_device(None, 1, 4, 4, 1, u8(t), m.ctypes.data_as(_abi.c_fp), 2, 2, 0, u8(o)) == -1
+    assert b.remap_device(None, 1, 4, 4, 1, u8(t), C.cast(mt.data_ptr(), _abi.c_fp), 2, 2, 0, out.ctypes.data_as(_abi.c_u8p)) == -1
+
+
+def test_remap_rejects_bad_arguments():
+    F = np.zeros((1, 4, 4), np.uint8)
+    m = np.zeros((2, 2, 2), np.float32)
+    with pytest.raises(ValueError):
+        cm.remap(F, m, batch=0)
+    with pytest.raises(ValueError):
+        cm.remap(np.zeros((1, 4, 4, 2), np.uint8), m)
+    with pytest.raises(ValueError):
+        cm.remap(F, m, border_value=256)
+
+
+# ---------------------------------------------------------------- undistort_frames
+def test_undistort_frames_on_rendered_views():
+    views = K.rendered_views()
+    F = views["images"]
+    model, intr, w, h = S.CAMERAS["gopro9_division"]
+    out, (dm, di, dw, dh), valid = cm.undistort_frames(F, model, intr)
+    assert dm == S.CAM_PINHOLE and (dw, dh) == (w, h) and valid.all()
+    mapxy, v, n = cm.rectify_map(model, intr, w, h, dm, di, dw, dh)
+    assert np.array_equal(out, cm.remap(F, mapxy))
+    ref = R.remap(F, R.rectify_map(model, intr, w, h, S.CAM_PINHOLE, R.rectified_pinhole(model, intr, w, h), w, h)[0])
+    diff = np.abs(out.astype(np.int16) - ref.astype(np.int16))
+    print("undistort_frames: %d of %d u8 values differ from the restatement, largest difference %d" % ((diff > 0).sum(), diff.size, diff.max()))
+    assert (diff > 0).sum() <= 1e-3 * diff.size
+    assert diff.max() <= 1
+
+
+# ---------------------------------------------------------------- discrepancy
+@pytest.mark.parametrize("size", ((1, 1), (65, 3), (960, 540)), ids=lambda s: "%dx%d" % s)
+def test_discrepancy_against_restatement(size):
+    w, h = size
+    am, ai, _, _ = S.CAMERAS["gopro9_division"]
+    bm, bi, _, _ = S.CAMERAS["gopro9_eucm"]
+    ref = R.discrepancy(am, ai, bm, bi, w, h)
+    d1 = cm.discrepancy(am, ai, bm, bi, w, h)
+    d2 = cm.discrepancy(am, ai, bm, bi, w, h)
+    assert d1 == d2                                           # bit-identical between runs
+    print("discrepancy %dx%d: device %r restatement %r" % (w, h, d1, ref))
+    assert d1["count"] == ref[0]
+    assert abs(d1["rms"] - ref[1]) <= 1e-12 * ref[1]
+    assert abs(d1["max"] - ref[2]) <= 1e-12 * ref[2]
+
+
+def test_discrepancy_counts_only_pixels_with_a_ray():
+    model, intr, w, h = R.FOLDING_CAMERA
+    bm, bi, _, _ = S.CAMERAS["pinhole"]
+    ref = R.discrepancy(model, intr, bm, bi, w, h)
+    d = cm.discrepancy(model, intr, bm, bi, w, h)
+    assert d["count"] == ref[0] < w * h
+    assert abs(d["rms"] - ref[1]) <= 1e-12 * ref[1] and abs(d["max"] - ref[2]) <= 1e-12 * ref[2]
+
+
+# ---------------------------------------------------------------- conversion
+@pytest.mark.parametrize("pair", K.CONVERSION_PAIRS, ids=lambda p: "%s-to-%d" % p)
+def test_conversion_reaches_the_scipy_optimum(pair):
+    src, dst_model = pair
+    model, intr, w, h = S.CAMERAS[src]
+    ref = K.conversion_reference(src, dst_model)
+    res = cm.convert_camera_model(model, intr, w, h, dst_model)
+    rms = K.grid_rms(src, dst_model, res["intrinsics"])
+    print("conversion %s -> %d: device fit rms %.6e (reported %.6e), scipy %.6e; full image rms %.3e max %.3e count %d; %s" % (
+        src, dst_model, rms, res["fit_rms_px"], ref["rms"], res["full_image_rms_px"], res["full_image_max_px"], res["valid_pixels"],
+        res["summary"]["message"]))
+    assert res["grid_points"] == ref["points"]
+    assert rms <= 1.01 * ref["rms"] + 1e-7
+    assert res["fit_rms_px"] <= 1.01 * ref["rms"] + 1e-7
+    assert res["intrinsics"][2] == 0.0 or dst_model == S.CAM_DIVISION_UNDISTORTION      # the skew stays fixed
+    d = cm.discrepancy(model, intr, dst_model, res["intrinsics"], w, h)
+    assert (res["valid_pixels"], res["full_image_rms_px"], res["full_image_max_px"]) == (d["count"], d["rms"], d["max"])
+    if dst_model == S.CAM_PINHOLE_RADIAL_TANGENTIAL:
+        assert res["full_image_max_px"] > 5.0              # a bad fit is reported as bad
+
+
+# ---------------------------------------------------------------- programs
+def _run(cmd, **kw):
+    return subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, universal_newlines=True, cwd=ROOT, **kw)
+
+
+def _write_calibration(path, name):
+    model, intr, w, h = S.CAMERAS[name]
+    io_files.write_camera_calibration(path, model, intr, w, h, 60.0, 10, 0.1)
+
+
+def test_undistort_images_programs_write_identical_pngs(tmp_path):
+    from PIL import Image
+    views = K.rendered_views()
+    src = tmp_path / "in"; src.mkdir()
+    rgb = np.stack([views["images"][1], views["images"][1][::-1], 255 - views["images"][1]], -1)
+    Image.fromarray(views["images"][0]).save(str(src / "100.png"))
+    Image.fromarray(np.ascontiguousarray(rgb)).save(str(src / "200.png"))
+    calib = str(tmp_path / "cam_calib.json")
+    _write_calibration(calib, "gopro9_division")
+    outs = {}
+    for tag, cmd in (("cpp", [os.path.join(CSRC, "undistort_images")]), ("py", [sys.executable, "-m", "openimucameracalibrator_amd.undistort_images"])):
+        out = tmp_path / ("out_" + tag)
+        cam = str(tmp_path / ("rectified_%s.json" % tag))
+        r = _run(cmd + ["--input_path", str(src), "--camera_calibration_json", calib, "--output_path", str(out), "--balance", "0.25",
+                        "--output_camera_json", cam])
+        assert r.returncode == 0, r.stdout
+        outs[tag] = {n: np.asarray(Image.open(str(out / n))) for n in ("100.png", "200.png")}
+        outs[tag + "_cam"] = io_files.read_camera_calibration(cam)
+    for n in ("100.png", "200.png"):
+        assert outs["cpp"][n].shape == outs["py"][n].shape
+        assert np.array_equal(outs["cpp"][n], outs["py"][n]), n
+    assert outs["cpp"]["100.png"].ndim == 2 and outs["cpp"]["200.png"].shape[2] == 3
+    assert outs["cpp_cam"][0] == outs["py_cam"][0] == S.CAM_PINHOLE
+    assert np.allclose(outs["cpp_cam"][1], outs["py_cam"][1], rtol=1e-12, atol=0)
+    model, intr, w, h = S.CAMERAS["gopro9_division"]
+    expect = cm.undistort_frames(views["images"][:1], model, intr, balance=0.25)[0][0]
+    assert np.array_equal(outs["py"]["100.png"], expect)
+
+
+def _numbers(obj, prefix=""):
+    out = {}
+    for k, v in obj.items():
+        if isinstance(v, dict):
+            out.update(_numbers(v, prefix + k + "."))
+        elif isinstance(v, (int, float)) and not isinstance(v, bool):
+            out[prefix + k] = float(v)
+    return out
+
+
+def test_convert_camera_model_programs_agree(tmp_path):
+    calib = str(tmp_path / "cam_calib.json")
+    _write_calibration(calib, "gopro9_division")
+    objs = {}
+    for tag, cmd in (("cpp", [os.path.join(CSRC, "convert_camera_model")]), ("py", [sys.executable, "-m", "openimucameracalibrator_amd.convert_camera_model"])):
+        out = str(tmp_path / ("converted_" + tag))
+        r = _run(cmd + ["--camera_calibration_json", calib, "--camera_model_to_calibrate", "FISHEYE", "--save_path_calib_dataset", out])
+        assert r.returncode == 0, r.stdout
+        assert "full_image_max_px" in r.stdout
+        objs[tag] = json.load(open(out + ".json"))
+        model, intr, w, h, fps = io_files.read_camera_calibration(out + ".json")
+        assert model == S.CAM_FISHEYE and (w, h) == (960, 540) and len(intr) == 9
+    a, b = _numbers(objs["cpp"]), _numbers(objs["py"])
+    assert sorted(a) == sorted(b)
+    for k in a:
+        print("convert_camera_model %s: C++ %.12g python %.12g" % (k, a[k], b[k]))
+        assert abs(a[k] - b[k]) <= 1e-9, k
+    conv = objs["cpp"]["conversion"]
+    assert conv["source_intrinsic_type"] == "DIVISION_UNDISTORTION" and objs["cpp"]["intrinsic_type"] == "FISHEYE"
+    assert sorted(conv) == ["fit_rms_px", "full_image_max_px", "full_image_rms_px", "source_intrinsic_type", "valid_pixels"]
+
+
+@pytest.mark.parametrize("program", ("undistort_images", "convert_camera_model"))
+def test_programs_reject_unknown_flags_and_missing_files(program, tmp_path):
+    calib = str(tmp_path / "cam_calib.json")
+    _write_calibration(calib, "gopro9_division")
+    (tmp_path / "in").mkdir()
+    good = {"undistort_images": ["--input_path", str(tmp_path / "in"), "--camera_calibration_json", calib, "--output_path", str(tmp_path / "o")],
+            "convert_camera_model": ["--camera_calibration_json", calib, "--camera_model_to_calibrate", "FISHEYE", "--save_path_calib_dataset",
+                                     str(tmp_path / "c")]}[program]
+    missing = [a if a != calib else str(tmp_path / "nothing.json") for a in good]
+    for cmd in ([os.path.join(CSRC, program)], [sys.executable, "-m", "openimucameracalibrator_amd." + program]):
+        assert _run(cmd + good + ["--no_such_flag", "1"]).returncode != 0
+        assert _run(cmd + missing).returncode != 0
