@@ -192,7 +192,7 @@ __device__ __forceinline__ void bcr_corner_solve(double* C, double* da, int* fai
 //   bcri_backward_kernel x_i = T_rhs - T_left^T x_il - T_right^T x_ir - T_arrow^T x_arrow: a matrix-vector product, no
 //                        triangular solve on the way back
 //   bcri_invert_schur_kernel   the first two in ONE launch where a level's Schur workgroups fit the chip at once (bcr_level_joined):
-//                        every workgroup of a pivot inverts D_i itself, Z_i stays in its LDS
+//                        every workgroup of a pivot factors D_i itself and forms its tile T_x = (B_x X) X^T from X = L^-T in LDS, no Z_i
 //   bcri_last_backward_kernel  the last block and the back substitution of the level below the top one in ONE launch where the
 //                        pairing of levels would leave that level alone (bcr_fold_level): one workgroup per pivot of the level
 //                        repeats the last block's work and finds its neighbours' x in its own LDS
@@ -267,14 +267,20 @@ __device__ __forceinline__ double bcri_back_body(const double (&lv)[kBackRows], 
 }
 
 // What follows the factorisation of [D_i ; I] (all waves, after a workgroup barrier): Z = X X^T, and for the last block (LAST) the arrow
-// corner and the first back substitution.  ZLDS: Z stays in LDS as it does for LAST (rows 0..63 of W) and is not stored -- the
-// workgroup goes on with a Schur group of its pivot (bcri_invert_schur_kernel).
+// corner and the first back substitution.  ZLDS (bcri_invert_schur_kernel): no Z at all -- the workgroup goes on with ONE Schur group
+// of its pivot and forms that group's tile T_x = (B_x X) X^T from X, which stays in rows 64..127 of W (bcri_tx_stage); only the
+// failure report is left here.
 // FOLD (bcri_last_backward_kernel; with LAST): the launch has one workgroup per pivot of the level below the top one, whose plan
 // fields are A.o, A.s, A.p, A.m.  Every workgroup does the last block's work with identical bits and then the back substitution of
 // its own pivot from LDS; only workgroup 0 stores what they all share and raises A.fail.
 template <bool LAST, bool ZLDS, bool FOLD>
 __device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* da, int* failp, const double* Fs, const double* Cs, double* Zg, int tid, int wave, int lane, bool report, double* x0s) {
   static_assert(!FOLD || LAST, "the folded level follows the last block");
+  static_assert(!ZLDS || !LAST, "the last block keeps Z");
+  if (ZLDS) {   // (failp: final behind the factorisation's last barrier)
+    if (report && tid == 0 && *failp) atomicOr(A.fail, 1);
+    return;
+  }
   constexpr int LD = kInvLD, NW = kInvWaves, NT = 64 * NW, FLD = 65;
   const int li = lane & 15, lq = lane >> 4;
   const int a = A.a, a1 = a + 1;
@@ -309,7 +315,7 @@ __device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* d
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int x = 16 * xt + li, y = 16 * yt + lq + 4 * r;
-      if (LAST || ZLDS) { W[y * LD + x] = g[r]; if (xt != yt) W[x * LD + y] = g[r]; }
+      if (LAST) { W[y * LD + x] = g[r]; if (xt != yt) W[x * LD + y] = g[r]; }
       else { Zg[y * 64 + x] = g[r]; if (xt != yt) Zg[x * 64 + y] = g[r]; }
     }
   }
@@ -433,9 +439,12 @@ __device__ __forceinline__ void bcri_tail(const BcrArgs& A, double* W, double* d
 // park (bcri_invert_schur_kernel): called once by every thread between the LDS fill of D_i and the first barrier -- the global loads
 // the caller issued before this function have landed with D_i's by then (one round trip for both), and what it writes behind `Fs`
 // is visible after the factorisation
+// shadow (bcri_invert_schur_kernel): called with p - 1 by the waves that run no chain while the panel waves run the chain of panel
+// p = 1..3 -- the columns of panel p - 1 are final then; it holds no barrier
 struct BcrNoPark { __device__ __forceinline__ void operator()(double*) const {} };
-template <bool LAST, bool PROF, bool ZLDS = false, bool FOLD = false, class LoadD, class Park = BcrNoPark>
-__device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, LoadD load_d, const bool report = true, Park park = Park()) {
+struct BcrNoShadow { __device__ __forceinline__ void operator()(int) const {} };
+template <bool LAST, bool PROF, bool ZLDS = false, bool FOLD = false, class LoadD, class Park = BcrNoPark, class Shadow = BcrNoShadow>
+__device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, LoadD load_d, const bool report = true, Park park = Park(), Shadow shadow = Shadow()) {
   constexpr int LD = kInvLD, NW = kInvWaves, NT = 64 * NW, NTILE = 20, SLOTS = (NTILE + NW - 1) / NW, RU = 128, NAW = 3, FLD = 65;
   static_assert(NW == 16, "the corner phases of block 0 take one tile per wave");
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -535,6 +544,8 @@ __device__ __forceinline__ void bcri_invert_body(const BcrArgs& A, const int i, 
         for (int c = 0; c < 16; ++c) cp[c * LD] = av[c];
       }
       if (bad && lane == 0) *failp = 1;
+    } else if (ZLDS && p > 0) {
+      shadow(p - 1);
     }
     BCR_MARK(1);
     bcr_lds_barrier();
@@ -598,8 +609,9 @@ __global__ __launch_bounds__(64 * kInvWaves) void bcri_last_backward_kernel(BcrA
 
 // ---- one Schur group of a pivot: (16-row tile x of the border rows, up to four column tiles y) ----
 // Run by bcri_schur_kernel (one workgroup of 4 waves per group, Z_i read from global memory, where bcri_invert_kernel left it) and by
-// bcri_invert_schur_kernel (every workgroup of a pivot inverts D_i itself and takes Z_i from its LDS): the same decoding, the same
-// MFMA sequence on the same operand values, the same stores and atomics -- only where the operands are read differs (`Ops` below).
+// bcri_invert_schur_kernel (every workgroup of a pivot factors D_i itself): the same decoding, the same update stage -T_x B_y^T with
+// the same stores and atomics.  The tile T_x = B_x Z_i is B_x (X X^T) in the one (the T stage of bcri_schur_body) and (B_x X) X^T in the other
+// (bcri_tx_stage): equal up to rounding, not bit for bit.
 struct BcrSchurGroup {
   int k, i, irs;                 // position among the active blocks, block, where the right neighbour's D / F live
   bool hasL, hasR, ghostR;       // (a pivot at position 0 -- odd number of active blocks -- has no left neighbour; ghostR: the right neighbour is the next rank's first block)
@@ -623,59 +635,73 @@ __device__ __forceinline__ BcrSchurGroup bcri_schur_group(const BcrArgs& A, int 
   G.leaves = ((G.xk == 1 || G.yk == 1) && !G.hasR) || ((G.xk == 0 || G.yk == 0) && !G.hasL);
   return G;
 }
-// The three MFMA operands of a group, element kk of a lane's sixteen: B_x (row 16 xt + li, pivot variable 4 kk + lq), Z (column
-// 16 wave + li, the same variable), B_y (row 16 wave + li, the same variable).  From global memory ...
+// The MFMA operands of a group, element kk of a lane's sixteen: B_x (row 16 xt + li, pivot variable 4 kk + lq), Z (column 16 wave + li,
+// the same variable), B_y (row 16 wave + li, the same variable), T_x (row li, the same variable).  kTStage: bcri_schur_body forms
+// T_x = B_x Z itself, in Ts.  From global memory ...
 struct BcrSchurGlobalOps {
+  static constexpr bool kTStage = true;
   static constexpr bool kLateY = false;   // (B_y is in flight with B_x and Z: one global round trip)
   const double *px, *pz, *py; int sx, sy; bool okx, oky;
   __device__ __forceinline__ double x(int kk) const { return px[4 * kk * sx]; }
   __device__ __forceinline__ double z(int kk) const { return pz[4 * kk * 64]; }
   __device__ __forceinline__ double y(int kk) const { return oky ? py[4 * kk * sy] : 0.0; }
+  __device__ __forceinline__ double t(const double (*Ts)[68], int kk, int li, int lq) const { return Ts[li][4 * kk + lq]; }
 };
-// ... or from LDS: Z in rows 0..63 of the inversion's W (bcri_tail<., ZLDS>), the border tiles parked as [pivot variable][16 rows]
-// with zeros where a row lies beyond the arrow (bcri_invert_schur_kernel)
+// ... or from LDS (bcri_invert_schur_kernel): the border tiles are parked as [pivot variable][16 rows] with zeros where a row lies
+// beyond the arrow; T_x was formed by bcri_tx_stage (below), which reads B_x itself and needs no Z, and is read as the sum of its
+// partial tiles TP
 struct BcrSchurLdsOps {
+  static constexpr bool kTStage = false;
   static constexpr bool kLateY = true;    // (an LDS read: B_y is loaded behind T, 32 registers fewer where 1024 threads leave 128)
-  const double *px, *pz, *py; bool okx;
-  __device__ __forceinline__ double x(int kk) const { return px[64 * kk]; }
-  __device__ __forceinline__ double z(int kk) const { return pz[4 * kk * kInvLD]; }
+  const double *py, *TP;
   __device__ __forceinline__ double y(int kk) const { return py[64 * kk]; }
+  __device__ __forceinline__ double t(const double (*)[68], int kk, int li, int lq) const;   // (behind bcri_tx_at)
 };
-// Called by every thread of the workgroup (one barrier inside); `active`: this wave is one of the group's four, `wave` its index among them.
+__device__ __forceinline__ int bcri_schur_trow0(const BcrSchurGroup& G) { return G.xk == 0 ? 16 * G.xt : (G.xk == 1 ? 64 + 16 * G.xt : 128 + 16 * G.xt); }
+// A group runs in two stages with a workgroup barrier between them: the T stage leaves the tile T_x = B_x Z_i in LDS and (store_t) in
+// the pivot's rows of T, the update stage forms -T_x B_y^T and adds or stores it.  bcri_schur_kernel runs both here; the joined kernel
+// (Ops::kTStage false) has run bcri_tx_stage with its barriers and bcri_tx_store, and runs the update stage alone.
+// Called by every thread of the workgroup; `active`: this wave is one of the group's four, `wave` its index among them.
 template <class Ops>
 __device__ __forceinline__ void bcri_schur_body(const BcrArgs& A, const BcrSchurGroup& G, double (*Ts)[68], const Ops& ops, const bool active, const int wave, const int lane) {
   const int li = lane & 15, lq = lane >> 4;
   const int a1 = A.a + 1, s = A.s;
   const int k = G.k, i = G.i, il = i - s, irs = G.irs, xk = G.xk, xt = G.xt, yk = G.yk, ny = G.ny;
-  const bool hasL = G.hasL, ghostR = G.ghostR, store_t = G.store_t, okx = ops.okx;
-  double* Tg = A.Lf + (int64_t)i * (192 + a1) * 64 + 4096;
-  double vx[16], vz[16], vy[16];
-  if (active) {
+  const bool hasL = G.hasL, ghostR = G.ghostR;
+  double vy[16];
+  // ---- T stage
+  if constexpr (Ops::kTStage) {
+    const bool store_t = G.store_t, okx = ops.okx;
+    double* Tg = A.Lf + (int64_t)i * (192 + a1) * 64 + 4096;
+    double vx[16], vz[16];
+    if (active) {
 #pragma unroll
-    for (int kk = 0; kk < 16; ++kk) { vx[kk] = ops.x(kk); vz[kk] = ops.z(kk); }
-    if (!Ops::kLateY) {
+      for (int kk = 0; kk < 16; ++kk) { vx[kk] = ops.x(kk); vz[kk] = ops.z(kk); }
+      if (!Ops::kLateY) {
 #pragma unroll
-      for (int kk = 0; kk < 16; ++kk) vy[kk] = ops.y(kk);
+        for (int kk = 0; kk < 16; ++kk) vy[kk] = ops.y(kk);
+      }
+      asm volatile("" ::: "memory");   // (every load above is issued before the first MFMA)
+      // T(x rows, columns 16 wave ..) = B_x Z: two accumulators, the dependent chain is 8 MFMAs
+      bcr_v4d tq = {0.0, 0.0, 0.0, 0.0}, tq2 = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int kk = 0; kk < 16; kk += 2) {
+        tq = __builtin_amdgcn_mfma_f64_16x16x4f64(okx ? vx[kk] : 0.0, vz[kk], tq, 0, 0, 0);
+        tq2 = __builtin_amdgcn_mfma_f64_16x16x4f64(okx ? vx[kk + 1] : 0.0, vz[kk + 1], tq2, 0, 0, 0);
+      }
+      tq += tq2;
+      // tq[r] <-> (column 16 wave + li, row lq + 4 r of the tile)
+      const int trow0 = bcri_schur_trow0(G);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = lq + 4 * r;
+        Ts[row][16 * wave + li] = tq[r];
+        if (store_t && (xk != 2 || 16 * xt + row < a1)) Tg[(int64_t)(trow0 + row) * 64 + 16 * wave + li] = tq[r];
+      }
     }
-    asm volatile("" ::: "memory");   // (every load above is issued before the first MFMA)
-    // T(x rows, columns 16 wave ..) = B_x Z: two accumulators, the dependent chain is 8 MFMAs
-    bcr_v4d tq = {0.0, 0.0, 0.0, 0.0}, tq2 = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kk = 0; kk < 16; kk += 2) {
-      tq = __builtin_amdgcn_mfma_f64_16x16x4f64(okx ? vx[kk] : 0.0, vz[kk], tq, 0, 0, 0);
-      tq2 = __builtin_amdgcn_mfma_f64_16x16x4f64(okx ? vx[kk + 1] : 0.0, vz[kk + 1], tq2, 0, 0, 0);
-    }
-    tq += tq2;
-    // tq[r] <-> (column 16 wave + li, row lq + 4 r of the tile)
-    const int trow0 = xk == 0 ? 16 * xt : (xk == 1 ? 64 + 16 * xt : 128 + 16 * xt);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = lq + 4 * r;
-      Ts[row][16 * wave + li] = tq[r];
-      if (store_t && (xk != 2 || 16 * xt + row < a1)) Tg[(int64_t)(trow0 + row) * 64 + 16 * wave + li] = tq[r];
-    }
+    __syncthreads();
   }
-  __syncthreads();
+  // ---- update stage
   if (!active || wave >= ny) return;
   const int yt = wave;
   // orientation of the new coupling (il, ir): il is at position kn of the next level, whose pivots have parity pn
@@ -688,7 +714,7 @@ __device__ __forceinline__ void bcri_schur_body(const BcrArgs& A, const BcrSchur
     for (int kk = 0; kk < 16; ++kk) vy[kk] = ops.y(kk);
   }
 #pragma unroll
-  for (int kk = 0; kk < 16; ++kk) vt[kk] = Ts[li][4 * kk + lq];
+  for (int kk = 0; kk < 16; ++kk) vt[kk] = ops.t(Ts, kk, li, lq);
   asm volatile("" ::: "memory");   // (every load above is issued before the first MFMA)
   bcr_v4d gq = {0.0, 0.0, 0.0, 0.0}, gq2 = {0.0, 0.0, 0.0, 0.0};
   if (swap) {
@@ -773,15 +799,179 @@ __global__ __launch_bounds__(256) void bcri_schur_kernel(BcrArgs A) {
   bcri_schur_body(A, G, Ts, ops, true, wave, lane);
 }
 
-// A level in ONE launch: grid (12 + 3 rtf groups, pivots of the level), 16 waves.  EVERY workgroup of a pivot inverts D_i itself --
-// the inversion is deterministic, all copies of Z_i are the same bits -- and then runs its Schur group with Z_i in its own LDS: no
-// store of Z, no second launch, nothing handed from one workgroup to another (no flag, no poll, no wait).  The group's border tiles
+// ---- T_x = (B_x X) X^T: the T stage of bcri_invert_schur_kernel, from X = L^-T (upper triangular, rows 64..127 of W), without Z ----
+// A workgroup of that kernel needs ONE 16 x 64 tile T_x = B_x Z_i, not Z_i = X X^T (80 MFMAs on every one of a pivot's 15 workgroups, a
+// barrier, then 16 dependent-pair MFMAs on each of four waves).  Both factors of (B_x X) X^T fall apart into ten chunks of 4 MFMAs
+// (chunk t <-> tri10(t) = (p, q), q <= p).  A chunk of panel p needs the columns of panel p of X only, which are final when that
+// panel has left the chain: the chunks of the panels 0..2 are formed while the panel waves run the next chain (bcri_tx_shadow), the
+// four of panel 3 behind the factorisation, one per wave and SIMD (bcri_tx_stage):
+//   Y chunk (p, q):  YP(p, q) = B_x[:, 16 q .. 16 q + 15] X[16 q .. 16 q + 15, panel p]        (X's tiles below the diagonal are zero: q <= p)
+//   T chunk (p, i):  TP(p, i) = Y_p X[16 i .. 16 i + 15, panel p]^T,   Y_p = YP(p, 0) + ... + YP(p, p) summed in that order   (i <= p)
+//   T_x[:, tile i] = TP(i, i) + ... + TP(3, i), summed in that order by whoever reads it (bcri_tx_at)
+// The orders are fixed, so every workgroup of a pivot has the same bits of T_x.  It is another association of B_x X X^T than the
+// two-launch route's B_x (X X^T): the joined kernel is held to the host solve's bounds, not to that route's bits.
+// Partial tiles are 16 x 16, element (row, col) at [col * stride + row] with an odd stride (LD = 145 and 17 are both 17 mod 32: the
+// stores of rows lq + 4 r at column li and the operand loads of row li at column 4 kk + lq both spread over the banks).  YP lives in
+// rows 0..63 of W -- the factor L, which nothing reads behind the factorisation's last barrier --, tile t at columns 16 (t & 3), rows
+// 16 (t >> 2); TP in an array of its own.  A non-positive pivot leaves NaN in X, hence in every YP, TP and update.
+constexpr int kTxChunks = 10, kTxStride = 17, kTxTileDoubles = 16 * kTxStride;
+__device__ __forceinline__ int bcri_tx_chunk(int p, int q) { return (p * (p + 1)) / 2 + q; }   // (tri10's inverse)
+__device__ __forceinline__ double* bcri_tx_ytile(double* W, int t) { return W + 16 * (t & 3) * kInvLD + 16 * (t >> 2); }
+// Called by every thread of the workgroup; two workgroup barriers inside, the second one behind the TP stores.
+// T0: the first chunk that is left to do -- 6: panel 3's four, the others came from bcri_tx_shadow (0: all ten behind the factorisation,
+// the form the shadow was measured against: DESIGN §8-1); chunk T0 + w on wave w.
+template <int T0>
+__device__ __forceinline__ void bcri_tx_stage(double* W, const double* P, double* TP, const int wave, const int lane) {
+  constexpr int LD = kInvLD;
+  const int li = lane & 15, lq = lane >> 4;
+  const int chunk = wave + T0;
+  int p, q; tri10(chunk < kTxChunks ? chunk : 0, p, q);
+  if (chunk < kTxChunks) {
+    const double* pb = P + (16 * q + lq) * 16 + li;               // B_x(row li, variable 16 q + 4 kk + lq)
+    const double* px = W + (16 * p + li) * LD + 64 + 16 * q + lq;   // X(16 q + 4 kk + lq, column 16 p + li)
+    double vb[4], vx[4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) { vb[kk] = pb[64 * kk]; vx[kk] = px[4 * kk]; }
+    asm volatile("" ::: "memory");   // (every load above is issued before the first MFMA)
+    bcr_v4d y = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) y = __builtin_amdgcn_mfma_f64_16x16x4f64(vb[kk], vx[kk], y, 0, 0, 0);
+    // y[r] <-> (row lq + 4 r, column li of panel p)
+    double* yp = bcri_tx_ytile(W, chunk) + li * LD + lq;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) yp[4 * r] = y[r];
+  }
+  bcr_lds_barrier();
+  if (chunk < kTxChunks) {
+    const int i = q, c0 = bcri_tx_chunk(p, 0);
+    const double* px = W + (16 * p + lq) * LD + 64 + 16 * i + li;   // X(row 16 i + li, column 16 p + 4 kk + lq)
+    double yv[4][4], vx[4];
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+      if (qq <= p) {   // (wave uniform)
+        const double* yp = bcri_tx_ytile(W, c0 + qq) + lq * LD + li;   // YP(p, qq)(row li, column 4 kk + lq)
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) yv[qq][kk] = yp[4 * kk * LD];
+      } else {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) yv[qq][kk] = 0.0;
+      }
+    }
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) vx[kk] = px[4 * kk * LD];
+    asm volatile("" ::: "memory");   // (every load above is issued before the first sum)
+    bcr_v4d t = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) {
+      double ys = yv[0][kk];
+#pragma unroll
+      for (int qq = 1; qq < 4; ++qq) if (qq <= p) ys += yv[qq][kk];
+      t = __builtin_amdgcn_mfma_f64_16x16x4f64(ys, vx[kk], t, 0, 0, 0);
+    }
+    // t[r] <-> (row lq + 4 r, column li of tile i)
+    double* tp = TP + chunk * kTxTileDoubles + li * kTxStride + lq;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) tp[4 * r] = t[r];
+  }
+  bcr_lds_barrier();
+}
+// The chunks of the panel pp = 0..2 in the shadow of the chain of panel pp + 1 (bcri_invert_body's `shadow`): the columns of panel pp
+// are final and thirteen waves wait for the panel waves.  ONE wave does a panel -- wave 3 + 4 pp: the waves 3, 7, 11 sit on the SIMD
+// that holds no panel wave -- so Y_pp needs no workgroup barrier: it goes through the wave's own tile of LDS (the MFMA's output layout
+// is not its operand layout) behind a wave-local wait.  The same sums in the same order as bcri_tx_stage<0>: YP(pp, q) from zero each,
+// added in q order; TP(pp, i) from zero each.  YS: [3] tiles.
+__device__ __forceinline__ void bcri_tx_shadow(const double* W, const double* P, double* TP, double* YS, const int pp, const int wave, const int lane) {
+  constexpr int LD = kInvLD;
+  if (wave != 3 + 4 * pp) return;
+  const int li = lane & 15, lq = lane >> 4;
+  double* ys = YS + pp * kTxTileDoubles;
+  {
+    const double* pb = P + lq * 16 + li;                           // B_x(row li, variable 16 q + 4 kk + lq)
+    const double* px = W + (16 * pp + li) * LD + 64 + lq;          // X(16 q + 4 kk + lq, column 16 pp + li)
+    double vb[3][4], vx[3][4];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) { vb[q][kk] = q <= pp ? pb[256 * q + 64 * kk] : 0.0; vx[q][kk] = q <= pp ? px[16 * q + 4 * kk] : 0.0; }
+    }
+    asm volatile("" ::: "memory");   // (every load above is issued before the first MFMA)
+    bcr_v4d y = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      if (q <= pp) {   // (wave uniform)
+        bcr_v4d yq = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) yq = __builtin_amdgcn_mfma_f64_16x16x4f64(vb[q][kk], vx[q][kk], yq, 0, 0, 0);
+        if (q == 0) y = yq; else y += yq;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) ys[li * kTxStride + lq + 4 * r] = y[r];   // y[r] <-> (row lq + 4 r, column li of panel pp)
+  }
+  bcr_wave_sync();
+  {
+    const double* px = W + (16 * pp + lq) * LD + 64 + li;          // X(row 16 i + li, column 16 pp + 4 kk + lq)
+    double vy[4], vx[3][4];
+#pragma unroll
+    for (int kk = 0; kk < 4; ++kk) vy[kk] = ys[(4 * kk + lq) * kTxStride + li];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+      for (int kk = 0; kk < 4; ++kk) vx[i][kk] = i <= pp ? px[4 * kk * LD + 16 * i] : 0.0;
+    }
+    asm volatile("" ::: "memory");   // (every load above is issued before the first MFMA)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      if (i <= pp) {   // (wave uniform)
+        bcr_v4d t = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) t = __builtin_amdgcn_mfma_f64_16x16x4f64(vy[kk], vx[i][kk], t, 0, 0, 0);
+        double* tp = TP + bcri_tx_chunk(pp, i) * kTxTileDoubles + li * kTxStride + lq;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) tp[4 * r] = t[r];
+      }
+    }
+  }
+}
+// T_x(row, column 16 I + cl): the partial tiles of the panels I..3 in panel order
+template <int I>
+__device__ __forceinline__ double bcri_tx_sum(const double* TP, int row, int cl) {
+  const double* tp = TP + cl * kTxStride + row;
+  double v = tp[bcri_tx_chunk(I, I) * kTxTileDoubles];
+#pragma unroll
+  for (int p = I + 1; p < 4; ++p) v += tp[bcri_tx_chunk(p, I) * kTxTileDoubles];
+  return v;
+}
+__device__ __forceinline__ double bcri_tx_at(const double* TP, int i, int row, int cl) {   // (i: uniform)
+  return i == 0 ? bcri_tx_sum<0>(TP, row, cl) : (i == 1 ? bcri_tx_sum<1>(TP, row, cl) : (i == 2 ? bcri_tx_sum<2>(TP, row, cl) : bcri_tx_sum<3>(TP, row, cl)));
+}
+__device__ __forceinline__ double BcrSchurLdsOps::t(const double (*)[68], int kk, int li, int lq) const { return bcri_tx_at(TP, kk >> 2, li, 4 * (kk & 3) + lq); }
+// the pivot's rows of T in global memory, as the T stage of bcri_schur_body stores them: wave w of four stores the column tile w
+__device__ __forceinline__ void bcri_tx_store(const BcrArgs& A, const BcrSchurGroup& G, const double* TP, const int w, const int lane) {
+  const int li = lane & 15, lq = lane >> 4;
+  const int a1 = A.a + 1;
+  double* Tg = A.Lf + (int64_t)G.i * (192 + a1) * 64 + 4096;
+  const int trow0 = bcri_schur_trow0(G);
+  double v[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) v[r] = bcri_tx_at(TP, w, lq + 4 * r, li);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = lq + 4 * r;
+    if (G.xk != 2 || 16 * G.xt + row < a1) Tg[(int64_t)(trow0 + row) * 64 + 16 * w + li] = v[r];
+  }
+}
+
+// A level in ONE launch: grid (12 + 3 rtf groups, pivots of the level), 16 waves.  EVERY workgroup of a pivot factors D_i itself --
+// the factorisation is deterministic, all copies of X = L^-T are the same bits -- and then runs its Schur group on T_x = (B_x X) X^T
+// from X in its own LDS (bcri_tx_stage): Z_i is never formed, no second launch, nothing handed from one workgroup to another (no flag,
+// no poll, no wait).  The group's border tiles
 // (one of B_x, up to four of B_y) do not depend on Z_i: their loads are issued with D_i's and parked in LDS behind the inversion's
 // arrays, so no global round trip stands behind the inversion.  Groups of a side the pivot has no neighbour on leave at once.  For
 // levels whose workgroups fit the chip at once (bcr_level_joined); level 0 is not among them while its inversions ride in the build
 // launch, whose workgroups still write the blocks the Schur updates land on.
 constexpr int kInvLdsDoubles = 64 * kInvLD + 64 + 8 + kInvMsDoubles;                 // W, da, failp, ms of bcri_invert_body
-constexpr int kJoinLdsDoubles = kInvLdsDoubles + 5 * 1024 + 16 * 68;       // + B_x tile, four B_y tiles ([64][16] each), Ts
+constexpr int kJoinLdsDoubles = kInvLdsDoubles + 5 * 1024 + (kTxChunks + 3) * kTxTileDoubles;       // + B_x tile, four B_y tiles ([64][16] each), the ten partial tiles of T_x, the shadow waves' Y tiles
 __global__ __launch_bounds__(64 * kInvWaves) void bcri_invert_schur_kernel(BcrArgs A) {
   BCR_RETURN_IF_DONE(A);
   const BcrSchurGroup G = bcri_schur_group(A, (int)blockIdx.x, (int)blockIdx.y);
@@ -805,25 +995,28 @@ __global__ __launch_bounds__(64 * kInvWaves) void bcri_invert_schur_kernel(BcrAr
   for (int t = 0; t < 4; ++t) by[t] = t < G.ny ? border_at(G.yk, t) : 0.0;
   asm volatile("" ::: "memory");   // (issued here, with D_i's loads; parked in LDS before the first barrier of the inversion)
   const double* Dg = A.D + (int64_t)G.i * 4096;
+  extern __shared__ __attribute__((aligned(16))) double lds_[];   // (bcri_invert_body's `lds`: W first; the parked tiles, TP and the shadow's Y tiles behind kInvLdsDoubles)
   const bool report = (int)blockIdx.x == (G.hasL ? 0 : 8);   // the pivot's first group that does not leave (left x left, or right x right)
   bcri_invert_body<false, false, true>(A, G.i, [Dg](int e) { return Dg[e]; }, report,
     [&](double* P) {
       P[tid] = bx;
 #pragma unroll
       for (int t = 0; t < 4; ++t) P[1024 * (1 + t) + tid] = by[t];
-    });
-  // (bcri_tail ended with a workgroup barrier: Z_i is in rows 0..63 of W, the parked tiles are visible)
+    },
+    [&](int pp) { bcri_tx_shadow(lds_, lds_ + kInvLdsDoubles, lds_ + kInvLdsDoubles + 5 * 1024, lds_ + kInvLdsDoubles + 5 * 1024 + kTxChunks * kTxTileDoubles, pp, wave, lane); });
+  // (the factorisation ended with a workgroup barrier: X is in rows 64..127 of W, the parked tiles are visible)
   extern __shared__ __attribute__((aligned(16))) double lds[];
-  const double* W = lds;
+  double* W = lds;
   const double* P = lds + kInvLdsDoubles;
-  double (*Ts)[68] = reinterpret_cast<double (*)[68]>(lds + kInvLdsDoubles + 5 * 1024);
+  double* TP = lds + kInvLdsDoubles + 5 * 1024;
+  bcri_tx_stage<6>(W, P, TP, wave, lane);   // (panel 3's chunks: the panels 0..2 came in the shadow of the chains)
+  // the waves 4..7 store the group's rows of T while the waves 0 .. ny - 1 run the update stage
+  if (G.store_t && wave >= 4 && wave < 8) bcri_tx_store(A, G, TP, wave - 4, lane);
   const bool active = wave < 4;
   BcrSchurLdsOps ops;
-  ops.okx = true;   // (rows beyond the arrow were parked as zeros)
-  ops.px = P + lq * 16 + li;
+  ops.TP = TP;
   ops.py = P + 1024 * (1 + (active && wave < G.ny ? wave : 0)) + lq * 16 + li;
-  ops.pz = W + lq * kInvLD + 16 * (active ? wave : 0) + li;
-  bcri_schur_body(A, G, Ts, ops, active, wave, lane);
+  bcri_schur_body(A, G, nullptr, ops, active, wave, lane);
 }
 
 // ---- the retraction inside the LAST launch of a whole-band solve (lm_retract.h; used by the two-level back-substitution kernel) ----
