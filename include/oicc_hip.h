@@ -888,6 +888,79 @@ int oicc_camera_remap_device(void* hip_stream, int32_t num_frames, int32_t src_w
                              const uint8_t* frames_dev, const float* map_dev, int32_t dst_w, int32_t dst_h, int32_t border_value,
                              uint8_t* out_dev);
 
+/* ---- rolling shutter: gyro-driven row maps, rectified frames and features (rolling_shutter.hip) ----------------------------
+ * What the calibrated line delay and gyro-to-camera rotation are for: taking the rolling shutter out of footage and features.
+ * Specified step by step by tests/rolling_shutter_restatement.py and DESIGN.md ("Rolling-shutter rectification").
+ *
+ * Model: rotation only, the standard gyro correction.  The camera is taken to turn about its centre during the readout;
+ * translation (parallax) is not modelled, nor is there any smoothing between frames.  Rays are (x, y, 1): fields of view of
+ * 180 degrees and more are out of scope.
+ *   Time.  Row y (continuous) of frame k is exposed at frame_t[k] + y line_delay_s in the camera clock; line_delay_s has any
+ *   sign, 0 included.  A gyro sample at IMU time t lies at t + time_offset_imu_to_cam in the camera clock (the offset the
+ *   spline calibration applies, same sign).  Times enter as differences: a_j = (gyro_t[j] - frame_t[k]) + time_offset, and
+ *   tau_j = a_j - reference_row line_delay_s is sample j relative to t_ref,k = frame_t[k] + reference_row line_delay_s.
+ *   Rates.  gyro_rates [n][3] are corrected rates MS_g (omega_m - b) in the IMU frame; they are rotated into the camera frame
+ *   once, omega_c = R(q_i_c)^T omega_i, q_i_c (w, x, y, z) the rotation of T_i_c as result.json holds it (normalised first).
+ *   Orientation.  Between samples j and j + 1 the rate is linear in time: Q(t) = Q_j Exp(phi_j(s)), s = t - t_j,
+ *   phi_j(s) = omega_j s + (omega_{j+1} - omega_j) s^2 / (2 dt_j), Q_{j+1} = Q_j Exp(phi_j(dt_j)) (right multiplication, body
+ *   rates).  R_rel,k(t) = Q(t_ref,k)^-1 Q(t); a ray d0 of the virtual global-shutter camera at t_ref is R_rel(t)^T d0 in the
+ *   camera at time t.  Rows are clamped to [0, src_h - 1] before they become a time.
+ *   Frame status, by time comparisons on the host.  The window of frame k is the span of (0, (src_h - 1) line_delay_s,
+ *   reference_row line_delay_s).  0: the window lies inside [a_0, a_{n-1}] and touches at most 256 samples (the last sample
+ *   with a_j <= the window's start up to the first with a_j >= its end); 1: no gyro coverage; 2: more than 256 samples.
+ *   Frames with a status other than 0 get all-invalid maps, border_value pixels, NaN points and rotations: never uncorrected data.
+ *   Per destination pixel.  The ray as in oicc_camera_rectify_map (closed form for a plain PINHOLE, else Newton), rotated by
+ *   R9 the same way; then the fixed point y_0 = reference_row, tau = (clamp(y_n) - reference_row) line_delay_s,
+ *   (x, y)_{n+1} = project_src(R_rel(tau)^T d0), stop at |y_{n+1} - y_n| <= 1e-10 (1 + |y_{n+1}|), at most 24 evaluations.
+ *   Valid: a ray, z > 0 before and after R_rel, every projection succeeded with finite values, converged, and coordinates
+ *   in [0, src_w - 1] x [0, src_h - 1]; otherwise NaN coordinates and validity 0.  Coordinates are rounded to float32.
+ *
+ * oicc_rs_rectify_map: map [num_frames][dst_h][dst_w][2] float32, valid [num_frames][dst_h][dst_w], evaluations (may be NULL)
+ *   [num_frames][dst_h][dst_w] projections spent, frame_status [num_frames], num_valid (may be NULL) [num_frames],
+ *   device_ms (may be NULL) [3] = table kernel, ray kernel, map kernel, by device events.
+ * oicc_rs_rectify_frames: host pointers, frames [num_frames][src_h][src_w][channels] u8 (channels 1 or 3) -> out
+ *   [num_frames][dst_h][dst_w][channels]; batches of `batch` frames through pinned staging, two in flight, as
+ *   oicc_camera_remap.  The fixed point and the bilinear rule of oicc_camera_remap run in one kernel on the float32-rounded
+ *   coordinates; no per-frame map is written.  The result equals oicc_camera_remap through oicc_rs_rectify_map's maps.
+ * oicc_rs_rectify_frames_device: frames and out on the current device, work enqueued on hip_stream (NULL = the default
+ *   stream); the stream and both arrays must belong to the current device (OICC_ERR_INVALID_ARG otherwise).  The small gyro
+ *   and frame-time arrays come from the host; the call returns once the stream has run the work and has freed its tables.
+ * oicc_rs_rectify_points: forward, no fixed point.  xy_in [n][2] observed in frame frame_index[i] -> source ray -> R_rel(tau(y))
+ *   -> R9^T -> destination camera: xy_out [n][2] global-shutter-equivalent coordinates in double.  status [n]: 0 a point,
+ *   1 none (no ray, z <= 0 or a failed projection), 2 the frame's status is not 0; 1 and 2 give NaN.
+ * oicc_rs_row_rotations: q [n][4] (w, x, y, z) of R_rel at (frame_index[i], rows[i]); status [n] 0, or 2 with NaN.
+ * OICC_ERR_INVALID_ARG for fewer than 2 gyro samples, gyro times that do not strictly increase, non-finite input, a q_i_c whose
+ * norm is further than 1e-6 from 1, no frames, a frame index out of range, null arrays, and whatever oicc_camera_rectify_map
+ * and oicc_camera_remap refuse.  Arguments are judged before the device is looked for; OICC_ERR_NO_DEVICE without one (no
+ * CPU fallback). */
+typedef struct oicc_rs_scene {
+  int32_t src_model, src_w, src_h, dst_model, dst_w, dst_h;
+  const double* src_intr;            /* the model's own count, as oicc_camera_rectify_map */
+  const double* dst_intr;
+  const double* R9;                  /* row-major, destination camera -> source camera; NULL = identity */
+  int64_t num_gyro;
+  const double* gyro_t;              /* [num_gyro] seconds, IMU clock, strictly increasing */
+  const double* gyro_rates;          /* [num_gyro][3] corrected rates, IMU frame, rad/s */
+  double q_i_c[4];                   /* w, x, y, z */
+  double time_offset_imu_to_cam;
+  int32_t num_frames, reserved;
+  const double* frame_t;             /* [num_frames] seconds, camera clock: exposure of row 0 */
+  double line_delay_s, reference_row;
+} oicc_rs_scene;
+typedef struct oicc_rs_frames_report {
+  double ms_table, ms_rays, ms_upload, ms_kernel, ms_download, ms_total;
+} oicc_rs_frames_report;
+int oicc_rs_rectify_map(int32_t device_ordinal, const oicc_rs_scene* scene, float* map, uint8_t* valid, uint8_t* evaluations,
+                        int32_t* frame_status, int64_t* num_valid, double* device_ms);
+int oicc_rs_rectify_frames(int32_t device_ordinal, const oicc_rs_scene* scene, int32_t channels, const uint8_t* frames,
+                           int32_t border_value, int32_t batch, uint8_t* out, int32_t* frame_status, oicc_rs_frames_report* report);
+int oicc_rs_rectify_frames_device(void* hip_stream, const oicc_rs_scene* scene, int32_t channels, const uint8_t* frames_dev,
+                                  int32_t border_value, uint8_t* out_dev, int32_t* frame_status);
+int oicc_rs_rectify_points(int32_t device_ordinal, const oicc_rs_scene* scene, int64_t n, const int32_t* frame_index, const double* xy_in,
+                           double* xy_out, uint8_t* status, int32_t* frame_status, double* device_ms);
+int oicc_rs_row_rotations(int32_t device_ordinal, const oicc_rs_scene* scene, int64_t n, const int32_t* frame_index, const double* rows,
+                          double* q, uint8_t* status, int32_t* frame_status, double* device_ms);
+
 /* ---- the elimination plan of the block cyclic reduction (kernels_bcr.hip), host arithmetic only: needs no device ----------
  * The damped LM system of n 64-column blocks is reduced level by level.  Level l: the active blocks are origin + k stride,
  * k < active; those with k mod 2 == parity are its pivots (parity 0 when `active` is odd -- both ends are pivots --, else 1;

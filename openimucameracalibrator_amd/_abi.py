@@ -468,3 +468,46 @@ class BoundCameraMaps:
             fn.restype = res
             fn.argtypes = args
             setattr(self, name, fn)
+
+
+class RsScene(C.Structure):
+    """oicc_rs_scene (include/oicc_hip.h): what every rolling-shutter entry takes."""
+    _fields_ = [("src_model", C.c_int32), ("src_w", C.c_int32), ("src_h", C.c_int32), ("dst_model", C.c_int32), ("dst_w", C.c_int32),
+                ("dst_h", C.c_int32), ("src_intr", c_dp), ("dst_intr", c_dp), ("R9", c_dp), ("num_gyro", C.c_int64), ("gyro_t", c_dp),
+                ("gyro_rates", c_dp), ("q_i_c", C.c_double * 4), ("time_offset_imu_to_cam", C.c_double), ("num_frames", C.c_int32),
+                ("reserved", C.c_int32), ("frame_t", c_dp), ("line_delay_s", C.c_double), ("reference_row", C.c_double)]
+
+
+class RsFramesReport(C.Structure):
+    """oicc_rs_frames_report (include/oicc_hip.h)."""
+    _fields_ = [("ms_table", C.c_double), ("ms_rays", C.c_double), ("ms_upload", C.c_double), ("ms_kernel", C.c_double),
+                ("ms_download", C.c_double), ("ms_total", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+c_scene = C.POINTER(RsScene)
+
+# Rolling-shutter rectification (oicc_rs_* in include/oicc_hip.h), a table of its own like CAMERA_MAPS_SIGNATURES: the CPU checker
+# has no counterpart of these entries.
+ROLLING_SHUTTER_SIGNATURES = {
+    "rectify_map": (C.c_int, [C.c_int32, c_scene, c_fp, c_u8p, c_u8p, c_i32p, c_i64p, c_dp]),
+    "rectify_frames": (C.c_int, [C.c_int32, c_scene, C.c_int32, c_u8p, C.c_int32, C.c_int32, c_u8p, c_i32p, C.POINTER(RsFramesReport)]),
+    "rectify_frames_device": (C.c_int, [C.c_void_p, c_scene, C.c_int32, c_u8p, C.c_int32, c_u8p, c_i32p]),
+    "rectify_points": (C.c_int, [C.c_int32, c_scene, C.c_int64, c_i32p, c_dp, c_dp, c_u8p, c_i32p, c_dp]),
+    "row_rotations": (C.c_int, [C.c_int32, c_scene, C.c_int64, c_i32p, c_dp, c_dp, c_u8p, c_i32p, c_dp]),
+}
+
+
+class BoundRollingShutter:
+    """Bound oicc_rs_* entry points of one library + prefix (``oicc_rs_`` for liboicc_hip.so)."""
+
+    def __init__(self, lib, prefix):
+        self.lib = lib
+        self.prefix = prefix
+        for name, (res, args) in ROLLING_SHUTTER_SIGNATURES.items():
+            fn = getattr(lib, prefix + name)  # AttributeError = missing symbol: fail loudly
+            fn.restype = res
+            fn.argtypes = args
+            setattr(self, name, fn)

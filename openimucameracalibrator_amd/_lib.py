@@ -7,7 +7,7 @@ fails when no HIP device is usable.
 import ctypes
 import os
 
-from ._abi import Bound, BoundAllan, BoundBa, BoundBcrPlan, BoundBoard, BoundCameraMaps, BoundLmRetract, BoundPlanarRansac, BoundStaticImu
+from ._abi import Bound, BoundAllan, BoundBa, BoundBcrPlan, BoundBoard, BoundCameraMaps, BoundLmRetract, BoundPlanarRansac, BoundRollingShutter, BoundStaticImu
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OICC_DEV_LIB") or os.path.join(_HERE, "csrc", "liboicc_hip.so")   # OICC_DEV_LIB: another BUILD of the same library (developer A/B timing, scripts/build_variant.sh)
@@ -18,6 +18,7 @@ _bound_static_imu = None
 _bound_board = None
 _bound_planar_ransac = None
 _bound_camera_maps = None
+_bound_rolling_shutter = None
 _bound_bcr_plan = None
 _bound_lm_retract = None
 
@@ -80,6 +81,14 @@ def load_camera_maps():
     if _bound_camera_maps is None:
         _bound_camera_maps = BoundCameraMaps(load().lib, "oicc_camera_")
     return _bound_camera_maps
+
+
+def load_rolling_shutter():
+    """oicc_rs_* entry points (rolling-shutter row maps, rectified frames, points, row rotations) of the same library."""
+    global _bound_rolling_shutter
+    if _bound_rolling_shutter is None:
+        _bound_rolling_shutter = BoundRollingShutter(load().lib, "oicc_rs_")
+    return _bound_rolling_shutter
 
 
 def load_bcr_plan():

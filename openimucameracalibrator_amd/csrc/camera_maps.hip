@@ -25,67 +25,11 @@
 #include <cstdint>
 #include <cstring>
 #include <vector>
-#include "../../include/oicc_hip.h"
-#include "spline_math.h"
+#include "camera_device.h"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWaves = kThreads / 64;
-constexpr int kNewtonSteps = 20;
-constexpr double kStepTol = 1e-13;
-constexpr double kReprojectionTol = 1e-9;
-constexpr int kMaxIntr = 10;
-
-struct Camera { int model; double in[kMaxIntr]; };
-
-__host__ __device__ inline int intrinsics_count(int model) {
-  switch (model) {
-    case oicc::CAM_PINHOLE: return 7;
-    case oicc::CAM_PINHOLE_RADIAL_TANGENTIAL: return 10;
-    case oicc::CAM_FISHEYE: return 9;
-    case oicc::CAM_DIVISION_UNDISTORTION: return 5;
-    case oicc::CAM_DOUBLE_SPHERE: return 7;
-    case oicc::CAM_EXTENDED_UNIFIED: return 7;
-    default: return 0;
-  }
-}
-
-__device__ __forceinline__ double max_abs2(double a, double b) { return fmax(fabs(a), fabs(b)); }
-
-// The ray (x, y, 1) of pixel (u, v) on the principal branch; false (and NaN) where there is none.
-__device__ bool unproject(const Camera& cam, double u, double v, double& x, double& y) {
-  const bool division = cam.model == oicc::CAM_DIVISION_UNDISTORTION;
-  const double f = cam.in[0], fa = cam.in[0] * cam.in[1];
-  const double cx = division ? cam.in[2] : cam.in[3], cy = division ? cam.in[3] : cam.in[4];
-  x = (u - cx) / f;
-  y = (v - cy) / fa;
-  double px[2], J[6];
-  bool ok = true;
-  for (int it = 0; it < kNewtonSteps; ++it) {
-    const double p[3] = {x, y, 1.0};
-    ok = oicc::camera_project<true>(cam.model, cam.in, p, px, J);
-    if (!ok) break;
-    const double ex = px[0] - u, ey = px[1] - v;
-    const double det = J[0] * J[4] - J[1] * J[3];
-    const double dx = (J[4] * ex - J[1] * ey) / det;
-    const double dy = (J[0] * ey - J[3] * ex) / det;
-    x -= dx;
-    y -= dy;
-    if (!(max_abs2(dx, dy) > kStepTol * (1.0 + max_abs2(x, y)))) break;    // also leaves on NaN
-  }
-  if (ok) {
-    const double p[3] = {x, y, 1.0};
-    ok = oicc::camera_project<true>(cam.model, cam.in, p, px, J);
-    const double err = max_abs2(px[0] - u, px[1] - v);
-    const double det = J[0] * J[4] - J[1] * J[3];
-    const double tr = J[0] / f + J[4] / fa;
-    ok = ok && isfinite(x) && isfinite(y) && isfinite(err) && isfinite(det) && isfinite(tr) &&
-         err <= kReprojectionTol * (1.0 + max_abs2(u, v)) && det > 0.0 && tr > 0.0;
-  }
-  if (!ok) { x = nan(""); y = nan(""); }
-  return ok;
-}
+using namespace oicc_camera;   // Camera, unproject and the bilinear tap: shared with rolling_shutter.hip
 
 __global__ __launch_bounds__(kThreads) void camera_unproject_kernel(Camera cam, int64_t n, const double* __restrict__ uv,
                                                                     double* __restrict__ xy, uint8_t* __restrict__ status) {
@@ -97,8 +41,6 @@ __global__ __launch_bounds__(kThreads) void camera_unproject_kernel(Camera cam, 
   *reinterpret_cast<double2*>(xy + 2 * i) = make_double2(x, y);
   status[i] = ok ? 0 : 1;
 }
-
-struct Rotation { double r[9]; };
 
 __global__ __launch_bounds__(kThreads) void camera_map_kernel(Camera src, int src_w, int src_h, Camera dst, int closed_form, int dst_w,
                                                               int dst_h, Rotation R, float2* __restrict__ map,
@@ -159,61 +101,23 @@ __global__ __launch_bounds__(kThreads) void camera_remap_kernel(const uint8_t* _
                                                                 uint8_t* __restrict__ out) {
   const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
   if (i >= dst_pixels) return;
-  const float2 m = map[i];
+  BilinearTap<CH> tap;
   const int64_t src_frame = int64_t(src_w) * src_h * CH, dst_frame = dst_pixels * CH;
   uint8_t* o = out + i * CH;
-  // NaN fails every comparison
-  const bool inside = m.x >= 0.0f && m.x <= float(src_w - 1) && m.y >= 0.0f && m.y <= float(src_h - 1);
-  if (!inside) {
+  if (!tap.set(map[i], src_w, src_h)) {
     for (int f = 0; f < num_frames; ++f, o += dst_frame)
 #pragma unroll
       for (int c = 0; c < CH; ++c) o[c] = uint8_t(border);
     return;
   }
-  const double xf = double(m.x), yf = double(m.y);
-  const double x0 = floor(xf), y0 = floor(yf);
-  const double a = xf - x0, b = yf - y0;
-  const double w00 = (1.0 - a) * (1.0 - b), w01 = a * (1.0 - b), w10 = (1.0 - a) * b, w11 = a * b;
-  const bool right = a != 0.0, down = b != 0.0;       // a weight of exactly 0: the neighbour is not read (last row / column)
-  const int64_t o00 = (int64_t(y0) * src_w + int64_t(x0)) * CH;
-  const int64_t o01 = right ? o00 + CH : o00, o10 = down ? o00 + int64_t(src_w) * CH : o00;
-  const int64_t o11 = o10 + (right ? CH : 0);
   const uint8_t* s = frames;
   for (int f = 0; f < num_frames; ++f, s += src_frame, o += dst_frame) {
 #pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      const double p00 = double(s[o00 + c]), p01 = double(s[o01 + c]), p10 = double(s[o10 + c]), p11 = double(s[o11 + c]);
-      const double val = (w00 * p00 + w01 * p01) + (w10 * p10 + w11 * p11);
-      const double r = floor(val + 0.5);
-      o[c] = uint8_t(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
-    }
+    for (int c = 0; c < CH; ++c) o[c] = tap.sample(s, c);
   }
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-
-bool make_camera(int32_t model, const double* intr, Camera* cam) {
-  const int n = intrinsics_count(model);
-  if (n == 0 || !intr) return false;
-  cam->model = model;
-  for (int k = 0; k < kMaxIntr; ++k) cam->in[k] = 0.0;
-  for (int k = 0; k < n; ++k) {
-    if (!std::isfinite(intr[k])) return false;
-    cam->in[k] = intr[k];
-  }
-  return true;
-}
-
-int select_device(int32_t device_ordinal) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device_ordinal < 0 || device_ordinal >= ndev) return OICC_ERR_NO_DEVICE;   // no CPU fallback
-  if (hipSetDevice(device_ordinal) != hipSuccess) return OICC_ERR_NO_DEVICE;
-  return OICC_OK;
-}
-
-constexpr int64_t kMaxLanes = ((int64_t(1) << 31) - 1) * kThreads;   // one lane per pixel: the grid's x dimension stays below 2^31 blocks
-
-inline unsigned blocks_for(int64_t n) { return unsigned((n + kThreads - 1) / kThreads); }
 
 bool remap_args_ok(int32_t num_frames, int32_t src_w, int32_t src_h, int32_t channels, int32_t dst_w, int32_t dst_h, int32_t border_value) {
   return num_frames >= 1 && src_w >= 1 && src_h >= 1 && dst_w >= 1 && dst_h >= 1 && (channels == 1 || channels == 3) &&
@@ -281,7 +185,7 @@ extern "C" int oicc_camera_rectify_map(int32_t device_ordinal, int32_t src_model
       R.r[k] = R9[k];
     }
   if (int rc = select_device(device_ordinal)) return rc;
-  const int closed_form = dst.model == oicc::CAM_PINHOLE && dst.in[5] == 0.0 && dst.in[6] == 0.0;
+  const int closed_form = is_plain_pinhole(dst);
   const int64_t pixels = int64_t(dst_w) * dst_h;
   int rc = OICC_OK;
   float2* d_map = nullptr; uint8_t* d_valid = nullptr;

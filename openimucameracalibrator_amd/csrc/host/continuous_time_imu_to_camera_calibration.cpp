@@ -46,28 +46,6 @@ bool ReadIMU2CamInit(const std::string& path, Quat* imu_to_cam, double* time_off
   *time_offset = j.at("time_offset_gyro_to_cam").as_double();
   return true;
 }
-// src/io/read_misc.cc:49-63,84-149
-bool ReadIMUIntrinsics(const std::string& path_intr, const std::string& path_bias, ThreeAxisSensorCalibParams* acc, ThreeAxisSensorCalibParams* gyr) {
-  if (!path_bias.empty()) {
-    Value j;
-    if (oicc_json::parse_file(path_bias, &j)) {
-      acc->bias = Vec3{{j.at("accl_bias").at("x").as_double(), j.at("accl_bias").at("y").as_double(), j.at("accl_bias").at("z").as_double()}};
-      gyr->bias = Vec3{{j.at("gyro_bias").at("x").as_double(), j.at("gyro_bias").at("y").as_double(), j.at("gyro_bias").at("z").as_double()}};
-    } else std::cerr << "Error loading IMU bias file: " << path_bias << "\n";
-  }
-  if (!path_intr.empty()) {
-    Value j; if (!oicc_json::parse_file(path_intr, &j)) return false;
-    auto M = [](const Value& m, int r, int c) { return m.at(size_t(r)).at(size_t(c)).as_double(); };
-    // misalignment matrix layout [[1,-yz,zy],[xz,1,-zx],[-xy,yx,1]] (utils/types.h:238-239)
-    const Value& ma = j.at("accelerometer").at("misalignment_matrix"); const Value& sa = j.at("accelerometer").at("scale_matrix");
-    acc->mis[0] = -M(ma, 0, 1); acc->mis[1] = M(ma, 0, 2); acc->mis[2] = -M(ma, 1, 2);     // accelerometer: upper triangle only
-    for (int i = 0; i < 3; ++i) acc->scale[i] = M(sa, i, i);
-    const Value& mg = j.at("gyroscope").at("misalignment_matrix"); const Value& sg = j.at("gyroscope").at("scale_matrix");
-    gyr->mis[0] = -M(mg, 0, 1); gyr->mis[1] = M(mg, 0, 2); gyr->mis[2] = -M(mg, 1, 2); gyr->mis[3] = M(mg, 1, 0); gyr->mis[4] = -M(mg, 2, 0); gyr->mis[5] = M(mg, 2, 1);
-    for (int i = 0; i < 3; ++i) gyr->scale[i] = M(sg, i, i);
-  }
-  return true;
-}
 Value xyz(const Vec3& v) { Value o; o["x"] = Value(v[0]); o["y"] = Value(v[1]); o["z"] = Value(v[2]); return o; }
 Value xyz(const double* v) { return xyz(Vec3{{v[0], v[1], v[2]}}); }
 

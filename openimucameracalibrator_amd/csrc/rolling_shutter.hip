@@ -1,0 +1,662 @@
+// Rolling-shutter rectification from gyroscope rates (include/oicc_hip.h, "rolling shutter"; DESIGN.md section 3, "Rolling-shutter
+// rectification").  Rotation only: the camera is taken to turn about its centre during the readout; translation (parallax) is
+// out of scope, and so are fields of view of 180 degrees and more (rays are (x, y, 1), as in camera_maps.hip).
+//
+//   rs_frame_table_kernel  one lane per frame: the chain of at most 256 quaternion products over the frame's window of gyro
+//                          samples, then (tau_j = t_j - t_ref, Q'_j = Q(t_ref)^-1 Q_j, omega_j) per window sample.  The host has
+//                          found the window (first sample, count) by time comparisons, because it needs them for frame_status.
+//   rs_ray_kernel          one lane per destination pixel: its ray (closed form for a plain PINHOLE, else Newton), once per call.
+//   rs_map_kernel          one lane per (frame, pixel), the frame in the grid's y: the workgroup stages its frame's table in LDS
+//                          (16 KB), every lane runs the fixed point on its source row; float2 coordinates and a validity byte.
+//   rs_rectify_kernel<CH>  the same fixed point, then the bilinear tap of camera_remap_kernel on the float32-rounded coordinates;
+//                          no per-frame map reaches memory.
+//   rs_points_kernel       forward: an observed pixel of frame k -> source ray -> R_rel(tau(y)) -> destination camera.
+//   rs_rotation_kernel     R_rel as a quaternion for (frame, row) queries.
+//
+// tests/rolling_shutter_restatement.py restates every step in numpy.  Compiled with -ffp-contract=off like camera_maps.o: with
+// all rates zero the map is bit-equal to camera_map_kernel's, and the fused frames are byte-equal to remapping through the map.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+#include "camera_device.h"
+
+namespace {
+
+using namespace oicc_camera;
+
+constexpr int kMaxWindow = 256;          // gyro samples per frame window
+constexpr int kEntry = 8;                // doubles per table entry: tau, Q' (w x y z), omega (x y z)
+constexpr int kMaxEvaluations = 24;
+constexpr double kRowTol = 1e-10;
+constexpr int kFrameChunk = 32768;       // frames per launch (the grid's y dimension)
+
+struct Q4 { double w, x, y, z; };
+
+__device__ __forceinline__ Q4 qmul(const Q4& a, const Q4& b) {
+  return Q4{((a.w * b.w - a.x * b.x) - a.y * b.y) - a.z * b.z, ((a.w * b.x + a.x * b.w) + a.y * b.z) - a.z * b.y,
+            ((a.w * b.y - a.x * b.z) + a.y * b.w) + a.z * b.x, ((a.w * b.z + a.x * b.y) - a.y * b.x) + a.z * b.w};
+}
+
+// Exp of the rotation vector phi_j(s) = om0 s + (om1 - om0) s^2 / (2 dt): the rate is linear inside a gyro interval
+__device__ __forceinline__ Q4 interval_exp(const double* om0, const double* om1, double dt, double s) {
+  const double c = s * s / (2.0 * dt);
+  const double p0 = om0[0] * s + (om1[0] - om0[0]) * c, p1 = om0[1] * s + (om1[1] - om0[1]) * c, p2 = om0[2] * s + (om1[2] - om0[2]) * c;
+  const double th = sqrt((p0 * p0 + p1 * p1) + p2 * p2);
+  const double half = th / 2.0;
+  const double k = th < 1e-8 ? 0.5 - th * th / 48.0 : sin(half) / th;
+  return Q4{cos(half), k * p0, k * p1, k * p2};
+}
+
+// R_rel(tau) from a frame's table (LDS or global): the interval j with tau_j <= tau, clipped to the window
+__device__ __forceinline__ Q4 table_rotation(const double* tab, int count, double tau) {
+  int lo = 0, hi = count - 1;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (tab[mid * kEntry] <= tau) lo = mid; else hi = mid;
+  }
+  const double* e = tab + lo * kEntry;
+  const Q4 q = {e[1], e[2], e[3], e[4]};
+  return qmul(q, interval_exp(e + 5, e + kEntry + 5, e[kEntry] - e[0], tau - e[0]));
+}
+
+__device__ __forceinline__ void rotation_matrix(const Q4& q, double M[9]) {
+  M[0] = 1.0 - 2.0 * (q.y * q.y + q.z * q.z); M[1] = 2.0 * (q.x * q.y - q.w * q.z); M[2] = 2.0 * (q.x * q.z + q.w * q.y);
+  M[3] = 2.0 * (q.x * q.y + q.w * q.z); M[4] = 1.0 - 2.0 * (q.x * q.x + q.z * q.z); M[5] = 2.0 * (q.y * q.z - q.w * q.x);
+  M[6] = 2.0 * (q.x * q.z - q.w * q.y); M[7] = 2.0 * (q.y * q.z + q.w * q.x); M[8] = 1.0 - 2.0 * (q.x * q.x + q.y * q.y);
+}
+
+struct RsParams {
+  Camera src, dst;
+  Rotation R;
+  int src_w, src_h, dst_w, dst_h, src_closed_form, dst_closed_form;
+  double line_delay, reference_row, time_offset;
+};
+
+__device__ __forceinline__ double row_tau(const RsParams& P, double row) {
+  return (fmin(fmax(row, 0.0), double(P.src_h - 1)) - P.reference_row) * P.line_delay;
+}
+
+// gyro_t / rates: all samples (rates already in the camera frame); first / count: the frame's window.  table [frames][256][8].
+__global__ __launch_bounds__(64) void rs_frame_table_kernel(int num_frames, const double* __restrict__ gyro_t, const double* __restrict__ rates,
+                                                            const double* __restrict__ frame_t, const int64_t* __restrict__ first,
+                                                            const int32_t* __restrict__ count, double time_offset, double reference_delay,
+                                                            double* __restrict__ table) {
+  const int k = blockIdx.x * 64 + threadIdx.x;
+  if (k >= num_frames) return;
+  const int n = count[k];
+  if (n < 2) return;
+  const double* t = gyro_t + first[k];
+  const double* om = rates + 3 * first[k];
+  double* tab = table + int64_t(k) * kMaxWindow * kEntry;
+  const double tk = frame_t[k];
+  // times as differences first: absolute times reach 1e4 s
+  Q4 q = {1.0, 0.0, 0.0, 0.0};
+  double tau = ((t[0] - tk) + time_offset) - reference_delay;
+  int jr = 0;
+  Q4 q_jr = q;
+  double tau_jr = tau;
+  for (int j = 0; j < n; ++j) {
+    double* e = tab + j * kEntry;
+    e[0] = tau; e[1] = q.w; e[2] = q.x; e[3] = q.y; e[4] = q.z; e[5] = om[3 * j]; e[6] = om[3 * j + 1]; e[7] = om[3 * j + 2];
+    if (j <= n - 2 && (j == 0 || tau <= 0.0)) { jr = j; q_jr = q; tau_jr = tau; }     // the interval of t_ref, clipped to the window
+    if (j + 1 < n) {
+      const double next = ((t[j + 1] - tk) + time_offset) - reference_delay;
+      q = qmul(q, interval_exp(om + 3 * j, om + 3 * j + 3, next - tau, next - tau));
+      tau = next;
+    }
+  }
+  const double dt = tab[(jr + 1) * kEntry] - tau_jr;
+  const Q4 qref = qmul(q_jr, interval_exp(om + 3 * jr, om + 3 * jr + 3, dt, 0.0 - tau_jr));
+  const Q4 inv = {qref.w, -qref.x, -qref.y, -qref.z};
+  for (int j = 0; j < n; ++j) {
+    double* e = tab + j * kEntry;
+    const Q4 r = qmul(inv, Q4{e[1], e[2], e[3], e[4]});
+    e[1] = r.w; e[2] = r.x; e[3] = r.y; e[4] = r.z;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void rs_ray_kernel(Camera dst, int closed_form, int dst_w, int64_t pixels, double2* __restrict__ rays,
+                                                          uint8_t* __restrict__ ray_status) {
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= pixels) return;
+  const double u = double(i % dst_w), v = double(i / dst_w);
+  double x, y;
+  bool ok = true;
+  if (closed_form) {
+    y = (v - dst.in[4]) / (dst.in[0] * dst.in[1]);
+    x = (u - dst.in[3] - dst.in[2] * y) / dst.in[0];
+  } else {
+    ok = unproject(dst, u, v, x, y);
+  }
+  rays[i] = make_double2(x, y);
+  ray_status[i] = ok ? 0 : 1;
+}
+
+// The fixed point on the source row of one destination ray.  tab: the frame's table in LDS.
+__device__ __forceinline__ bool solve_pixel(const RsParams& P, const double* tab, int count, double x, double y, bool ok, double px[2], int& evaluations) {
+  const double p[3] = {(P.R.r[0] * x + P.R.r[1] * y) + P.R.r[2], (P.R.r[3] * x + P.R.r[4] * y) + P.R.r[5], (P.R.r[6] * x + P.R.r[7] * y) + P.R.r[8]};
+  px[0] = 0.0; px[1] = 0.0;
+  evaluations = 0;
+  ok = ok && p[2] > 0.0;
+  if (!ok) return false;
+  double row = P.reference_row;
+  bool converged = false;
+  for (int it = 0; it < kMaxEvaluations; ++it) {
+    double M[9];
+    rotation_matrix(table_rotation(tab, count, row_tau(P, row)), M);
+    const double d[3] = {(M[0] * p[0] + M[3] * p[1]) + M[6] * p[2], (M[1] * p[0] + M[4] * p[1]) + M[7] * p[2], (M[2] * p[0] + M[5] * p[1]) + M[8] * p[2]};   // R_rel^T p
+    ++evaluations;
+    if (!(d[2] > 0.0) || !oicc::camera_project<false>(P.src.model, P.src.in, d, px, nullptr) || !isfinite(px[0]) || !isfinite(px[1])) return false;
+    const double step = fabs(px[1] - row);
+    row = px[1];
+    if (step <= kRowTol * (1.0 + fabs(row))) { converged = true; break; }
+  }
+  return converged && px[0] >= 0.0 && px[0] <= double(P.src_w - 1) && px[1] >= 0.0 && px[1] <= double(P.src_h - 1);
+}
+
+// stages the table of frame blockIdx.y in LDS; false (for the whole workgroup) when the frame has none
+__device__ __forceinline__ bool stage_table(const double* __restrict__ table, const int32_t* __restrict__ count, int frame, double* lds, int& n) {
+  n = count[frame];
+  if (n < 2) return false;
+  const double* src = table + int64_t(frame) * kMaxWindow * kEntry;
+  for (int i = threadIdx.x; i < n * kEntry; i += kThreads) lds[i] = src[i];
+  __syncthreads();
+  return true;
+}
+
+// map [frames][pixels], valid [frames][pixels], evaluations [frames][pixels] or null
+__global__ __launch_bounds__(kThreads) void rs_map_kernel(RsParams P, int first_frame, const double* __restrict__ table,
+                                                          const int32_t* __restrict__ count, const double2* __restrict__ rays,
+                                                          const uint8_t* __restrict__ ray_status, int64_t pixels, float2* __restrict__ map,
+                                                          uint8_t* __restrict__ valid, uint8_t* __restrict__ evaluations) {
+  __shared__ double lds[kMaxWindow * kEntry];
+  const int frame = first_frame + blockIdx.y;
+  int n;
+  const bool have = stage_table(table, count, frame, lds, n);
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= pixels) return;
+  double px[2] = {0.0, 0.0};
+  int evals = 0;
+  bool ok = false;
+  if (have) {
+    const double2 r = rays[i];
+    ok = solve_pixel(P, lds, n, r.x, r.y, ray_status[i] == 0, px, evals);
+  }
+  const float qnan = __builtin_nanf("");
+  const int64_t o = int64_t(frame) * pixels + i;
+  map[o] = ok ? make_float2(float(px[0]), float(px[1])) : make_float2(qnan, qnan);
+  valid[o] = ok ? 1 : 0;
+  if (evaluations) evaluations[o] = uint8_t(evals);
+}
+
+// frames / out: the batch's first frame at index 0; table and count are indexed by first_frame + blockIdx.y
+template <int CH>
+__global__ __launch_bounds__(kThreads) void rs_rectify_kernel(RsParams P, int first_frame, const double* __restrict__ table,
+                                                              const int32_t* __restrict__ count, const double2* __restrict__ rays,
+                                                              const uint8_t* __restrict__ ray_status, int64_t pixels,
+                                                              const uint8_t* __restrict__ frames, int border, uint8_t* __restrict__ out) {
+  __shared__ double lds[kMaxWindow * kEntry];
+  int n;
+  const bool have = stage_table(table, count, first_frame + blockIdx.y, lds, n);
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= pixels) return;
+  double px[2] = {0.0, 0.0};
+  int evals = 0;
+  bool ok = false;
+  if (have) {
+    const double2 r = rays[i];
+    ok = solve_pixel(P, lds, n, r.x, r.y, ray_status[i] == 0, px, evals);
+  }
+  uint8_t* o = out + (int64_t(blockIdx.y) * pixels + i) * CH;
+  BilinearTap<CH> tap;
+  if (!ok || !tap.set(make_float2(float(px[0]), float(px[1])), P.src_w, P.src_h)) {
+#pragma unroll
+    for (int c = 0; c < CH; ++c) o[c] = uint8_t(border);
+    return;
+  }
+  const uint8_t* s = frames + int64_t(blockIdx.y) * P.src_w * P.src_h * CH;
+#pragma unroll
+  for (int c = 0; c < CH; ++c) o[c] = tap.sample(s, c);
+}
+
+// status: 0 a point, 1 none (no ray, z <= 0, a failed projection; NaN), 2 the frame has no table (NaN)
+__global__ __launch_bounds__(kThreads) void rs_points_kernel(RsParams P, const double* __restrict__ table, const int32_t* __restrict__ count,
+                                                             int64_t n, const int32_t* __restrict__ frame, const double* __restrict__ xy_in,
+                                                             double* __restrict__ xy_out, uint8_t* __restrict__ status) {
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const double2 uv = *reinterpret_cast<const double2*>(xy_in + 2 * i);
+  const int k = frame[i];
+  const int cnt = count[k];
+  double px[2] = {0.0, 0.0};
+  int st = cnt < 2 ? 2 : 0;
+  if (st == 0) {
+    double x, y;
+    bool ok = true;
+    if (P.src_closed_form) {
+      y = (uv.y - P.src.in[4]) / (P.src.in[0] * P.src.in[1]);
+      x = (uv.x - P.src.in[3] - P.src.in[2] * y) / P.src.in[0];
+      ok = isfinite(x) && isfinite(y);
+    } else {
+      ok = unproject(P.src, uv.x, uv.y, x, y);
+    }
+    if (ok) {
+      double M[9];
+      rotation_matrix(table_rotation(table + int64_t(k) * kMaxWindow * kEntry, cnt, row_tau(P, uv.y)), M);
+      const double d0[3] = {(M[0] * x + M[1] * y) + M[2], (M[3] * x + M[4] * y) + M[5], (M[6] * x + M[7] * y) + M[8]};                  // R_rel d
+      const double* R = P.R.r;
+      const double d[3] = {(R[0] * d0[0] + R[3] * d0[1]) + R[6] * d0[2], (R[1] * d0[0] + R[4] * d0[1]) + R[7] * d0[2], (R[2] * d0[0] + R[5] * d0[1]) + R[8] * d0[2]};   // R9^T
+      ok = d[2] > 0.0 && oicc::camera_project<false>(P.dst.model, P.dst.in, d, px, nullptr) && isfinite(px[0]) && isfinite(px[1]);
+    }
+    if (!ok) st = 1;
+  }
+  const double qnan = nan("");
+  *reinterpret_cast<double2*>(xy_out + 2 * i) = st == 0 ? make_double2(px[0], px[1]) : make_double2(qnan, qnan);
+  status[i] = uint8_t(st);
+}
+
+// q [n][4] (w, x, y, z) of R_rel at (frame, row); status 0, or 2 where the frame has no table (NaN)
+__global__ __launch_bounds__(kThreads) void rs_rotation_kernel(RsParams P, const double* __restrict__ table, const int32_t* __restrict__ count,
+                                                               int64_t n, const int32_t* __restrict__ frame, const double* __restrict__ rows,
+                                                               double* __restrict__ q, uint8_t* __restrict__ status) {
+  const int64_t i = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const int k = frame[i];
+  const int cnt = count[k];
+  const double qnan = nan("");
+  Q4 r = {qnan, qnan, qnan, qnan};
+  if (cnt >= 2) r = table_rotation(table + int64_t(k) * kMaxWindow * kEntry, cnt, row_tau(P, rows[i]));
+  double* o = q + 4 * i;
+  o[0] = r.w; o[1] = r.x; o[2] = r.y; o[3] = r.z;
+  status[i] = cnt >= 2 ? 0 : 2;
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------------
+
+#define RS_TRY(expr) do { if ((expr) != hipSuccess) { rc = OICC_ERR_HIP; goto done; } } while (0)
+
+// What every entry judges before it looks for a device, and the frame windows, found by time comparisons only.
+struct Judged {
+  RsParams P;
+  int num_frames = 0;
+  int64_t num_gyro = 0;
+  std::vector<double> rates_cam;       // [n][3]
+  std::vector<int64_t> first;          // [frames] first window sample
+  std::vector<int32_t> count, status;  // [frames] window samples (0 where status != 0), oicc frame status
+};
+
+bool all_finite(const double* a, int64_t n) {
+  for (int64_t i = 0; i < n; ++i) if (!std::isfinite(a[i])) return false;
+  return true;
+}
+
+int judge(const oicc_rs_scene* s, Judged* J) {
+  if (!s) return OICC_ERR_INVALID_ARG;
+  RsParams& P = J->P;
+  if (!make_camera(s->src_model, s->src_intr, &P.src) || !make_camera(s->dst_model, s->dst_intr, &P.dst) || s->src_w < 1 || s->src_h < 1 ||
+      s->dst_w < 1 || s->dst_h < 1 || int64_t(s->dst_w) * s->dst_h > kMaxLanes) return OICC_ERR_INVALID_ARG;
+  P.R = Rotation{{1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}};
+  if (s->R9) {
+    if (!all_finite(s->R9, 9)) return OICC_ERR_INVALID_ARG;
+    for (int k = 0; k < 9; ++k) P.R.r[k] = s->R9[k];
+  }
+  if (s->num_gyro < 2 || !s->gyro_t || !s->gyro_rates || s->num_frames < 1 || !s->frame_t) return OICC_ERR_INVALID_ARG;
+  if (!all_finite(s->gyro_t, s->num_gyro) || !all_finite(s->gyro_rates, 3 * s->num_gyro) || !all_finite(s->frame_t, s->num_frames) ||
+      !all_finite(s->q_i_c, 4) || !std::isfinite(s->time_offset_imu_to_cam) || !std::isfinite(s->line_delay_s) ||
+      !std::isfinite(s->reference_row)) return OICC_ERR_INVALID_ARG;
+  for (int64_t j = 1; j < s->num_gyro; ++j) if (!(s->gyro_t[j] > s->gyro_t[j - 1])) return OICC_ERR_INVALID_ARG;
+  const double* qi = s->q_i_c;
+  const double norm = std::sqrt(((qi[0] * qi[0] + qi[1] * qi[1]) + qi[2] * qi[2]) + qi[3] * qi[3]);
+  if (!(std::fabs(norm - 1.0) <= 1e-6)) return OICC_ERR_INVALID_ARG;
+  P.src_w = s->src_w; P.src_h = s->src_h; P.dst_w = s->dst_w; P.dst_h = s->dst_h;
+  P.src_closed_form = is_plain_pinhole(P.src); P.dst_closed_form = is_plain_pinhole(P.dst);
+  P.line_delay = s->line_delay_s; P.reference_row = s->reference_row; P.time_offset = s->time_offset_imu_to_cam;
+  J->num_frames = s->num_frames; J->num_gyro = s->num_gyro;
+  // rates into the camera frame, once: T_i_c takes camera coordinates to IMU coordinates, so omega_c = R(q_i_c)^T omega_i
+  {
+    const double w = qi[0] / norm, x = qi[1] / norm, y = qi[2] / norm, z = qi[3] / norm;
+    const double M[9] = {1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
+                         2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
+                         2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)};
+    J->rates_cam.resize(size_t(3 * s->num_gyro));
+    for (int64_t j = 0; j < s->num_gyro; ++j) {
+      const double* o = s->gyro_rates + 3 * j;
+      for (int c = 0; c < 3; ++c) J->rates_cam[size_t(3 * j + c)] = (M[c] * o[0] + M[3 + c] * o[1]) + M[6 + c] * o[2];
+    }
+  }
+  // windows: the row times of y in [0, src_h - 1] together with t_ref, relative to the frame time, against a_j = (t_j - t_k) + offset
+  const double last = double(s->src_h - 1) * s->line_delay_s, ref = s->reference_row * s->line_delay_s;
+  const double lo = std::min(std::min(0.0, last), ref), hi = std::max(std::max(0.0, last), ref);
+  const int64_t n = s->num_gyro;
+  J->first.assign(size_t(s->num_frames), 0); J->count.assign(size_t(s->num_frames), 0); J->status.assign(size_t(s->num_frames), 0);
+  for (int k = 0; k < s->num_frames; ++k) {
+    const double tk = s->frame_t[k], off = s->time_offset_imu_to_cam;
+    auto a = [&](int64_t j) { return (s->gyro_t[j] - tk) + off; };
+    if (lo < a(0) || hi > a(n - 1)) { J->status[size_t(k)] = 1; continue; }
+    int64_t b = 0, e = n;                       // number of samples with a_j <= lo
+    while (b < e) { const int64_t m = (b + e) / 2; if (a(m) <= lo) b = m + 1; else e = m; }
+    const int64_t j0 = std::min(b - 1, n - 2);
+    b = 0; e = n;                               // number of samples with a_j < hi
+    while (b < e) { const int64_t m = (b + e) / 2; if (a(m) < hi) b = m + 1; else e = m; }
+    const int64_t j1 = std::max(b, j0 + 1);
+    if (j1 - j0 + 1 > kMaxWindow) { J->status[size_t(k)] = 2; continue; }
+    J->first[size_t(k)] = j0; J->count[size_t(k)] = int32_t(j1 - j0 + 1);
+  }
+  return OICC_OK;
+}
+
+// The device side of a scene: the per-frame tables and, where wanted, the destination rays.
+struct Prepared {
+  double *gyro_t = nullptr, *rates = nullptr, *frame_t = nullptr, *table = nullptr;
+  int64_t* first = nullptr;
+  int32_t* count = nullptr;
+  double2* rays = nullptr;
+  uint8_t* ray_status = nullptr;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};     // before the table kernel, behind it, behind the ray kernel
+
+  void release() {
+    for (void* p : {(void*)gyro_t, (void*)rates, (void*)frame_t, (void*)table, (void*)first, (void*)count, (void*)rays, (void*)ray_status})
+      if (p) (void)hipFree(p);
+    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
+  }
+};
+
+// Enqueues the uploads, the table kernel and (with_rays) the ray kernel on st; J and the scene arrays must outlive the stream's work.
+int prepare(const oicc_rs_scene* s, const Judged& J, bool with_rays, hipStream_t st, Prepared* D) {
+  int rc = OICC_OK;
+  const size_t n = size_t(J.num_gyro), f = size_t(J.num_frames);
+  const int64_t pixels = int64_t(J.P.dst_w) * J.P.dst_h;
+  for (auto& e : D->ev) RS_TRY(hipEventCreate(&e));
+  RS_TRY(hipMalloc(&D->gyro_t, sizeof(double) * n));
+  RS_TRY(hipMalloc(&D->rates, sizeof(double) * 3 * n));
+  RS_TRY(hipMalloc(&D->frame_t, sizeof(double) * f));
+  RS_TRY(hipMalloc(&D->first, sizeof(int64_t) * f));
+  RS_TRY(hipMalloc(&D->count, sizeof(int32_t) * f));
+  RS_TRY(hipMalloc(&D->table, sizeof(double) * kMaxWindow * kEntry * f));
+  if (with_rays) {                          // every allocation before the first event: none sits inside a timed span
+    RS_TRY(hipMalloc(&D->rays, sizeof(double2) * size_t(pixels)));
+    RS_TRY(hipMalloc(&D->ray_status, size_t(pixels)));
+  }
+  RS_TRY(hipMemcpyAsync(D->gyro_t, s->gyro_t, sizeof(double) * n, hipMemcpyHostToDevice, st));
+  RS_TRY(hipMemcpyAsync(D->rates, J.rates_cam.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
+  RS_TRY(hipMemcpyAsync(D->frame_t, s->frame_t, sizeof(double) * f, hipMemcpyHostToDevice, st));
+  RS_TRY(hipMemcpyAsync(D->first, J.first.data(), sizeof(int64_t) * f, hipMemcpyHostToDevice, st));
+  RS_TRY(hipMemcpyAsync(D->count, J.count.data(), sizeof(int32_t) * f, hipMemcpyHostToDevice, st));
+  RS_TRY(hipEventRecord(D->ev[0], st));
+  hipLaunchKernelGGL(rs_frame_table_kernel, dim3(unsigned((J.num_frames + 63) / 64)), dim3(64), 0, st, J.num_frames, D->gyro_t, D->rates,
+                     D->frame_t, D->first, D->count, J.P.time_offset, J.P.reference_row * J.P.line_delay, D->table);
+  RS_TRY(hipGetLastError());
+  RS_TRY(hipEventRecord(D->ev[1], st));
+  if (with_rays) {
+    hipLaunchKernelGGL(rs_ray_kernel, dim3(blocks_for(pixels)), dim3(kThreads), 0, st, J.P.dst, J.P.dst_closed_form, J.P.dst_w, pixels, D->rays,
+                       D->ray_status);
+    RS_TRY(hipGetLastError());
+  }
+  RS_TRY(hipEventRecord(D->ev[2], st));
+done:
+  return rc;
+}
+
+// frames [first, first + num) of the scene; frames_dev / out_dev start at frame `first`
+int launch_rectify(hipStream_t st, const Judged& J, const Prepared& D, int first, int num, int channels, const uint8_t* frames_dev, int border,
+                   uint8_t* out_dev) {
+  const int64_t pixels = int64_t(J.P.dst_w) * J.P.dst_h;
+  const int64_t in_frame = int64_t(J.P.src_w) * J.P.src_h * channels, out_frame = pixels * channels;
+  for (int done = 0; done < num; done += kFrameChunk) {
+    const int m = std::min(kFrameChunk, num - done);
+    const dim3 grid(blocks_for(pixels), unsigned(m));
+    if (channels == 1)
+      hipLaunchKernelGGL(rs_rectify_kernel<1>, grid, dim3(kThreads), 0, st, J.P, first + done, D.table, D.count, D.rays, D.ray_status, pixels,
+                         frames_dev + done * in_frame, border, out_dev + done * out_frame);
+    else
+      hipLaunchKernelGGL(rs_rectify_kernel<3>, grid, dim3(kThreads), 0, st, J.P, first + done, D.table, D.count, D.rays, D.ray_status, pixels,
+                         frames_dev + done * in_frame, border, out_dev + done * out_frame);
+    if (hipGetLastError() != hipSuccess) return OICC_ERR_HIP;
+  }
+  return OICC_OK;
+}
+
+void copy_status(const Judged& J, int32_t* frame_status) {
+  if (frame_status) std::memcpy(frame_status, J.status.data(), sizeof(int32_t) * J.status.size());
+}
+
+bool frames_args_ok(int32_t channels, int32_t border_value) {
+  return (channels == 1 || channels == 3) && border_value >= 0 && border_value <= 255;
+}
+
+struct RsSlot {
+  uint8_t *pin_in = nullptr, *pin_out = nullptr, *d_in = nullptr, *d_out = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};    // upload start, upload end, kernel end, download end
+  int first = 0, num = 0;
+};
+
+}  // namespace
+
+extern "C" int oicc_rs_rectify_map(int32_t device_ordinal, const oicc_rs_scene* scene, float* map, uint8_t* valid, uint8_t* evaluations,
+                                   int32_t* frame_status, int64_t* num_valid, double* device_ms) {
+  Judged J;
+  if (int rc = judge(scene, &J)) return rc;
+  if (!map || !valid || !frame_status) return OICC_ERR_INVALID_ARG;
+  if (int rc = select_device(device_ordinal)) return rc;
+  const int64_t pixels = int64_t(J.P.dst_w) * J.P.dst_h;
+  const size_t total = size_t(pixels) * size_t(J.num_frames);
+  int rc = OICC_OK;
+  Prepared D;
+  float2* d_map = nullptr; uint8_t *d_valid = nullptr, *d_evals = nullptr;
+  hipStream_t st = nullptr; hipEvent_t e1 = nullptr;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  RS_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  RS_TRY(hipEventCreate(&e1));
+  RS_TRY(hipMalloc(&d_map, sizeof(float2) * total));
+  RS_TRY(hipMalloc(&d_valid, total));
+  if (evaluations) RS_TRY(hipMalloc(&d_evals, total));
+  if ((rc = prepare(scene, J, true, st, &D)) != OICC_OK) goto done;
+  for (int first = 0; first < J.num_frames; first += kFrameChunk) {
+    const int m = std::min(kFrameChunk, J.num_frames - first);
+    hipLaunchKernelGGL(rs_map_kernel, dim3(blocks_for(pixels), unsigned(m)), dim3(kThreads), 0, st, J.P, first, D.table, D.count, D.rays,
+                       D.ray_status, pixels, d_map, d_valid, d_evals);
+    RS_TRY(hipGetLastError());
+  }
+  RS_TRY(hipEventRecord(e1, st));
+  RS_TRY(hipMemcpyAsync(map, d_map, sizeof(float2) * total, hipMemcpyDeviceToHost, st));
+  RS_TRY(hipMemcpyAsync(valid, d_valid, total, hipMemcpyDeviceToHost, st));
+  if (evaluations) RS_TRY(hipMemcpyAsync(evaluations, d_evals, total, hipMemcpyDeviceToHost, st));
+  RS_TRY(hipStreamSynchronize(st));
+  RS_TRY(hipEventElapsedTime(&ms[0], D.ev[0], D.ev[1]));
+  RS_TRY(hipEventElapsedTime(&ms[1], D.ev[1], D.ev[2]));
+  RS_TRY(hipEventElapsedTime(&ms[2], D.ev[2], e1));
+  if (device_ms) for (int k = 0; k < 3; ++k) device_ms[k] = double(ms[k]);
+  copy_status(J, frame_status);
+  if (num_valid)
+    for (int k = 0; k < J.num_frames; ++k) {
+      int64_t c = 0;
+      for (int64_t i = 0; i < pixels; ++i) c += valid[int64_t(k) * pixels + i];
+      num_valid[k] = c;
+    }
+done:
+  if (rc != OICC_OK && st) (void)hipStreamSynchronize(st);
+  D.release();
+  for (void* p : {(void*)d_map, (void*)d_valid, (void*)d_evals}) if (p) (void)hipFree(p);
+  if (e1) (void)hipEventDestroy(e1);
+  if (st) (void)hipStreamDestroy(st);
+  return rc;
+}
+
+extern "C" int oicc_rs_rectify_frames_device(void* hip_stream, const oicc_rs_scene* scene, int32_t channels, const uint8_t* frames_dev,
+                                             int32_t border_value, uint8_t* out_dev, int32_t* frame_status) {
+  Judged J;
+  if (int rc = judge(scene, &J)) return rc;
+  if (!frames_args_ok(channels, border_value) || !frames_dev || !out_dev || !frame_status) return OICC_ERR_INVALID_ARG;
+  int ndev = 0, cur = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || hipGetDevice(&cur) != hipSuccess) return OICC_ERR_NO_DEVICE;   // no CPU fallback
+  // the launches go to the current device: the stream and the two arrays have to live there
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  if (stream) {
+    hipDevice_t of_stream = 0, of_current = 0;
+    if (hipStreamGetDevice(stream, &of_stream) != hipSuccess || hipDeviceGet(&of_current, cur) != hipSuccess || of_stream != of_current) {
+      (void)hipGetLastError();
+      return OICC_ERR_INVALID_ARG;
+    }
+  }
+  for (const void* p : {(const void*)frames_dev, (const void*)out_dev}) {
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type == hipMemoryTypeUnregistered || (a.type == hipMemoryTypeDevice && a.device != cur)) {
+      (void)hipGetLastError();
+      return OICC_ERR_INVALID_ARG;
+    }
+  }
+  Prepared D;
+  int rc = prepare(scene, J, true, stream, &D);
+  if (rc == OICC_OK) rc = launch_rectify(stream, J, D, 0, J.num_frames, channels, frames_dev, border_value, out_dev);
+  // the tables are this call's own: it returns once the stream has run the work, and frees them
+  if (hipStreamSynchronize(stream) != hipSuccess && rc == OICC_OK) rc = OICC_ERR_HIP;
+  D.release();
+  if (rc == OICC_OK) copy_status(J, frame_status);
+  return rc;
+}
+
+extern "C" int oicc_rs_rectify_frames(int32_t device_ordinal, const oicc_rs_scene* scene, int32_t channels, const uint8_t* frames,
+                                      int32_t border_value, int32_t batch, uint8_t* out, int32_t* frame_status, oicc_rs_frames_report* report) {
+  Judged J;
+  if (int rc = judge(scene, &J)) return rc;
+  if (!frames_args_ok(channels, border_value) || batch < 1 || !frames || !out || !frame_status) return OICC_ERR_INVALID_ARG;
+  if (int rc = select_device(device_ordinal)) return rc;
+  const auto t_start = std::chrono::steady_clock::now();
+  oicc_rs_frames_report rep = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  const int num_frames = J.num_frames;
+  const int64_t in_frame = int64_t(J.P.src_w) * J.P.src_h * channels, out_frame = int64_t(J.P.dst_w) * J.P.dst_h * channels;
+  const int64_t nbatch = std::min<int64_t>(batch, num_frames);
+  const int nslots = num_frames > nbatch ? 2 : 1;     // a second staging slot only when a second batch exists
+  int rc = OICC_OK;
+  Prepared D;
+  hipStream_t st[2] = {nullptr, nullptr};
+  RsSlot slot[2];
+  for (int q = 0; q < nslots; ++q) RS_TRY(hipStreamCreateWithFlags(&st[q], hipStreamNonBlocking));
+  if ((rc = prepare(scene, J, true, st[0], &D)) != OICC_OK) goto done;
+  RS_TRY(hipStreamSynchronize(st[0]));                 // both streams read the tables
+  {
+    float ms = 0.0f;
+    RS_TRY(hipEventElapsedTime(&ms, D.ev[0], D.ev[1])); rep.ms_table = ms;
+    RS_TRY(hipEventElapsedTime(&ms, D.ev[1], D.ev[2])); rep.ms_rays = ms;
+  }
+  for (int q = 0; q < nslots; ++q) {
+    RsSlot& s = slot[q];
+    RS_TRY(hipHostMalloc(&s.pin_in, size_t(nbatch * in_frame), hipHostMallocDefault));
+    RS_TRY(hipHostMalloc(&s.pin_out, size_t(nbatch * out_frame), hipHostMallocDefault));
+    RS_TRY(hipMalloc(&s.d_in, size_t(nbatch * in_frame)));
+    RS_TRY(hipMalloc(&s.d_out, size_t(nbatch * out_frame)));
+    for (auto& e : s.ev) RS_TRY(hipEventCreate(&e));
+  }
+  {
+    // one batch per slot and stream: host copy into pinned memory, upload, kernel, download; the other slot's batch overlaps
+    auto enqueue = [&](int q, int first) -> int {
+      RsSlot& s = slot[q];
+      s.first = first; s.num = int(std::min<int64_t>(nbatch, num_frames - first));
+      if (s.num <= 0) return OICC_OK;
+      std::memcpy(s.pin_in, frames + int64_t(first) * in_frame, size_t(s.num * in_frame));
+      if (hipEventRecord(s.ev[0], st[q]) != hipSuccess ||
+          hipMemcpyAsync(s.d_in, s.pin_in, size_t(s.num * in_frame), hipMemcpyHostToDevice, st[q]) != hipSuccess ||
+          hipEventRecord(s.ev[1], st[q]) != hipSuccess) return OICC_ERR_HIP;
+      if (launch_rectify(st[q], J, D, first, s.num, channels, s.d_in, border_value, s.d_out) != OICC_OK) return OICC_ERR_HIP;
+      if (hipEventRecord(s.ev[2], st[q]) != hipSuccess ||
+          hipMemcpyAsync(s.pin_out, s.d_out, size_t(s.num * out_frame), hipMemcpyDeviceToHost, st[q]) != hipSuccess ||
+          hipEventRecord(s.ev[3], st[q]) != hipSuccess) return OICC_ERR_HIP;
+      return OICC_OK;
+    };
+    int next = 0;
+    for (int q = 0; q < nslots && next < num_frames; ++q) { if ((rc = enqueue(q, next)) != OICC_OK) goto done; next += slot[q].num; }
+    for (int k = 0; slot[k % nslots].num > 0; ++k) {        // batches complete in order, alternating between the slots
+      const int q = k % nslots;
+      RsSlot& s = slot[q];
+      RS_TRY(hipStreamSynchronize(st[q]));
+      float ms = 0.0f;
+      double* acc[3] = {&rep.ms_upload, &rep.ms_kernel, &rep.ms_download};
+      for (int j = 0; j < 3; ++j) { RS_TRY(hipEventElapsedTime(&ms, s.ev[j], s.ev[j + 1])); *acc[j] += ms; }
+      std::memcpy(out + int64_t(s.first) * out_frame, s.pin_out, size_t(s.num * out_frame));
+      s.num = 0;
+      if (next < num_frames) { if ((rc = enqueue(q, next)) != OICC_OK) goto done; next += s.num; }
+    }
+  }
+  copy_status(J, frame_status);
+  rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+  if (report) *report = rep;
+done:
+  for (int q = 0; q < 2; ++q) if (st[q]) (void)hipStreamSynchronize(st[q]);
+  for (int q = 0; q < 2; ++q) {
+    RsSlot& s = slot[q];
+    if (s.pin_in) (void)hipHostFree(s.pin_in);
+    if (s.pin_out) (void)hipHostFree(s.pin_out);
+    if (s.d_in) (void)hipFree(s.d_in);
+    if (s.d_out) (void)hipFree(s.d_out);
+    for (auto& e : s.ev) if (e) (void)hipEventDestroy(e);
+  }
+  D.release();
+  for (int q = 0; q < 2; ++q) if (st[q]) (void)hipStreamDestroy(st[q]);
+  return rc;
+}
+
+namespace {
+
+// points (QUERY 0: xy_in [n][2] -> xy_out [n][2]) and row rotations (QUERY 1: rows [n] -> q [n][4]) share everything but the kernel
+template <int QUERY>
+int run_queries(int32_t device_ordinal, const oicc_rs_scene* scene, int64_t n, const int32_t* frame_index, const double* in, double* out,
+                uint8_t* status, int32_t* frame_status, double* device_ms) {
+  constexpr int kIn = QUERY == 0 ? 2 : 1, kOut = QUERY == 0 ? 2 : 4;
+  Judged J;
+  if (int rc = judge(scene, &J)) return rc;
+  if (n < 1 || n > kMaxLanes || !frame_index || !in || !out || !status || !frame_status) return OICC_ERR_INVALID_ARG;
+  for (int64_t i = 0; i < n; ++i) if (frame_index[i] < 0 || frame_index[i] >= J.num_frames) return OICC_ERR_INVALID_ARG;
+  if (QUERY == 1 && !all_finite(in, n)) return OICC_ERR_INVALID_ARG;
+  if (int rc = select_device(device_ordinal)) return rc;
+  int rc = OICC_OK;
+  Prepared D;
+  int32_t* d_frame = nullptr; double *d_in = nullptr, *d_out = nullptr; uint8_t* d_st = nullptr;
+  hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
+  float ms = 0.0f;
+  RS_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  RS_TRY(hipEventCreate(&e0)); RS_TRY(hipEventCreate(&e1));
+  if ((rc = prepare(scene, J, false, st, &D)) != OICC_OK) goto done;
+  RS_TRY(hipMalloc(&d_frame, sizeof(int32_t) * size_t(n)));
+  RS_TRY(hipMalloc(&d_in, sizeof(double) * kIn * size_t(n)));
+  RS_TRY(hipMalloc(&d_out, sizeof(double) * kOut * size_t(n)));
+  RS_TRY(hipMalloc(&d_st, size_t(n)));
+  RS_TRY(hipMemcpyAsync(d_frame, frame_index, sizeof(int32_t) * size_t(n), hipMemcpyHostToDevice, st));
+  RS_TRY(hipMemcpyAsync(d_in, in, sizeof(double) * kIn * size_t(n), hipMemcpyHostToDevice, st));
+  RS_TRY(hipEventRecord(e0, st));
+  if (QUERY == 0)
+    hipLaunchKernelGGL(rs_points_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, J.P, D.table, D.count, n, d_frame, d_in, d_out, d_st);
+  else
+    hipLaunchKernelGGL(rs_rotation_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, J.P, D.table, D.count, n, d_frame, d_in, d_out, d_st);
+  RS_TRY(hipGetLastError());
+  RS_TRY(hipEventRecord(e1, st));
+  RS_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * kOut * size_t(n), hipMemcpyDeviceToHost, st));
+  RS_TRY(hipMemcpyAsync(status, d_st, size_t(n), hipMemcpyDeviceToHost, st));
+  RS_TRY(hipStreamSynchronize(st));
+  RS_TRY(hipEventElapsedTime(&ms, e0, e1));
+  if (device_ms) *device_ms = double(ms);
+  copy_status(J, frame_status);
+done:
+  if (rc != OICC_OK && st) (void)hipStreamSynchronize(st);
+  D.release();
+  for (void* p : {(void*)d_frame, (void*)d_in, (void*)d_out, (void*)d_st}) if (p) (void)hipFree(p);
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (st) (void)hipStreamDestroy(st);
+  return rc;
+}
+
+}  // namespace
+
+extern "C" int oicc_rs_rectify_points(int32_t device_ordinal, const oicc_rs_scene* scene, int64_t n, const int32_t* frame_index,
+                                      const double* xy_in, double* xy_out, uint8_t* status, int32_t* frame_status, double* device_ms) {
+  return run_queries<0>(device_ordinal, scene, n, frame_index, xy_in, xy_out, status, frame_status, device_ms);
+}
+
+extern "C" int oicc_rs_row_rotations(int32_t device_ordinal, const oicc_rs_scene* scene, int64_t n, const int32_t* frame_index,
+                                     const double* rows, double* q, uint8_t* status, int32_t* frame_status, double* device_ms) {
+  return run_queries<1>(device_ordinal, scene, n, frame_index, rows, q, status, frame_status, device_ms);
+}
