@@ -20,6 +20,7 @@
 #include <cstdint>
 #include <vector>
 #include "../../include/oicc_hip.h"
+#include "hip_resources.h"
 
 namespace {
 
@@ -376,9 +377,7 @@ extern "C" int oicc_allan_variance(int32_t device_ordinal, int32_t channels, int
   if (!samples || !t_s || !scale || !num_factors || !factors || !taus || !sigma2 || !freq_out || !period_out || !mean_out ||
       channels < 1 || n < 8 || n > INT32_MAX || num_clusters < 2) return OICC_ERR_INVALID_ARG;
   for (int64_t i = 1; i < n; ++i) if (!(t_s[i] > t_s[i - 1])) return OICC_ERR_INVALID_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device_ordinal < 0 || device_ordinal >= ndev) return OICC_ERR_NO_DEVICE;   // no CPU fallback
-  if (hipSetDevice(device_ordinal) != hipSuccess) return OICC_ERR_NO_DEVICE;
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
 
   // host, sequential as the reference: getAvgDt (:205-214), freq = 1 / avgDt, period = avgDt, getAvgValue of the scaled samples
   double sum_dt = 0.0;
@@ -412,44 +411,43 @@ extern "C" int oicc_allan_variance(int32_t device_ordinal, int32_t channels, int
   }
   const int64_t part_stride = std::max<int64_t>(out, 1);
 
-  double *d_w = nullptr, *d_th = nullptr, *d_scale = nullptr, *d_mean = nullptr, *d_part = nullptr, *d_s2 = nullptr;
-  int32_t *d_fac = nullptr, *d_fs = nullptr, *d_fc = nullptr; int64_t* d_fo = nullptr; WorkItem* d_items = nullptr;
-  hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = OICC_OK;
-  auto ok = [&](hipError_t e) { if (e != hipSuccess && rc == OICC_OK) rc = OICC_ERR_HIP; return rc == OICC_OK; };
+  oicc::DevBuf<double> d_w, d_th, d_scale, d_mean, d_part, d_s2;
+  oicc::DevBuf<int32_t> d_fac, d_fs, d_fc; oicc::DevBuf<int64_t> d_fo; oicc::DevBuf<WorkItem> d_items;
+  oicc::Event e0, e1;
+  oicc::Stream st;
   const size_t nw = size_t(channels) * size_t(n);
-  if (ok(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) && ok(hipEventCreate(&e0)) && ok(hipEventCreate(&e1)) &&
-      ok(hipMalloc(&d_w, sizeof(double) * nw)) && ok(hipMalloc(&d_th, sizeof(double) * nw)) &&
-      ok(hipMalloc(&d_scale, sizeof(double) * channels)) && ok(hipMalloc(&d_mean, sizeof(double) * channels)) &&
-      ok(hipMalloc(&d_part, sizeof(double) * size_t(channels) * size_t(part_stride))) && ok(hipMalloc(&d_s2, sizeof(double) * size_t(channels) * nf)) &&
-      ok(hipMalloc(&d_fac, sizeof(int32_t) * nf)) && ok(hipMalloc(&d_fs, sizeof(int32_t) * nf)) && ok(hipMalloc(&d_fc, sizeof(int32_t) * nf)) &&
-      ok(hipMalloc(&d_fo, sizeof(int64_t) * nf)) && ok(hipMalloc(&d_items, sizeof(WorkItem) * std::max<size_t>(items.size(), 1))) &&
-      ok(hipMemcpyAsync(d_w, samples, sizeof(double) * nw, hipMemcpyHostToDevice, st)) &&
-      ok(hipMemcpyAsync(d_scale, scale, sizeof(double) * channels, hipMemcpyHostToDevice, st)) &&
-      ok(hipMemcpyAsync(d_mean, mean.data(), sizeof(double) * channels, hipMemcpyHostToDevice, st)) &&
-      ok(hipMemcpyAsync(d_fac, factors, sizeof(int32_t) * nf, hipMemcpyHostToDevice, st)) &&
-      ok(hipMemcpyAsync(d_fs, f_stride.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, st)) &&
-      ok(hipMemcpyAsync(d_fc, f_chunks.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, st)) &&
-      ok(hipMemcpyAsync(d_fo, f_out.data(), sizeof(int64_t) * nf, hipMemcpyHostToDevice, st)) &&
-      (items.empty() || ok(hipMemcpyAsync(d_items, items.data(), sizeof(WorkItem) * items.size(), hipMemcpyHostToDevice, st))) &&
-      ok(hipEventRecord(e0, st))) {
-    hipLaunchKernelGGL(allan_scan_kernel, dim3(channels), dim3(kScanThreads), 0, st, d_w, n, d_scale, d_mean, freq, d_th);
-    if (!items.empty())
-      hipLaunchKernelGGL(allan_partial_kernel, dim3(unsigned(items.size()), channels), dim3(kThreads), 0, st, d_th, n, d_fac, d_items, d_part, part_stride);
-    hipLaunchKernelGGL(allan_reduce_kernel, dim3(unsigned((nf + 255) / 256), channels), dim3(256), 0, st, d_part, part_stride, d_fo, d_fs, d_fc, d_fac,
-                       nf, n, period, d_s2);
-    if (ok(hipGetLastError()) && ok(hipEventRecord(e1, st)) &&
-        ok(hipMemcpyAsync(sigma2, d_s2, sizeof(double) * size_t(channels) * nf, hipMemcpyDeviceToHost, st)) && ok(hipStreamSynchronize(st))) {
-      float ms = 0.0f;
-      if (device_ms && ok(hipEventElapsedTime(&ms, e0, e1))) *device_ms = double(ms);
-    }
+  OICC_HIP_TRY(st.create());
+  OICC_HIP_TRY(e0.create()); OICC_HIP_TRY(e1.create());
+  // every allocation ahead of the first copy, as ahead of the timed span
+  OICC_HIP_TRY(d_w.resize(nw)); OICC_HIP_TRY(d_th.resize(nw));
+  OICC_HIP_TRY(d_scale.resize(size_t(channels))); OICC_HIP_TRY(d_mean.resize(size_t(channels)));
+  OICC_HIP_TRY(d_part.resize(size_t(channels) * size_t(part_stride))); OICC_HIP_TRY(d_s2.resize(size_t(channels) * nf));
+  OICC_HIP_TRY(d_fac.resize(size_t(nf))); OICC_HIP_TRY(d_fs.resize(size_t(nf))); OICC_HIP_TRY(d_fc.resize(size_t(nf)));
+  OICC_HIP_TRY(d_fo.resize(size_t(nf))); OICC_HIP_TRY(d_items.resize(std::max<size_t>(items.size(), 1)));
+  OICC_HIP_TRY(hipMemcpyAsync(d_w.p, samples, sizeof(double) * nw, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(d_scale.p, scale, sizeof(double) * channels, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(d_mean.p, mean.data(), sizeof(double) * channels, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(d_fac.p, factors, sizeof(int32_t) * nf, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(d_fs.p, f_stride.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(d_fc.p, f_chunks.data(), sizeof(int32_t) * nf, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(d_fo.p, f_out.data(), sizeof(int64_t) * nf, hipMemcpyHostToDevice, st));
+  if (!items.empty()) OICC_HIP_TRY(hipMemcpyAsync(d_items.p, items.data(), sizeof(WorkItem) * items.size(), hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipEventRecord(e0, st));
+  hipLaunchKernelGGL(allan_scan_kernel, dim3(channels), dim3(kScanThreads), 0, st, d_w.p, n, d_scale.p, d_mean.p, freq, d_th.p);
+  if (!items.empty())
+    hipLaunchKernelGGL(allan_partial_kernel, dim3(unsigned(items.size()), channels), dim3(kThreads), 0, st, d_th.p, n, d_fac.p, d_items.p, d_part.p, part_stride);
+  hipLaunchKernelGGL(allan_reduce_kernel, dim3(unsigned((nf + 255) / 256), channels), dim3(256), 0, st, d_part.p, part_stride, d_fo.p, d_fs.p, d_fc.p, d_fac.p,
+                     nf, n, period, d_s2.p);
+  OICC_HIP_TRY(hipGetLastError());
+  OICC_HIP_TRY(hipEventRecord(e1, st));
+  OICC_HIP_TRY(hipMemcpyAsync(sigma2, d_s2.p, sizeof(double) * size_t(channels) * nf, hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipStreamSynchronize(st));
+  if (device_ms) {
+    float ms = 0.0f;
+    OICC_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    *device_ms = double(ms);
   }
-  for (void* q : {(void*)d_w, (void*)d_th, (void*)d_scale, (void*)d_mean, (void*)d_part, (void*)d_s2, (void*)d_fac, (void*)d_fs, (void*)d_fc,
-                  (void*)d_fo, (void*)d_items}) if (q) (void)hipFree(q);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  return OICC_OK;
 }
 
 extern "C" int oicc_allan_fit(int32_t kind, int64_t num, const double* taus, const double* sigma2, double freq, double params_QNBKR[5],

@@ -23,6 +23,8 @@
 #include <set>
 #include <vector>
 #include "../../include/oicc_hip.h"
+#include "frame_batches.h"
+#include "hip_resources.h"
 
 namespace {
 
@@ -486,10 +488,15 @@ void resize_axis(int n_src, double factor, int* n_dst, std::vector<int>* idx, st
 }
 
 struct Slot {
-  uint8_t* pinned = nullptr; uint8_t* d_src = nullptr; uint8_t* d_gray = nullptr; float* d_resp = nullptr; uint8_t* d_pol = nullptr;
-  float* d_blur = nullptr; unsigned int* d_max = nullptr; int* d_count = nullptr; Cand* d_cand = nullptr; double* d_ref = nullptr;
-  hipEvent_t up = nullptr, ev[6] = {}, done = nullptr;
-  int first = 0, num = 0;
+  oicc::PinnedBuf<uint8_t> pinned;
+  oicc::DevBuf<uint8_t> d_src, d_gray, d_pol;
+  oicc::DevBuf<float> d_resp, d_blur;
+  oicc::DevBuf<unsigned int> d_max;
+  oicc::DevBuf<int> d_count;
+  oicc::DevBuf<Cand> d_cand;
+  oicc::DevBuf<double> d_ref;
+  oicc::DevBuf<GridRef> d_gr; oicc::DevBuf<double> d_gc, d_disc, d_ring;    // kernel 6: grown to the batch's grids, kept for the slot's next batch
+  oicc::Event up, ev[6], done;
 };
 
 }  // namespace
@@ -504,8 +511,6 @@ extern "C" int oicc_board_output_size(int32_t width, int32_t height, double down
   return OICC_OK;
 }
 
-#define BOARD_TRY(expr) do { if ((expr) != hipSuccess) { rc = OICC_ERR_HIP; goto done; } } while (0)
-
 extern "C" int oicc_board_radon_detect(int32_t device_ordinal, int32_t num_frames, int32_t width, int32_t height, int32_t channels,
                                        const uint8_t* frames, double downsample_factor, int32_t W, int32_t H,
                                        const oicc_board_options* opt, double* corners, int32_t* found, int32_t* candidates_per_frame,
@@ -519,9 +524,7 @@ extern "C" int oicc_board_radon_detect(int32_t device_ordinal, int32_t num_frame
   resize_axis(width, downsample_factor, &wd, &xi, &xw);
   resize_axis(height, downsample_factor, &hd, &yi, &yw);
   if (wd < 2 * r + 3 || hd < 2 * r + 3) return OICC_ERR_INVALID_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device_ordinal < 0 || device_ordinal >= ndev) return OICC_ERR_NO_DEVICE;   // no CPU fallback
-  if (hipSetDevice(device_ordinal) != hipSuccess) return OICC_ERR_NO_DEVICE;
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
   oicc_board_report rep;
   std::memset(&rep, 0, sizeof(rep));
   const auto t_start = std::chrono::steady_clock::now();
@@ -531,89 +534,92 @@ extern "C" int oicc_board_radon_detect(int32_t device_ordinal, int32_t num_frame
   const int WH = W * H;
   const float inv = float(1.0 / (16.0 * 255.0 * (2 * r + 1)));
   const int win = r + 2;
-  int rc = OICC_OK;
-  int* d_tab = nullptr;
-  hipStream_t cs = nullptr, ks = nullptr;
-  Slot slot[2];
   std::vector<int> tab;
   for (int i = 0; i < num_frames * WH * 2; ++i) corners[i] = std::nan("");
   for (int i = 0; i < num_frames; ++i) { found[i] = 0; if (candidates_per_frame) candidates_per_frame[i] = 0; }
   tab.insert(tab.end(), xi.begin(), xi.end()); tab.insert(tab.end(), xw.begin(), xw.end());
   tab.insert(tab.end(), yi.begin(), yi.end()); tab.insert(tab.end(), yw.begin(), yw.end());
-  BOARD_TRY(hipStreamCreateWithFlags(&cs, hipStreamNonBlocking));
-  BOARD_TRY(hipStreamCreateWithFlags(&ks, hipStreamNonBlocking));
-  BOARD_TRY(hipMalloc(&d_tab, sizeof(int) * tab.size()));
-  BOARD_TRY(hipMemcpy(d_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
-  for (int q = 0; q < nslots; ++q) {
-    Slot& s = slot[q];
-    BOARD_TRY(hipHostMalloc(&s.pinned, size_t(nbatch * in_frame), hipHostMallocDefault));
-    BOARD_TRY(hipMalloc(&s.d_src, size_t(nbatch * in_frame)));
-    BOARD_TRY(hipMalloc(&s.d_gray, size_t(nbatch * out_frame)));
-    BOARD_TRY(hipMalloc(&s.d_resp, sizeof(float) * size_t(nbatch * out_frame)));
-    BOARD_TRY(hipMalloc(&s.d_pol, size_t(nbatch * out_frame)));
-    BOARD_TRY(hipMalloc(&s.d_blur, sizeof(float) * size_t(nbatch * out_frame)));
-    BOARD_TRY(hipMalloc(&s.d_max, sizeof(unsigned int) * size_t(nbatch)));
-    BOARD_TRY(hipMalloc(&s.d_count, sizeof(int) * size_t(nbatch)));
-    BOARD_TRY(hipMalloc(&s.d_cand, sizeof(Cand) * size_t(nbatch * cap)));
-    BOARD_TRY(hipMalloc(&s.d_ref, sizeof(double) * 2 * size_t(nbatch * cap)));
-    BOARD_TRY(hipEventCreate(&s.up)); BOARD_TRY(hipEventCreate(&s.done));
-    for (auto& e : s.ev) BOARD_TRY(hipEventCreate(&e));
-  }
-  {
+  // the device work in a scope of its own: its streams and buffers are gone before ms_total is taken and the report written
+  const int rc = [&]() -> int {
+    oicc::DevBuf<int> d_tab_buf;
+    Slot slot[2];
+    std::vector<GridRef> gr; std::vector<double> gc, disc, ring;      // kernel 6's arguments and results: asynchronous copies on ks read and write them
+    oicc::Stream cs, ks;      // behind every buffer and event their work uses (hip_resources.h)
+    OICC_HIP_TRY(cs.create());
+    OICC_HIP_TRY(ks.create());
+    OICC_HIP_TRY(d_tab_buf.resize(tab.size()));
+    const int* d_tab = d_tab_buf.p;
+    OICC_HIP_TRY(hipMemcpy(d_tab_buf.p, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    for (int q = 0; q < nslots; ++q) {
+      Slot& s = slot[q];
+      OICC_HIP_TRY(s.pinned.alloc(size_t(nbatch * in_frame)));
+      OICC_HIP_TRY(s.d_src.resize(size_t(nbatch * in_frame)));
+      OICC_HIP_TRY(s.d_gray.resize(size_t(nbatch * out_frame)));
+      OICC_HIP_TRY(s.d_resp.resize(size_t(nbatch * out_frame)));
+      OICC_HIP_TRY(s.d_pol.resize(size_t(nbatch * out_frame)));
+      OICC_HIP_TRY(s.d_blur.resize(size_t(nbatch * out_frame)));
+      OICC_HIP_TRY(s.d_max.resize(size_t(nbatch)));
+      OICC_HIP_TRY(s.d_count.resize(size_t(nbatch)));
+      OICC_HIP_TRY(s.d_cand.resize(size_t(nbatch * cap)));
+      OICC_HIP_TRY(s.d_ref.resize(2 * size_t(nbatch * cap)));
+      OICC_HIP_TRY(s.up.create()); OICC_HIP_TRY(s.done.create());
+      for (auto& e : s.ev) OICC_HIP_TRY(e.create());
+    }
     // enqueue: host copy into the slot's pinned buffer, upload on the copy stream, kernels 1-4 on the compute stream
-    auto enqueue = [&](Slot& s, int first) -> int {
-      s.first = first; s.num = int(std::min<int64_t>(nbatch, num_frames - first));
-      if (s.num <= 0) return OICC_OK;
-      if (hipEventSynchronize(s.done) != hipSuccess) return OICC_ERR_HIP;
-      std::memcpy(s.pinned, frames + int64_t(first) * in_frame, size_t(s.num * in_frame));
-      if (hipMemcpyAsync(s.d_src, s.pinned, size_t(s.num * in_frame), hipMemcpyHostToDevice, cs) != hipSuccess ||
-          hipEventRecord(s.up, cs) != hipSuccess || hipStreamWaitEvent(ks, s.up, 0) != hipSuccess ||
-          hipMemsetAsync(s.d_max, 0, sizeof(unsigned int) * size_t(s.num), ks) != hipSuccess ||
-          hipMemsetAsync(s.d_count, 0, sizeof(int) * size_t(s.num), ks) != hipSuccess || hipEventRecord(s.ev[0], ks) != hipSuccess) return OICC_ERR_HIP;
-      board_resize_gray_kernel<<<dim3((wd + kThreads - 1) / kThreads, hd, s.num), kThreads, 0, ks>>>(
-          s.d_src, width, height, channels, wd, hd, d_tab, d_tab + wd, d_tab + 2 * wd, d_tab + 2 * wd + hd, s.d_gray);
-      if (hipEventRecord(s.ev[1], ks) != hipSuccess) return OICC_ERR_HIP;
-      board_response_kernel<<<dim3((wd + kTileX - 1) / kTileX, (hd + kTileY - 1) / kTileY, s.num), kThreads, 0, ks>>>(
-          s.d_gray, wd, hd, r, inv, s.d_resp, s.d_pol, s.d_blur, s.d_max);
-      if (hipEventRecord(s.ev[2], ks) != hipSuccess) return OICC_ERR_HIP;
-      board_candidates_kernel<<<dim3((wd + kThreads - 1) / kThreads, hd, s.num), kThreads, 0, ks>>>(
-          s.d_resp, s.d_pol, wd, hd, r, opt->threshold_rel, s.d_max, cap, s.d_count, s.d_cand);
-      if (hipEventRecord(s.ev[3], ks) != hipSuccess) return OICC_ERR_HIP;
-      const int64_t waves = int64_t(s.num) * cap;
-      board_subpix_kernel<<<dim3(unsigned((waves + 3) / 4)), kThreads, 0, ks>>>(s.d_blur, wd, hd, s.num, cap, s.d_count, s.d_cand, win,
-                                                                               opt->subpix_iterations, opt->subpix_eps, s.d_ref);
-      if (hipGetLastError() != hipSuccess || hipEventRecord(s.ev[4], ks) != hipSuccess || hipEventRecord(s.done, ks) != hipSuccess) return OICC_ERR_HIP;
+    auto enqueue = [&](int q, int first, int num) -> int {
+      Slot& s = slot[q];
+      OICC_HIP_TRY(hipEventSynchronize(s.done));
+      std::memcpy(s.pinned.p, frames + int64_t(first) * in_frame, size_t(num * in_frame));
+      OICC_HIP_TRY(hipMemcpyAsync(s.d_src.p, s.pinned.p, size_t(num * in_frame), hipMemcpyHostToDevice, cs));
+      OICC_HIP_TRY(hipEventRecord(s.up, cs));
+      OICC_HIP_TRY(hipStreamWaitEvent(ks, s.up, 0));
+      OICC_HIP_TRY(hipMemsetAsync(s.d_max.p, 0, sizeof(unsigned int) * size_t(num), ks));
+      OICC_HIP_TRY(hipMemsetAsync(s.d_count.p, 0, sizeof(int) * size_t(num), ks));
+      OICC_HIP_TRY(hipEventRecord(s.ev[0], ks));
+      board_resize_gray_kernel<<<dim3((wd + kThreads - 1) / kThreads, hd, num), kThreads, 0, ks>>>(
+          s.d_src.p, width, height, channels, wd, hd, d_tab, d_tab + wd, d_tab + 2 * wd, d_tab + 2 * wd + hd, s.d_gray.p);
+      OICC_HIP_TRY(hipEventRecord(s.ev[1], ks));
+      board_response_kernel<<<dim3((wd + kTileX - 1) / kTileX, (hd + kTileY - 1) / kTileY, num), kThreads, 0, ks>>>(
+          s.d_gray.p, wd, hd, r, inv, s.d_resp.p, s.d_pol.p, s.d_blur.p, s.d_max.p);
+      OICC_HIP_TRY(hipEventRecord(s.ev[2], ks));
+      board_candidates_kernel<<<dim3((wd + kThreads - 1) / kThreads, hd, num), kThreads, 0, ks>>>(
+          s.d_resp.p, s.d_pol.p, wd, hd, r, opt->threshold_rel, s.d_max.p, cap, s.d_count.p, s.d_cand.p);
+      OICC_HIP_TRY(hipEventRecord(s.ev[3], ks));
+      const int64_t waves = int64_t(num) * cap;
+      board_subpix_kernel<<<dim3(unsigned((waves + 3) / 4)), kThreads, 0, ks>>>(s.d_blur.p, wd, hd, num, cap, s.d_count.p, s.d_cand.p, win,
+                                                                               opt->subpix_iterations, opt->subpix_eps, s.d_ref.p);
+      OICC_HIP_TRY(hipGetLastError());
+      OICC_HIP_TRY(hipEventRecord(s.ev[4], ks));
+      OICC_HIP_TRY(hipEventRecord(s.done, ks));
       return OICC_OK;
     };
-    for (int q = 0; q < nslots; ++q) BOARD_TRY(hipEventRecord(slot[q].done, ks));
-    int next = 0;
-    for (int k = 0; k < nslots && next < num_frames; ++k) { if ((rc = enqueue(slot[k], next)) != OICC_OK) goto done; next += slot[k].num; }
-    for (int k = 0; slot[k & 1].num > 0; ++k) {        // batches complete in order, alternating between the slots
-      Slot& s = slot[k & 1];
-      BOARD_TRY(hipEventSynchronize(s.done));
+    // complete: the batch's candidates to the host, grids assembled there, kernel 6 over them, the corners written
+    auto complete = [&](int q, int first, int num) -> int {
+      Slot& s = slot[q];
+      OICC_HIP_TRY(hipEventSynchronize(s.done));
       float ms = 0;
       double* acc[4] = {&rep.ms_resize, &rep.ms_response, &rep.ms_candidates, &rep.ms_subpix};
-      for (int q = 0; q < 4; ++q) { BOARD_TRY(hipEventElapsedTime(&ms, s.ev[q], s.ev[q + 1])); *acc[q] += ms; }
-      std::vector<int> cnt(size_t(s.num));
-      std::vector<Cand> cand(size_t(s.num) * cap);
-      std::vector<double> ref(size_t(s.num) * cap * 2);
-      BOARD_TRY(hipMemcpy(cnt.data(), s.d_count, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
-      BOARD_TRY(hipMemcpy(cand.data(), s.d_cand, sizeof(Cand) * cand.size(), hipMemcpyDeviceToHost));
-      BOARD_TRY(hipMemcpy(ref.data(), s.d_ref, sizeof(double) * ref.size(), hipMemcpyDeviceToHost));
+      for (int j = 0; j < 4; ++j) { OICC_HIP_TRY(hipEventElapsedTime(&ms, s.ev[j], s.ev[j + 1])); *acc[j] += ms; }
+      std::vector<int> cnt(static_cast<size_t>(num));
+      std::vector<Cand> cand(size_t(num) * cap);
+      std::vector<double> ref(size_t(num) * cap * 2);
+      OICC_HIP_TRY(hipMemcpy(cnt.data(), s.d_count.p, sizeof(int) * cnt.size(), hipMemcpyDeviceToHost));
+      OICC_HIP_TRY(hipMemcpy(cand.data(), s.d_cand.p, sizeof(Cand) * cand.size(), hipMemcpyDeviceToHost));
+      OICC_HIP_TRY(hipMemcpy(ref.data(), s.d_ref.p, sizeof(double) * ref.size(), hipMemcpyDeviceToHost));
       if (stages) {
-        for (int f = 0; f < s.num; ++f) {
-          const int64_t F = s.first + f;
-          if (stages->gray) BOARD_TRY(hipMemcpy(stages->gray + F * out_frame, s.d_gray + f * out_frame, size_t(out_frame), hipMemcpyDeviceToHost));
-          if (stages->response) BOARD_TRY(hipMemcpy(stages->response + F * out_frame, s.d_resp + f * out_frame, sizeof(float) * size_t(out_frame), hipMemcpyDeviceToHost));
+        for (int f = 0; f < num; ++f) {
+          const int64_t F = first + f;
+          if (stages->gray) OICC_HIP_TRY(hipMemcpy(stages->gray + F * out_frame, s.d_gray.p + f * out_frame, size_t(out_frame), hipMemcpyDeviceToHost));
+          if (stages->response) OICC_HIP_TRY(hipMemcpy(stages->response + F * out_frame, s.d_resp.p + f * out_frame, sizeof(float) * size_t(out_frame), hipMemcpyDeviceToHost));
         }
       }
       const auto th0 = std::chrono::steady_clock::now();
       // per frame: candidates in raster order, then the grid
-      std::vector<std::vector<V2>> fpts(size_t(s.num));
-      std::vector<Grid> grids(size_t(s.num));
-      std::vector<char> has(size_t(s.num), 0);
-      for (int f = 0; f < s.num; ++f) {
-        const int n = cnt[size_t(f)], F = s.first + f;
+      std::vector<std::vector<V2>> fpts(static_cast<size_t>(num));
+      std::vector<Grid> grids(static_cast<size_t>(num));
+      std::vector<char> has(static_cast<size_t>(num), 0);
+      for (int f = 0; f < num; ++f) {
+        const int n = cnt[size_t(f)], F = first + f;
         if (candidates_per_frame) candidates_per_frame[F] = n;
         rep.num_candidates += n;
         if (n > cap) { ++rep.frames_overflow; continue; }
@@ -638,9 +644,9 @@ extern "C" int oicc_board_radon_detect(int32_t device_ordinal, int32_t num_frame
       }
       rep.ms_assembly_host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count();
       // kernel 6 over every assembled grid of the batch
-      std::vector<GridRef> gr; std::vector<double> gc;
+      gr.clear(); gc.clear();
       int ncell = 0;
-      for (int f = 0; f < s.num; ++f) {
+      for (int f = 0; f < num; ++f) {
         if (!has[size_t(f)]) continue;
         const Grid& G = grids[size_t(f)];
         gr.push_back(GridRef{f, G.A, G.B, int(gc.size() / 2), ncell});
@@ -648,33 +654,26 @@ extern "C" int oicc_board_radon_detect(int32_t device_ordinal, int32_t num_frame
         ncell += (G.A - 1) * (G.B - 1);
       }
       if (!gr.empty()) {
-        GridRef* d_gr = nullptr; double *d_gc = nullptr, *d_disc = nullptr, *d_ring = nullptr;
-        std::vector<double> disc(static_cast<size_t>(ncell)), ring(static_cast<size_t>(ncell));
-        int krc = OICC_OK;
-        if (hipMalloc(&d_gr, sizeof(GridRef) * gr.size()) != hipSuccess || hipMalloc(&d_gc, sizeof(double) * gc.size()) != hipSuccess ||
-            hipMalloc(&d_disc, sizeof(double) * size_t(ncell)) != hipSuccess || hipMalloc(&d_ring, sizeof(double) * size_t(ncell)) != hipSuccess ||
-            hipMemcpyAsync(d_gr, gr.data(), sizeof(GridRef) * gr.size(), hipMemcpyHostToDevice, ks) != hipSuccess ||
-            hipMemcpyAsync(d_gc, gc.data(), sizeof(double) * gc.size(), hipMemcpyHostToDevice, ks) != hipSuccess ||
-            hipEventRecord(s.ev[4], ks) != hipSuccess) krc = OICC_ERR_HIP;
-        if (krc == OICC_OK) {
-          board_marker_kernel<<<dim3((ncell + kThreads - 1) / kThreads), kThreads, 0, ks>>>(s.d_blur, wd, hd, int(gr.size()), d_gr, d_gc, ncell, d_disc, d_ring);
-          if (hipGetLastError() != hipSuccess || hipEventRecord(s.ev[5], ks) != hipSuccess ||
-              hipMemcpyAsync(disc.data(), d_disc, sizeof(double) * size_t(ncell), hipMemcpyDeviceToHost, ks) != hipSuccess ||
-              hipMemcpyAsync(ring.data(), d_ring, sizeof(double) * size_t(ncell), hipMemcpyDeviceToHost, ks) != hipSuccess ||
-              hipStreamSynchronize(ks) != hipSuccess || hipEventElapsedTime(&ms, s.ev[4], s.ev[5]) != hipSuccess) krc = OICC_ERR_HIP;
-          else rep.ms_marker += ms;
-        }
-        if (d_gr) (void)hipFree(d_gr);
-        if (d_gc) (void)hipFree(d_gc);
-        if (d_disc) (void)hipFree(d_disc);
-        if (d_ring) (void)hipFree(d_ring);
-        if (krc != OICC_OK) { rc = krc; goto done; }
+        disc.assign(size_t(ncell), 0.0); ring.assign(size_t(ncell), 0.0);
+        OICC_HIP_TRY(s.d_gr.resize(gr.size())); OICC_HIP_TRY(s.d_gc.resize(gc.size()));
+        OICC_HIP_TRY(s.d_disc.resize(size_t(ncell))); OICC_HIP_TRY(s.d_ring.resize(size_t(ncell)));
+        OICC_HIP_TRY(hipMemcpyAsync(s.d_gr.p, gr.data(), sizeof(GridRef) * gr.size(), hipMemcpyHostToDevice, ks));
+        OICC_HIP_TRY(hipMemcpyAsync(s.d_gc.p, gc.data(), sizeof(double) * gc.size(), hipMemcpyHostToDevice, ks));
+        OICC_HIP_TRY(hipEventRecord(s.ev[4], ks));
+        board_marker_kernel<<<dim3((ncell + kThreads - 1) / kThreads), kThreads, 0, ks>>>(s.d_blur.p, wd, hd, int(gr.size()), s.d_gr.p, s.d_gc.p, ncell, s.d_disc.p, s.d_ring.p);
+        OICC_HIP_TRY(hipGetLastError());
+        OICC_HIP_TRY(hipEventRecord(s.ev[5], ks));
+        OICC_HIP_TRY(hipMemcpyAsync(disc.data(), s.d_disc.p, sizeof(double) * size_t(ncell), hipMemcpyDeviceToHost, ks));
+        OICC_HIP_TRY(hipMemcpyAsync(ring.data(), s.d_ring.p, sizeof(double) * size_t(ncell), hipMemcpyDeviceToHost, ks));
+        OICC_HIP_TRY(hipStreamSynchronize(ks));
+        OICC_HIP_TRY(hipEventElapsedTime(&ms, s.ev[4], s.ev[5]));
+        rep.ms_marker += ms;
         const auto th1 = std::chrono::steady_clock::now();
         for (const GridRef& g : gr) {
           const Grid& G = grids[size_t(g.frame)];
           std::vector<int> ids;
           if (!marker_ids(G, fpts[size_t(g.frame)], disc.data() + g.cell0, ring.data() + g.cell0, W, H, &ids)) continue;
-          const int F = s.first + g.frame;
+          const int F = first + g.frame;
           for (size_t q = 0; q < ids.size(); ++q) {
             const V2 p = fpts[size_t(g.frame)][size_t(G.idx[q])];
             corners[2 * (int64_t(F) * WH + ids[q])] = p.x; corners[2 * (int64_t(F) * WH + ids[q]) + 1] = p.y;
@@ -683,26 +682,11 @@ extern "C" int oicc_board_radon_detect(int32_t device_ordinal, int32_t num_frame
         }
         rep.ms_assembly_host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th1).count();
       }
-      // the slot is free again: queue the batch after the next one
-      const int nf = next;
-      s.num = 0;
-      if (nf < num_frames) { if ((rc = enqueue(s, nf)) != OICC_OK) goto done; next += s.num; }
-    }
-  }
-done:
-  if (cs) (void)hipStreamSynchronize(cs);
-  if (ks) (void)hipStreamSynchronize(ks);
-  for (auto& s : slot) {
-    if (s.pinned) (void)hipHostFree(s.pinned);
-    for (void* p : {(void*)s.d_src, (void*)s.d_gray, (void*)s.d_resp, (void*)s.d_pol, (void*)s.d_blur, (void*)s.d_max, (void*)s.d_count, (void*)s.d_cand, (void*)s.d_ref})
-      if (p) (void)hipFree(p);
-    if (s.up) (void)hipEventDestroy(s.up);
-    if (s.done) (void)hipEventDestroy(s.done);
-    for (auto& e : s.ev) if (e) (void)hipEventDestroy(e);
-  }
-  if (d_tab) (void)hipFree(d_tab);
-  if (cs) (void)hipStreamDestroy(cs);
-  if (ks) (void)hipStreamDestroy(ks);
+      return OICC_OK;
+    };
+    for (int q = 0; q < nslots; ++q) OICC_HIP_TRY(hipEventRecord(slot[q].done, ks));
+    return oicc::run_frame_batches(num_frames, int(nbatch), enqueue, complete);
+  }();
   rep.output_width = wd; rep.output_height = hd;
   rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
   if (report) *report = rep;

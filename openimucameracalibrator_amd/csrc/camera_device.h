@@ -1,11 +1,15 @@
 // Device code shared by the camera maps (camera_maps.hip) and the rolling-shutter rectification (rolling_shutter.hip): the camera
 // argument, pixel -> ray by Newton on the principal branch, and the bilinear sample of a u8 frame.  Both units are compiled with
-// -ffp-contract=off (csrc/Makefile), so every sum here rounds as tests/camera_maps_restatement.py does.
+// -ffp-contract=off (csrc/Makefile), so every sum here rounds as tests/camera_maps_restatement.py does.  Behind the device code,
+// the host pipeline that both units' frame entries run their batches through (FramePipeline).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include "../../include/oicc_hip.h"
+#include "frame_batches.h"
+#include "hip_resources.h"
 #include "spline_math.h"
 
 namespace oicc_camera {
@@ -47,13 +51,6 @@ inline bool make_camera(int32_t model, const double* intr, Camera* cam) {
 
 // the destination camera whose rays have a closed form (camera_map_kernel)
 inline int is_plain_pinhole(const Camera& cam) { return cam.model == oicc::CAM_PINHOLE && cam.in[5] == 0.0 && cam.in[6] == 0.0; }
-
-inline int select_device(int32_t device_ordinal) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device_ordinal < 0 || device_ordinal >= ndev) return OICC_ERR_NO_DEVICE;   // no CPU fallback
-  if (hipSetDevice(device_ordinal) != hipSuccess) return OICC_ERR_NO_DEVICE;
-  return OICC_OK;
-}
 
 constexpr int64_t kMaxLanes = ((int64_t(1) << 31) - 1) * kThreads;   // one lane per pixel: the grid's x dimension stays below 2^31 blocks
 
@@ -120,6 +117,70 @@ struct BilinearTap {
     const double val = (w00 * p00 + w01 * p01) + (w10 * p10 + w11 * p11);
     const double r = floor(val + 0.5);
     return uint8_t(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
+  }
+};
+
+// ---- host side: u8 frames through the device in batches ------------------------------------------------------------------------
+// One batch per slot and stream: host copy into pinned memory, upload, the caller's kernels, download, host copy out; the other
+// slot's batch overlaps.  open() makes every allocation, so none sits inside a timed span.  launch(stream, first, num, d_in,
+// d_out) enqueues the kernels for frames [first, first + num), whose input lies at d_in and whose output goes to d_out.
+struct FramePipeline {
+  struct Slot {
+    oicc::Stream st;      // ahead of the staging, so destroyed behind it: ~FramePipeline has drained it by then
+    oicc::Event ev[4];    // upload start, upload end, kernel end, download end
+    oicc::DevBuf<uint8_t> d_out, d_in;
+    oicc::PinnedBuf<uint8_t> pin_out, pin_in;
+  };
+  Slot slot[2];
+  // Both streams drained first, then (members, in reverse) per slot the staging freed and its stream destroyed last: drained
+  // before freed, as the order rule of hip_resources.h asks, by this destructor and not by where the streams are declared.
+  ~FramePipeline() { for (Slot& s : slot) if (s.st) (void)hipStreamSynchronize(s.st); }
+  int num_frames = 0, batch = 0;
+  int64_t in_frame = 0, out_frame = 0;     // bytes per source / destination frame
+  double ms_upload = 0.0, ms_kernel = 0.0, ms_download = 0.0;    // summed over the batches
+
+  int open(int num_frames_, int batch_, int64_t in_frame_, int64_t out_frame_) {
+    num_frames = num_frames_; batch = std::min(batch_, num_frames_); in_frame = in_frame_; out_frame = out_frame_;
+    for (int q = 0; q < oicc::frame_batch_slots(num_frames, batch); ++q) {
+      Slot& s = slot[q];
+      OICC_HIP_TRY(s.st.create());
+      OICC_HIP_TRY(s.pin_in.alloc(size_t(batch * in_frame)));
+      OICC_HIP_TRY(s.pin_out.alloc(size_t(batch * out_frame)));
+      OICC_HIP_TRY(s.d_in.resize(size_t(batch * in_frame)));
+      OICC_HIP_TRY(s.d_out.resize(size_t(batch * out_frame)));
+      for (auto& e : s.ev) OICC_HIP_TRY(e.create());
+    }
+    return OICC_OK;
+  }
+
+  template <class Launch>
+  int run(const uint8_t* frames, uint8_t* out, Launch&& launch) {
+    return oicc::run_frame_batches(
+        num_frames, batch,
+        [&](int q, int first, int num) -> int {
+          Slot& s = slot[q];
+          std::memcpy(s.pin_in.p, frames + int64_t(first) * in_frame, size_t(num * in_frame));
+          OICC_HIP_TRY(hipEventRecord(s.ev[0], s.st));
+          OICC_HIP_TRY(hipMemcpyAsync(s.d_in.p, s.pin_in.p, size_t(num * in_frame), hipMemcpyHostToDevice, s.st));
+          OICC_HIP_TRY(hipEventRecord(s.ev[1], s.st));
+          if (launch(s.st.s, first, num, s.d_in.p, s.d_out.p) != OICC_OK) return OICC_ERR_HIP;
+          OICC_HIP_TRY(hipEventRecord(s.ev[2], s.st));
+          OICC_HIP_TRY(hipMemcpyAsync(s.pin_out.p, s.d_out.p, size_t(num * out_frame), hipMemcpyDeviceToHost, s.st));
+          OICC_HIP_TRY(hipEventRecord(s.ev[3], s.st));
+          return OICC_OK;
+        },
+        [&](int q, int first, int num) -> int {
+          Slot& s = slot[q];
+          OICC_HIP_TRY(hipStreamSynchronize(s.st));
+          double* acc[3] = {&ms_upload, &ms_kernel, &ms_download};
+          for (int j = 0; j < 3; ++j) {
+            float ms = 0.0f;
+            OICC_HIP_TRY(hipEventElapsedTime(&ms, s.ev[j], s.ev[j + 1]));
+            *acc[j] += ms;
+          }
+          std::memcpy(out + int64_t(first) * out_frame, s.pin_out.p, size_t(num * out_frame));
+          return OICC_OK;
+        });
   }
 };
 

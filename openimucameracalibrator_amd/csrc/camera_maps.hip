@@ -137,39 +137,31 @@ int launch_remap(hipStream_t st, int num_frames, int src_w, int src_h, int chann
 
 }  // namespace
 
-#define CAMERA_TRY(expr) do { if ((expr) != hipSuccess) { rc = OICC_ERR_HIP; goto done; } } while (0)
-
 extern "C" int oicc_camera_unproject(int32_t device_ordinal, int32_t model, const double* intrinsics, int32_t n_intr, int64_t n,
                                      const double* uv, double* xy, uint8_t* status, double* device_ms) {
   Camera cam;
   if (n_intr != intrinsics_count(model) || !make_camera(model, intrinsics, &cam) || n < 1 || n > kMaxLanes || !uv || !xy || !status) return OICC_ERR_INVALID_ARG;
-  if (int rc = select_device(device_ordinal)) return rc;
-  int rc = OICC_OK;
-  double *d_uv = nullptr, *d_xy = nullptr; uint8_t* d_st = nullptr;
-  hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
+  oicc::DevBuf<double> d_uv, d_xy; oicc::DevBuf<uint8_t> d_st;
+  oicc::Event e0, e1;
+  oicc::Stream st;
   float ms = 0.0f;
-  CAMERA_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  CAMERA_TRY(hipEventCreate(&e0)); CAMERA_TRY(hipEventCreate(&e1));
-  CAMERA_TRY(hipMalloc(&d_uv, sizeof(double) * 2 * size_t(n)));
-  CAMERA_TRY(hipMalloc(&d_xy, sizeof(double) * 2 * size_t(n)));
-  CAMERA_TRY(hipMalloc(&d_st, size_t(n)));
-  CAMERA_TRY(hipMemcpyAsync(d_uv, uv, sizeof(double) * 2 * size_t(n), hipMemcpyHostToDevice, st));
-  CAMERA_TRY(hipEventRecord(e0, st));
-  hipLaunchKernelGGL(camera_unproject_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, cam, n, d_uv, d_xy, d_st);
-  CAMERA_TRY(hipGetLastError());
-  CAMERA_TRY(hipEventRecord(e1, st));
-  CAMERA_TRY(hipMemcpyAsync(xy, d_xy, sizeof(double) * 2 * size_t(n), hipMemcpyDeviceToHost, st));
-  CAMERA_TRY(hipMemcpyAsync(status, d_st, size_t(n), hipMemcpyDeviceToHost, st));
-  CAMERA_TRY(hipStreamSynchronize(st));
-  CAMERA_TRY(hipEventElapsedTime(&ms, e0, e1));
+  OICC_HIP_TRY(st.create());
+  OICC_HIP_TRY(e0.create()); OICC_HIP_TRY(e1.create());
+  OICC_HIP_TRY(d_uv.resize(2 * size_t(n)));
+  OICC_HIP_TRY(d_xy.resize(2 * size_t(n)));
+  OICC_HIP_TRY(d_st.resize(size_t(n)));
+  OICC_HIP_TRY(hipMemcpyAsync(d_uv.p, uv, sizeof(double) * 2 * size_t(n), hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipEventRecord(e0, st));
+  hipLaunchKernelGGL(camera_unproject_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, cam, n, d_uv.p, d_xy.p, d_st.p);
+  OICC_HIP_TRY(hipGetLastError());
+  OICC_HIP_TRY(hipEventRecord(e1, st));
+  OICC_HIP_TRY(hipMemcpyAsync(xy, d_xy.p, sizeof(double) * 2 * size_t(n), hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipMemcpyAsync(status, d_st.p, size_t(n), hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipStreamSynchronize(st));
+  OICC_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
   if (device_ms) *device_ms = double(ms);
-done:
-  if (rc != OICC_OK && st) (void)hipStreamSynchronize(st);
-  for (void* p : {(void*)d_uv, (void*)d_xy, (void*)d_st}) if (p) (void)hipFree(p);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  return OICC_OK;
 }
 
 extern "C" int oicc_camera_rectify_map(int32_t device_ordinal, int32_t src_model, const double* src_intr, int32_t src_w, int32_t src_h,
@@ -184,77 +176,62 @@ extern "C" int oicc_camera_rectify_map(int32_t device_ordinal, int32_t src_model
       if (!std::isfinite(R9[k])) return OICC_ERR_INVALID_ARG;
       R.r[k] = R9[k];
     }
-  if (int rc = select_device(device_ordinal)) return rc;
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
   const int closed_form = is_plain_pinhole(dst);
   const int64_t pixels = int64_t(dst_w) * dst_h;
-  int rc = OICC_OK;
-  float2* d_map = nullptr; uint8_t* d_valid = nullptr;
-  hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
+  oicc::DevBuf<float2> d_map; oicc::DevBuf<uint8_t> d_valid;
+  oicc::Event e0, e1;
+  oicc::Stream st;
   float ms = 0.0f;
-  CAMERA_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  CAMERA_TRY(hipEventCreate(&e0)); CAMERA_TRY(hipEventCreate(&e1));
-  CAMERA_TRY(hipMalloc(&d_map, sizeof(float2) * size_t(pixels)));
-  CAMERA_TRY(hipMalloc(&d_valid, size_t(pixels)));
-  CAMERA_TRY(hipEventRecord(e0, st));
+  OICC_HIP_TRY(st.create());
+  OICC_HIP_TRY(e0.create()); OICC_HIP_TRY(e1.create());
+  OICC_HIP_TRY(d_map.resize(size_t(pixels)));
+  OICC_HIP_TRY(d_valid.resize(size_t(pixels)));
+  OICC_HIP_TRY(hipEventRecord(e0, st));
   hipLaunchKernelGGL(camera_map_kernel, dim3(blocks_for(pixels)), dim3(kThreads), 0, st, src, int(src_w), int(src_h), dst, closed_form,
-                     int(dst_w), int(dst_h), R, d_map, d_valid);
-  CAMERA_TRY(hipGetLastError());
-  CAMERA_TRY(hipEventRecord(e1, st));
-  CAMERA_TRY(hipMemcpyAsync(map, d_map, sizeof(float2) * size_t(pixels), hipMemcpyDeviceToHost, st));
-  CAMERA_TRY(hipMemcpyAsync(valid, d_valid, size_t(pixels), hipMemcpyDeviceToHost, st));
-  CAMERA_TRY(hipStreamSynchronize(st));
-  CAMERA_TRY(hipEventElapsedTime(&ms, e0, e1));
+                     int(dst_w), int(dst_h), R, d_map.p, d_valid.p);
+  OICC_HIP_TRY(hipGetLastError());
+  OICC_HIP_TRY(hipEventRecord(e1, st));
+  OICC_HIP_TRY(hipMemcpyAsync(map, d_map.p, sizeof(float2) * size_t(pixels), hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipMemcpyAsync(valid, d_valid.p, size_t(pixels), hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipStreamSynchronize(st));
+  OICC_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
   if (device_ms) *device_ms = double(ms);
   if (num_valid) {
     int64_t c = 0;
     for (int64_t i = 0; i < pixels; ++i) c += valid[i];
     *num_valid = c;
   }
-done:
-  if (rc != OICC_OK && st) (void)hipStreamSynchronize(st);
-  if (d_map) (void)hipFree(d_map);
-  if (d_valid) (void)hipFree(d_valid);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  return OICC_OK;
 }
 
 extern "C" int oicc_camera_discrepancy(int32_t device_ordinal, int32_t model_a, const double* intr_a, int32_t model_b,
                                        const double* intr_b, int32_t w, int32_t h, double stats[3], double* device_ms) {
   Camera a, b;
   if (!make_camera(model_a, intr_a, &a) || !make_camera(model_b, intr_b, &b) || w < 1 || h < 1 || int64_t(w) * h > kMaxLanes || !stats) return OICC_ERR_INVALID_ARG;
-  if (int rc = select_device(device_ordinal)) return rc;
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
   const int64_t pixels = int64_t(w) * h;
   const unsigned blocks = blocks_for(pixels);
   std::vector<double> rows(size_t(blocks) * kWaves * 3);
-  int rc = OICC_OK;
-  double* d_rows = nullptr;
-  hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
+  oicc::DevBuf<double> d_rows;
+  oicc::Event e0, e1;
+  oicc::Stream st;
   float ms = 0.0f;
-  CAMERA_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  CAMERA_TRY(hipEventCreate(&e0)); CAMERA_TRY(hipEventCreate(&e1));
-  CAMERA_TRY(hipMalloc(&d_rows, sizeof(double) * rows.size()));
-  CAMERA_TRY(hipEventRecord(e0, st));
-  hipLaunchKernelGGL(camera_discrepancy_kernel, dim3(blocks), dim3(kThreads), 0, st, a, b, int(w), int(h), d_rows);
-  CAMERA_TRY(hipGetLastError());
-  CAMERA_TRY(hipEventRecord(e1, st));
-  CAMERA_TRY(hipMemcpyAsync(rows.data(), d_rows, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, st));
-  CAMERA_TRY(hipStreamSynchronize(st));
-  CAMERA_TRY(hipEventElapsedTime(&ms, e0, e1));
+  OICC_HIP_TRY(st.create());
+  OICC_HIP_TRY(e0.create()); OICC_HIP_TRY(e1.create());
+  OICC_HIP_TRY(d_rows.resize(rows.size()));
+  OICC_HIP_TRY(hipEventRecord(e0, st));
+  hipLaunchKernelGGL(camera_discrepancy_kernel, dim3(blocks), dim3(kThreads), 0, st, a, b, int(w), int(h), d_rows.p);
+  OICC_HIP_TRY(hipGetLastError());
+  OICC_HIP_TRY(hipEventRecord(e1, st));
+  OICC_HIP_TRY(hipMemcpyAsync(rows.data(), d_rows.p, sizeof(double) * rows.size(), hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipStreamSynchronize(st));
+  OICC_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
   if (device_ms) *device_ms = double(ms);
-  {
-    double cnt = 0.0, sum = 0.0, mx = 0.0;
-    for (size_t r = 0; r < rows.size() / 3; ++r) { cnt += rows[3 * r]; sum += rows[3 * r + 1]; mx = std::max(mx, rows[3 * r + 2]); }
-    stats[0] = cnt; stats[1] = cnt > 0.0 ? std::sqrt(sum / cnt) : 0.0; stats[2] = mx;
-  }
-done:
-  if (rc != OICC_OK && st) (void)hipStreamSynchronize(st);
-  if (d_rows) (void)hipFree(d_rows);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  double cnt = 0.0, sum = 0.0, mx = 0.0;
+  for (size_t r = 0; r < rows.size() / 3; ++r) { cnt += rows[3 * r]; sum += rows[3 * r + 1]; mx = std::max(mx, rows[3 * r + 2]); }
+  stats[0] = cnt; stats[1] = cnt > 0.0 ? std::sqrt(sum / cnt) : 0.0; stats[2] = mx;
+  return OICC_OK;
 }
 
 extern "C" int oicc_camera_remap_device(void* hip_stream, int32_t num_frames, int32_t src_w, int32_t src_h, int32_t channels,
@@ -262,106 +239,32 @@ extern "C" int oicc_camera_remap_device(void* hip_stream, int32_t num_frames, in
                                         int32_t border_value, uint8_t* out_dev) {
   if (!remap_args_ok(num_frames, src_w, src_h, channels, dst_w, dst_h, border_value) || !frames_dev || !map_dev || !out_dev)
     return OICC_ERR_INVALID_ARG;
-  int ndev = 0, cur = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || hipGetDevice(&cur) != hipSuccess) return OICC_ERR_NO_DEVICE;   // no CPU fallback
-  // the launch goes to the current device: the stream and the three arrays have to live there
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (stream) {
-    hipDevice_t of_stream = 0, of_current = 0;
-    if (hipStreamGetDevice(stream, &of_stream) != hipSuccess || hipDeviceGet(&of_current, cur) != hipSuccess || of_stream != of_current) {
-      (void)hipGetLastError();
-      return OICC_ERR_INVALID_ARG;
-    }
-  }
-  for (const void* p : {(const void*)frames_dev, (const void*)map_dev, (const void*)out_dev}) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type == hipMemoryTypeUnregistered || (a.type == hipMemoryTypeDevice && a.device != cur)) {
-      (void)hipGetLastError();
-      return OICC_ERR_INVALID_ARG;
-    }
-  }
+  if (int rc = oicc::on_current_device(stream, {frames_dev, map_dev, out_dev})) return rc;
   return launch_remap(stream, num_frames, src_w, src_h, channels, frames_dev, map_dev, dst_w, dst_h,
                       border_value, out_dev);
 }
-
-namespace {
-struct RemapSlot {
-  uint8_t *pin_in = nullptr, *pin_out = nullptr, *d_in = nullptr, *d_out = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};    // upload start, upload end, kernel end, download end
-  int first = 0, num = 0;
-};
-}  // namespace
 
 extern "C" int oicc_camera_remap(int32_t device_ordinal, int32_t num_frames, int32_t src_w, int32_t src_h, int32_t channels,
                                  const uint8_t* frames, const float* map, int32_t dst_w, int32_t dst_h, int32_t border_value,
                                  int32_t batch, uint8_t* out, oicc_camera_remap_report* report) {
   if (!remap_args_ok(num_frames, src_w, src_h, channels, dst_w, dst_h, border_value) || batch < 1 || !frames || !map || !out)
     return OICC_ERR_INVALID_ARG;
-  if (int rc = select_device(device_ordinal)) return rc;
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
   const auto t_start = std::chrono::steady_clock::now();
-  oicc_camera_remap_report rep = {0.0, 0.0, 0.0, 0.0};
-  const int64_t in_frame = int64_t(src_w) * src_h * channels, out_frame = int64_t(dst_w) * dst_h * channels;
-  const int64_t nbatch = std::min<int64_t>(batch, num_frames);
-  const int nslots = num_frames > nbatch ? 2 : 1;     // a second staging slot only when a second batch exists
-  const size_t map_bytes = sizeof(float) * 2 * size_t(dst_w) * size_t(dst_h);
-  int rc = OICC_OK;
-  float* d_map = nullptr;
-  hipStream_t st[2] = {nullptr, nullptr};
-  RemapSlot slot[2];
-  CAMERA_TRY(hipMalloc(&d_map, map_bytes));
-  CAMERA_TRY(hipMemcpy(d_map, map, map_bytes, hipMemcpyHostToDevice));
-  for (int q = 0; q < nslots; ++q) {
-    RemapSlot& s = slot[q];
-    CAMERA_TRY(hipStreamCreateWithFlags(&st[q], hipStreamNonBlocking));
-    CAMERA_TRY(hipHostMalloc(&s.pin_in, size_t(nbatch * in_frame), hipHostMallocDefault));
-    CAMERA_TRY(hipHostMalloc(&s.pin_out, size_t(nbatch * out_frame), hipHostMallocDefault));
-    CAMERA_TRY(hipMalloc(&s.d_in, size_t(nbatch * in_frame)));
-    CAMERA_TRY(hipMalloc(&s.d_out, size_t(nbatch * out_frame)));
-    for (auto& e : s.ev) CAMERA_TRY(hipEventCreate(&e));
+  const size_t map_floats = 2 * size_t(dst_w) * size_t(dst_h);
+  oicc::DevBuf<float> d_map;
+  FramePipeline pipe;      // behind the map: its streams are drained before the map goes
+  OICC_HIP_TRY(d_map.resize(map_floats));
+  OICC_HIP_TRY(hipMemcpy(d_map.p, map, sizeof(float) * map_floats, hipMemcpyHostToDevice));
+  if (int rc = pipe.open(num_frames, batch, int64_t(src_w) * src_h * channels, int64_t(dst_w) * dst_h * channels)) return rc;
+  const int rc = pipe.run(frames, out, [&](hipStream_t st, int, int num, const uint8_t* d_in, uint8_t* d_out) {
+    return oicc_camera_remap_device(st, num, src_w, src_h, channels, d_in, d_map.p, dst_w, dst_h, border_value, d_out);
+  });
+  if (rc != OICC_OK) return rc;
+  if (report) {
+    const double ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+    *report = oicc_camera_remap_report{pipe.ms_upload, pipe.ms_kernel, pipe.ms_download, ms_total};
   }
-  {
-    // one batch per slot and stream: host copy into pinned memory, upload, kernel, download; the other slot's batch overlaps
-    auto enqueue = [&](int q, int first) -> int {
-      RemapSlot& s = slot[q];
-      s.first = first; s.num = int(std::min<int64_t>(nbatch, num_frames - first));
-      if (s.num <= 0) return OICC_OK;
-      std::memcpy(s.pin_in, frames + int64_t(first) * in_frame, size_t(s.num * in_frame));
-      if (hipEventRecord(s.ev[0], st[q]) != hipSuccess ||
-          hipMemcpyAsync(s.d_in, s.pin_in, size_t(s.num * in_frame), hipMemcpyHostToDevice, st[q]) != hipSuccess ||
-          hipEventRecord(s.ev[1], st[q]) != hipSuccess) return OICC_ERR_HIP;
-      if (oicc_camera_remap_device(st[q], s.num, src_w, src_h, channels, s.d_in, d_map, dst_w, dst_h, border_value, s.d_out) != OICC_OK) return OICC_ERR_HIP;
-      if (hipEventRecord(s.ev[2], st[q]) != hipSuccess ||
-          hipMemcpyAsync(s.pin_out, s.d_out, size_t(s.num * out_frame), hipMemcpyDeviceToHost, st[q]) != hipSuccess ||
-          hipEventRecord(s.ev[3], st[q]) != hipSuccess) return OICC_ERR_HIP;
-      return OICC_OK;
-    };
-    int next = 0;
-    for (int q = 0; q < nslots && next < num_frames; ++q) { if ((rc = enqueue(q, next)) != OICC_OK) goto done; next += slot[q].num; }
-    for (int k = 0; slot[k % nslots].num > 0; ++k) {        // batches complete in order, alternating between the slots
-      const int q = k % nslots;
-      RemapSlot& s = slot[q];
-      CAMERA_TRY(hipStreamSynchronize(st[q]));
-      float ms = 0.0f;
-      double* acc[3] = {&rep.ms_upload, &rep.ms_kernel, &rep.ms_download};
-      for (int j = 0; j < 3; ++j) { CAMERA_TRY(hipEventElapsedTime(&ms, s.ev[j], s.ev[j + 1])); *acc[j] += ms; }
-      std::memcpy(out + int64_t(s.first) * out_frame, s.pin_out, size_t(s.num * out_frame));
-      s.num = 0;
-      if (next < num_frames) { if ((rc = enqueue(q, next)) != OICC_OK) goto done; next += s.num; }
-    }
-  }
-  rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-  if (report) *report = rep;
-done:
-  for (int q = 0; q < 2; ++q) if (st[q]) (void)hipStreamSynchronize(st[q]);
-  for (int q = 0; q < 2; ++q) {
-    RemapSlot& s = slot[q];
-    if (s.pin_in) (void)hipHostFree(s.pin_in);
-    if (s.pin_out) (void)hipHostFree(s.pin_out);
-    if (s.d_in) (void)hipFree(s.d_in);
-    if (s.d_out) (void)hipFree(s.d_out);
-    for (auto& e : s.ev) if (e) (void)hipEventDestroy(e);
-    if (st[q]) (void)hipStreamDestroy(st[q]);
-  }
-  if (d_map) (void)hipFree(d_map);
-  return rc;
+  return OICC_OK;
 }

@@ -23,6 +23,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "oicc_device.h"
+#include "hip_resources.h"
 #include "block_items.h"
 #include "ba_math.h"   // homogeneous_plus4 / homogeneous_tangent_rows: the board points under SplineOptimFlags::POINTS
 #include "inner_plan.h"
@@ -1035,19 +1036,18 @@ extern "C" int oicc_debug_inner_cholesky(int32_t device, int32_t D, int64_t n, c
   if (n <= 0 || !M || !rhs || !x || !ok || (D != 1 && D != 3 && D != 6 && D != 9)) return 2;
   if (hipSetDevice(device) != hipSuccess) return 5;
   const size_t nm = size_t(n) * size_t(D * D), nd = size_t(n) * size_t(D);
-  double* d = nullptr; unsigned char* dk = nullptr;
-  if (hipMalloc(&d, (nm + 2 * nd) * sizeof(double)) != hipSuccess) return 4;
-  if (hipMalloc(&dk, size_t(n)) != hipSuccess) { (void)hipFree(d); return 4; }
+  oicc::DevBuf<double> buf; oicc::DevBuf<unsigned char> dk;      // the null stream runs the kernel, and the blocking copies behind it wait for it
+  if (!buf.resize(nm + 2 * nd) || !dk.resize(size_t(n))) return 4;
+  double* d = buf.p;
   bool good = hipMemcpy(d, M, nm * sizeof(double), hipMemcpyHostToDevice) == hipSuccess && hipMemcpy(d + nm, rhs, nd * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
   if (good) {
     const dim3 grid(unsigned((n + 63) / 64)), block(64);
-    if (D == 1) hipLaunchKernelGGL(oicc::inner_cholesky_debug_kernel<1>, grid, block, 0, nullptr, n, d, d + nm, d + nm + nd, dk);
-    else if (D == 3) hipLaunchKernelGGL(oicc::inner_cholesky_debug_kernel<3>, grid, block, 0, nullptr, n, d, d + nm, d + nm + nd, dk);
-    else if (D == 6) hipLaunchKernelGGL(oicc::inner_cholesky_debug_kernel<6>, grid, block, 0, nullptr, n, d, d + nm, d + nm + nd, dk);
-    else hipLaunchKernelGGL(oicc::inner_cholesky_debug_kernel<9>, grid, block, 0, nullptr, n, d, d + nm, d + nm + nd, dk);
+    if (D == 1) hipLaunchKernelGGL(oicc::inner_cholesky_debug_kernel<1>, grid, block, 0, nullptr, n, d, d + nm, d + nm + nd, dk.p);
+    else if (D == 3) hipLaunchKernelGGL(oicc::inner_cholesky_debug_kernel<3>, grid, block, 0, nullptr, n, d, d + nm, d + nm + nd, dk.p);
+    else if (D == 6) hipLaunchKernelGGL(oicc::inner_cholesky_debug_kernel<6>, grid, block, 0, nullptr, n, d, d + nm, d + nm + nd, dk.p);
+    else hipLaunchKernelGGL(oicc::inner_cholesky_debug_kernel<9>, grid, block, 0, nullptr, n, d, d + nm, d + nm + nd, dk.p);
     good = hipGetLastError() == hipSuccess && hipMemcpy(x, d + nm + nd, nd * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
-           hipMemcpy(ok, dk, size_t(n), hipMemcpyDeviceToHost) == hipSuccess;
+           hipMemcpy(ok, dk.p, size_t(n), hipMemcpyDeviceToHost) == hipSuccess;
   }
-  (void)hipFree(d); (void)hipFree(dk);
   return good ? 0 : 4;
 }

@@ -1,6 +1,7 @@
 // A15: trajectory read-back of the spline estimator (one lane per timestamp).
 #include <hip/hip_runtime.h>
 #include "oicc_device.h"
+#include "hip_resources.h"
 #include "spline_math.h"
 
 namespace oicc {
@@ -74,14 +75,14 @@ __global__ void fast_sincos_kernel(int64_t n, const double* x, double* s, double
 extern "C" int oicc_debug_fast_sincos(int32_t device, int64_t n, const double* x, double* s, double* c) {
   if (n <= 0 || !x || !s || !c) return 2;
   if (hipSetDevice(device) != hipSuccess) return 5;
-  double* d = nullptr;
-  if (hipMalloc(&d, size_t(3) * size_t(n) * sizeof(double)) != hipSuccess) return 4;
+  oicc::DevBuf<double> buf;      // the null stream runs the kernel, and the blocking copies behind it wait for it
+  if (!buf.resize(size_t(3) * size_t(n))) return 4;
+  double* d = buf.p;
   bool ok = hipMemcpy(d, x, size_t(n) * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
   if (ok) {
     hipLaunchKernelGGL(oicc::fast_sincos_kernel, dim3(unsigned((n + 255) / 256)), dim3(256), 0, nullptr, n, d, d + n, d + 2 * n);
     ok = hipGetLastError() == hipSuccess && hipMemcpy(s, d + n, size_t(n) * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess &&
          hipMemcpy(c, d + 2 * n, size_t(n) * sizeof(double), hipMemcpyDeviceToHost) == hipSuccess;
   }
-  (void)hipFree(d);
   return ok ? 0 : 4;
 }

@@ -8,6 +8,7 @@
 #include <utility>
 #include <cstring>
 #include "oicc_device.h"
+#include "hip_resources.h"   // DevBuf
 
 namespace oicc {
 // kernels_solve.hip
@@ -53,28 +54,6 @@ static inline int launch_lm_solve(const NormalEq& ne, const TangentLayout& tl, c
   launch_lm_build(ne, tl, sb, reuse_diagonal, min_diag, max_diag, st);
   return launch_band_arrow_cholesky(tl, sb, st);
 }
-
-// device buffer that grows on demand (host-side RAII)
-template <class T>
-struct DevBuf {
-  T* p = nullptr; size_t n = 0;
-  bool owned = true;   // false: a piece of a DevArena block
-  ~DevBuf() { if (p && owned) (void)hipFree(p); }
-  void release() { if (p && owned) (void)hipFree(p); p = nullptr; n = 0; owned = true; }
-  bool resize(size_t count) {
-    if (count <= n && p) return true;
-    release();
-    if (count == 0) return true;
-    if (hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T)) != hipSuccess) { p = nullptr; return false; }
-    n = count; return true;
-  }
-  bool upload(const std::vector<T>& h, hipStream_t st) {
-    if (!resize(std::max<size_t>(h.size(), 1))) return false;
-    if (h.empty()) return true;
-    return hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st) == hipSuccess;
-  }
-  void attach(T* ptr, size_t count) { release(); p = ptr; n = count; owned = false; }
-};
 
 // Many host arrays -> ONE device block with ONE copy (a hipMalloc + hipMemcpy per array costs 10-20 us each: 0.3 ms for the ~30
 // measurement arrays of the GoPro9 configuration).  add() registers an array, commit() packs them into a host staging block

@@ -18,6 +18,7 @@
 #include <cmath>
 #include <cstdint>
 #include "../../include/oicc_hip.h"
+#include "hip_resources.h"
 
 namespace {
 
@@ -559,47 +560,41 @@ extern "C" int oicc_planar_ransac(int32_t device_ordinal, int32_t num_views, con
   for (int32_t v = 0; v < num_views; ++v) long_view |= corner_offsets[v + 1] - corner_offsets[v] > kStage;
   for (int64_t i = 0; i < 2 * n; ++i)
     if (!std::isfinite(ab[i]) || !std::isfinite(xy[i])) return OICC_ERR_INVALID_ARG;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device_ordinal < 0 || device_ordinal >= ndev) return OICC_ERR_NO_DEVICE;   // no CPU fallback
-  if (hipSetDevice(device_ordinal) != hipSuccess) return OICC_ERR_NO_DEVICE;
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
   if (device_ms) *device_ms = 0.0;
   if (num_views == 0) return OICC_OK;
 
-  int64_t* d_off = nullptr; double *d_ab = nullptr, *d_xy = nullptr, *d_q = nullptr, *d_pose = nullptr, *d_tz = nullptr;
-  uint8_t* d_in = nullptr; int32_t *d_num = nullptr, *d_cnt = nullptr;
-  hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
-  int rc = OICC_OK;
-  auto ok = [&](hipError_t e) { if (e != hipSuccess && rc == OICC_OK) rc = OICC_ERR_HIP; return rc == OICC_OK; };
+  oicc::DevBuf<int64_t> d_off; oicc::DevBuf<double> d_ab, d_xy, d_q, d_pose, d_tz;
+  oicc::DevBuf<uint8_t> d_in; oicc::DevBuf<int32_t> d_num, d_cnt;
+  oicc::Event e0, e1;
+  oicc::Stream st;
   const size_t n1 = size_t(n > 0 ? n : 1), nv = size_t(num_views);
-  if (ok(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)) && ok(hipEventCreate(&e0)) && ok(hipEventCreate(&e1)) &&
-      ok(hipMalloc(&d_off, sizeof(int64_t) * (nv + 1))) && ok(hipMalloc(&d_ab, sizeof(double) * 2 * n1)) &&
-      ok(hipMalloc(&d_xy, sizeof(double) * 2 * n1)) && ok(hipMalloc(&d_in, n1)) && ok(hipMalloc(&d_num, sizeof(int32_t) * nv)) &&
-      ok(hipMalloc(&d_q, sizeof(double) * 6 * nv)) && ok(hipMalloc(&d_pose, sizeof(double) * 12 * nv)) &&
-      (!(long_view && mode == 1) || ok(hipMalloc(&d_tz, sizeof(double) * n1))) &&
-      (!hypothesis_counts || ok(hipMalloc(&d_cnt, sizeof(int32_t) * nv * size_t(num_hypotheses)))) &&
-      ok(hipMemcpyAsync(d_off, corner_offsets, sizeof(int64_t) * (nv + 1), hipMemcpyHostToDevice, st)) &&
-      (n == 0 || (ok(hipMemcpyAsync(d_ab, ab, sizeof(double) * 2 * size_t(n), hipMemcpyHostToDevice, st)) &&
-                  ok(hipMemcpyAsync(d_xy, xy, sizeof(double) * 2 * size_t(n), hipMemcpyHostToDevice, st)))) &&
-      ok(hipEventRecord(e0, st))) {
-    hipLaunchKernelGGL(planar_ransac_kernel, dim3(unsigned(num_views)), dim3(kThreads), 0, st, d_off, d_ab, d_xy, int(mode),
-                       threshold * threshold, int(num_hypotheses), seed * kGolden, d_in, d_num, d_q, d_pose, d_cnt, d_tz);
-    if (ok(hipGetLastError()) && ok(hipEventRecord(e1, st)) &&
-        (n == 0 || ok(hipMemcpyAsync(inlier, d_in, size_t(n), hipMemcpyDeviceToHost, st))) &&
-        ok(hipMemcpyAsync(num_inliers, d_num, sizeof(int32_t) * nv, hipMemcpyDeviceToHost, st)) &&
-        ok(hipMemcpyAsync(q, d_q, sizeof(double) * 6 * nv, hipMemcpyDeviceToHost, st)) &&
-        (mode != 1 || ok(hipMemcpyAsync(pose, d_pose, sizeof(double) * 12 * nv, hipMemcpyDeviceToHost, st))) &&
-        (!hypothesis_counts ||
-         ok(hipMemcpyAsync(hypothesis_counts, d_cnt, sizeof(int32_t) * nv * size_t(num_hypotheses), hipMemcpyDeviceToHost, st))) &&
-        ok(hipStreamSynchronize(st))) {
-      float ms = 0.0f;
-      if (ok(hipEventElapsedTime(&ms, e0, e1)) && device_ms) *device_ms = double(ms);
-    }
+  OICC_HIP_TRY(st.create());
+  OICC_HIP_TRY(e0.create()); OICC_HIP_TRY(e1.create());
+  OICC_HIP_TRY(d_off.resize(nv + 1)); OICC_HIP_TRY(d_ab.resize(2 * n1));
+  OICC_HIP_TRY(d_xy.resize(2 * n1)); OICC_HIP_TRY(d_in.resize(n1)); OICC_HIP_TRY(d_num.resize(nv));
+  OICC_HIP_TRY(d_q.resize(6 * nv)); OICC_HIP_TRY(d_pose.resize(12 * nv));
+  if (long_view && mode == 1) OICC_HIP_TRY(d_tz.resize(n1));
+  if (hypothesis_counts) OICC_HIP_TRY(d_cnt.resize(nv * size_t(num_hypotheses)));
+  OICC_HIP_TRY(hipMemcpyAsync(d_off.p, corner_offsets, sizeof(int64_t) * (nv + 1), hipMemcpyHostToDevice, st));
+  if (n > 0) {
+    OICC_HIP_TRY(hipMemcpyAsync(d_ab.p, ab, sizeof(double) * 2 * size_t(n), hipMemcpyHostToDevice, st));
+    OICC_HIP_TRY(hipMemcpyAsync(d_xy.p, xy, sizeof(double) * 2 * size_t(n), hipMemcpyHostToDevice, st));
   }
-  if (rc != OICC_OK && st) (void)hipStreamSynchronize(st);
-  for (void* p : {(void*)d_off, (void*)d_ab, (void*)d_xy, (void*)d_in, (void*)d_num, (void*)d_q, (void*)d_pose, (void*)d_tz, (void*)d_cnt})
-    if (p) (void)hipFree(p);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  OICC_HIP_TRY(hipEventRecord(e0, st));
+  hipLaunchKernelGGL(planar_ransac_kernel, dim3(unsigned(num_views)), dim3(kThreads), 0, st, d_off.p, d_ab.p, d_xy.p, int(mode),
+                     threshold * threshold, int(num_hypotheses), seed * kGolden, d_in.p, d_num.p, d_q.p, d_pose.p, d_cnt.p, d_tz.p);
+  OICC_HIP_TRY(hipGetLastError());
+  OICC_HIP_TRY(hipEventRecord(e1, st));
+  if (n > 0) OICC_HIP_TRY(hipMemcpyAsync(inlier, d_in.p, size_t(n), hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipMemcpyAsync(num_inliers, d_num.p, sizeof(int32_t) * nv, hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipMemcpyAsync(q, d_q.p, sizeof(double) * 6 * nv, hipMemcpyDeviceToHost, st));
+  if (mode == 1) OICC_HIP_TRY(hipMemcpyAsync(pose, d_pose.p, sizeof(double) * 12 * nv, hipMemcpyDeviceToHost, st));
+  if (hypothesis_counts)
+    OICC_HIP_TRY(hipMemcpyAsync(hypothesis_counts, d_cnt.p, sizeof(int32_t) * nv * size_t(num_hypotheses), hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0.0f;
+  OICC_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+  if (device_ms) *device_ms = double(ms);
+  return OICC_OK;
 }

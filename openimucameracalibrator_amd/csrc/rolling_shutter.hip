@@ -277,8 +277,6 @@ __global__ __launch_bounds__(kThreads) void rs_rotation_kernel(RsParams P, const
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 
-#define RS_TRY(expr) do { if ((expr) != hipSuccess) { rc = OICC_ERR_HIP; goto done; } } while (0)
-
 // What every entry judges before it looks for a device, and the frame windows, found by time comparisons only.
 struct Judged {
   RsParams P;
@@ -351,54 +349,46 @@ int judge(const oicc_rs_scene* s, Judged* J) {
 
 // The device side of a scene: the per-frame tables and, where wanted, the destination rays.
 struct Prepared {
-  double *gyro_t = nullptr, *rates = nullptr, *frame_t = nullptr, *table = nullptr;
-  int64_t* first = nullptr;
-  int32_t* count = nullptr;
-  double2* rays = nullptr;
-  uint8_t* ray_status = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};     // before the table kernel, behind it, behind the ray kernel
-
-  void release() {
-    for (void* p : {(void*)gyro_t, (void*)rates, (void*)frame_t, (void*)table, (void*)first, (void*)count, (void*)rays, (void*)ray_status})
-      if (p) (void)hipFree(p);
-    for (auto& e : ev) if (e) (void)hipEventDestroy(e);
-  }
+  oicc::DevBuf<double> gyro_t, rates, frame_t, table;
+  oicc::DevBuf<int64_t> first;
+  oicc::DevBuf<int32_t> count;
+  oicc::DevBuf<double2> rays;
+  oicc::DevBuf<uint8_t> ray_status;
+  oicc::Event ev[3];     // before the table kernel, behind it, behind the ray kernel
 };
 
 // Enqueues the uploads, the table kernel and (with_rays) the ray kernel on st; J and the scene arrays must outlive the stream's work.
 int prepare(const oicc_rs_scene* s, const Judged& J, bool with_rays, hipStream_t st, Prepared* D) {
-  int rc = OICC_OK;
   const size_t n = size_t(J.num_gyro), f = size_t(J.num_frames);
   const int64_t pixels = int64_t(J.P.dst_w) * J.P.dst_h;
-  for (auto& e : D->ev) RS_TRY(hipEventCreate(&e));
-  RS_TRY(hipMalloc(&D->gyro_t, sizeof(double) * n));
-  RS_TRY(hipMalloc(&D->rates, sizeof(double) * 3 * n));
-  RS_TRY(hipMalloc(&D->frame_t, sizeof(double) * f));
-  RS_TRY(hipMalloc(&D->first, sizeof(int64_t) * f));
-  RS_TRY(hipMalloc(&D->count, sizeof(int32_t) * f));
-  RS_TRY(hipMalloc(&D->table, sizeof(double) * kMaxWindow * kEntry * f));
+  for (auto& e : D->ev) OICC_HIP_TRY(e.create());
+  OICC_HIP_TRY(D->gyro_t.resize(n));
+  OICC_HIP_TRY(D->rates.resize(3 * n));
+  OICC_HIP_TRY(D->frame_t.resize(f));
+  OICC_HIP_TRY(D->first.resize(f));
+  OICC_HIP_TRY(D->count.resize(f));
+  OICC_HIP_TRY(D->table.resize(size_t(kMaxWindow) * kEntry * f));
   if (with_rays) {                          // every allocation before the first event: none sits inside a timed span
-    RS_TRY(hipMalloc(&D->rays, sizeof(double2) * size_t(pixels)));
-    RS_TRY(hipMalloc(&D->ray_status, size_t(pixels)));
+    OICC_HIP_TRY(D->rays.resize(size_t(pixels)));
+    OICC_HIP_TRY(D->ray_status.resize(size_t(pixels)));
   }
-  RS_TRY(hipMemcpyAsync(D->gyro_t, s->gyro_t, sizeof(double) * n, hipMemcpyHostToDevice, st));
-  RS_TRY(hipMemcpyAsync(D->rates, J.rates_cam.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
-  RS_TRY(hipMemcpyAsync(D->frame_t, s->frame_t, sizeof(double) * f, hipMemcpyHostToDevice, st));
-  RS_TRY(hipMemcpyAsync(D->first, J.first.data(), sizeof(int64_t) * f, hipMemcpyHostToDevice, st));
-  RS_TRY(hipMemcpyAsync(D->count, J.count.data(), sizeof(int32_t) * f, hipMemcpyHostToDevice, st));
-  RS_TRY(hipEventRecord(D->ev[0], st));
-  hipLaunchKernelGGL(rs_frame_table_kernel, dim3(unsigned((J.num_frames + 63) / 64)), dim3(64), 0, st, J.num_frames, D->gyro_t, D->rates,
-                     D->frame_t, D->first, D->count, J.P.time_offset, J.P.reference_row * J.P.line_delay, D->table);
-  RS_TRY(hipGetLastError());
-  RS_TRY(hipEventRecord(D->ev[1], st));
+  OICC_HIP_TRY(hipMemcpyAsync(D->gyro_t.p, s->gyro_t, sizeof(double) * n, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(D->rates.p, J.rates_cam.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(D->frame_t.p, s->frame_t, sizeof(double) * f, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(D->first.p, J.first.data(), sizeof(int64_t) * f, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(D->count.p, J.count.data(), sizeof(int32_t) * f, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipEventRecord(D->ev[0], st));
+  hipLaunchKernelGGL(rs_frame_table_kernel, dim3(unsigned((J.num_frames + 63) / 64)), dim3(64), 0, st, J.num_frames, D->gyro_t.p, D->rates.p,
+                     D->frame_t.p, D->first.p, D->count.p, J.P.time_offset, J.P.reference_row * J.P.line_delay, D->table.p);
+  OICC_HIP_TRY(hipGetLastError());
+  OICC_HIP_TRY(hipEventRecord(D->ev[1], st));
   if (with_rays) {
-    hipLaunchKernelGGL(rs_ray_kernel, dim3(blocks_for(pixels)), dim3(kThreads), 0, st, J.P.dst, J.P.dst_closed_form, J.P.dst_w, pixels, D->rays,
-                       D->ray_status);
-    RS_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rs_ray_kernel, dim3(blocks_for(pixels)), dim3(kThreads), 0, st, J.P.dst, J.P.dst_closed_form, J.P.dst_w, pixels, D->rays.p,
+                       D->ray_status.p);
+    OICC_HIP_TRY(hipGetLastError());
   }
-  RS_TRY(hipEventRecord(D->ev[2], st));
-done:
-  return rc;
+  OICC_HIP_TRY(hipEventRecord(D->ev[2], st));
+  return OICC_OK;
 }
 
 // frames [first, first + num) of the scene; frames_dev / out_dev start at frame `first`
@@ -410,10 +400,10 @@ int launch_rectify(hipStream_t st, const Judged& J, const Prepared& D, int first
     const int m = std::min(kFrameChunk, num - done);
     const dim3 grid(blocks_for(pixels), unsigned(m));
     if (channels == 1)
-      hipLaunchKernelGGL(rs_rectify_kernel<1>, grid, dim3(kThreads), 0, st, J.P, first + done, D.table, D.count, D.rays, D.ray_status, pixels,
+      hipLaunchKernelGGL(rs_rectify_kernel<1>, grid, dim3(kThreads), 0, st, J.P, first + done, D.table.p, D.count.p, D.rays.p, D.ray_status.p, pixels,
                          frames_dev + done * in_frame, border, out_dev + done * out_frame);
     else
-      hipLaunchKernelGGL(rs_rectify_kernel<3>, grid, dim3(kThreads), 0, st, J.P, first + done, D.table, D.count, D.rays, D.ray_status, pixels,
+      hipLaunchKernelGGL(rs_rectify_kernel<3>, grid, dim3(kThreads), 0, st, J.P, first + done, D.table.p, D.count.p, D.rays.p, D.ray_status.p, pixels,
                          frames_dev + done * in_frame, border, out_dev + done * out_frame);
     if (hipGetLastError() != hipSuccess) return OICC_ERR_HIP;
   }
@@ -428,12 +418,6 @@ bool frames_args_ok(int32_t channels, int32_t border_value) {
   return (channels == 1 || channels == 3) && border_value >= 0 && border_value <= 255;
 }
 
-struct RsSlot {
-  uint8_t *pin_in = nullptr, *pin_out = nullptr, *d_in = nullptr, *d_out = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};    // upload start, upload end, kernel end, download end
-  int first = 0, num = 0;
-};
-
 }  // namespace
 
 extern "C" int oicc_rs_rectify_map(int32_t device_ordinal, const oicc_rs_scene* scene, float* map, uint8_t* valid, uint8_t* evaluations,
@@ -441,34 +425,34 @@ extern "C" int oicc_rs_rectify_map(int32_t device_ordinal, const oicc_rs_scene* 
   Judged J;
   if (int rc = judge(scene, &J)) return rc;
   if (!map || !valid || !frame_status) return OICC_ERR_INVALID_ARG;
-  if (int rc = select_device(device_ordinal)) return rc;
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
   const int64_t pixels = int64_t(J.P.dst_w) * J.P.dst_h;
   const size_t total = size_t(pixels) * size_t(J.num_frames);
-  int rc = OICC_OK;
   Prepared D;
-  float2* d_map = nullptr; uint8_t *d_valid = nullptr, *d_evals = nullptr;
-  hipStream_t st = nullptr; hipEvent_t e1 = nullptr;
+  oicc::DevBuf<float2> d_map; oicc::DevBuf<uint8_t> d_valid, d_evals;
+  oicc::Event e1;
+  oicc::Stream st;
   float ms[3] = {0.0f, 0.0f, 0.0f};
-  RS_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  RS_TRY(hipEventCreate(&e1));
-  RS_TRY(hipMalloc(&d_map, sizeof(float2) * total));
-  RS_TRY(hipMalloc(&d_valid, total));
-  if (evaluations) RS_TRY(hipMalloc(&d_evals, total));
-  if ((rc = prepare(scene, J, true, st, &D)) != OICC_OK) goto done;
+  OICC_HIP_TRY(st.create());
+  OICC_HIP_TRY(e1.create());
+  OICC_HIP_TRY(d_map.resize(total));
+  OICC_HIP_TRY(d_valid.resize(total));
+  if (evaluations) OICC_HIP_TRY(d_evals.resize(total));
+  if (int rc = prepare(scene, J, true, st, &D)) return rc;
   for (int first = 0; first < J.num_frames; first += kFrameChunk) {
     const int m = std::min(kFrameChunk, J.num_frames - first);
-    hipLaunchKernelGGL(rs_map_kernel, dim3(blocks_for(pixels), unsigned(m)), dim3(kThreads), 0, st, J.P, first, D.table, D.count, D.rays,
-                       D.ray_status, pixels, d_map, d_valid, d_evals);
-    RS_TRY(hipGetLastError());
+    hipLaunchKernelGGL(rs_map_kernel, dim3(blocks_for(pixels), unsigned(m)), dim3(kThreads), 0, st, J.P, first, D.table.p, D.count.p, D.rays.p,
+                       D.ray_status.p, pixels, d_map.p, d_valid.p, d_evals.p);
+    OICC_HIP_TRY(hipGetLastError());
   }
-  RS_TRY(hipEventRecord(e1, st));
-  RS_TRY(hipMemcpyAsync(map, d_map, sizeof(float2) * total, hipMemcpyDeviceToHost, st));
-  RS_TRY(hipMemcpyAsync(valid, d_valid, total, hipMemcpyDeviceToHost, st));
-  if (evaluations) RS_TRY(hipMemcpyAsync(evaluations, d_evals, total, hipMemcpyDeviceToHost, st));
-  RS_TRY(hipStreamSynchronize(st));
-  RS_TRY(hipEventElapsedTime(&ms[0], D.ev[0], D.ev[1]));
-  RS_TRY(hipEventElapsedTime(&ms[1], D.ev[1], D.ev[2]));
-  RS_TRY(hipEventElapsedTime(&ms[2], D.ev[2], e1));
+  OICC_HIP_TRY(hipEventRecord(e1, st));
+  OICC_HIP_TRY(hipMemcpyAsync(map, d_map.p, sizeof(float2) * total, hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipMemcpyAsync(valid, d_valid.p, total, hipMemcpyDeviceToHost, st));
+  if (evaluations) OICC_HIP_TRY(hipMemcpyAsync(evaluations, d_evals.p, total, hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipStreamSynchronize(st));
+  OICC_HIP_TRY(hipEventElapsedTime(&ms[0], D.ev[0], D.ev[1]));
+  OICC_HIP_TRY(hipEventElapsedTime(&ms[1], D.ev[1], D.ev[2]));
+  OICC_HIP_TRY(hipEventElapsedTime(&ms[2], D.ev[2], e1));
   if (device_ms) for (int k = 0; k < 3; ++k) device_ms[k] = double(ms[k]);
   copy_status(J, frame_status);
   if (num_valid)
@@ -477,13 +461,7 @@ extern "C" int oicc_rs_rectify_map(int32_t device_ordinal, const oicc_rs_scene* 
       for (int64_t i = 0; i < pixels; ++i) c += valid[int64_t(k) * pixels + i];
       num_valid[k] = c;
     }
-done:
-  if (rc != OICC_OK && st) (void)hipStreamSynchronize(st);
-  D.release();
-  for (void* p : {(void*)d_map, (void*)d_valid, (void*)d_evals}) if (p) (void)hipFree(p);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  return OICC_OK;
 }
 
 extern "C" int oicc_rs_rectify_frames_device(void* hip_stream, const oicc_rs_scene* scene, int32_t channels, const uint8_t* frames_dev,
@@ -491,30 +469,13 @@ extern "C" int oicc_rs_rectify_frames_device(void* hip_stream, const oicc_rs_sce
   Judged J;
   if (int rc = judge(scene, &J)) return rc;
   if (!frames_args_ok(channels, border_value) || !frames_dev || !out_dev || !frame_status) return OICC_ERR_INVALID_ARG;
-  int ndev = 0, cur = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1 || hipGetDevice(&cur) != hipSuccess) return OICC_ERR_NO_DEVICE;   // no CPU fallback
-  // the launches go to the current device: the stream and the two arrays have to live there
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (stream) {
-    hipDevice_t of_stream = 0, of_current = 0;
-    if (hipStreamGetDevice(stream, &of_stream) != hipSuccess || hipDeviceGet(&of_current, cur) != hipSuccess || of_stream != of_current) {
-      (void)hipGetLastError();
-      return OICC_ERR_INVALID_ARG;
-    }
-  }
-  for (const void* p : {(const void*)frames_dev, (const void*)out_dev}) {
-    hipPointerAttribute_t a;
-    if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type == hipMemoryTypeUnregistered || (a.type == hipMemoryTypeDevice && a.device != cur)) {
-      (void)hipGetLastError();
-      return OICC_ERR_INVALID_ARG;
-    }
-  }
+  if (int rc = oicc::on_current_device(stream, {frames_dev, out_dev})) return rc;
   Prepared D;
   int rc = prepare(scene, J, true, stream, &D);
   if (rc == OICC_OK) rc = launch_rectify(stream, J, D, 0, J.num_frames, channels, frames_dev, border_value, out_dev);
   // the tables are this call's own: it returns once the stream has run the work, and frees them
   if (hipStreamSynchronize(stream) != hipSuccess && rc == OICC_OK) rc = OICC_ERR_HIP;
-  D.release();
   if (rc == OICC_OK) copy_status(J, frame_status);
   return rc;
 }
@@ -524,79 +485,26 @@ extern "C" int oicc_rs_rectify_frames(int32_t device_ordinal, const oicc_rs_scen
   Judged J;
   if (int rc = judge(scene, &J)) return rc;
   if (!frames_args_ok(channels, border_value) || batch < 1 || !frames || !out || !frame_status) return OICC_ERR_INVALID_ARG;
-  if (int rc = select_device(device_ordinal)) return rc;
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
   const auto t_start = std::chrono::steady_clock::now();
   oicc_rs_frames_report rep = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-  const int num_frames = J.num_frames;
-  const int64_t in_frame = int64_t(J.P.src_w) * J.P.src_h * channels, out_frame = int64_t(J.P.dst_w) * J.P.dst_h * channels;
-  const int64_t nbatch = std::min<int64_t>(batch, num_frames);
-  const int nslots = num_frames > nbatch ? 2 : 1;     // a second staging slot only when a second batch exists
-  int rc = OICC_OK;
   Prepared D;
-  hipStream_t st[2] = {nullptr, nullptr};
-  RsSlot slot[2];
-  for (int q = 0; q < nslots; ++q) RS_TRY(hipStreamCreateWithFlags(&st[q], hipStreamNonBlocking));
-  if ((rc = prepare(scene, J, true, st[0], &D)) != OICC_OK) goto done;
-  RS_TRY(hipStreamSynchronize(st[0]));                 // both streams read the tables
-  {
-    float ms = 0.0f;
-    RS_TRY(hipEventElapsedTime(&ms, D.ev[0], D.ev[1])); rep.ms_table = ms;
-    RS_TRY(hipEventElapsedTime(&ms, D.ev[1], D.ev[2])); rep.ms_rays = ms;
-  }
-  for (int q = 0; q < nslots; ++q) {
-    RsSlot& s = slot[q];
-    RS_TRY(hipHostMalloc(&s.pin_in, size_t(nbatch * in_frame), hipHostMallocDefault));
-    RS_TRY(hipHostMalloc(&s.pin_out, size_t(nbatch * out_frame), hipHostMallocDefault));
-    RS_TRY(hipMalloc(&s.d_in, size_t(nbatch * in_frame)));
-    RS_TRY(hipMalloc(&s.d_out, size_t(nbatch * out_frame)));
-    for (auto& e : s.ev) RS_TRY(hipEventCreate(&e));
-  }
-  {
-    // one batch per slot and stream: host copy into pinned memory, upload, kernel, download; the other slot's batch overlaps
-    auto enqueue = [&](int q, int first) -> int {
-      RsSlot& s = slot[q];
-      s.first = first; s.num = int(std::min<int64_t>(nbatch, num_frames - first));
-      if (s.num <= 0) return OICC_OK;
-      std::memcpy(s.pin_in, frames + int64_t(first) * in_frame, size_t(s.num * in_frame));
-      if (hipEventRecord(s.ev[0], st[q]) != hipSuccess ||
-          hipMemcpyAsync(s.d_in, s.pin_in, size_t(s.num * in_frame), hipMemcpyHostToDevice, st[q]) != hipSuccess ||
-          hipEventRecord(s.ev[1], st[q]) != hipSuccess) return OICC_ERR_HIP;
-      if (launch_rectify(st[q], J, D, first, s.num, channels, s.d_in, border_value, s.d_out) != OICC_OK) return OICC_ERR_HIP;
-      if (hipEventRecord(s.ev[2], st[q]) != hipSuccess ||
-          hipMemcpyAsync(s.pin_out, s.d_out, size_t(s.num * out_frame), hipMemcpyDeviceToHost, st[q]) != hipSuccess ||
-          hipEventRecord(s.ev[3], st[q]) != hipSuccess) return OICC_ERR_HIP;
-      return OICC_OK;
-    };
-    int next = 0;
-    for (int q = 0; q < nslots && next < num_frames; ++q) { if ((rc = enqueue(q, next)) != OICC_OK) goto done; next += slot[q].num; }
-    for (int k = 0; slot[k % nslots].num > 0; ++k) {        // batches complete in order, alternating between the slots
-      const int q = k % nslots;
-      RsSlot& s = slot[q];
-      RS_TRY(hipStreamSynchronize(st[q]));
-      float ms = 0.0f;
-      double* acc[3] = {&rep.ms_upload, &rep.ms_kernel, &rep.ms_download};
-      for (int j = 0; j < 3; ++j) { RS_TRY(hipEventElapsedTime(&ms, s.ev[j], s.ev[j + 1])); *acc[j] += ms; }
-      std::memcpy(out + int64_t(s.first) * out_frame, s.pin_out, size_t(s.num * out_frame));
-      s.num = 0;
-      if (next < num_frames) { if ((rc = enqueue(q, next)) != OICC_OK) goto done; next += s.num; }
-    }
-  }
+  FramePipeline pipe;      // behind the tables: its streams are drained before the tables go
+  if (int rc = pipe.open(J.num_frames, batch, int64_t(J.P.src_w) * J.P.src_h * channels, int64_t(J.P.dst_w) * J.P.dst_h * channels)) return rc;
+  if (int rc = prepare(scene, J, true, pipe.slot[0].st, &D)) return rc;
+  OICC_HIP_TRY(hipStreamSynchronize(pipe.slot[0].st));      // both streams read the tables
+  float ms = 0.0f;
+  OICC_HIP_TRY(hipEventElapsedTime(&ms, D.ev[0], D.ev[1])); rep.ms_table = ms;
+  OICC_HIP_TRY(hipEventElapsedTime(&ms, D.ev[1], D.ev[2])); rep.ms_rays = ms;
+  const int rc = pipe.run(frames, out, [&](hipStream_t st, int first, int num, const uint8_t* d_in, uint8_t* d_out) {
+    return launch_rectify(st, J, D, first, num, channels, d_in, border_value, d_out);
+  });
+  if (rc != OICC_OK) return rc;
   copy_status(J, frame_status);
+  rep.ms_upload = pipe.ms_upload; rep.ms_kernel = pipe.ms_kernel; rep.ms_download = pipe.ms_download;
   rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
   if (report) *report = rep;
-done:
-  for (int q = 0; q < 2; ++q) if (st[q]) (void)hipStreamSynchronize(st[q]);
-  for (int q = 0; q < 2; ++q) {
-    RsSlot& s = slot[q];
-    if (s.pin_in) (void)hipHostFree(s.pin_in);
-    if (s.pin_out) (void)hipHostFree(s.pin_out);
-    if (s.d_in) (void)hipFree(s.d_in);
-    if (s.d_out) (void)hipFree(s.d_out);
-    for (auto& e : s.ev) if (e) (void)hipEventDestroy(e);
-  }
-  D.release();
-  for (int q = 0; q < 2; ++q) if (st[q]) (void)hipStreamDestroy(st[q]);
-  return rc;
+  return OICC_OK;
 }
 
 namespace {
@@ -611,42 +519,35 @@ int run_queries(int32_t device_ordinal, const oicc_rs_scene* scene, int64_t n, c
   if (n < 1 || n > kMaxLanes || !frame_index || !in || !out || !status || !frame_status) return OICC_ERR_INVALID_ARG;
   for (int64_t i = 0; i < n; ++i) if (frame_index[i] < 0 || frame_index[i] >= J.num_frames) return OICC_ERR_INVALID_ARG;
   if (QUERY == 1 && !all_finite(in, n)) return OICC_ERR_INVALID_ARG;
-  if (int rc = select_device(device_ordinal)) return rc;
-  int rc = OICC_OK;
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
   Prepared D;
-  int32_t* d_frame = nullptr; double *d_in = nullptr, *d_out = nullptr; uint8_t* d_st = nullptr;
-  hipStream_t st = nullptr; hipEvent_t e0 = nullptr, e1 = nullptr;
+  oicc::DevBuf<int32_t> d_frame; oicc::DevBuf<double> d_in, d_out; oicc::DevBuf<uint8_t> d_st;
+  oicc::Event e0, e1;
+  oicc::Stream st;
   float ms = 0.0f;
-  RS_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  RS_TRY(hipEventCreate(&e0)); RS_TRY(hipEventCreate(&e1));
-  if ((rc = prepare(scene, J, false, st, &D)) != OICC_OK) goto done;
-  RS_TRY(hipMalloc(&d_frame, sizeof(int32_t) * size_t(n)));
-  RS_TRY(hipMalloc(&d_in, sizeof(double) * kIn * size_t(n)));
-  RS_TRY(hipMalloc(&d_out, sizeof(double) * kOut * size_t(n)));
-  RS_TRY(hipMalloc(&d_st, size_t(n)));
-  RS_TRY(hipMemcpyAsync(d_frame, frame_index, sizeof(int32_t) * size_t(n), hipMemcpyHostToDevice, st));
-  RS_TRY(hipMemcpyAsync(d_in, in, sizeof(double) * kIn * size_t(n), hipMemcpyHostToDevice, st));
-  RS_TRY(hipEventRecord(e0, st));
+  OICC_HIP_TRY(st.create());
+  OICC_HIP_TRY(e0.create()); OICC_HIP_TRY(e1.create());
+  if (int rc = prepare(scene, J, false, st, &D)) return rc;
+  OICC_HIP_TRY(d_frame.resize(size_t(n)));
+  OICC_HIP_TRY(d_in.resize(kIn * size_t(n)));
+  OICC_HIP_TRY(d_out.resize(kOut * size_t(n)));
+  OICC_HIP_TRY(d_st.resize(size_t(n)));
+  OICC_HIP_TRY(hipMemcpyAsync(d_frame.p, frame_index, sizeof(int32_t) * size_t(n), hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(d_in.p, in, sizeof(double) * kIn * size_t(n), hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipEventRecord(e0, st));
   if (QUERY == 0)
-    hipLaunchKernelGGL(rs_points_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, J.P, D.table, D.count, n, d_frame, d_in, d_out, d_st);
+    hipLaunchKernelGGL(rs_points_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, J.P, D.table.p, D.count.p, n, d_frame.p, d_in.p, d_out.p, d_st.p);
   else
-    hipLaunchKernelGGL(rs_rotation_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, J.P, D.table, D.count, n, d_frame, d_in, d_out, d_st);
-  RS_TRY(hipGetLastError());
-  RS_TRY(hipEventRecord(e1, st));
-  RS_TRY(hipMemcpyAsync(out, d_out, sizeof(double) * kOut * size_t(n), hipMemcpyDeviceToHost, st));
-  RS_TRY(hipMemcpyAsync(status, d_st, size_t(n), hipMemcpyDeviceToHost, st));
-  RS_TRY(hipStreamSynchronize(st));
-  RS_TRY(hipEventElapsedTime(&ms, e0, e1));
+    hipLaunchKernelGGL(rs_rotation_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, J.P, D.table.p, D.count.p, n, d_frame.p, d_in.p, d_out.p, d_st.p);
+  OICC_HIP_TRY(hipGetLastError());
+  OICC_HIP_TRY(hipEventRecord(e1, st));
+  OICC_HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(double) * kOut * size_t(n), hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipMemcpyAsync(status, d_st.p, size_t(n), hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipStreamSynchronize(st));
+  OICC_HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
   if (device_ms) *device_ms = double(ms);
   copy_status(J, frame_status);
-done:
-  if (rc != OICC_OK && st) (void)hipStreamSynchronize(st);
-  D.release();
-  for (void* p : {(void*)d_frame, (void*)d_in, (void*)d_out, (void*)d_st}) if (p) (void)hipFree(p);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  return OICC_OK;
 }
 
 }  // namespace

@@ -23,6 +23,7 @@
 #include <cstring>
 #include <vector>
 #include "../../include/oicc_hip.h"
+#include "hip_resources.h"
 
 namespace {
 
@@ -244,28 +245,27 @@ constexpr int kRotGridCap = 512;   // workgroups of the two probe kernels; longe
 // ---- one probe of the golden-section search on the device: SolveClosedForm (cc:39-124) ----------------------------------
 // Holds the prepared series on the device; the calibration entry and the debug entry below both drive this one object.
 struct RotationProbe {
-  double *d_t = nullptr, *d_imu = nullptr, *d_vis = nullptr, *d_acc = nullptr, *d_Rb = nullptr; hipStream_t st = nullptr;
+  oicc::DevBuf<double> d_t, d_imu, d_vis, d_acc, d_Rb;
+  oicc::Stream st;      // behind the buffers (hip_resources.h); the series it uploads must outlive the probe
   size_t n = 0; int grid = 0; int estimate_gyro_bias = 0; bool ok = true;
-  void cleanup() {
-    if (d_t) (void)hipFree(d_t); if (d_imu) (void)hipFree(d_imu); if (d_vis) (void)hipFree(d_vis); if (d_acc) (void)hipFree(d_acc); if (d_Rb) (void)hipFree(d_Rb); if (st) (void)hipStreamDestroy(st);
-    d_t = d_imu = d_vis = d_acc = d_Rb = nullptr; st = nullptr;
-  }
   // times [n], smoothed gyroscope and visual rates [n, 3] (host) -> device
   int upload(size_t n_, const double* tI, const double* sImu, const double* sVis, int grid_cap, int estimate_bias) {
     n = n_; estimate_gyro_bias = estimate_bias;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess || hipMalloc(&d_t, n * 8) != hipSuccess || hipMalloc(&d_imu, 3 * n * 8) != hipSuccess ||
-        hipMalloc(&d_vis, 3 * n * 8) != hipSuccess || hipMalloc(&d_acc, 16 * 8) != hipSuccess || hipMalloc(&d_Rb, 12 * 8) != hipSuccess) { cleanup(); return OICC_ERR_HIP; }
-    if (hipMemcpyAsync(d_t, tI, n * 8, hipMemcpyHostToDevice, st) != hipSuccess || hipMemcpyAsync(d_imu, sImu, 3 * n * 8, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(d_vis, sVis, 3 * n * 8, hipMemcpyHostToDevice, st) != hipSuccess) { cleanup(); return OICC_ERR_HIP; }
+    OICC_HIP_TRY(st.create());
+    OICC_HIP_TRY(d_t.resize(n)); OICC_HIP_TRY(d_imu.resize(3 * n)); OICC_HIP_TRY(d_vis.resize(3 * n));
+    OICC_HIP_TRY(d_acc.resize(16)); OICC_HIP_TRY(d_Rb.resize(12));
+    OICC_HIP_TRY(hipMemcpyAsync(d_t.p, tI, n * 8, hipMemcpyHostToDevice, st));
+    OICC_HIP_TRY(hipMemcpyAsync(d_imu.p, sImu, 3 * n * 8, hipMemcpyHostToDevice, st));
+    OICC_HIP_TRY(hipMemcpyAsync(d_vis.p, sVis, 3 * n * 8, hipMemcpyHostToDevice, st));
     grid = int(std::min<size_t>((n + 255) / 256, size_t(grid_cap)));
     return OICC_OK;
   }
   // returns the error, fills R (row major) and the bias; moments (optional): the 15 sums of rot_moments_kernel
   double solve_closed_form(double td, double R[9], double b[3], double* moments = nullptr) {
     double h[16];
-    if (hipMemsetAsync(d_acc, 0, 16 * 8, st) != hipSuccess) { ok = false; return 0.0; }
-    hipLaunchKernelGGL(rot_moments_kernel, dim3(grid), dim3(256), 0, st, d_t, d_imu, d_vis, int(n), td, d_acc);
-    if (hipMemcpyAsync(h, d_acc, 15 * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { ok = false; return 0.0; }
+    if (hipMemsetAsync(d_acc.p, 0, 16 * 8, st) != hipSuccess) { ok = false; return 0.0; }
+    hipLaunchKernelGGL(rot_moments_kernel, dim3(grid), dim3(256), 0, st, d_t.p, d_imu.p, d_vis.p, int(n), td, d_acc.p);
+    if (hipMemcpyAsync(h, d_acc.p, 15 * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { ok = false; return 0.0; }
     if (moments) std::memcpy(moments, h, 15 * sizeof(double));
     const double N = double(n);
     const double mi[3] = {h[0] / N, h[1] / N, h[2] / N}, mv[3] = {h[3] / N, h[4] / N, h[5] / N};
@@ -275,20 +275,13 @@ struct RotationProbe {
     double Rb[12];
     for (int k = 0; k < 9; ++k) Rb[k] = R[k];
     for (int r = 0; r < 3; ++r) { b[r] = estimate_gyro_bias ? mv[r] - (R[3 * r] * mi[0] + R[3 * r + 1] * mi[1] + R[3 * r + 2] * mi[2]) : 0.0; Rb[9 + r] = b[r]; }
-    if (hipMemcpyAsync(d_Rb, Rb, sizeof(Rb), hipMemcpyHostToDevice, st) != hipSuccess || hipMemsetAsync(d_acc, 0, 8, st) != hipSuccess) { ok = false; return 0.0; }
-    hipLaunchKernelGGL(rot_error_kernel, dim3(grid), dim3(256), 0, st, d_t, d_imu, d_vis, int(n), td, d_Rb, d_acc);
+    if (hipMemcpyAsync(d_Rb.p, Rb, sizeof(Rb), hipMemcpyHostToDevice, st) != hipSuccess || hipMemsetAsync(d_acc.p, 0, 8, st) != hipSuccess) { ok = false; return 0.0; }
+    hipLaunchKernelGGL(rot_error_kernel, dim3(grid), dim3(256), 0, st, d_t.p, d_imu.p, d_vis.p, int(n), td, d_Rb.p, d_acc.p);
     double e = 0.0;
-    if (hipMemcpyAsync(&e, d_acc, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { ok = false; return 0.0; }
+    if (hipMemcpyAsync(&e, d_acc.p, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) { ok = false; return 0.0; }
     return e;
   }
 };
-
-int rot_select_device(int32_t device_ordinal) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device_ordinal < 0 || device_ordinal >= ndev) return OICC_ERR_NO_DEVICE;   // no CPU fallback
-  if (hipSetDevice(device_ordinal) != hipSuccess) return OICC_ERR_NO_DEVICE;
-  return OICC_OK;
-}
 
 }  // namespace
 
@@ -298,7 +291,7 @@ extern "C" int oicc_estimate_imu_to_camera_rotation(int32_t device_ordinal, int6
                                                     double gyro_bias[3], double* alignment_error, int32_t* iterations) {
   if (!t_vis_s || !q_vis_xyzw || !t_imu_s || !gyro_xyz || !q_imu_to_cam_xyzw || !time_offset_imu_to_cam || !gyro_bias || n_vis < 2 || n_imu < 2 || !(dt_imu > 0.0))
     return OICC_ERR_INVALID_ARG;
-  if (int rc = rot_select_device(device_ordinal)) return rc;
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
   RotationSeries S;
   if (int rc = prepare_rotation_series(n_vis, t_vis_s, q_vis_xyzw, n_imu, t_imu_s, gyro_xyz, dt_imu, &S)) return rc;
   RotationProbe P;
@@ -316,7 +309,6 @@ extern "C" int oicc_estimate_imu_to_camera_rotation(int32_t device_ordinal, int6
     c = b - (b - a) / gRatio; d = a + (b - a) / gRatio;
     ++iter;
   }
-  P.cleanup();
   if (!P.ok) return OICC_ERR_HIP;
   quat_from_rotation(R, q_imu_to_cam_xyzw);
   *time_offset_imu_to_cam = (b + a) / 2.0;
@@ -336,11 +328,10 @@ extern "C" int oicc_debug_rotation_probe(int32_t device_ordinal, int64_t n, cons
   if (!ts || !imu || !vis || !tds || !moments_out || !R_out || !b_out || !err_out || n < 2 || n > INT32_MAX || num_td < 1 || grid_cap < 0) return OICC_ERR_INVALID_ARG;
   for (int64_t i = 0; i < n; ++i) if (!std::isfinite(ts[i]) || (i > 0 && !(ts[i] > ts[i - 1]))) return OICC_ERR_INVALID_ARG;
   for (int32_t i = 0; i < num_td; ++i) if (!std::isfinite(tds[i])) return OICC_ERR_INVALID_ARG;
-  if (int rc = rot_select_device(device_ordinal)) return rc;
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
   RotationProbe P;
   if (int rc = P.upload(size_t(n), ts, imu, vis, grid_cap > 0 ? grid_cap : kRotGridCap, estimate_bias)) return rc;
   for (int32_t i = 0; i < num_td && P.ok; ++i) err_out[i] = P.solve_closed_form(tds[i], R_out + 9 * i, b_out + 3 * i, moments_out + 15 * i);
-  P.cleanup();
   return P.ok ? OICC_OK : OICC_ERR_HIP;
 }
 

@@ -13,6 +13,7 @@
 #include <mutex>
 #include <vector>
 #include "../../include/oicc_hip.h"
+#include "hip_resources.h"
 
 namespace {
 
@@ -57,23 +58,22 @@ constexpr int kSewGridCap = 1024;   // workgroups of the spectral reduction; lon
 // per data set (accelerometer, gyroscope) and plan creation costs milliseconds.
 struct SewSpectrum {
   int device = -1, dims = 0; int64_t n = 0, nh = 0;
-  double* d_sig = nullptr; hipfftDoubleComplex* d_spec = nullptr; double* pw = nullptr; double* acc = nullptr;
-  hipStream_t st = nullptr; hipfftHandle plan = 0; bool have_plan = false;
+  oicc::DevBuf<double> d_sig; oicc::DevBuf<hipfftDoubleComplex> d_spec; oicc::DevBuf<double> pw, acc;
+  oicc::Stream st; hipfftHandle plan = 0; bool have_plan = false;
   double bin_hz = 0.0; int evals = 0; int grid_cap = kSewGridCap;   // of the series loaded last
+  // the object outlives its resources (g_sew below): the plan first, then the stream, drained, then the buffers its work used
   void release() {
     if (have_plan) (void)hipfftDestroy(plan);
-    if (d_sig) (void)hipFree(d_sig); if (d_spec) (void)hipFree(d_spec); if (pw) (void)hipFree(pw); if (acc) (void)hipFree(acc);
-    if (st) (void)hipStreamDestroy(st);
-    *this = SewSpectrum();
+    have_plan = false; device = -1;
+    st.reset();
+    d_sig.release(); d_spec.release(); pw.release(); acc.release();
   }
   // buffers and plan for (device, dims, n): kept when they fit, rebuilt when they do not
   int bind(int device_ordinal, int dims_, int64_t n_) {
     if (device == device_ordinal && dims == dims_ && n == n_) return OICC_OK;
     release();
     const int64_t nh_ = n_ / 2 + 1;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&d_sig, sizeof(double) * dims_ * n_) != hipSuccess || hipMalloc(&d_spec, sizeof(hipfftDoubleComplex) * dims_ * nh_) != hipSuccess ||
-        hipMalloc(&pw, sizeof(double) * nh_) != hipSuccess || hipMalloc(&acc, 2 * sizeof(double)) != hipSuccess) { release(); return OICC_ERR_HIP; }
+    if (!st.create() || !d_sig.resize(size_t(dims_ * n_)) || !d_spec.resize(size_t(dims_ * nh_)) || !pw.resize(size_t(nh_)) || !acc.resize(2)) { release(); return OICC_ERR_HIP; }
     int len = int(n_);
     if (hipfftPlanMany(&plan, 1, &len, nullptr, 1, len, nullptr, 1, int(nh_), HIPFFT_D2Z, dims_) != HIPFFT_SUCCESS) { release(); return OICC_ERR_HIP; }
     have_plan = true;
@@ -84,17 +84,17 @@ struct SewSpectrum {
   // signal [dims, n] (host) -> pw[0 .. n/2] on the device
   int transform(const double* signal, double sample_rate, int cap) {
     bin_hz = sample_rate / double(n); evals = 0; grid_cap = cap;
-    if (hipMemcpyAsync(d_sig, signal, sizeof(double) * dims * n, hipMemcpyHostToDevice, st) != hipSuccess) { release(); return OICC_ERR_HIP; }
-    if (hipfftExecD2Z(plan, d_sig, d_spec) != HIPFFT_SUCCESS) { release(); return OICC_ERR_HIP; }
-    hipLaunchKernelGGL(sew_power_kernel, dim3(int((nh + 255) / 256)), dim3(256), 0, st, d_spec, dims, n, nh, pw);
+    if (hipMemcpyAsync(d_sig.p, signal, sizeof(double) * dims * n, hipMemcpyHostToDevice, st) != hipSuccess) { release(); return OICC_ERR_HIP; }
+    if (hipfftExecD2Z(plan, d_sig.p, d_spec.p) != HIPFFT_SUCCESS) { release(); return OICC_ERR_HIP; }
+    hipLaunchKernelGGL(sew_power_kernel, dim3(int((nh + 255) / 256)), dim3(256), 0, st, d_spec.p, dims, n, nh, pw.p);
     return OICC_OK;
   }
   // h[0] = sum_k pw[k], h[1] = sum_k pw[k] (1 - H(f_k, dt))^2
   bool sums(double dt, double h[2]) {
-    if (hipMemsetAsync(acc, 0, 2 * sizeof(double), st) != hipSuccess) return false;
+    if (hipMemsetAsync(acc.p, 0, 2 * sizeof(double), st) != hipSuccess) return false;
     int grid = int((nh + 255) / 256); if (grid > grid_cap) grid = grid_cap;
-    hipLaunchKernelGGL(sew_reduce_kernel, dim3(grid), dim3(256), 0, st, pw, nh, bin_hz, dt, acc);
-    if (hipMemcpyAsync(h, acc, 2 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return false;
+    hipLaunchKernelGGL(sew_reduce_kernel, dim3(grid), dim3(256), 0, st, pw.p, nh, bin_hz, dt, acc.p);
+    if (hipMemcpyAsync(h, acc.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return false;
     ++evals;
     return true;
   }
@@ -107,15 +107,8 @@ struct SewSpectrum {
   }
 };
 
-SewSpectrum g_sew;
+SewSpectrum& g_sew = *new SewSpectrum;   // never destroyed: at process exit the HIP runtime may be gone before a static's destructor runs
 std::mutex g_sew_mutex;   // one call at a time: concurrent callers (other devices, other sizes) would rebuild each other's plan mid-use
-
-int sew_select_device(int32_t device_ordinal) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device_ordinal < 0 || device_ordinal >= ndev) return OICC_ERR_NO_DEVICE;   // no CPU fallback
-  if (hipSetDevice(device_ordinal) != hipSuccess) return OICC_ERR_NO_DEVICE;
-  return OICC_OK;
-}
 
 }  // namespace
 
@@ -123,7 +116,7 @@ extern "C" int oicc_sew_knot_spacing_and_variance(int32_t device_ordinal, int32_
                                                   const double* times, double quality, double min_dt, double max_dt,
                                                   double* dt_out, double* var_out, int32_t* num_evaluations) {
   if (!signal || !times || !dt_out || !var_out || dims < 1 || n < 8 || !(quality > 0.0 && quality < 1.0)) return OICC_ERR_INVALID_ARG;
-  if (int rc = sew_select_device(device_ordinal)) return rc;
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
   // sample rate = 1 / mean(diff(times))  (sew.py:144)
   const double span = times[n - 1] - times[0];
   if (!(span > 0.0)) return OICC_ERR_INVALID_ARG;
@@ -211,14 +204,14 @@ extern "C" int oicc_debug_sew_spectrum(int32_t device_ordinal, int32_t dims, int
   if (!signal || !pw_out || dims < 1 || n < 8 || n > INT32_MAX || !(sample_rate > 0.0) || !std::isfinite(sample_rate) || num_dt < 0 || grid_cap < 0 ||
       (num_dt > 0 && (!dts || !sums_out))) return OICC_ERR_INVALID_ARG;
   for (int32_t i = 0; i < num_dt; ++i) if (!(dts[i] > 0.0) || !std::isfinite(dts[i])) return OICC_ERR_INVALID_ARG;
-  if (int rc = sew_select_device(device_ordinal)) return rc;
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
   std::lock_guard<std::mutex> lock(g_sew_mutex);
   SewSpectrum& D = g_sew;
   int rc = D.bind(device_ordinal, dims, n);
   if (rc != OICC_OK) return rc;
   rc = D.transform(signal, sample_rate, grid_cap > 0 ? grid_cap : kSewGridCap);
   if (rc != OICC_OK) return rc;
-  if (hipMemcpyAsync(pw_out, D.pw, sizeof(double) * D.nh, hipMemcpyDeviceToHost, D.st) != hipSuccess || hipStreamSynchronize(D.st) != hipSuccess) return OICC_ERR_HIP;
+  if (hipMemcpyAsync(pw_out, D.pw.p, sizeof(double) * D.nh, hipMemcpyDeviceToHost, D.st) != hipSuccess || hipStreamSynchronize(D.st) != hipSuccess) return OICC_ERR_HIP;
   for (int32_t i = 0; i < num_dt; ++i) if (!D.sums(dts[i], sums_out + 2 * i)) return OICC_ERR_HIP;
   return OICC_OK;
 }

@@ -27,6 +27,7 @@
 #include <limits>
 #include <vector>
 #include "../../include/oicc_hip.h"
+#include "hip_resources.h"
 #include "lm_small.h"
 
 namespace {
@@ -376,14 +377,7 @@ void data_variance(const double* x, int s, int e, double v[3]) {
 }
 int normalized_win(int w) { if (w < 11) w = 11; if (!(w % 2)) w++; return w; }
 
-#define SIMU_TRY(expr) do { if ((expr) != hipSuccess) { rc = OICC_ERR_HIP; goto done; } } while (0)
-
-int select_device(int32_t dev) {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || dev < 0 || dev >= ndev) return OICC_ERR_NO_DEVICE;   // no CPU fallback
-  if (hipSetDevice(dev) != hipSuccess) return OICC_ERR_NO_DEVICE;
-  return OICC_OK;
-}
+using oicc::select_device;
 
 // The detector on device memory d_acc [n][3]: per threshold the interval list.  ms: device time.
 int run_detector(const double* d_acc, int64_t n, int w, int nt, const double* th, std::vector<std::vector<int32_t>>* out,
@@ -393,68 +387,64 @@ int run_detector(const double* d_acc, int64_t n, int w, int nt, const double* th
   if (w >= n) { if (norms_host) for (int64_t i = 0; i < n; ++i) norms_host[i] = std::nan(""); return OICC_OK; }   // .cc:119
   const int64_t M = n - 2 * int64_t(h), nb = (M + kThreads - 1) / kThreads;
   const int64_t cap = (M + 1) / 2 + 1;
-  int rc = OICC_OK;
-  double *d_norm = nullptr, *d_th = nullptr;
-  int32_t *d_cnt = nullptr, *d_tot = nullptr, *d_st = nullptr, *d_en = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  oicc::DevBuf<double> d_norm, d_th;
+  oicc::DevBuf<int32_t> d_cnt, d_tot, d_st, d_en;
+  oicc::Event e0, e1;
   std::vector<int32_t> tot(size_t(nt), 0);
+  oicc::DrainOnExit drain{st};      // st is the caller's: no way out of here leaves work on it that uses the buffers above
   float f = 0.0f;
   const size_t lds = sizeof(double) * 3 * size_t(kThreads + 2 * h);
-  SIMU_TRY(hipEventCreate(&e0)); SIMU_TRY(hipEventCreate(&e1));
-  SIMU_TRY(hipMalloc(&d_norm, sizeof(double) * n)); SIMU_TRY(hipMalloc(&d_th, sizeof(double) * nt));
-  SIMU_TRY(hipMalloc(&d_cnt, sizeof(int32_t) * nb * nt)); SIMU_TRY(hipMalloc(&d_tot, sizeof(int32_t) * nt));
-  SIMU_TRY(hipMalloc(&d_st, sizeof(int32_t) * cap * nt)); SIMU_TRY(hipMalloc(&d_en, sizeof(int32_t) * cap * nt));
-  SIMU_TRY(hipMemcpyAsync(d_th, th, sizeof(double) * nt, hipMemcpyHostToDevice, st));
-  SIMU_TRY(hipEventRecord(e0, st));
-  hipLaunchKernelGGL(simu_norm_kernel, dim3(unsigned(nb)), dim3(kThreads), lds, st, d_acc, n, h, d_norm);
-  hipLaunchKernelGGL(simu_edge_count_kernel, dim3(unsigned(nb)), dim3(kThreads), 0, st, d_norm, n, h, d_th, nt, d_cnt);
-  hipLaunchKernelGGL(simu_edge_scan_kernel, dim3(1), dim3(64), 0, st, d_cnt, nb, nt, d_tot);
-  hipLaunchKernelGGL(simu_edge_write_kernel, dim3(unsigned(nb)), dim3(kThreads), 0, st, d_norm, n, h, d_th, nt, d_cnt, int32_t(cap), d_st, d_en);
-  SIMU_TRY(hipGetLastError());
-  SIMU_TRY(hipEventRecord(e1, st));
-  SIMU_TRY(hipMemcpyAsync(tot.data(), d_tot, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
-  SIMU_TRY(hipStreamSynchronize(st));
-  SIMU_TRY(hipEventElapsedTime(&f, e0, e1));
+  OICC_HIP_TRY(e0.create()); OICC_HIP_TRY(e1.create());
+  OICC_HIP_TRY(d_norm.resize(size_t(n))); OICC_HIP_TRY(d_th.resize(size_t(nt)));
+  OICC_HIP_TRY(d_cnt.resize(size_t(nb * nt))); OICC_HIP_TRY(d_tot.resize(size_t(nt)));
+  OICC_HIP_TRY(d_st.resize(size_t(cap * nt))); OICC_HIP_TRY(d_en.resize(size_t(cap * nt)));
+  OICC_HIP_TRY(hipMemcpyAsync(d_th.p, th, sizeof(double) * nt, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipEventRecord(e0, st));
+  hipLaunchKernelGGL(simu_norm_kernel, dim3(unsigned(nb)), dim3(kThreads), lds, st, d_acc, n, h, d_norm.p);
+  hipLaunchKernelGGL(simu_edge_count_kernel, dim3(unsigned(nb)), dim3(kThreads), 0, st, d_norm.p, n, h, d_th.p, nt, d_cnt.p);
+  hipLaunchKernelGGL(simu_edge_scan_kernel, dim3(1), dim3(64), 0, st, d_cnt.p, nb, nt, d_tot.p);
+  hipLaunchKernelGGL(simu_edge_write_kernel, dim3(unsigned(nb)), dim3(kThreads), 0, st, d_norm.p, n, h, d_th.p, nt, d_cnt.p, int32_t(cap), d_st.p, d_en.p);
+  OICC_HIP_TRY(hipGetLastError());
+  OICC_HIP_TRY(hipEventRecord(e1, st));
+  OICC_HIP_TRY(hipMemcpyAsync(tot.data(), d_tot.p, sizeof(int32_t) * nt, hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipStreamSynchronize(st));
+  OICC_HIP_TRY(hipEventElapsedTime(&f, e0, e1));
   if (ms) *ms += double(f);
   for (int t = 0; t < nt; ++t) {
     const int64_t k = std::min<int64_t>(tot[size_t(t)], cap);
     std::vector<int32_t> s(static_cast<size_t>(k)), e(static_cast<size_t>(k));
     if (k > 0) {
-      SIMU_TRY(hipMemcpy(s.data(), d_st + int64_t(t) * cap, sizeof(int32_t) * k, hipMemcpyDeviceToHost));
-      SIMU_TRY(hipMemcpy(e.data(), d_en + int64_t(t) * cap, sizeof(int32_t) * k, hipMemcpyDeviceToHost));
+      OICC_HIP_TRY(hipMemcpy(s.data(), d_st.p + int64_t(t) * cap, sizeof(int32_t) * k, hipMemcpyDeviceToHost));
+      OICC_HIP_TRY(hipMemcpy(e.data(), d_en.p + int64_t(t) * cap, sizeof(int32_t) * k, hipMemcpyDeviceToHost));
     }
     auto& o = (*out)[size_t(t)];
     o.resize(size_t(2 * k));
     for (int64_t j = 0; j < k; ++j) { o[size_t(2 * j)] = s[size_t(j)]; o[size_t(2 * j + 1)] = e[size_t(j)]; }
   }
   if (norms_host) {
-    SIMU_TRY(hipMemcpy(norms_host + h, d_norm + h, sizeof(double) * M, hipMemcpyDeviceToHost));
+    OICC_HIP_TRY(hipMemcpy(norms_host + h, d_norm.p + h, sizeof(double) * M, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < h; ++i) { norms_host[i] = std::nan(""); norms_host[n - 1 - i] = std::nan(""); }
   }
-done:
-  for (void* q : {(void*)d_norm, (void*)d_th, (void*)d_cnt, (void*)d_tot, (void*)d_st, (void*)d_en}) if (q) (void)hipFree(q);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  return rc;
+  return OICC_OK;
 }
 
 // Gyro blocks on the device for repeated evaluation: samples, timestamps and the block table stay resident.
 struct GyroDev {
-  double *t = nullptr, *w = nullptr, *res = nullptr, *jac = nullptr;
-  GyroBlock* blk = nullptr;
+  oicc::DevBuf<double> t, w, res, jac;
+  oicc::DevBuf<GyroBlock> blk;
   int nb = 0, np = 9, optimize_bias = 0;
   double gyro_dt = -1.0, ms = 0.0;
-  hipStream_t st = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  oicc::Event e0, e1;
+  oicc::Stream st;      // behind the buffers and events (hip_resources.h)
   int init(const double* t_s, const double* gyro, int64_t n, const std::vector<GyroBlock>& blocks, int opt_bias, double dt) {
     nb = int(blocks.size()); optimize_bias = opt_bias; np = opt_bias ? 12 : 9; gyro_dt = dt;
-    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess || hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess ||
-        hipMalloc(&t, sizeof(double) * n) != hipSuccess || hipMalloc(&w, sizeof(double) * 3 * n) != hipSuccess ||
-        hipMalloc(&res, sizeof(double) * 3 * std::max(nb, 1)) != hipSuccess || hipMalloc(&jac, sizeof(double) * 3 * std::max(nb, 1) * np) != hipSuccess ||
-        hipMalloc(&blk, sizeof(GyroBlock) * std::max(nb, 1)) != hipSuccess ||
-        hipMemcpy(t, t_s, sizeof(double) * n, hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(w, gyro, sizeof(double) * 3 * n, hipMemcpyHostToDevice) != hipSuccess ||
-        (nb > 0 && hipMemcpy(blk, blocks.data(), sizeof(GyroBlock) * nb, hipMemcpyHostToDevice) != hipSuccess)) return OICC_ERR_HIP;
+    OICC_HIP_TRY(st.create()); OICC_HIP_TRY(e0.create()); OICC_HIP_TRY(e1.create());
+    OICC_HIP_TRY(t.resize(size_t(n))); OICC_HIP_TRY(w.resize(3 * size_t(n)));
+    OICC_HIP_TRY(res.resize(3 * size_t(std::max(nb, 1)))); OICC_HIP_TRY(jac.resize(3 * size_t(std::max(nb, 1)) * np));
+    OICC_HIP_TRY(blk.resize(size_t(std::max(nb, 1))));
+    OICC_HIP_TRY(hipMemcpy(t.p, t_s, sizeof(double) * n, hipMemcpyHostToDevice));
+    OICC_HIP_TRY(hipMemcpy(w.p, gyro, sizeof(double) * 3 * n, hipMemcpyHostToDevice));
+    if (nb > 0) OICC_HIP_TRY(hipMemcpy(blk.p, blocks.data(), sizeof(GyroBlock) * nb, hipMemcpyHostToDevice));
     return OICC_OK;
   }
   // r [3 nb], J [3 nb][np]
@@ -463,21 +453,15 @@ struct GyroDev {
     GyroParams gp;
     for (int k = 0; k < 12; ++k) gp.p[k] = p[k];
     if (hipEventRecord(e0, st) != hipSuccess) return OICC_ERR_HIP;
-    hipLaunchKernelGGL(simu_gyro_kernel, dim3(unsigned(nb), unsigned(np)), dim3(kThreads), 0, st, t, w, blk, gp, optimize_bias, gyro_dt, np, res, jac);
+    hipLaunchKernelGGL(simu_gyro_kernel, dim3(unsigned(nb), unsigned(np)), dim3(kThreads), 0, st, t.p, w.p, blk.p, gp, optimize_bias, gyro_dt, np, res.p, jac.p);
     if (hipGetLastError() != hipSuccess || hipEventRecord(e1, st) != hipSuccess) return OICC_ERR_HIP;
     r->resize(size_t(3 * nb)); J->resize(size_t(3 * nb * np));
-    if (hipMemcpyAsync(r->data(), res, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(J->data(), jac, sizeof(double) * 3 * nb * np, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) return OICC_ERR_HIP;
+    const bool copied = hipMemcpyAsync(r->data(), res.p, sizeof(double) * 3 * nb, hipMemcpyDeviceToHost, st) == hipSuccess &&
+                        hipMemcpyAsync(J->data(), jac.p, sizeof(double) * 3 * nb * np, hipMemcpyDeviceToHost, st) == hipSuccess;
+    if (hipStreamSynchronize(st) != hipSuccess || !copied) return OICC_ERR_HIP;      // r and J are the caller's: nothing writes them after the return
     float f = 0.0f;
     if (hipEventElapsedTime(&f, e0, e1) == hipSuccess) ms += double(f);
     return OICC_OK;
-  }
-  ~GyroDev() {
-    for (void* q : {(void*)t, (void*)w, (void*)res, (void*)jac, (void*)blk}) if (q) (void)hipFree(q);
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    if (st) (void)hipStreamDestroy(st);
   }
 };
 
@@ -524,17 +508,14 @@ extern "C" int oicc_static_imu_intervals(int32_t device_ordinal, int64_t n, cons
     return OICC_ERR_INVALID_ARG;
   const int w = normalized_win(win_size);
   if (w > 2 * kMaxHalf + 1 || !all_finite(acc, 3 * n)) return OICC_ERR_INVALID_ARG;
-  int rc = select_device(device_ordinal);
-  if (rc != OICC_OK) return rc;
-  double* d_acc = nullptr;
-  hipStream_t st = nullptr;
+  if (int rc = select_device(device_ordinal)) return rc;
+  oicc::DevBuf<double> d_acc;
+  oicc::Stream st;
   std::vector<std::vector<int32_t>> iv;
   double ms = 0.0;
-  SIMU_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  SIMU_TRY(hipMalloc(&d_acc, sizeof(double) * 3 * n));
-  SIMU_TRY(hipMemcpyAsync(d_acc, acc, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
-  rc = run_detector(d_acc, n, w, num_thresholds, thresholds, &iv, norms, &ms, st);
-  if (rc != OICC_OK) goto done;
+  OICC_HIP_TRY(st.create());
+  OICC_HIP_TRY(d_acc.upload(acc, 3 * size_t(n), st));
+  if (int rc = run_detector(d_acc.p, n, w, num_thresholds, thresholds, &iv, norms, &ms, st)) return rc;
   for (int t = 0; t < num_thresholds; ++t) {
     const auto& o = iv[size_t(t)];
     counts[t] = int32_t(o.size() / 2);
@@ -542,35 +523,29 @@ extern "C" int oicc_static_imu_intervals(int32_t device_ordinal, int64_t n, cons
     std::memcpy(intervals + int64_t(t) * 2 * capacity, o.data(), sizeof(int32_t) * 2 * k);
   }
   if (device_ms) *device_ms = ms;
-done:
-  if (d_acc) (void)hipFree(d_acc);
-  if (st) (void)hipStreamDestroy(st);
-  return rc;
+  return OICC_OK;
 }
 
 extern "C" int oicc_static_imu_eval_acc(int32_t device_ordinal, int64_t num, const double* samples, double g_mag, const double* params,
                                         double* residuals, double* jacobian, double* cost, double* gram, double* gradient) {
   if (!samples || !params || !cost || !gram || !gradient || num < 1 || num > INT32_MAX) return OICC_ERR_INVALID_ARG;
-  int rc = select_device(device_ordinal);
-  if (rc != OICC_OK) return rc;
-  double *d_s = nullptr, *d_p = nullptr, *d_r = nullptr, *d_j = nullptr, *d_o = nullptr;
+  if (int rc = select_device(device_ordinal)) return rc;
+  oicc::DevBuf<double> d_s, d_p, d_r, d_j, d_o;      // the null stream runs the kernel, and the blocking copies behind it wait for it
   double out[10 + kAccNH];
-  SIMU_TRY(hipMalloc(&d_s, sizeof(double) * 3 * num)); SIMU_TRY(hipMalloc(&d_p, sizeof(double) * 9));
-  SIMU_TRY(hipMalloc(&d_r, sizeof(double) * num)); SIMU_TRY(hipMalloc(&d_j, sizeof(double) * 9 * num));
-  SIMU_TRY(hipMalloc(&d_o, sizeof(out)));
-  SIMU_TRY(hipMemcpy(d_s, samples, sizeof(double) * 3 * num, hipMemcpyHostToDevice));
-  SIMU_TRY(hipMemcpy(d_p, params, sizeof(double) * 9, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(simu_acc_eval_kernel, dim3(1), dim3(kThreads), 0, 0, d_s, num, g_mag, d_p, d_r, d_j, d_o);
-  SIMU_TRY(hipGetLastError());
-  SIMU_TRY(hipMemcpy(out, d_o, sizeof(out), hipMemcpyDeviceToHost));
-  if (residuals) SIMU_TRY(hipMemcpy(residuals, d_r, sizeof(double) * num, hipMemcpyDeviceToHost));
-  if (jacobian) SIMU_TRY(hipMemcpy(jacobian, d_j, sizeof(double) * 9 * num, hipMemcpyDeviceToHost));
+  OICC_HIP_TRY(d_s.resize(3 * size_t(num))); OICC_HIP_TRY(d_p.resize(9));
+  OICC_HIP_TRY(d_r.resize(size_t(num))); OICC_HIP_TRY(d_j.resize(9 * size_t(num)));
+  OICC_HIP_TRY(d_o.resize(10 + kAccNH));
+  OICC_HIP_TRY(hipMemcpy(d_s.p, samples, sizeof(double) * 3 * num, hipMemcpyHostToDevice));
+  OICC_HIP_TRY(hipMemcpy(d_p.p, params, sizeof(double) * 9, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(simu_acc_eval_kernel, dim3(1), dim3(kThreads), 0, 0, d_s.p, num, g_mag, d_p.p, d_r.p, d_j.p, d_o.p);
+  OICC_HIP_TRY(hipGetLastError());
+  OICC_HIP_TRY(hipMemcpy(out, d_o.p, sizeof(out), hipMemcpyDeviceToHost));
+  if (residuals) OICC_HIP_TRY(hipMemcpy(residuals, d_r.p, sizeof(double) * num, hipMemcpyDeviceToHost));
+  if (jacobian) OICC_HIP_TRY(hipMemcpy(jacobian, d_j.p, sizeof(double) * 9 * num, hipMemcpyDeviceToHost));
   *cost = out[0];
   for (int k = 0; k < 9; ++k) gradient[k] = out[1 + k];
   unpack_gram(out + 10, 9, gram);
-done:
-  for (void* q : {(void*)d_s, (void*)d_p, (void*)d_r, (void*)d_j, (void*)d_o}) if (q) (void)hipFree(q);
-  return rc;
+  return OICC_OK;
 }
 
 extern "C" int oicc_static_imu_eval_gyro(int32_t device_ordinal, int64_t n, const double* t_s, const double* gyro, int32_t num_blocks,
@@ -605,28 +580,12 @@ extern "C" int oicc_static_imu_eval_gyro(int32_t device_ordinal, int64_t n, cons
   return OICC_OK;
 }
 
-extern "C" int oicc_static_imu_calibrate(int32_t device_ordinal, int64_t n, const double* t_s, const double* acc, const double* gyro,
-                                         const oicc_static_imu_options* opt_in, double* acc_params, double* gyro_params,
-                                         oicc_static_imu_report* report) {
-  oicc_static_imu_options opt{9.81, 30.0, -1.0, 100, 12, 101, 0, 0, 0};   // StaticImuCalibrator() (.cc:44-52)
-  if (opt_in) opt = *opt_in;
-  if (!t_s || !acc || !gyro || !acc_params || !gyro_params || n < 3 || n > INT32_MAX || !(opt.init_interval_duration_s > 0) ||
-      opt.interval_n_samples < 1 || opt.min_num_intervals < 0)
-    return OICC_ERR_INVALID_ARG;   // InitialInterval throws for these (imu_data_interval.h)
-  const int w = normalized_win(opt.win_size);
-  if (w > 2 * kMaxHalf + 1 || !all_finite(acc, 3 * n) || !all_finite(gyro, 3 * n) || !all_finite(t_s, n)) return OICC_ERR_INVALID_ARG;
-  int rc = select_device(device_ordinal);
-  if (rc != OICC_OK) return rc;
-  oicc_static_imu_report rep;
-  std::memset(&rep, 0, sizeof(rep));
-  rep.th_mult = -1;
-  for (int t = 0; t < kMaxTh; ++t) { rep.acc_final_cost[t] = std::nan(""); rep.acc_termination[t] = OICC_SIMU_TERM_SKIPPED; }
-  rep.gyro_termination = OICC_SIMU_TERM_SKIPPED;
-  rep.gyro_initial_cost = rep.gyro_final_cost = std::nan("");
-  const double default_acc[9] = {0, 0, 0, 1, 1, 1, 0, 0, 0};
-  const double default_gyro[12] = {0, 0, 0, 0, 0, 0, 1, 1, 1, 0, 0, 0};
-  std::memcpy(acc_params, default_acc, sizeof(default_acc));
-  std::memcpy(gyro_params, default_gyro, sizeof(default_gyro));
+namespace {
+
+// The calibration behind oicc_static_imu_calibrate's argument checks; rep and the two parameter sets hold their defaults.  The entry
+// writes the report whatever this returns.
+int calibrate(int64_t n, const double* t_s, const double* acc, const double* gyro, const oicc_static_imu_options& opt, int w,
+              double* acc_params, double* gyro_params, oicc_static_imu_report& rep) {
   const oicc::BaLmOptions lmo = oicc::ceres_default_lm_options();
 
   // CalibrateAcc (.cc:54-186): initial bias and threshold
@@ -643,11 +602,10 @@ extern "C" int oicc_static_imu_calibrate(int32_t device_ordinal, int64_t n, cons
   double th[kMaxTh];
   for (int t = 0; t < kMaxTh; ++t) th[t] = double(t + 1) * norm_th;
 
-  double* d_acc = nullptr, *d_samp = nullptr, *d_x0 = nullptr, *d_x = nullptr, *d_cost = nullptr;
-  AccProblem* d_prob = nullptr;
-  int32_t *d_it = nullptr, *d_term = nullptr;
-  hipStream_t st = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  oicc::DevBuf<double> d_acc, d_samp, d_x0, d_x, d_cost;
+  oicc::DevBuf<AccProblem> d_prob;
+  oicc::DevBuf<int32_t> d_it, d_term;
+  oicc::Event e0, e1;
   std::vector<std::vector<int32_t>> iv;
   std::vector<std::vector<int32_t>> valid(kMaxTh);   // extracted intervals per threshold, (start, end) pairs
   std::vector<double> packed;
@@ -662,13 +620,12 @@ extern "C" int oicc_static_imu_calibrate(int32_t device_ordinal, int64_t n, cons
   std::vector<int32_t> its, terms;
   int best = -1;
   double min_cost = std::numeric_limits<double>::max();
+  oicc::Stream st;      // behind the buffers, the events and the host vectors its copies fill (hip_resources.h)
 
-  SIMU_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  SIMU_TRY(hipEventCreate(&e0)); SIMU_TRY(hipEventCreate(&e1));
-  SIMU_TRY(hipMalloc(&d_acc, sizeof(double) * 3 * n));
-  SIMU_TRY(hipMemcpyAsync(d_acc, acc, sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
-  rc = run_detector(d_acc, n, w, kMaxTh, th, &iv, nullptr, &rep.ms_detector, st);
-  if (rc != OICC_OK) goto done;
+  OICC_HIP_TRY(st.create());
+  OICC_HIP_TRY(e0.create()); OICC_HIP_TRY(e1.create());
+  OICC_HIP_TRY(d_acc.upload(acc, 3 * size_t(n), st));
+  if (int rc = run_detector(d_acc.p, n, w, kMaxTh, th, &iv, nullptr, &rep.ms_detector, st)) return rc;
   // ExtractIntervalsSamples (imu_data_interval.cc:64-109), acc_use_means_ false: the first ns samples of every interval
   // with at least ns samples; true: the interval's mean
   for (int t = 0; t < kMaxTh; ++t) {
@@ -688,23 +645,23 @@ extern "C" int oicc_static_imu_calibrate(int32_t device_ordinal, int64_t n, cons
   }
   np_acc = int(probs.size());
   if (np_acc > 0) {
-    SIMU_TRY(hipMalloc(&d_samp, sizeof(double) * packed.size())); SIMU_TRY(hipMalloc(&d_prob, sizeof(AccProblem) * np_acc));
-    SIMU_TRY(hipMalloc(&d_x0, sizeof(double) * 9)); SIMU_TRY(hipMalloc(&d_x, sizeof(double) * 9 * np_acc));
-    SIMU_TRY(hipMalloc(&d_cost, sizeof(double) * np_acc)); SIMU_TRY(hipMalloc(&d_it, sizeof(int32_t) * np_acc)); SIMU_TRY(hipMalloc(&d_term, sizeof(int32_t) * np_acc));
-    SIMU_TRY(hipMemcpyAsync(d_samp, packed.data(), sizeof(double) * packed.size(), hipMemcpyHostToDevice, st));
-    SIMU_TRY(hipMemcpyAsync(d_prob, probs.data(), sizeof(AccProblem) * np_acc, hipMemcpyHostToDevice, st));
-    SIMU_TRY(hipMemcpyAsync(d_x0, x0, sizeof(double) * 9, hipMemcpyHostToDevice, st));
-    SIMU_TRY(hipEventRecord(e0, st));
-    hipLaunchKernelGGL(simu_acc_lm_kernel, dim3(unsigned(np_acc)), dim3(kThreads), 0, st, d_samp, d_prob, opt.gravity_magnitude, d_x0, lmo, d_x, d_cost, d_it, d_term);
-    SIMU_TRY(hipGetLastError());
-    SIMU_TRY(hipEventRecord(e1, st));
+    OICC_HIP_TRY(d_samp.resize(packed.size())); OICC_HIP_TRY(d_prob.resize(size_t(np_acc)));
+    OICC_HIP_TRY(d_x0.resize(9)); OICC_HIP_TRY(d_x.resize(9 * size_t(np_acc)));
+    OICC_HIP_TRY(d_cost.resize(size_t(np_acc))); OICC_HIP_TRY(d_it.resize(size_t(np_acc))); OICC_HIP_TRY(d_term.resize(size_t(np_acc)));
+    OICC_HIP_TRY(hipMemcpyAsync(d_samp.p, packed.data(), sizeof(double) * packed.size(), hipMemcpyHostToDevice, st));
+    OICC_HIP_TRY(hipMemcpyAsync(d_prob.p, probs.data(), sizeof(AccProblem) * np_acc, hipMemcpyHostToDevice, st));
+    OICC_HIP_TRY(hipMemcpyAsync(d_x0.p, x0, sizeof(double) * 9, hipMemcpyHostToDevice, st));
+    OICC_HIP_TRY(hipEventRecord(e0, st));
+    hipLaunchKernelGGL(simu_acc_lm_kernel, dim3(unsigned(np_acc)), dim3(kThreads), 0, st, d_samp.p, d_prob.p, opt.gravity_magnitude, d_x0.p, lmo, d_x.p, d_cost.p, d_it.p, d_term.p);
+    OICC_HIP_TRY(hipGetLastError());
+    OICC_HIP_TRY(hipEventRecord(e1, st));
     xs.resize(size_t(9 * np_acc)); costs.resize(size_t(np_acc)); its.resize(size_t(np_acc)); terms.resize(size_t(np_acc));
-    SIMU_TRY(hipMemcpyAsync(xs.data(), d_x, sizeof(double) * xs.size(), hipMemcpyDeviceToHost, st));
-    SIMU_TRY(hipMemcpyAsync(costs.data(), d_cost, sizeof(double) * costs.size(), hipMemcpyDeviceToHost, st));
-    SIMU_TRY(hipMemcpyAsync(its.data(), d_it, sizeof(int32_t) * its.size(), hipMemcpyDeviceToHost, st));
-    SIMU_TRY(hipMemcpyAsync(terms.data(), d_term, sizeof(int32_t) * terms.size(), hipMemcpyDeviceToHost, st));
-    SIMU_TRY(hipStreamSynchronize(st));
-    SIMU_TRY(hipEventElapsedTime(&f, e0, e1));
+    OICC_HIP_TRY(hipMemcpyAsync(xs.data(), d_x.p, sizeof(double) * xs.size(), hipMemcpyDeviceToHost, st));
+    OICC_HIP_TRY(hipMemcpyAsync(costs.data(), d_cost.p, sizeof(double) * costs.size(), hipMemcpyDeviceToHost, st));
+    OICC_HIP_TRY(hipMemcpyAsync(its.data(), d_it.p, sizeof(int32_t) * its.size(), hipMemcpyDeviceToHost, st));
+    OICC_HIP_TRY(hipMemcpyAsync(terms.data(), d_term.p, sizeof(int32_t) * terms.size(), hipMemcpyDeviceToHost, st));
+    OICC_HIP_TRY(hipStreamSynchronize(st));
+    OICC_HIP_TRY(hipEventElapsedTime(&f, e0, e1));
     rep.ms_acc = double(f);
   }
   for (int q = 0; q < np_acc; ++q) {
@@ -712,7 +669,7 @@ extern "C" int oicc_static_imu_calibrate(int32_t device_ordinal, int64_t n, cons
     rep.acc_final_cost[t] = costs[size_t(q)]; rep.acc_iterations[t] = its[size_t(q)]; rep.acc_termination[t] = terms[size_t(q)];
     if (costs[size_t(q)] < min_cost) { min_cost = costs[size_t(q)]; best = q; }   // strictly smaller: ties keep the earlier
   }
-  if (best < 0) { rc = OICC_SIMU_ACC_IMPOSSIBLE; goto done; }
+  if (best < 0) return OICC_SIMU_ACC_IMPOSSIBLE;
   rep.th_mult = prob_th[size_t(best)] + 1;
   std::memcpy(acc_params, xs.data() + 9 * best, sizeof(double) * 9);
 
@@ -758,30 +715,51 @@ extern "C" int oicc_static_imu_calibrate(int32_t device_ordinal, int64_t n, cons
     }
     rep.gyro_num_blocks = int(blocks.size());
     GyroDev dev;
-    rc = dev.init(t_s, gw.data(), n, blocks, opt.optimize_gyro_bias ? 1 : 0, opt.gyro_dt);
-    if (rc != OICC_OK) goto done;
+    if (int rc = dev.init(t_s, gw.data(), n, blocks, opt.optimize_gyro_bias ? 1 : 0, opt.gyro_dt)) return rc;
     double x[12] = {0, 0, 0, 0, 0, 0, 1, 1, 1, 0, 0, 0};   // init_gyro_calib_ (default triad), bias terms 0
     int it = 0, term = 0;
     double fc = 0.0;
     {
       std::vector<double> r0, J0;
-      rc = dev.eval(x, &r0, &J0);
-      if (rc != OICC_OK) goto done;
+      if (int rc = dev.eval(x, &r0, &J0)) return rc;
       double c0 = 0.0; for (double v : r0) c0 += v * v;
       rep.gyro_initial_cost = 0.5 * c0;
     }
+    int rc = OICC_OK;
     if (opt.optimize_gyro_bias) { GyroEval<12> ev{&dev}; term = oicc::small_lm<12>(lmo, x, ev, &it, &fc); rc = ev.status; }
     else { GyroEval<9> ev{&dev}; term = oicc::small_lm<9>(lmo, x, ev, &it, &fc); rc = ev.status; }
-    if (rc != OICC_OK) goto done;
+    if (rc != OICC_OK) return rc;
     rep.gyro_iterations = it; rep.gyro_termination = term; rep.gyro_final_cost = fc; rep.ms_gyro = dev.ms;
     for (int k = 0; k < 9; ++k) gyro_params[k] = x[k];
     for (int c = 0; c < 3; ++c) gyro_params[9 + c] = gb[c] + (opt.optimize_gyro_bias ? x[9 + c] : 0.0);
   }
-done:
-  for (void* q : {(void*)d_acc, (void*)d_samp, (void*)d_x0, (void*)d_x, (void*)d_cost, (void*)d_prob, (void*)d_it, (void*)d_term}) if (q) (void)hipFree(q);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (st) (void)hipStreamDestroy(st);
+  return OICC_OK;
+}
+
+}  // namespace
+
+extern "C" int oicc_static_imu_calibrate(int32_t device_ordinal, int64_t n, const double* t_s, const double* acc, const double* gyro,
+                                         const oicc_static_imu_options* opt_in, double* acc_params, double* gyro_params,
+                                         oicc_static_imu_report* report) {
+  oicc_static_imu_options opt{9.81, 30.0, -1.0, 100, 12, 101, 0, 0, 0};   // StaticImuCalibrator() (.cc:44-52)
+  if (opt_in) opt = *opt_in;
+  if (!t_s || !acc || !gyro || !acc_params || !gyro_params || n < 3 || n > INT32_MAX || !(opt.init_interval_duration_s > 0) ||
+      opt.interval_n_samples < 1 || opt.min_num_intervals < 0)
+    return OICC_ERR_INVALID_ARG;   // InitialInterval throws for these (imu_data_interval.h)
+  const int w = normalized_win(opt.win_size);
+  if (w > 2 * kMaxHalf + 1 || !all_finite(acc, 3 * n) || !all_finite(gyro, 3 * n) || !all_finite(t_s, n)) return OICC_ERR_INVALID_ARG;
+  if (int rc = select_device(device_ordinal)) return rc;
+  oicc_static_imu_report rep;
+  std::memset(&rep, 0, sizeof(rep));
+  rep.th_mult = -1;
+  for (int t = 0; t < kMaxTh; ++t) { rep.acc_final_cost[t] = std::nan(""); rep.acc_termination[t] = OICC_SIMU_TERM_SKIPPED; }
+  rep.gyro_termination = OICC_SIMU_TERM_SKIPPED;
+  rep.gyro_initial_cost = rep.gyro_final_cost = std::nan("");
+  const double default_acc[9] = {0, 0, 0, 1, 1, 1, 0, 0, 0};
+  const double default_gyro[12] = {0, 0, 0, 0, 0, 0, 1, 1, 1, 0, 0, 0};
+  std::memcpy(acc_params, default_acc, sizeof(default_acc));
+  std::memcpy(gyro_params, default_gyro, sizeof(default_gyro));
+  const int rc = calibrate(n, t_s, acc, gyro, opt, w, acc_params, gyro_params, rep);
   if (report) *report = rep;
   if (rc == OICC_SIMU_ACC_IMPOSSIBLE) { std::memcpy(acc_params, default_acc, sizeof(default_acc)); std::memcpy(gyro_params, default_gyro, sizeof(default_gyro)); }
   return rc;

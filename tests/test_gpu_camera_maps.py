@@ -155,6 +155,17 @@ def test_rectified_pinhole_equals_restatement_and_balance_one_loses_pixels():
 
 
 # ---------------------------------------------------------------- remap
+# (frames, batch) beside the five frames at batch 2: both slots recycled more than once; no short batch; one slot alone, the
+# batch as long as the frames and longer.  The first `frames` of the five frames, held to the batch-2 result byte for byte.
+OTHER_BATCHES = ((3, 1), (4, 2), (5, 5), (5, 8))
+
+
+def _check_report(rep):
+    parts = [rep[k] for k in ("ms_upload", "ms_kernel", "ms_download")]
+    assert all(np.isfinite(v) and v >= 0 for v in parts + [rep["ms_total"]]), rep
+    assert all(rep["ms_total"] >= v for v in parts), rep
+
+
 @pytest.mark.parametrize("border", (0, 255))
 @pytest.mark.parametrize("num_frames", (1, 5))
 @pytest.mark.parametrize("channels", (1, 3))
@@ -167,6 +178,12 @@ def test_remap_is_byte_identical_to_restatement(channels, num_frames, border):
         assert out.shape == ref.shape and out.dtype == np.uint8
         assert np.array_equal(out, ref), name
         assert rep["ms_total"] > 0 and rep["ms_kernel"] > 0
+        _check_report(rep)
+        for frames, batch in OTHER_BATCHES if num_frames == 5 else ():
+            rep = {}
+            again = cm.remap(F[:frames], m, border_value=border, batch=batch, report=rep)
+            assert np.array_equal(again, out[:frames]), (name, frames, batch)
+            _check_report(rep)
     # the ties of the half-pixel shift round up: (0 + 255 + 255 + 0) / 4 = 127.5 -> 128
     F = K.remap_frames("half-pixel-shift", num_frames, channels)
     out = cm.remap(F, K.REMAP_MAPS["half-pixel-shift"][1], border_value=border, batch=2)

@@ -117,6 +117,17 @@ def _random_frames(num_frames, channels, seed=0):
     return rng.randint(0, 256, (num_frames, 540, 960) if channels == 1 else (num_frames, 540, 960, channels)).astype(np.uint8)
 
 
+# (frames, batch) beside the five frames at batch 2: both slots recycled more than once; no short batch; one slot alone, the
+# batch as long as the frames and longer.  The first `frames` of the five frames, held to the batch-2 result byte for byte.
+OTHER_BATCHES = ((3, 1), (4, 2), (5, 5), (5, 8))
+
+
+def _check_report(rep):
+    parts = [rep[k] for k in ("ms_table", "ms_rays", "ms_upload", "ms_kernel", "ms_download")]
+    assert all(np.isfinite(v) and v >= 0 for v in parts + [rep["ms_total"]]), rep
+    assert all(rep["ms_total"] >= v for v in parts), rep
+
+
 @pytest.mark.parametrize("border", (0, 255))
 @pytest.mark.parametrize("num_frames", (1, 5))
 @pytest.mark.parametrize("channels", (1, 3))
@@ -138,6 +149,12 @@ def test_frames_are_byte_identical_to_remapping_through_the_maps(channels, num_f
                 assert np.all(out[k] == border) and not valid[k].any()
         assert valid[0].any() and (out[0] != border).any()
         assert rep["ms_total"] > 0 and rep["ms_kernel"] > 0 and rep["ms_table"] > 0
+        _check_report(rep)
+        for frames, batch in OTHER_BATCHES if num_frames == 5 else ():
+            rep = {}
+            again, again_status = rs.rs_rectify_frames(F[:frames], rs.Scene(**_frames_scene(frames, size)), border_value=border, batch=batch, report=rep)
+            assert np.array_equal(again, out[:frames]) and np.array_equal(again_status, status[:frames]), (size, frames, batch)
+            _check_report(rep)
 
 
 def test_frames_on_a_cuda_tensor_equal_the_host_route():
