@@ -893,7 +893,7 @@ int oicc_camera_remap_device(void* hip_stream, int32_t num_frames, int32_t src_w
  * Specified step by step by tests/rolling_shutter_restatement.py and DESIGN.md ("Rolling-shutter rectification").
  *
  * Model: rotation only, the standard gyro correction.  The camera is taken to turn about its centre during the readout;
- * translation (parallax) is not modelled, nor is there any smoothing between frames.  Rays are (x, y, 1): fields of view of
+ * translation (parallax) is not modelled; smoothing between frames is the next section's.  Rays are (x, y, 1): fields of view of
  * 180 degrees and more are out of scope.
  *   Time.  Row y (continuous) of frame k is exposed at frame_t[k] + y line_delay_s in the camera clock; line_delay_s has any
  *   sign, 0 included.  A gyro sample at IMU time t lies at t + time_offset_imu_to_cam in the camera clock (the offset the
@@ -960,6 +960,73 @@ int oicc_rs_rectify_points(int32_t device_ordinal, const oicc_rs_scene* scene, i
                            double* xy_out, uint8_t* status, int32_t* frame_status, double* device_ms);
 int oicc_rs_row_rotations(int32_t device_ordinal, const oicc_rs_scene* scene, int64_t n, const int32_t* frame_index, const double* rows,
                           double* q, uint8_t* status, int32_t* frame_status, double* device_ms);
+
+/* ---- stabilisation: the orientation path of a clip, a smooth virtual camera, the zoom, the warp (stabilization.hip) ---------
+ * What footage is calibrated for: every frame seen from a camera that turns smoothly, the rolling shutter taken out on the way.
+ * Specified step by step by tests/stabilization_restatement.py and DESIGN.md ("Stabilisation").  Everything not said here is
+ * the rolling-shutter section's: times as differences first, Q(t) with the rate linear inside a gyro interval, right
+ * multiplication, reference_row, frame status 0 / 1 / 2, and frames whose status is not 0 never passed through uncorrected.
+ * The scene is an oicc_rs_scene with two further requirements (OICC_ERR_INVALID_ARG otherwise): frame_t strictly increasing, and
+ * the destination camera a plain PINHOLE (no distortion coefficients), whose rays have a closed form.
+ *   1. Path.  Frame k is on the path when t_ref,k lies inside the gyro coverage: tau_0 <= 0 <= tau_{n-1} with
+ *   tau_j = ((gyro_t[j] - frame_t[k]) + time_offset) - reference_row line_delay_s.  Such frames are contiguous.  path_q of the first
+ *   is the identity; path_{k+1} = path_k D_k, D_k = Q(t_ref,k)^-1 Q(t_ref,k+1) = Exp(phi_a(s_a))^-1 Exp(phi_a(dt_a)) ... Exp(phi_b(s_b)),
+ *   chained from the left through the partial interval of t_ref,k, the whole intervals and the partial interval of t_ref,k+1 (one
+ *   interval: Exp(phi_a(s_a))^-1 Exp(phi_a(s_b))), any number of gyro samples between two frames; s = -tau of the interval's first
+ *   sample against the frame's own time, dt_j = gyro_t[j+1] - gyro_t[j].  The definition is the left-to-right product over the
+ *   frames (the device chains runs of frames and scans the run products); each path_k is normalised once at the end.  Frames off
+ *   the path have NaN path_q and smooth_q, the identity as correction_q, and a status other than 0.
+ *   2. Smooth camera.  The window of frame k: the on-path frames m with |frame_t[m] - frame_t[k]| <= 3 sigma, weights
+ *   exp(-dt^2 / (2 sigma^2)).  S_k is their weighted intrinsic mean: S = path_k, then S <- S Exp(sum w_m Log(S^-1 path_m) / sum w_m)
+ *   until the step is <= 1e-12 rad, at most 16 times (iterations[k]; the step that meets the bound is applied and counted); S_k is
+ *   normalised.  sigma = 0 or a window of one frame: S_k = path_k bit for bit, 0 iterations, correction (1, 0, 0, 0).  Correction
+ *   C_k = path_k^-1 S_k, normalised, w >= 0: a ray d0 of the stabilised camera is C_k d0 in the real camera at t_ref,k.  With
+ *   max_correction_rad > 0 a C_k of a larger angle is shortened along its own axis to that angle (smooth_q stays the mean).
+ *   The warp's rotation of frame k is M_k = R(C_k) R9: R9 is applied to the destination ray first.
+ *   3. Required zoom z_k.  Zoom Z multiplies the destination's focal length and skew: the ray of a pixel at zoom Z is its zoom-1
+ *   ray divided by Z.  For every border pixel of the destination rectangle (2 (w + h) - 4 of them; all pixels of a rectangle one
+ *   pixel wide or high) with zoom-1 ray p, s = j / 32, j = 1 .. 32, marches from the centre outwards; s p is valid when the fixed
+ *   point of the rolling-shutter section, with M_k for R9, calls it valid.  At the first invalid sample 16 bisections between it
+ *   and its predecessor keep the valid end; no invalid sample: s = 1; an invalid centre (ray (0, 0, 1)): s = 0.
+ *   z_k = 1 / min s, +inf for an invalid centre; NaN for frames whose status is not 0.
+ *   4. Applied zoom Z_k, on the host.  zoom_mode 0: 1 (borders show).  1: the maximum of z over the status-0 frames.  2: with
+ *   T = zoom_window_s, Y_k = max z_m over the status-0 frames with |frame_t[m] - frame_t[k]| <= T (1 if there is none), then
+ *   Z_k = sum g Y_m / sum g over the same window, g = exp(-dt^2 / (2 (T / 2)^2)), held inside [min Y_m, max Y_m] of that window:
+ *   every Y_m there has z_k in its own window, so Z_k >= z_k.  A Z_k above max_zoom becomes max_zoom and zoom_clamped[k] = 1;
+ *   such a frame's invalid pixels get border_value.
+ *
+ * oicc_stab_plan: the whole clip's frame times in the scene.  path_q, smooth_q, correction_q [num_frames][4] (w, x, y, z);
+ *   required_zoom, zoom [num_frames]; iterations, frame_status [num_frames]; zoom_clamped [num_frames]; device_ms (may be NULL) [3]
+ *   = path, smoothing and zoom kernels, by device events.
+ * oicc_stab_map, oicc_stab_frames, oicc_stab_frames_device: oicc_rs_rectify_map, oicc_rs_rectify_frames and
+ *   oicc_rs_rectify_frames_device with two more arrays for the frames of THAT CALL's scene, correction_q [num_frames][4] (unit
+ *   within 1e-6, used as given) and zoom [num_frames] (finite, > 0): a program plans once over the clip and then streams chunks
+ *   of frames.  Per frame the destination ray is (v - cy) / ((f Z) a), (u - cx - (skew Z) y) / (f Z), f Z and skew Z rounded once;
+ *   the map equals oicc_rs_rectify_map's with R9 = M_k and those intrinsics bit for bit.  device_ms / the report's ms_rays: the
+ *   kernel that forms M_k.
+ * oicc_debug_stab_zoom: step 4 alone, host arithmetic only (needs no device): required_zoom [num_frames] (not NaN where the
+ *   status is 0) -> zoom, zoom_clamped.
+ * OICC_ERR_INVALID_ARG for what the rolling-shutter entries refuse, frame times that do not strictly increase, a destination
+ * that is not a plain PINHOLE, a negative or non-finite smoothing_sigma_s, max_correction_rad or zoom_window_s, a zoom_mode other
+ * than 0, 1, 2, a max_zoom below 1 or not finite.  Arguments are judged before the device is looked for; OICC_ERR_NO_DEVICE
+ * without one (no CPU fallback). */
+typedef struct oicc_stab_options {
+  double smoothing_sigma_s, max_correction_rad;
+  int32_t zoom_mode, reserved;
+  double zoom_window_s, max_zoom;
+} oicc_stab_options;
+int oicc_stab_plan(int32_t device_ordinal, const oicc_rs_scene* scene, const oicc_stab_options* options, double* path_q, double* smooth_q,
+                   double* correction_q, double* required_zoom, double* zoom, int32_t* iterations, int32_t* frame_status,
+                   uint8_t* zoom_clamped, double* device_ms);
+int oicc_stab_map(int32_t device_ordinal, const oicc_rs_scene* scene, const double* correction_q, const double* zoom, float* map,
+                  uint8_t* valid, uint8_t* evaluations, int32_t* frame_status, int64_t* num_valid, double* device_ms);
+int oicc_stab_frames(int32_t device_ordinal, const oicc_rs_scene* scene, const double* correction_q, const double* zoom, int32_t channels,
+                     const uint8_t* frames, int32_t border_value, int32_t batch, uint8_t* out, int32_t* frame_status,
+                     oicc_rs_frames_report* report);
+int oicc_stab_frames_device(void* hip_stream, const oicc_rs_scene* scene, const double* correction_q, const double* zoom, int32_t channels,
+                            const uint8_t* frames_dev, int32_t border_value, uint8_t* out_dev, int32_t* frame_status);
+int oicc_debug_stab_zoom(int32_t num_frames, const double* frame_t, const double* required_zoom, const int32_t* frame_status,
+                         const oicc_stab_options* options, double* zoom, uint8_t* zoom_clamped);
 
 /* ---- the elimination plan of the block cyclic reduction (kernels_bcr.hip), host arithmetic only: needs no device ----------
  * The damped LM system of n 64-column blocks is reduced level by level.  Level l: the active blocks are origin + k stride,

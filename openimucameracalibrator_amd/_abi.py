@@ -511,3 +511,43 @@ class BoundRollingShutter:
             fn.restype = res
             fn.argtypes = args
             setattr(self, name, fn)
+
+
+class StabOptions(C.Structure):
+    """oicc_stab_options (include/oicc_hip.h)."""
+    _fields_ = [("smoothing_sigma_s", C.c_double), ("max_correction_rad", C.c_double), ("zoom_mode", C.c_int32), ("reserved", C.c_int32),
+                ("zoom_window_s", C.c_double), ("max_zoom", C.c_double)]
+
+
+c_stab_options = C.POINTER(StabOptions)
+
+# Stabilisation (oicc_stab_* in include/oicc_hip.h), a table of its own like ROLLING_SHUTTER_SIGNATURES.
+STABILIZATION_SIGNATURES = {
+    "plan": (C.c_int, [C.c_int32, c_scene, c_stab_options, c_dp, c_dp, c_dp, c_dp, c_dp, c_i32p, c_i32p, c_u8p, c_dp]),
+    "map": (C.c_int, [C.c_int32, c_scene, c_dp, c_dp, c_fp, c_u8p, c_u8p, c_i32p, c_i64p, c_dp]),
+    "frames": (C.c_int, [C.c_int32, c_scene, c_dp, c_dp, C.c_int32, c_u8p, C.c_int32, C.c_int32, c_u8p, c_i32p, C.POINTER(RsFramesReport)]),
+    "frames_device": (C.c_int, [C.c_void_p, c_scene, c_dp, c_dp, C.c_int32, c_u8p, C.c_int32, c_u8p, c_i32p]),
+}
+# host arithmetic only (oicc_debug_stab_zoom): the applied zoom from the required one
+STABILIZATION_DEBUG_SIGNATURES = {
+    "zoom": (C.c_int, [C.c_int32, c_dp, c_dp, c_i32p, c_stab_options, c_dp, c_u8p]),
+}
+
+
+class BoundStabilization:
+    """Bound oicc_stab_* entry points of one library + prefix (``oicc_stab_`` for liboicc_hip.so), and oicc_debug_stab_zoom as
+    ``debug_zoom``."""
+
+    def __init__(self, lib, prefix):
+        self.lib = lib
+        self.prefix = prefix
+        for name, (res, args) in STABILIZATION_SIGNATURES.items():
+            fn = getattr(lib, prefix + name)  # AttributeError = missing symbol: fail loudly
+            fn.restype = res
+            fn.argtypes = args
+            setattr(self, name, fn)
+        for name, (res, args) in STABILIZATION_DEBUG_SIGNATURES.items():
+            fn = getattr(lib, "oicc_debug_stab_" + name)
+            fn.restype = res
+            fn.argtypes = args
+            setattr(self, "debug_" + name, fn)

@@ -7,7 +7,7 @@ fails when no HIP device is usable.
 import ctypes
 import os
 
-from ._abi import Bound, BoundAllan, BoundBa, BoundBcrPlan, BoundBoard, BoundCameraMaps, BoundLmRetract, BoundPlanarRansac, BoundRollingShutter, BoundStaticImu
+from ._abi import Bound, BoundAllan, BoundBa, BoundBcrPlan, BoundBoard, BoundCameraMaps, BoundLmRetract, BoundPlanarRansac, BoundRollingShutter, BoundStabilization, BoundStaticImu
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("OICC_DEV_LIB") or os.path.join(_HERE, "csrc", "liboicc_hip.so")   # OICC_DEV_LIB: another BUILD of the same library (developer A/B timing, scripts/build_variant.sh)
@@ -19,6 +19,7 @@ _bound_board = None
 _bound_planar_ransac = None
 _bound_camera_maps = None
 _bound_rolling_shutter = None
+_bound_stabilization = None
 _bound_bcr_plan = None
 _bound_lm_retract = None
 
@@ -89,6 +90,14 @@ def load_rolling_shutter():
     if _bound_rolling_shutter is None:
         _bound_rolling_shutter = BoundRollingShutter(load().lib, "oicc_rs_")
     return _bound_rolling_shutter
+
+
+def load_stabilization():
+    """oicc_stab_* entry points (orientation path, smooth camera, zoom, stabilised maps and frames) of the same library."""
+    global _bound_stabilization
+    if _bound_stabilization is None:
+        _bound_stabilization = BoundStabilization(load().lib, "oicc_stab_")
+    return _bound_stabilization
 
 
 def load_bcr_plan():

@@ -4,8 +4,8 @@ include/oicc_hip.h; DESIGN.md, "Rolling-shutter rectification").
 The spline calibration ends in q_i_c, time_offset_imu_to_cam_s and calib_line_delay_us.  This module uses them for what they are
 calibrated for: every destination pixel of a frame looks up the source row it was exposed on and is rotated by the gyro-integrated
 orientation between that row's time and the frame's reference time.  Rotation only: translation during the readout (parallax) is
-out of scope, and so are smoothing between frames and fields of view of 180 degrees and more.  There is no CPU path: every
-function raises without the HIP library or a device."""
+out of scope, and so are fields of view of 180 degrees and more; smoothing between frames is stabilization.py's.  There is no CPU
+path: every function raises without the HIP library or a device."""
 import ctypes as C
 
 import numpy as np
