@@ -789,14 +789,27 @@ typedef struct oicc_board_report {
 } oicc_board_report;
 /* Optional per-stage outputs for checking (any pointer may be NULL): gray and response [frames][h'][w'], candidates
  * (x, y) and refined (x, y) [frames][capacity][2] in raster order of the candidates (entries beyond the frame's count
- * are left untouched). */
+ * are left untouched).  extended = 0: the struct ends at that field, as callers built before it grew pass it, and nothing
+ * behind it is read.  Non-zero: the fields behind it are present, each of which may be NULL again:
+ *   polarity   [frames][h'][w']: the index of the brightest line (0 within the radius of the border);
+ *   blurred    [frames][h'][w']: the 3x3 binomial blur as float, the image the sub-pixel and marker kernels read;
+ *   grid_shape [frames][2]: (A, B) of the assembled grid, {A, B} = {W, H}, or (0, 0) when no grid was assembled;
+ *   grid       [frames][W*H]: for grid cell a*B + b the index of its candidate in the frame's raster-ordered list;
+ *   disc, ring [frames][(W-1)*(H-1)]: the marker kernel's means of square a*(B-1) + b of that grid.
+ * grid, disc and ring of a frame without a grid are left untouched.  Every copy happens only when its pointer is set. */
 typedef struct oicc_board_stages {
   uint8_t* gray;
   float* response;
   int32_t* candidates;
   double* refined;
   int32_t capacity;
-  int32_t reserved;
+  int32_t extended;
+  uint8_t* polarity;
+  float* blurred;
+  int32_t* grid_shape;
+  int32_t* grid;
+  double* disc;
+  double* ring;
 } oicc_board_stages;
 /* The resize of ExtractImageFolderToJson (board_extractor.cc:317-318): output size round(width / factor). */
 int oicc_board_output_size(int32_t width, int32_t height, double downsample_factor, int32_t* out_width, int32_t* out_height);

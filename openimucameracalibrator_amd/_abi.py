@@ -344,7 +344,8 @@ class BoardReport(C.Structure):
 class BoardStages(C.Structure):
     """oicc_board_stages (include/oicc_hip.h)."""
     _fields_ = [("gray", c_u8p), ("response", C.POINTER(C.c_float)), ("candidates", c_i32p), ("refined", c_dp),
-                ("capacity", C.c_int32), ("reserved", C.c_int32)]
+                ("capacity", C.c_int32), ("extended", C.c_int32), ("polarity", c_u8p), ("blurred", C.POINTER(C.c_float)),
+                ("grid_shape", c_i32p), ("grid", c_i32p), ("disc", c_dp), ("ring", c_dp)]
 
 
 # Radon checkerboard extraction (oicc_board_* in include/oicc_hip.h), a table of its own like ALLAN_SIGNATURES.

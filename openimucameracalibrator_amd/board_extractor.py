@@ -23,8 +23,10 @@ NS_TO_S, S_TO_US = 1e-9, 1e6                # utils/types.h:29-33
 
 def radon_detect(frames, downsample_factor, W, H, device=0, stages=False, **options):
     """oicc_board_radon_detect on frames [F, h, w] (gray) or [F, h, w, 3] (BGR) u8.  Returns corners [F, W*H, 2] (NaN
-    where not found), found [F] bool, candidates per frame, the report dict, and with stages=True also the gray images,
-    the response maps and the per-frame candidate / refined lists (raster order)."""
+    where not found), found [F] bool, candidates per frame, the report dict, and with stages=True also the gray and
+    blurred images, the response and polarity maps, the per-frame candidate / refined lists (raster order), and per frame
+    the assembled grid of candidate indices [A, B] with its disc / ring means [A-1, B-1] (None without a grid) and
+    grid_shape [F, 2] ((0, 0) without a grid)."""
     b = _lib.load_board()
     fr = np.ascontiguousarray(np.asarray(frames, dtype=np.uint8))
     if fr.ndim not in (3, 4) or (fr.ndim == 4 and fr.shape[3] != 3):
@@ -48,8 +50,16 @@ def radon_detect(frames, downsample_factor, W, H, device=0, stages=False, **opti
         resp = np.zeros((F, hd.value, wd.value), np.float32)
         cxy = np.zeros((F, cap, 2), np.int32)
         ref = np.zeros((F, cap, 2), np.float64)
+        pol = np.zeros((F, hd.value, wd.value), np.uint8)
+        blur = np.zeros((F, hd.value, wd.value), np.float32)
+        gshape = np.zeros((F, 2), np.int32)
+        grid = np.zeros((F, W * H), np.int32)
+        disc = np.zeros((F, (W - 1) * (H - 1)), np.float64)
+        ring = np.zeros((F, (W - 1) * (H - 1)), np.float64)
         st = _abi.BoardStages(gray.ctypes.data_as(_abi.c_u8p), resp.ctypes.data_as(C.POINTER(C.c_float)), cxy.ctypes.data_as(_abi.c_i32p),
-                              ref.ctypes.data_as(_abi.c_dp), cap, 0)
+                              ref.ctypes.data_as(_abi.c_dp), cap, 1, pol.ctypes.data_as(_abi.c_u8p), blur.ctypes.data_as(C.POINTER(C.c_float)),
+                              gshape.ctypes.data_as(_abi.c_i32p), grid.ctypes.data_as(_abi.c_i32p), disc.ctypes.data_as(_abi.c_dp),
+                              ring.ctypes.data_as(_abi.c_dp))
     rc = b.radon_detect(int(device), F, w, h, ch, fr.ctypes.data_as(_abi.c_u8p), float(downsample_factor), int(W), int(H), C.byref(opt),
                         corners.ctypes.data_as(_abi.c_dp), found.ctypes.data_as(_abi.c_i32p), ncand.ctypes.data_as(_abi.c_i32p),
                         C.byref(rep), C.byref(st) if st is not None else None)
@@ -58,8 +68,12 @@ def radon_detect(frames, downsample_factor, W, H, device=0, stages=False, **opti
     out = (corners, found.astype(bool), ncand, rep.as_dict())
     if stages:
         n = np.minimum(ncand, cap)
+        has = [bool(gshape[f, 0]) for f in range(F)]
+        cells = lambda a, f: a[f].reshape(gshape[f, 0] - 1, gshape[f, 1] - 1).copy() if has[f] else None
         out += (dict(gray=gray, response=resp, candidates=[cxy[f, :n[f], ::-1].copy() for f in range(F)],
-                     refined=[ref[f, :n[f]].copy() for f in range(F)]),)
+                     refined=[ref[f, :n[f]].copy() for f in range(F)], polarity=pol, blurred=blur, grid_shape=gshape,
+                     grid=[grid[f].reshape(gshape[f]).copy() if has[f] else None for f in range(F)],
+                     disc=[cells(disc, f) for f in range(F)], ring=[cells(ring, f) for f in range(F)]),)
     return out
 
 

@@ -534,6 +534,7 @@ extern "C" int oicc_board_radon_detect(int32_t device_ordinal, int32_t num_frame
   const int WH = W * H;
   const float inv = float(1.0 / (16.0 * 255.0 * (2 * r + 1)));
   const int win = r + 2;
+  const oicc_board_stages* ext = stages && stages->extended ? stages : nullptr;     // the fields behind `extended` exist only then
   std::vector<int> tab;
   for (int i = 0; i < num_frames * WH * 2; ++i) corners[i] = std::nan("");
   for (int i = 0; i < num_frames; ++i) { found[i] = 0; if (candidates_per_frame) candidates_per_frame[i] = 0; }
@@ -611,6 +612,9 @@ extern "C" int oicc_board_radon_detect(int32_t device_ordinal, int32_t num_frame
           const int64_t F = first + f;
           if (stages->gray) OICC_HIP_TRY(hipMemcpy(stages->gray + F * out_frame, s.d_gray.p + f * out_frame, size_t(out_frame), hipMemcpyDeviceToHost));
           if (stages->response) OICC_HIP_TRY(hipMemcpy(stages->response + F * out_frame, s.d_resp.p + f * out_frame, sizeof(float) * size_t(out_frame), hipMemcpyDeviceToHost));
+          if (ext && ext->polarity) OICC_HIP_TRY(hipMemcpy(ext->polarity + F * out_frame, s.d_pol.p + f * out_frame, size_t(out_frame), hipMemcpyDeviceToHost));
+          if (ext && ext->blurred) OICC_HIP_TRY(hipMemcpy(ext->blurred + F * out_frame, s.d_blur.p + f * out_frame, sizeof(float) * size_t(out_frame), hipMemcpyDeviceToHost));
+          if (ext && ext->grid_shape) { ext->grid_shape[2 * F] = 0; ext->grid_shape[2 * F + 1] = 0; }
         }
       }
       const auto th0 = std::chrono::steady_clock::now();
@@ -641,6 +645,11 @@ extern "C" int oicc_board_radon_detect(int32_t device_ordinal, int32_t num_frame
         }
         fpts[size_t(f)] = pts;
         if (n >= WH && assemble(pts, pol, rs, W, H, &grids[size_t(f)])) has[size_t(f)] = 1;
+        if (ext && has[size_t(f)]) {
+          const Grid& G = grids[size_t(f)];
+          if (ext->grid_shape) { ext->grid_shape[2 * int64_t(F)] = G.A; ext->grid_shape[2 * int64_t(F) + 1] = G.B; }
+          if (ext->grid) std::copy(G.idx.begin(), G.idx.end(), ext->grid + int64_t(F) * WH);
+        }
       }
       rep.ms_assembly_host += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - th0).count();
       // kernel 6 over every assembled grid of the batch
@@ -671,6 +680,9 @@ extern "C" int oicc_board_radon_detect(int32_t device_ordinal, int32_t num_frame
         const auto th1 = std::chrono::steady_clock::now();
         for (const GridRef& g : gr) {
           const Grid& G = grids[size_t(g.frame)];
+          const int nc = (G.A - 1) * (G.B - 1);
+          if (ext && ext->disc) std::copy(disc.begin() + g.cell0, disc.begin() + g.cell0 + nc, ext->disc + int64_t(first + g.frame) * nc);
+          if (ext && ext->ring) std::copy(ring.begin() + g.cell0, ring.begin() + g.cell0 + nc, ext->ring + int64_t(first + g.frame) * nc);
           std::vector<int> ids;
           if (!marker_ids(G, fpts[size_t(g.frame)], disc.data() + g.cell0, ring.data() + g.cell0, W, H, &ids)) continue;
           const int F = first + g.frame;

@@ -116,31 +116,34 @@ def candidates(resp, r, threshold_rel, max_candidates):
 
 
 # ---- 4 sub-pixel refinement -----------------------------------------------------------------------------------------
-def _sample(I, x, y):
+def _sample(I, x, y, dtype=np.float64):
     h, w = I.shape
     x0 = np.floor(x); y0 = np.floor(y)
     ax = x - x0; ay = y - y0
     xi0 = np.clip(x0.astype(np.int64), 0, w - 1); xi1 = np.clip(x0.astype(np.int64) + 1, 0, w - 1)
     yi0 = np.clip(y0.astype(np.int64), 0, h - 1); yi1 = np.clip(y0.astype(np.int64) + 1, 0, h - 1)
-    I = I.astype(np.float64)
+    I = I.astype(dtype)
     return (1 - ay) * ((1 - ax) * I[yi0, xi0] + ax * I[yi0, xi1]) + ay * ((1 - ax) * I[yi1, xi0] + ax * I[yi1, xi1])
 
 
-def subpix(I, xy, win, iterations=20, eps=0.01):
+def subpix(I, xy, win, iterations=20, eps=0.01, dtype=np.float64, trace=None):
     """cornerSubPix (OpenCV imgproc/cornersubpix.cpp) on the float image I for start points xy [n,2]: Gaussian window
     weights exp(-(u/win)^2 - (v/win)^2), central differences of bilinear samples, 2x2 solve per step; stops at
-    iterations or a squared step <= eps^2, leaves the image -> stop; a result farther than win from the start -> start."""
+    iterations or a squared step <= eps^2, leaves the image -> stop; a result farther than win from the start -> start.
+    dtype: the type of the window, the weights and every sum (np.longdouble runs the same statements in extended
+    precision).  trace: a list that receives, per start point, the iterates before the final "farther than win" rule."""
     h, w = I.shape
-    u = np.arange(-win, win + 1, dtype=np.float64)
+    u = np.arange(-win, win + 1, dtype=dtype)
     V, U = np.meshgrid(u, u, indexing="ij")
     m = np.exp(-(U / win) ** 2) * np.exp(-(V / win) ** 2)
-    out = np.array(xy, np.float64)
+    out = np.array(xy, dtype)
     for n in range(len(out)):
         c0 = out[n].copy(); c = c0.copy()
+        steps = []
         for _ in range(iterations):
             X = c[0] + U; Y = c[1] + V
-            gx = _sample(I, X + 1, Y) - _sample(I, X - 1, Y)
-            gy = _sample(I, X, Y + 1) - _sample(I, X, Y - 1)
+            gx = _sample(I, X + 1, Y, dtype) - _sample(I, X - 1, Y, dtype)
+            gy = _sample(I, X, Y + 1, dtype) - _sample(I, X, Y - 1, dtype)
             gxx, gxy, gyy = gx * gx * m, gx * gy * m, gy * gy * m
             a, b, cc = gxx.sum(), gxy.sum(), gyy.sum()
             bb1 = (gxx * U + gxy * V).sum(); bb2 = (gxy * U + gyy * V).sum()
@@ -148,14 +151,17 @@ def subpix(I, xy, win, iterations=20, eps=0.01):
             if abs(det) <= np.finfo(np.float64).eps ** 2:
                 break
             s = 1.0 / det
-            c2 = np.array([c[0] + cc * s * bb1 - b * s * bb2, c[1] - b * s * bb1 + a * s * bb2])
+            c2 = np.array([c[0] + cc * s * bb1 - b * s * bb2, c[1] - b * s * bb1 + a * s * bb2], dtype)
             err = ((c2 - c) ** 2).sum()
             c = c2
+            steps.append(c.copy())
             if c[0] < 0 or c[0] >= w or c[1] < 0 or c[1] >= h or err <= eps * eps:
                 break
         if abs(c[0] - c0[0]) > win or abs(c[1] - c0[1]) > win:
             c = c0
         out[n] = c
+        if trace is not None:
+            trace.append(steps)
     return out
 
 
@@ -297,10 +303,12 @@ def square_to_quad(q):
     return (x1 - x0 + g * x1, x3 - x0 + hh * x3, x0, y1 - y0 + g * y1, y3 - y0 + hh * y3, y0, g, hh)
 
 
-def cell_means(I, C):
-    """C [A, B, 2] grid corner pixels -> disc and ring means [A-1, B-1] of every square (bilinear samples)."""
+def cell_means(I, C, dtype=np.float64):
+    """C [A, B, 2] grid corner pixels -> disc and ring means [A-1, B-1] of every square (bilinear samples), computed
+    in dtype."""
+    C = np.asarray(C, dtype)
     A, B = C.shape[:2]
-    disc = np.zeros((A - 1, B - 1)); ring = np.zeros((A - 1, B - 1))
+    disc = np.zeros((A - 1, B - 1), dtype); ring = np.zeros((A - 1, B - 1), dtype)
     for a in range(A - 1):
         for b in range(B - 1):
             k = square_to_quad([C[a, b], C[a + 1, b], C[a + 1, b + 1], C[a, b + 1]])
@@ -309,7 +317,7 @@ def cell_means(I, C):
                 for du, dv in pts:
                     s, t = 0.5 + du, 0.5 + dv
                     den = k[6] * s + k[7] * t + 1.0
-                    acc += _sample(I, np.array((k[0] * s + k[1] * t + k[2]) / den), np.array((k[3] * s + k[4] * t + k[5]) / den))
+                    acc += _sample(I, np.array((k[0] * s + k[1] * t + k[2]) / den), np.array((k[3] * s + k[4] * t + k[5]) / den), dtype)
                 out[a, b] = acc / len(pts)
     return disc, ring
 
@@ -366,7 +374,8 @@ def ids_from_marker(grid_shape, row, col, bc, W, H):
 # ---- the whole detector ---------------------------------------------------------------------------------------------
 def detect(frames, factor, W, H, radius=3, threshold_rel=0.5, max_candidates=512, subpix_iterations=20, subpix_eps=0.01,
            debug=False):
-    """frames -> corners [F, W*H, 2] (NaN where not found), found [F] (and the per-stage pieces with debug)."""
+    """frames -> corners [F, W*H, 2] (NaN where not found), found [F] (and the per-stage pieces with debug: per frame also
+    the grid of candidate indices [A, B] or None, its shape or (0, 0), and the disc / ring means of its squares)."""
     gray = resize_gray(frames, factor)
     B = blur16(gray)
     resp, pol = response(B, radius)
@@ -375,6 +384,7 @@ def detect(frames, factor, W, H, radius=3, threshold_rel=0.5, max_candidates=512
     F = gray.shape[0]
     corners = np.full((F, W * H, 2), np.nan); found = np.zeros(F, bool)
     refined_all = []
+    grids = [None] * F; shapes = [(0, 0)] * F; discs = [None] * F; rings = [None] * F
     for f in range(F):
         yx, overflow = cands[f]
         ref = subpix(I[f], yx[:, ::-1].astype(np.float64), radius + 2, subpix_iterations, subpix_eps)
@@ -385,6 +395,7 @@ def detect(frames, factor, W, H, radius=3, threshold_rel=0.5, max_candidates=512
         if G is None:
             continue
         disc, ring = cell_means(I[f], ref[G])
+        grids[f], shapes[f], discs[f], rings[f] = G, G.shape, disc, ring
         m = marker_ids(disc, ring, ref[G])
         if m is None:
             continue
@@ -394,5 +405,6 @@ def detect(frames, factor, W, H, radius=3, threshold_rel=0.5, max_candidates=512
         corners[f][ids.ravel()] = ref[G.ravel()]
         found[f] = True
     if debug:
-        return corners, found, dict(gray=gray, blur=B, response=resp, polarity=pol, candidates=cands, refined=refined_all)
+        return corners, found, dict(gray=gray, blur=B, response=resp, polarity=pol, candidates=cands, refined=refined_all,
+                                    blurred=I, grid=grids, grid_shape=shapes, disc=discs, ring=rings)
     return corners, found

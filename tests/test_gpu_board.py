@@ -30,8 +30,8 @@ def test_stages_equal_restatement(factor, bgr, width):
     corners, found, ncand, rep, st = BE.radon_detect(frames, factor, 14, 9, stages=True)
     rc, rf, dbg = BR.detect(frames, factor, 14, 9, debug=True)
     assert np.array_equal(st["gray"], dbg["gray"])
-    scale = np.abs(dbg["response"]).max()
-    assert np.abs(st["response"] - dbg["response"]).max() <= 1e-5 * scale
+    assert np.array_equal(st["response"], dbg["response"])
+    assert np.array_equal(st["polarity"], dbg["polarity"]) and np.array_equal(st["blurred"], dbg["blurred"])
     for f in range(len(frames)):
         yx, _ = dbg["candidates"][f]
         assert ncand[f] == len(yx) and np.array_equal(st["candidates"][f], yx)
