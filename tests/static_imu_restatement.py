@@ -222,7 +222,8 @@ def gyro_blocks_eval(t, gyro, ranges, gv, p, optimize_bias=False, gyro_dt=-1.0, 
 
 
 def normal_eq(r, J):
-    return 0.5 * seq_sum(r * r), J.T @ J, J.T @ r
+    # einsum, not BLAS: rows in order on every machine (static_imu_reference.YARDSTICK is measured from these sums)
+    return 0.5 * seq_sum(r * r), np.einsum("ri,rj->ij", J, J), np.einsum("ri,r->i", J, r)
 
 
 # ---- minimiser ----------------------------------------------------------------------------------------------------

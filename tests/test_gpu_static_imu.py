@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import static_imu_restatement as R
+from static_imu_cases import plain_detector_loop
 from openimucameracalibrator_amd import io_files, static_imu as SI, synthetic
 
 pytestmark = pytest.mark.gpu
@@ -64,17 +65,7 @@ def test_detector_plain_loop_and_short_series():
     th = np.array([0.5, 1.0, 2.0]) * 1e-3
     dev = SI.static_intervals(acc, th)
     for k in range(3):   # utils::StaticIntervalsDetector, literally
-        out, look, cur = [], True, None
-        for i in range(50, len(acc) - 50):
-            v = R.data_variance(acc, i - 50, i + 50)
-            nrm = float(R.norm3(v))
-            if look and nrm < th[k]:
-                cur, look = i, False
-            elif not look and nrm >= th[k]:
-                out.append((cur, i - 1)); look = True
-        if not look:
-            out.append((cur, len(acc) - 51))
-        assert [tuple(x) for x in dev[k]] == out
+        assert [tuple(x) for x in dev[k]] == plain_detector_loop(acc, th[k])
     for n in (101, 60, 3):   # win_size >= n: no intervals
         lists, norms, _ = SI.static_intervals(acc[:n], th, with_norms=True)
         assert all(len(x) == 0 for x in lists) and np.all(np.isnan(norms))
