@@ -1059,6 +1059,12 @@ int oicc_debug_bcr_plan(int32_t n, int32_t ghost, int32_t odd_only, int64_t* lev
  * Returns the number of levels, OICC_ERR_INVALID_ARG as above or for rtf, budget, b0 out of range. */
 int oicc_debug_bcr_join_plan(int32_t n, int32_t ghost, int32_t odd_only, int32_t b0, int32_t rtf, int32_t join_levels, int32_t budget,
                              int32_t build_inverts, int32_t* joined, int32_t cap_levels);
+/* Whether level 0 of that plan runs as ONE launch behind a plain build launch, instead of a build launch that also inverts level 0's
+ * pivots and a Schur launch (the solver's own rule, host arithmetic only): join_levels (option bcr_join_levels) neither 0 nor 2, the
+ * whole band (ghost == 0, b0 == 0), 8 <= n <= 512 and level 0's pivots x (12 + 3 rtf) <= budget.  oicc_debug_bcr_join_plan keeps
+ * its meaning: with build_inverts < 0 it answers for the levels above level 0 of such a solve.
+ * Returns 1 / 0, or OICC_ERR_INVALID_ARG for n < 1 or rtf, budget, b0 out of range. */
+int oicc_debug_bcr_level0_plan(int32_t n, int32_t ghost, int32_t odd_only, int32_t b0, int32_t rtf, int32_t join_levels, int32_t budget);
 /* Which level's back substitution the solver runs inside the last block's launch -- one workgroup per pivot of the level, each
  * repeating the last block's work and taking its neighbours' solution from LDS -- instead of a launch of its own (the solver's own
  * rule, host arithmetic only).  The back substitution pairs the levels from the bottom up; an even number of levels leaves level

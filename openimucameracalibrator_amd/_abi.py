@@ -374,6 +374,8 @@ class BoundBoard:
 BCR_PLAN_SIGNATURES = {
     "plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, c_i64p, C.c_int32, c_i64p]),
     "join_plan": (C.c_int, [C.c_int32] * 8 + [c_i32p, C.c_int32]),   # which levels run as one launch (oicc_debug_bcr_join_plan)
+    "level0_plan": (C.c_int, [C.c_int32] * 7),   # whether level 0 runs as one launch behind a plain build launch (oicc_debug_bcr_level0_plan)
+    "level0_info": (C.c_int, [C.c_void_p, c_i64p]),   # whether level 0 of the last whole-band solve of a problem did, how many have (oicc_debug_bcr_level0_info)
     "fold_plan": (C.c_int, [C.c_int32] * 5),   # which level's back substitution rides in the last block's launch (oicc_debug_bcr_fold_plan)
     "chain_schedule": (C.c_int, [c_i32p, C.c_int32]),   # the panel chain's events in program order: where each deferred update is issued (oicc_debug_bcr_chain_schedule)
     "fold_info": (C.c_int, [C.c_void_p, c_i64p]),   # whether the last whole-band solve of a problem did, how many have (oicc_debug_bcr_fold_info)

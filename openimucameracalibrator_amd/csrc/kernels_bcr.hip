@@ -969,7 +969,8 @@ __device__ __forceinline__ void bcri_tx_store(const BcrArgs& A, const BcrSchurGr
 // (one of B_x, up to four of B_y) do not depend on Z_i: their loads are issued with D_i's and parked in LDS behind the inversion's
 // arrays, so no global round trip stands behind the inversion.  Groups of a side the pivot has no neighbour on leave at once.  For
 // levels whose workgroups fit the chip at once (bcr_level_joined); level 0 is not among them while its inversions ride in the build
-// launch, whose workgroups still write the blocks the Schur updates land on.
+// launch, whose workgroups still write the blocks the Schur updates land on -- it is behind a plain build launch
+// (bcr_level0_behind_build), where the reporting workgroup of a level-0 pivot raises the failure flag that build's thread 0 reset.
 constexpr int kInvLdsDoubles = 64 * kInvLD + 64 + 8 + kInvMsDoubles;                 // W, da, failp, ms of bcri_invert_body
 constexpr int kJoinLdsDoubles = kInvLdsDoubles + 5 * 1024 + (kTxChunks + 3) * kTxTileDoubles;       // + B_x tile, four B_y tiles ([64][16] each), the ten partial tiles of T_x, the shadow waves' Y tiles
 __global__ __launch_bounds__(64 * kInvWaves) void bcri_invert_schur_kernel(BcrArgs A) {
@@ -1452,10 +1453,23 @@ static void bcr_set_level(BcrArgs& A, const BcrLevels& L, int l) {
 }
 // build + the inversions of level 0 in one launch (while the level-0 pivots fit on the chip at once)
 static bool bcr_fused_build(int n, const long long* prof) { return n >= 2 && n <= 512 && prof == nullptr; }
-// the damped system in block form (+ the inversions of level 0 in the same launch when they fit the chip at once); returns whether level 0 is inverted
-static bool bcr_launch_build(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb, int reuse_diagonal, double min_diag, double max_diag, BcrArgs A, const BcrLevels& L, hipStream_t st) {
+// option bcr_join_levels (0: no level joined; 2: the levels above level 0 only; any other value: level 0 as well, where
+// bcr_level0_behind_build says so) and the workgroup budget of a joined level
+struct BcrJoin { int on = 0; int budget = 0; };
+// Level 0 as ONE launch (bcri_invert_schur_kernel) behind a PLAIN build launch (bcr_build_kernel) instead of the build launch with
+// level 0's inversions (bcri_build_invert_kernel, which forms and stores Z) and a Schur launch that loads Z again: THE rule, host
+// arithmetic only (exported as oicc_debug_bcr_level0_plan).  It holds when joining is on and not held to the upper levels, no phase
+// clocks are asked for, the solve is the whole band, 8 <= n <= 512 -- below eight blocks nothing of the timed plans runs and the
+// recorded bits of the two- and three-block solves are those of B (X X^T); above 512 the build is plain anyway and bcr_level_joined
+// alone decides -- and level 0's pivots x groups fit the workgroup budget.
+static bool bcr_level0_behind_build(const BcrJoin& J, bool prof, int ghost, int b0, int n, int npiv0, int rtf) {
+  return J.on != 0 && J.on != 2 && !prof && ghost == 0 && b0 == 0 && n >= 8 && n <= 512 && (int64_t)npiv0 * (12 + 3 * rtf) <= (int64_t)J.budget;
+}
+// the damped system in block form (+ the inversions of level 0 in the same launch when they fit the chip at once and level 0 does not
+// join behind a plain build: level0_joins, bcr_level0_behind_build's answer); returns whether level 0 is inverted
+static bool bcr_launch_build(const NormalEq& ne, const TangentLayout& tl, const SolveBuffers& sb, int reuse_diagonal, double min_diag, double max_diag, BcrArgs A, const BcrLevels& L, hipStream_t st, bool level0_joins = false) {
   const int n = A.n;
-  const bool fused_build = bcr_fused_build(n, A.prof);
+  const bool fused_build = bcr_fused_build(n, A.prof) && !level0_joins;
   const int64_t work = (int64_t)(n + A.ghost) * 4096;
   A.o = 0; A.s = 1; A.p = 1; A.m = n; A.pn = 1; A.offS_in = 0; A.offS_out = 0;
   if (L.nlev > 0) bcr_set_level(A, L, 0);
@@ -1475,13 +1489,12 @@ static bool bcr_launch_build(const NormalEq& ne, const TangentLayout& tl, const 
 // level's inversions are not already part of the build launch, and its pivots x groups fit the workgroup budget (default: one per
 // compute unit): every workgroup of a pivot repeats the inversion, which costs nothing on compute units that would idle and
 // everything on a level that is throughput bound.
-struct BcrJoin { int on = 0; int budget = 0; };
 static bool bcr_level_joined(const BcrJoin& J, bool prof, int ghost, int b0, bool carry, bool in_build, int npiv, int rtf) {
   return J.on != 0 && !prof && ghost == 0 && b0 == 0 && !carry && !in_build && (int64_t)npiv * (12 + 3 * rtf) <= (int64_t)J.budget;
 }
 // forward levels while more than one (local) block is active: inversions of the pivots, Schur complements onto their neighbours;
-// returns the number of joined levels
-static int bcr_launch_forward(BcrArgs A, bool level0_inverted, const BcrLevels& L, hipStream_t st, const BcrJoin& J = BcrJoin()) {
+// returns the number of joined levels; *joined0 (optional): whether level 0 is one of them
+static int bcr_launch_forward(BcrArgs A, bool level0_inverted, const BcrLevels& L, hipStream_t st, const BcrJoin& J = BcrJoin(), int* joined0 = nullptr) {
   using KernelFn = void (*)(BcrArgs);
   KernelFn k_inv = A.prof ? bcri_invert_kernel<false, true> : bcri_invert_kernel<false, false>;
   bcr_allow_lds(reinterpret_cast<const void*>(k_inv), bcr_lds_inv());
@@ -1498,6 +1511,7 @@ static int bcr_launch_forward(BcrArgs A, bool level0_inverted, const BcrLevels& 
       bcr_allow_lds(reinterpret_cast<const void*>(bcri_invert_schur_kernel), lds_join);
       hipLaunchKernelGGL(bcri_invert_schur_kernel, dim3(12 + 3 * A.rtf, npiv), dim3(64 * kInvWaves), lds_join, st, A);
       ++joined;
+      if (l == 0 && joined0 != nullptr) *joined0 = 1;
       continue;
     }
     BcrArgs Ai = A; if (l != 0) Ai.prof = nullptr;
@@ -1557,7 +1571,9 @@ static bool bcr_launch_last_and_back(BcrArgs A, const BcrLevels& L, hipStream_t 
   return bcr_launch_back(A, L, fold >= 0 ? fold - 1 : nlev - 2, st, R, sb);        // (the top level went with the last block)
 }
 
-// the route of one cyclic-reduction solve (lm_solve_route): fused or separate build, or kRouteNone where it does not apply
+// the route of one cyclic-reduction solve (lm_solve_route): fused or separate build, or kRouteNone where it does not apply.
+// kRouteBcrFused ("bcr_fused") names the family of 2..512 blocks without phase clocks, whichever launch inverts level 0: the build
+// launch, or -- where bcr_level0_behind_build says so -- the joined level-0 launch behind a plain build.
 int bcr_route(const TangentLayout& tl, const SolveBuffers& sb) {
   if (!bcr_applicable(tl) || tl.a + 1 > sb.bcr_max_border || sb.ws == nullptr || sb.ws_doubles < bcr_workspace_doubles(tl)) return kRouteNone;
   if (sb.algo != 0 && sb.algo != 4) return kRouteNone;   // (algorithms 2 and 3 -- the factor-based levels of rounds 1-2 and their parallel form -- left the library in round 4)
@@ -1579,10 +1595,14 @@ int launch_bcr_solve(const NormalEq& ne, const TangentLayout& tl, const SolveBuf
   A.n = n; A.a = tl.a; A.Pb = tl.Pb; A.delay = sb.bcr_delay;
   A.rtf = (a1 + 15) / 16; A.ctl = sb.ctl;
   const BcrLevels L = bcr_plan(n, 0, false);
-  const bool inverted = bcr_launch_build(ne, tl, sb, reuse_diagonal, min_diag, max_diag, A, L, st);
   BcrJoin J; J.on = sb.bcr_join; J.budget = sb.bcr_join_budget;
-  const int joined = bcr_launch_forward(A, inverted, L, st, J);
-  if (sb.bcr_joined != nullptr) { sb.bcr_joined[0] = joined; sb.bcr_joined[1] += joined; }
+  const bool level0_joins = L.nlev > 0 && bcr_level0_behind_build(J, A.prof != nullptr, A.ghost, A.b0, n, L.npivs[0], A.rtf);
+  const bool inverted = bcr_launch_build(ne, tl, sb, reuse_diagonal, min_diag, max_diag, A, L, st, level0_joins);
+  int joined0 = 0;
+  int joined = bcr_launch_forward(A, inverted, L, st, J, &joined0);
+  // (a level 0 that joins behind the plain build of 8..512 blocks has counters of its own: [0..1] count what oicc_debug_bcr_join_plan says)
+  joined0 = level0_joins ? joined0 : 0; joined -= joined0;
+  if (sb.bcr_joined != nullptr) { sb.bcr_joined[0] = joined; sb.bcr_joined[1] += joined; sb.bcr_joined[2] = joined0; sb.bcr_joined[3] += joined0; }
   // the ONE place that decides: a request that is on, for the unscaled step, and a plan whose last launch is the two-level back
   // substitution on the levels (1, 0); this entry always solves the whole band (b0 = 0, no ghost block)
   const bool honour = retract != nullptr && retract->on != 0 && retract->rmap != nullptr && retract->alpha == 1.0 && L.nlev >= 3 && A.ghost == 0 && A.b0 == 0;
@@ -1759,6 +1779,13 @@ extern "C" int oicc_debug_bcr_join_plan(int32_t n, int32_t ghost, int32_t odd_on
     joined[l] = oicc::bcr_level_joined(J, false, ghost, b0, carry, in_build0 && l == 0, L.npivs[l], rtf) ? 1 : 0;
   }
   return L.nlev;
+}
+
+extern "C" int oicc_debug_bcr_level0_plan(int32_t n, int32_t ghost, int32_t odd_only, int32_t b0, int32_t rtf, int32_t join_levels, int32_t budget) {
+  if (n < 1 || rtf < 1 || rtf > 4 || budget < 0 || b0 < 0) return OICC_ERR_INVALID_ARG;
+  const oicc::BcrLevels L = oicc::bcr_plan(n, ghost, odd_only != 0);
+  oicc::BcrJoin J; J.on = join_levels; J.budget = budget;
+  return L.nlev > 0 && oicc::bcr_level0_behind_build(J, false, ghost, b0, n, L.npivs[0], rtf) ? 1 : 0;
 }
 
 extern "C" int oicc_debug_bcr_fold_plan(int32_t n, int32_t ghost, int32_t odd_only, int32_t b0, int32_t on) {

@@ -147,8 +147,9 @@ struct SolveBuffers {
   double radius;   // trust-region radius of this step (kernel argument, no host->device copy)
   int bcr_max_border = 64;      // arrow + rhs rows the block cyclic reduction accepts (per problem: option bcr_max_border)
   int bcr_delay = 0;            // debug: panel waves other than wave 0 start every panel this many ~1000-cycle sleeps late (option debug_bcr_delay)
-  // cyclic reduction, levels as one launch (kernels_bcr.hip: bcr_level_joined; options bcr_join_levels, bcr_join_max_workgroups): on / off,
-  // the workgroup budget of a joined level, and (host memory, optional) where a whole-band solve leaves [its joined levels, += them]
+  // cyclic reduction, levels as one launch (kernels_bcr.hip: bcr_level_joined, bcr_level0_behind_build; options bcr_join_levels,
+  // bcr_join_max_workgroups): the option's value (0: off; 2: the levels above level 0 only), the workgroup budget of a joined level, and
+  // (host memory, optional) where a whole-band solve leaves [its joined levels, += them, 1 if level 0 joined behind a plain build, += that]
   int bcr_join = 0, bcr_join_budget = 0; int64_t* bcr_joined = nullptr;
   // cyclic reduction, the level below the top one inside the last block's launch (kernels_bcr.hip: bcr_fold_level; option bcr_fold_back):
   // on / off, and (host memory, optional) where a whole-band solve leaves [1 if it folded, += that]

@@ -531,6 +531,13 @@ int oicc_debug_bcr_join_info(oicc_problem* p, int64_t out4[4]) {
   out4[0] = p->bcr_joined[0]; out4[1] = p->bcr_joined[1]; out4[2] = sb.bcr_join_budget; out4[3] = sb.bcr_join;
   return OICC_OK;
 }
+// debug read-out (tests): out2 = [1 if level 0 of the last whole-band cyclic-reduction solve ran as one launch behind a plain build launch
+// (kernels_bcr.hip: bcr_level0_behind_build), the solves whose level 0 did so far]; oicc_debug_bcr_join_info counts the levels above it
+int oicc_debug_bcr_level0_info(oicc_problem* p, int64_t out2[2]) {
+  if (!p || !out2) return OICC_ERR_INVALID_ARG;
+  out2[0] = p->bcr_joined[2]; out2[1] = p->bcr_joined[3];
+  return OICC_OK;
+}
 // debug read-out (tests): out3 = [1 if the last whole-band cyclic-reduction solve ran a back-substitution level inside the last block's
 // launch (bcri_last_backward_kernel), the solves that did so far, option bcr_fold_back]
 int oicc_debug_bcr_fold_info(oicc_problem* p, int64_t out3[3]) {

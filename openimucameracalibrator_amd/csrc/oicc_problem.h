@@ -178,7 +178,7 @@ struct oicc_problem {
   // Tables once per parameter vector pay when the tiles run in several rounds (every tile would recompute its halo pairs and wait
   // 1.2 us for them); on a one-round problem the dependent chain they add to the retraction kernel (+9 us at C2) costs more.
   int n_cu = 256;
-  int64_t bcr_joined[2] = {0, 0};   // cyclic-reduction levels that ran as one launch: in the last whole-band solve, in all of them (oicc_debug_bcr_join_info)
+  int64_t bcr_joined[4] = {0, 0, 0, 0};   // cyclic-reduction levels that ran as one launch: in the last whole-band solve, in all of them (oicc_debug_bcr_join_info); [2..3]: the same for a level 0 that joined behind a plain build launch, counted apart (oicc_debug_bcr_level0_info)
   int64_t bcr_folded[2] = {0, 0};   // whether the last whole-band cyclic-reduction solve folded a back-substitution level into the last block's launch; solves that did (oicc_debug_bcr_fold_info)
   bool seg_precomputed() const { const int force = int(opt.debug_seg_precompute); return force == 1 || (force == 0 && tp.n_tiles > n_cu); }
   DevBuf<int32_t> d_corner_view, d_corner_pt, d_view_s_so3, d_view_s_r3;

@@ -87,7 +87,7 @@ SolveBuffers solve_buffers(oicc_problem* p, long long* prof) {
   SolveBuffers sb{p->d_Mb.p, p->d_Mt.p, p->d_Mc.p, p->d_scale.p, p->d_diag.p, p->d_D2.p, p->d_step.p, p->d_state.p, prof, p->d_ws.p, (int64_t)p->d_ws.n, int(p->opt.solver_partitions), int(p->opt.solver_algorithm)};
   sb.radius = 0.0; sb.bcr_max_border = int(p->opt.bcr_max_border); sb.bcr_delay = int(p->opt.debug_bcr_delay);
   const int join_max = int(p->opt.bcr_join_max_workgroups);
-  sb.bcr_join = p->opt.bcr_join_levels != 0.0 ? 1 : 0; sb.bcr_join_budget = join_max > 0 ? join_max : p->n_cu; sb.bcr_joined = p->bcr_joined;
+  sb.bcr_join = int(p->opt.bcr_join_levels); sb.bcr_join_budget = join_max > 0 ? join_max : p->n_cu; sb.bcr_joined = p->bcr_joined;
   sb.bcr_fold = p->opt.bcr_fold_back != 0.0 ? 1 : 0; sb.bcr_folded = p->bcr_folded;
   return sb;
 }

@@ -383,12 +383,17 @@ class SplineTrajectoryEstimator:
     def BcrJoinInfo(self):
         """Debug read-out (device library only): levels of the last whole-band cyclic-reduction solve that ran as one launch
         (inversion and Schur updates joined), such levels in all solves so far, the workgroup budget of a joined level, whether
-        option bcr_join_levels is on."""
+        option bcr_join_levels is on.  last / total count the levels above level 0; level0_last / level0_total: whether level 0 of the
+        last solve ran as one launch behind a plain build launch (oicc_debug_bcr_level0_plan), the solves whose level 0 did."""
         fn = self._b.lib.oicc_debug_bcr_join_info
         fn.restype = C.c_int; fn.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
         out = (C.c_int64 * 4)()
         self._ck(fn(self._h, out))
-        return dict(last=int(out[0]), total=int(out[1]), budget=int(out[2]), on=bool(out[3]))
+        fn0 = self._b.lib.oicc_debug_bcr_level0_info
+        fn0.restype = C.c_int; fn0.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        out0 = (C.c_int64 * 2)()
+        self._ck(fn0(self._h, out0))
+        return dict(last=int(out[0]), total=int(out[1]), budget=int(out[2]), on=bool(out[3]), level0_last=int(out0[0]), level0_total=int(out0[1]))
 
     def BcrFoldInfo(self):
         """Debug read-out (device library only): whether the last whole-band cyclic-reduction solve ran the back substitution of the
