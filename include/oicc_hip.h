@@ -1041,6 +1041,53 @@ int oicc_stab_frames_device(void* hip_stream, const oicc_rs_scene* scene, const 
 int oicc_debug_stab_zoom(int32_t num_frames, const double* frame_t, const double* required_zoom, const int32_t* frame_status,
                          const oicc_stab_options* options, double* zoom, uint8_t* zoom_clamped);
 
+/* ---- horizon lock: the smooth camera levelled by gravity from the accelerometer (stabilization.hip) -------------------------
+ * The smooth camera of the section above still carries the roll the operator held.  With the accelerometer the plan can take it
+ * out: a different correction_q from the same path and smooth camera; the zoom and the warp are the section above's, unchanged.
+ * Specified step by step by tests/horizon_restatement.py and DESIGN.md ("Horizon lock").
+ *   Input.  accl [num_accl][3] is the corrected specific force MS_a (a_m - b_a) in the IMU frame, m/s^2: at rest it points up.
+ *   accl_t [num_accl] are its times in the IMU clock, strictly increasing; they need not be the gyroscope's.
+ *   G1.  Per sample j and on-path frame k, s_jk = ((accl_t[j] - frame_t[k]) + time_offset) - reference_row line_delay_s.  The
+ *   sample's frame k(j) is the last on-path frame with s_jk >= 0; a sample before the first on-path frame's reference time or
+ *   behind the last one's is unused (NaN vector, frame -1).  D_j is the chain D_k of the path with the sample's time in place of
+ *   t_ref,k+1: through the partial interval of t_ref,k, the whole gyro intervals and the partial interval that holds the sample, the
+ *   last i <= n - 2 with tau_i(k) <= s_jk, entered by s_jk - tau_i(k).  q_j = normalised(path_k D_j) and
+ *   u_j = R(q_j) (R(q_i_c)^T a_j): the sample in the frame of the path.  Gate g_j = 1 if accl_gate == 0 or
+ *   | |a_j| - gravity_const | <= accl_gate, else 0.
+ *   G2.  Per on-path frame k the window is the used samples with |s_jk| <= 3 gravity_sigma_s, w = exp(-s^2 / (2 sigma_g^2)) g_j;
+ *   gbar_k = sum w u / sum w; gravity_samples[k] counts the window's samples with g_j = 1.  level_status[k] = 2 when that count is 0
+ *   or |gbar_k| < 0.5 gravity_const (and for frames off the path): no angle, NaN up and roll.  Otherwise
+ *   up_k = R(S_k)^T gbar_k / |gbar_k| is up in the smooth camera (x right, y down, z forward), h = sqrt(up_x^2 + up_y^2),
+ *   roll_k = atan2(up_x, -up_y), fade = clamp((h - sin 10 deg) / (sin 20 deg - sin 10 deg), 0, 1).  level_status[k] = 1 when
+ *   h < sin 10 deg: the camera looks along gravity, the roll is undefined and not applied.  Otherwise status 0 and
+ *   level_angle_k = lock fade wrap(roll_k - roll_rad), wrap into (-pi, pi] (roll_rad is reduced by the IEEE remainder of 2 pi first).
+ *   L_k = normalised(S_k (cos angle/2, 0, 0, sin angle/2)); C_k = path_k^-1 L_k, normalised, w >= 0, then the max_correction_rad
+ *   clamp of the section above.  A frame whose angle is exactly 0 (lock 0, status 1 or 2, a level camera) keeps level_q = smooth_q
+ *   and the correction_q of oicc_stab_plan bit for bit.  This also runs at smoothing_sigma_s = 0 or a window of one frame, where
+ *   S_k = path_k.  smooth_q stays the mean.  A partial lock is discontinuous at roll = +-pi (camera upside down): not solved.
+ *   G3.  Required and applied zoom as in the section above, from the new C_k.
+ *
+ * oicc_stab_plan_level: oicc_stab_plan with a level (NULL: no horizon lock; every common output is oicc_stab_plan's bit for bit,
+ *   level_q = smooth_q, NaN up and roll, zeros elsewhere) and six more arrays: level_q [num_frames][4], up [num_frames][3], roll,
+ *   level_angle [num_frames], gravity_samples, level_status [num_frames].  device_ms (may be NULL) [5]: path, smoothing, zoom,
+ *   G1 and G2 kernels.
+ * oicc_debug_stab_accl_world: G1 alone: world [num_accl][3], frame_of [num_accl].
+ * OICC_ERR_INVALID_ARG for everything oicc_stab_plan refuses, num_accl < 1, null arrays, accelerometer times that do not strictly
+ * increase, non-finite samples, gravity_sigma_s <= 0, gravity_const <= 0, accl_gate < 0, lock outside [0, 1] or a non-finite
+ * roll_rad.  Arguments are judged before the device is looked for; OICC_ERR_NO_DEVICE without one (no CPU fallback). */
+typedef struct oicc_stab_level {
+  int64_t num_accl;
+  const double* accl_t;              /* [num_accl] seconds, IMU clock, strictly increasing */
+  const double* accl;                /* [num_accl][3] corrected specific force, IMU frame, m/s^2 */
+  double gravity_sigma_s, gravity_const, accl_gate, lock, roll_rad;
+} oicc_stab_level;
+int oicc_stab_plan_level(int32_t device_ordinal, const oicc_rs_scene* scene, const oicc_stab_options* options, const oicc_stab_level* level,
+                         double* path_q, double* smooth_q, double* correction_q, double* required_zoom, double* zoom, int32_t* iterations,
+                         int32_t* frame_status, uint8_t* zoom_clamped, double* level_q, double* up, double* roll, double* level_angle,
+                         int32_t* gravity_samples, int32_t* level_status, double* device_ms);
+int oicc_debug_stab_accl_world(int32_t device_ordinal, const oicc_rs_scene* scene, const oicc_stab_level* level, double* world,
+                               int32_t* frame_of);
+
 /* ---- the elimination plan of the block cyclic reduction (kernels_bcr.hip), host arithmetic only: needs no device ----------
  * The damped LM system of n 64-column blocks is reduced level by level.  Level l: the active blocks are origin + k stride,
  * k < active; those with k mod 2 == parity are its pivots (parity 0 when `active` is odd -- both ends are pivots --, else 1;

@@ -524,22 +524,36 @@ class StabOptions(C.Structure):
 
 c_stab_options = C.POINTER(StabOptions)
 
+
+class StabLevel(C.Structure):
+    """oicc_stab_level (include/oicc_hip.h): the accelerometer samples and the options of the horizon lock."""
+    _fields_ = [("num_accl", C.c_int64), ("accl_t", c_dp), ("accl", c_dp), ("gravity_sigma_s", C.c_double), ("gravity_const", C.c_double),
+                ("accl_gate", C.c_double), ("lock", C.c_double), ("roll_rad", C.c_double)]
+
+
+c_stab_level = C.POINTER(StabLevel)
+
 # Stabilisation (oicc_stab_* in include/oicc_hip.h), a table of its own like ROLLING_SHUTTER_SIGNATURES.
 STABILIZATION_SIGNATURES = {
     "plan": (C.c_int, [C.c_int32, c_scene, c_stab_options, c_dp, c_dp, c_dp, c_dp, c_dp, c_i32p, c_i32p, c_u8p, c_dp]),
     "map": (C.c_int, [C.c_int32, c_scene, c_dp, c_dp, c_fp, c_u8p, c_u8p, c_i32p, c_i64p, c_dp]),
     "frames": (C.c_int, [C.c_int32, c_scene, c_dp, c_dp, C.c_int32, c_u8p, C.c_int32, C.c_int32, c_u8p, c_i32p, C.POINTER(RsFramesReport)]),
     "frames_device": (C.c_int, [C.c_void_p, c_scene, c_dp, c_dp, C.c_int32, c_u8p, C.c_int32, c_u8p, c_i32p]),
+    # oicc_stab_plan with a level and, behind its outputs, level_q, up, roll, level_angle, gravity_samples, level_status
+    "plan_level": (C.c_int, [C.c_int32, c_scene, c_stab_options, c_stab_level, c_dp, c_dp, c_dp, c_dp, c_dp, c_i32p, c_i32p, c_u8p,
+                             c_dp, c_dp, c_dp, c_dp, c_i32p, c_i32p, c_dp]),
 }
-# host arithmetic only (oicc_debug_stab_zoom): the applied zoom from the required one
+# oicc_debug_stab_zoom: the applied zoom from the required one (host arithmetic only); oicc_debug_stab_accl_world: step G1 of the
+# horizon lock alone
 STABILIZATION_DEBUG_SIGNATURES = {
     "zoom": (C.c_int, [C.c_int32, c_dp, c_dp, c_i32p, c_stab_options, c_dp, c_u8p]),
+    "accl_world": (C.c_int, [C.c_int32, c_scene, c_stab_level, c_dp, c_i32p]),
 }
 
 
 class BoundStabilization:
-    """Bound oicc_stab_* entry points of one library + prefix (``oicc_stab_`` for liboicc_hip.so), and oicc_debug_stab_zoom as
-    ``debug_zoom``."""
+    """Bound oicc_stab_* entry points of one library + prefix (``oicc_stab_`` for liboicc_hip.so), and the oicc_debug_stab_* entries as
+    ``debug_zoom`` and ``debug_accl_world``."""
 
     def __init__(self, lib, prefix):
         self.lib = lib

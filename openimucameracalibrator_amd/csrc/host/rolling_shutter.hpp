@@ -50,6 +50,22 @@ inline void CorrectedGyro(const CameraTelemetryData& telemetry, const ThreeAxisS
   }
 }
 
+// MS_a (a_m - b_a), the correction of the accelerometer residual, in CorrectedGyro's order (the accelerometer's lower misalignments
+// are 0): t [n] seconds, accl [n][3] in m/s^2, up at rest
+inline void CorrectedAccl(const CameraTelemetryData& telemetry, const ThreeAxisSensorCalibParams& acc, std::vector<double>* t,
+                          std::vector<double>* accl) {
+  const double* m = acc.mis; const double* s = acc.scale;
+  const double MS[9] = {s[0], -m[0] * s[1], m[1] * s[2], m[3] * s[0], s[1], -m[2] * s[2], -m[4] * s[0], m[5] * s[1], s[2]};
+  const size_t n = telemetry.accelerometer.size();
+  t->resize(n); accl->resize(3 * n);
+  for (size_t i = 0; i < n; ++i) {
+    const ImuReading& r = telemetry.accelerometer[i];
+    const double d[3] = {r.v[0] - acc.bias[0], r.v[1] - acc.bias[1], r.v[2] - acc.bias[2]};
+    (*t)[i] = r.t_s;
+    for (int k = 0; k < 3; ++k) (*accl)[3 * i + size_t(k)] = (MS[3 * k] * d[0] + MS[3 * k + 1] * d[1]) + MS[3 * k + 2] * d[2];
+  }
+}
+
 // "<timestamp_ns>.png" -> t = name_ns 1e-9 + t_offset_cam_s (the first img_timestamps_ns of the telemetry, or 0): the rule the
 // calibration program applies to view keys.  false: the name is not a decimal number followed by .png
 inline bool FrameTimeFromName(const std::string& name, double t_offset_cam_s, double* t) {

@@ -37,16 +37,35 @@ inline std::string JsonNumber(double v) {
   return buf;
 }
 
-// names without quotes or backslashes (they are <timestamp_ns>.png).  One line per frame.
+// what oicc_stab_plan_level returns on top of oicc_stab_plan, over the frames
+struct LevelArrays {
+  std::vector<double> level_q, up, roll, level_angle;      // [n][4], [n][3], [n], [n]
+  std::vector<int32_t> gravity_samples, level_status;
+
+  explicit LevelArrays(size_t n = 0) : level_q(4 * n), up(3 * n), roll(n), level_angle(n), gravity_samples(n), level_status(n) {}
+};
+
+// names without quotes or backslashes (they are <timestamp_ns>.png).  One line per frame.  level: the horizon lock is on, and
+// every frame also gets level_q, up, roll, level_angle, gravity_samples and level_status.
 inline std::string PlanJson(const std::vector<std::string>& names, const std::vector<int32_t>& status, const std::vector<double>& correction_q,
-                            const std::vector<double>& required_zoom, const std::vector<double>& zoom, const std::vector<uint8_t>& zoom_clamped) {
+                            const std::vector<double>& required_zoom, const std::vector<double>& zoom, const std::vector<uint8_t>& zoom_clamped,
+                            const LevelArrays* level = nullptr) {
   std::string s = "{\"frames\": [";
   for (size_t k = 0; k < names.size(); ++k) {
     s += k ? ",\n" : "\n";
     s += " {\"name\": \"" + names[k] + "\", \"status\": " + std::to_string(status[k]) + ", \"correction_q\": [";
     for (int c = 0; c < 4; ++c) s += (c ? ", " : "") + JsonNumber(correction_q[4 * k + size_t(c)]);
     s += "], \"required_zoom\": " + JsonNumber(required_zoom[k]) + ", \"zoom\": " + JsonNumber(zoom[k]) + ", \"zoom_clamped\": " +
-         std::to_string(int(zoom_clamped[k])) + "}";
+         std::to_string(int(zoom_clamped[k]));
+    if (level) {
+      s += ", \"level_q\": [";
+      for (int c = 0; c < 4; ++c) s += (c ? ", " : "") + JsonNumber(level->level_q[4 * k + size_t(c)]);
+      s += "], \"up\": [";
+      for (int c = 0; c < 3; ++c) s += (c ? ", " : "") + JsonNumber(level->up[3 * k + size_t(c)]);
+      s += "], \"roll\": " + JsonNumber(level->roll[k]) + ", \"level_angle\": " + JsonNumber(level->level_angle[k]) + ", \"gravity_samples\": " +
+           std::to_string(level->gravity_samples[k]) + ", \"level_status\": " + std::to_string(level->level_status[k]);
+    }
+    s += "}";
   }
   s += "\n]}\n";
   return s;

@@ -5,13 +5,19 @@
 //                    [--reference_row Y] [--undistort] [--balance 0] [--output_camera_json F] [--device 0]
 //                    [--smoothing_s 0.5] [--max_correction_deg 0] [--zoom_mode none|fixed|dynamic] [--zoom_window_s 1]
 //                    [--max_zoom 4] [--output_plan_json F]
+//                    [--horizon_lock 0] [--horizon_roll_deg 0] [--gravity_window_s 1] [--gravity_const 9.811104] [--accl_gate 0]
 //
 // The flags and files of rectify_rolling_shutter.  The destination is always the rectified pinhole of --balance (--undistort is
 // accepted and changes nothing).  oicc_stab_plan sees the times of every <timestamp_ns>.png of the folder, in the order of their
 // times: the orientation path, the smooth camera (--smoothing_s: sigma of the Gaussian window; --max_correction_deg: 0 = no bound)
 // and the zoom (--zoom_mode, --zoom_window_s, --max_zoom).  Then the frames are read in chunks and oicc_stab_frames warps each
 // chunk with its part of the plan (include/oicc_hip.h "stabilisation": rotation only).  --output_plan_json receives, per frame,
-// name, status, correction quaternion, required and applied zoom.  Frames without gyro coverage are not written: they are listed
+// name, status, correction quaternion, required and applied zoom.  --horizon_lock X in (0, 1] turns the horizon lock on
+// (oicc_stab_plan_level): the accelerometer of the telemetry, corrected by the accelerometer part of --imu_intrinsics and
+// --imu_bias_file, gives gravity over a Gaussian window of sigma --gravity_window_s, and the part X of the smooth camera's roll
+// against --horizon_roll_deg is taken out (--accl_gate G: samples whose norm is further than G from --gravity_const are left out;
+// 0 = no gate); the plan file then also holds level_q, up, roll, level_angle, gravity_samples and level_status per frame.  With
+// --horizon_lock 0 the PNGs and the plan file are what they are without these flags.  Frames without gyro coverage are not written: they are listed
 // on stderr with the reason.  The twin of openimucameracalibrator_amd/stabilize_frames.py: the same PNGs, the same plan file.
 // The reference has no such application.
 #include <dirent.h>
@@ -62,7 +68,8 @@ static int run_main(int argc, char* argv[]) {
   Flags F({{"input_path", ""}, {"telemetry_json", ""}, {"camera_calibration_json", ""}, {"imu_camera_calibration_json", ""}, {"line_delay_us", ""},
            {"time_offset_imu_to_cam_s", ""}, {"imu_intrinsics", ""}, {"imu_bias_file", ""}, {"reference_row", ""}, {"undistort", "false"},
            {"balance", "0"}, {"output_camera_json", ""}, {"output_path", ""}, {"device", "0"}, {"smoothing_s", "0.5"}, {"max_correction_deg", "0"},
-           {"zoom_mode", "fixed"}, {"zoom_window_s", "1"}, {"max_zoom", "4"}, {"output_plan_json", ""}});
+           {"zoom_mode", "fixed"}, {"zoom_window_s", "1"}, {"max_zoom", "4"}, {"output_plan_json", ""}, {"horizon_lock", "0"}, {"horizon_roll_deg", "0"},
+           {"gravity_window_s", "1"}, {"gravity_const", "9.811104"}, {"accl_gate", "0"}});
   if (!F.parse(argc, argv)) return 2;
   const std::string input = F.str("input_path"), output = F.str("output_path"), calib_json = F.str("camera_calibration_json");
   const int device = std::stoi(F.str("device"));
@@ -117,7 +124,22 @@ static int run_main(int argc, char* argv[]) {
   std::vector<int32_t> iterations(total), plan_status(total);
   std::vector<uint8_t> clamped(total);
   scene.frame_t = times;
-  {
+  const bool horizon = F.d("horizon_lock") != 0.0;            // off: the plan and its file as without the horizon lock
+  sth::LevelArrays levelled(horizon ? total : 0);
+  if (horizon) {
+    std::vector<double> accl_t, accl;
+    rsh::CorrectedAccl(telemetry, acc_intr, &accl_t, &accl);
+    oicc_stab_level level;
+    level.num_accl = int64_t(accl_t.size()); level.accl_t = accl_t.data(); level.accl = accl.data();
+    level.gravity_sigma_s = F.d("gravity_window_s"); level.gravity_const = F.d("gravity_const"); level.accl_gate = F.d("accl_gate");
+    level.lock = F.d("horizon_lock"); level.roll_rad = F.d("horizon_roll_deg") * kPi / 180.0;
+    const oicc_rs_scene c = scene.c();
+    const int rc = oicc_stab_plan_level(device, &c, &opt, &level, path_q.data(), smooth_q.data(), correction_q.data(), required.data(), zoom.data(),
+                                        iterations.data(), plan_status.data(), clamped.data(), levelled.level_q.data(), levelled.up.data(),
+                                        levelled.roll.data(), levelled.level_angle.data(), levelled.gravity_samples.data(),
+                                        levelled.level_status.data(), nullptr);
+    CHECK_MSG(rc == OICC_OK, "oicc_stab_plan_level failed (" << rc << ")");
+  } else {
     const oicc_rs_scene c = scene.c();
     const int rc = oicc_stab_plan(device, &c, &opt, path_q.data(), smooth_q.data(), correction_q.data(), required.data(), zoom.data(), iterations.data(),
                                   plan_status.data(), clamped.data(), nullptr);
@@ -125,7 +147,7 @@ static int run_main(int argc, char* argv[]) {
   }
   if (!F.str("output_plan_json").empty()) {
     std::ofstream f(F.str("output_plan_json"), std::ios::binary);
-    f << sth::PlanJson(names, plan_status, correction_q, required, zoom, clamped);
+    f << sth::PlanJson(names, plan_status, correction_q, required, zoom, clamped, horizon ? &levelled : nullptr);
     CHECK_MSG(bool(f), "cannot write " << F.str("output_plan_json"));
   }
   mkdir(output.c_str(), 0777);

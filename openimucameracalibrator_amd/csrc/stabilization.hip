@@ -8,6 +8,10 @@
 //                           applies its prefix; every path quaternion is normalised once at the end.
 //   stab_smooth_kernel      one wave per on-path frame, lanes across the window members (strided by 64): the weighted intrinsic
 //                           mean by a fixed butterfly, then the correction C_k and its clamp.
+//   stab_accl_world_kernel  horizon lock, one lane per accelerometer sample: the orientation at the sample by the delta kernel's chain
+//                           from its frame's t_ref, and the corrected specific force in the path's frame; the gate.
+//   stab_level_kernel       horizon lock, one wave per on-path frame, lanes across the gravity window (strided by 64): the weighted mean
+//                           of those vectors by the same butterfly, up and roll in the smooth camera, the levelled camera and its C_k.
 //   stab_record_kernel      one lane per frame: M_k = R(C_k) R9 and the scaled focal length and skew.
 //   stab_zoom_kernel        one lane per (frame, border point), the frame in the grid's y, its table in LDS: the march from the
 //                           centre and the bisection; the minimum per wave.  stab_zoom_min_kernel: per frame, z = 1 / min s.
@@ -37,6 +41,8 @@ constexpr int kMeanIterations = 16;
 constexpr double kMeanTol = 1e-12;       // rad
 constexpr int kMarch = 32;               // samples from the centre to a border point
 constexpr int kBisections = 16;
+constexpr double kPi = 3.141592653589793, kTwoPi = 6.283185307179586;
+constexpr double kSin10 = 0.17364817766693033, kSin20 = 0.3420201433256687;      // the horizon lock fades in between these tilts
 
 struct StabRecord { double M[9], f, skew; };      // per frame: R(C_k) R9, f Z_k, skew Z_k
 
@@ -67,6 +73,32 @@ __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) v = v + __shfl_xor(v, d, 64);
   return v;
+}
+
+// R(q) v, rows summed from the left
+__device__ __forceinline__ void qrotate(const Q4& q, const double v[3], double o[3]) {
+  double M[9];
+  rotation_matrix(q, M);
+  for (int r = 0; r < 3; ++r) o[r] = (M[3 * r] * v[0] + M[3 * r + 1] * v[1]) + M[3 * r + 2] * v[2];
+}
+
+// into (-pi, pi], for |d| <= 2 pi
+__device__ __forceinline__ double wrap_angle(double d) {
+  if (d > kPi) d = d - kTwoPi;
+  if (d <= -kPi) d = d + kTwoPi;
+  return d;
+}
+
+// C = path^-1 L, normalised, w >= 0, shortened along its own axis to max_correction (0: no bound): the rule of stab_smooth_kernel
+__device__ __forceinline__ Q4 correction_of(const Q4& path, const Q4& L, double max_correction) {
+  Q4 Cq = qnormalized(qmul(qconj(path), L));
+  if (Cq.w < 0.0) Cq = Q4{-Cq.w, -Cq.x, -Cq.y, -Cq.z};
+  const double n = sqrt((Cq.x * Cq.x + Cq.y * Cq.y) + Cq.z * Cq.z);
+  if (max_correction > 0.0 && 2.0 * atan2(n, Cq.w) > max_correction) {
+    const double h = max_correction / 2.0, sn = sin(h) / n;
+    Cq = Q4{cos(h), sn * Cq.x, sn * Cq.y, sn * Cq.z};
+  }
+  return Cq;
 }
 
 // delta [pairs][4]: pair i joins the on-path frames first + i and first + i + 1; interval [frames]: the gyro interval of t_ref
@@ -175,6 +207,114 @@ __global__ __launch_bounds__(kThreads) void stab_smooth_kernel(int count, int fi
     s[0] = S.w; s[1] = S.x; s[2] = S.y; s[3] = S.z;
     c[0] = Cq.w; c[1] = Cq.x; c[2] = Cq.y; c[3] = Cq.z;
     iterations[k] = it;
+  }
+}
+
+// G1 of the horizon lock, one lane per accelerometer sample.  frame_of [na]: the sample's on-path frame k or -1; sample_interval [na]:
+// its gyro interval; interval [frames]: the gyro interval of t_ref.  The chain is stab_path_delta_kernel's with the sample's time in
+// place of t_ref,k+1.  world [na][3] = R(path_k D_j) R(q_i_c)^T a_j, NaN for an unused sample; gate [na] 1 / 0.
+__global__ __launch_bounds__(kThreads) void stab_accl_world_kernel(int64_t na, const double* __restrict__ accl_t, const double* __restrict__ accl,
+                                                                   const int32_t* __restrict__ frame_of, const int64_t* __restrict__ sample_interval,
+                                                                   const double* __restrict__ gyro_t, const double* __restrict__ rates,
+                                                                   const double* __restrict__ frame_t, const int64_t* __restrict__ interval,
+                                                                   const double* __restrict__ path, Rotation Ric, double time_offset, double reference_delay,
+                                                                   double gravity_const, double accl_gate, double* __restrict__ world,
+                                                                   uint8_t* __restrict__ gate) {
+  const int64_t j = int64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (j >= na) return;
+  const double a[3] = {accl[3 * j], accl[3 * j + 1], accl[3 * j + 2]};
+  const double norm = sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+  gate[j] = (accl_gate == 0.0 || fabs(norm - gravity_const) <= accl_gate) ? 1 : 0;
+  double* o = world + 3 * j;
+  const int k = frame_of[j];
+  if (k < 0) { o[0] = nan(""); o[1] = nan(""); o[2] = nan(""); return; }
+  const int64_t ja = interval[k], jb = sample_interval[j] > ja ? sample_interval[j] : ja;
+  const double s = ((accl_t[j] - frame_t[k]) + time_offset) - reference_delay;
+  const double sa = 0.0 - (((gyro_t[ja] - frame_t[k]) + time_offset) - reference_delay);
+  const double sb = s - (((gyro_t[jb] - frame_t[k]) + time_offset) - reference_delay);
+  const double dta = gyro_t[ja + 1] - gyro_t[ja];
+  Q4 q = qconj(interval_exp(rates + 3 * ja, rates + 3 * ja + 3, dta, sa));
+  if (ja == jb) {
+    q = qmul(q, interval_exp(rates + 3 * ja, rates + 3 * ja + 3, dta, sb));
+  } else {
+    q = qmul(q, interval_exp(rates + 3 * ja, rates + 3 * ja + 3, dta, dta));
+    for (int64_t i = ja + 1; i < jb; ++i) {
+      const double dt = gyro_t[i + 1] - gyro_t[i];
+      q = qmul(q, interval_exp(rates + 3 * i, rates + 3 * i + 3, dt, dt));
+    }
+    q = qmul(q, interval_exp(rates + 3 * jb, rates + 3 * jb + 3, gyro_t[jb + 1] - gyro_t[jb], sb));
+  }
+  const double* p = path + 4 * int64_t(k);
+  q = qnormalized(qmul(Q4{p[0], p[1], p[2], p[3]}, q));
+  double cam[3];
+  for (int c = 0; c < 3; ++c) cam[c] = (Ric.r[c] * a[0] + Ric.r[3 + c] * a[1]) + Ric.r[6 + c] * a[2];      // R(q_i_c)^T a
+  qrotate(q, cam, o);
+}
+
+// G2 of the horizon lock, one wave per on-path frame, lanes across the gravity window (strided by 64): the weighted mean of the world
+// vectors by the fixed butterfly, up and roll in the smooth camera, the levelled camera L_k and its correction.  win_lo / win_hi:
+// sample indices, both ends included (hi < lo: empty).  A frame whose angle is 0 keeps smooth_q as level_q and the correction it has.
+__global__ __launch_bounds__(kThreads) void stab_level_kernel(int count, int first, const double* __restrict__ frame_t, const double* __restrict__ accl_t,
+                                                              const double* __restrict__ world, const uint8_t* __restrict__ gate,
+                                                              const int64_t* __restrict__ win_lo, const int64_t* __restrict__ win_hi,
+                                                              const double* __restrict__ path, const double* __restrict__ smooth, double time_offset,
+                                                              double reference_delay, double sigma, double gravity_const, double lock, double roll_wanted,
+                                                              double max_correction, double* __restrict__ level_q, double* __restrict__ correction,
+                                                              double* __restrict__ up, double* __restrict__ roll, double* __restrict__ angle,
+                                                              int32_t* __restrict__ samples, int32_t* __restrict__ status) {
+  const int lane = threadIdx.x & 63;
+  const int i = blockIdx.x * kWaves + (threadIdx.x >> 6);
+  if (i >= count) return;                                  // whole waves leave
+  const int k = first + i;
+  const int64_t lo = win_lo[k], hi = win_hi[k];
+  const double tk = frame_t[k], den = 2.0 * (sigma * sigma);
+  double sw = 0.0, a0 = 0.0, a1 = 0.0, a2 = 0.0, cnt = 0.0;
+  for (int64_t m = lo + lane; m <= hi; m += 64) {
+    const double s = ((accl_t[m] - tk) + time_offset) - reference_delay;
+    const double g = double(gate[m]);
+    const double w = exp(-(s * s) / den) * g;
+    const double* u = world + 3 * m;
+    sw = sw + w; a0 = a0 + w * u[0]; a1 = a1 + w * u[1]; a2 = a2 + w * u[2]; cnt = cnt + g;
+  }
+  sw = wave_sum(sw); a0 = wave_sum(a0); a1 = wave_sum(a1); a2 = wave_sum(a2); cnt = wave_sum(cnt);
+  auto load = [&](const double* b) { return Q4{b[4 * int64_t(k)], b[4 * int64_t(k) + 1], b[4 * int64_t(k) + 2], b[4 * int64_t(k) + 3]}; };
+  const Q4 S = load(smooth);
+  Q4 L = S;
+  double nu[3] = {nan(""), nan(""), nan("")}, rho = nan(""), theta = 0.0;
+  int st = 2;
+  if (cnt > 0.0) {
+    const double gm[3] = {a0 / sw, a1 / sw, a2 / sw};
+    const double norm = sqrt((gm[0] * gm[0] + gm[1] * gm[1]) + gm[2] * gm[2]);
+    if (!(norm < 0.5 * gravity_const)) {
+      const double n[3] = {gm[0] / norm, gm[1] / norm, gm[2] / norm};
+      double M[9];
+      rotation_matrix(S, M);
+      for (int c = 0; c < 3; ++c) nu[c] = (M[c] * n[0] + M[3 + c] * n[1]) + M[6 + c] * n[2];        // R(S_k)^T: up in the smooth camera
+      const double h = sqrt(nu[0] * nu[0] + nu[1] * nu[1]);
+      rho = atan2(nu[0], -nu[1]);
+      st = h < kSin10 ? 1 : 0;
+      if (st == 0) {
+        const double fade = fmin(fmax((h - kSin10) / (kSin20 - kSin10), 0.0), 1.0);
+        theta = (lock * fade) * wrap_angle(rho - roll_wanted);
+        if (theta == 0.0) theta = 0.0;                     // no -0
+      }
+    }
+  }
+  Q4 Cq = {1.0, 0.0, 0.0, 0.0};
+  if (theta != 0.0) {
+    const double half = theta / 2.0;
+    L = qnormalized(qmul(S, Q4{cos(half), 0.0, 0.0, sin(half)}));
+    Cq = correction_of(load(path), L, max_correction);
+  }
+  if (lane == 0) {
+    double* l = level_q + 4 * int64_t(k);
+    l[0] = L.w; l[1] = L.x; l[2] = L.y; l[3] = L.z;
+    if (theta != 0.0) {
+      double* c = correction + 4 * int64_t(k);
+      c[0] = Cq.w; c[1] = Cq.x; c[2] = Cq.y; c[3] = Cq.z;
+    }
+    up[3 * int64_t(k)] = nu[0]; up[3 * int64_t(k) + 1] = nu[1]; up[3 * int64_t(k) + 2] = nu[2];
+    roll[k] = rho; angle[k] = theta; samples[k] = int32_t(cnt); status[k] = st;
   }
 }
 
@@ -465,20 +605,13 @@ void applied_zoom(int frames, const double* t, const double* z, const int32_t* s
   }
 }
 
-}  // namespace
-
-extern "C" int oicc_stab_plan(int32_t device_ordinal, const oicc_rs_scene* scene, const oicc_stab_options* options, double* path_q, double* smooth_q,
-                              double* correction_q, double* required_zoom, double* zoom, int32_t* iterations, int32_t* frame_status,
-                              uint8_t* zoom_clamped, double* device_ms) {
-  Judged J;
-  if (int rc = judge_scene(scene, &J)) return rc;
-  if (!options_ok(options) || !path_q || !smooth_q || !correction_q || !required_zoom || !zoom || !iterations || !frame_status || !zoom_clamped)
-    return OICC_ERR_INVALID_ARG;
+// the path by time comparisons: tau_j = ((t_j - t_k) + offset) - reference delay, on the path when tau_0 <= 0 <= tau_{n-1};
+// interval [frames]: the gyro interval of t_ref
+int find_path(const oicc_rs_scene* scene, const Judged& J, std::vector<int64_t>* interval, int* first_out, int* count_out) {
   const int F = J.num_frames;
   const int64_t n = J.num_gyro;
-  const double off = J.P.time_offset, refd = J.P.reference_row * J.P.line_delay, sigma = options->smoothing_sigma_s;
-  // the path by time comparisons: tau_j = ((t_j - t_k) + offset) - reference delay, on the path when tau_0 <= 0 <= tau_{n-1}
-  std::vector<int64_t> interval(size_t(F), 0);
+  const double off = J.P.time_offset, refd = J.P.reference_row * J.P.line_delay;
+  interval->assign(size_t(F), 0);
   int first = 0, count = 0;
   for (int k = 0; k < F; ++k) {
     auto tau = [&](int64_t j) { return ((scene->gyro_t[j] - scene->frame_t[k]) + off) - refd; };
@@ -488,8 +621,132 @@ extern "C" int oicc_stab_plan(int32_t device_ordinal, const oicc_rs_scene* scene
     ++count;
     int64_t b = 0, e = n;                                       // number of samples with tau_j <= 0
     while (b < e) { const int64_t m = (b + e) / 2; if (tau(m) <= 0.0) b = m + 1; else e = m; }
-    interval[size_t(k)] = std::min(b - 1, n - 2);
+    (*interval)[size_t(k)] = std::min(b - 1, n - 2);
   }
+  *first_out = first; *count_out = count;
+  return OICC_OK;
+}
+
+// the delta and the scan kernel: d_path [frames][4] gets the on-path frames
+int launch_path(const Judged& J, hipStream_t st, const Prepared& D, const int64_t* d_interval, int first, int count, double* d_delta, double* d_path) {
+  if (count < 1) return OICC_OK;
+  if (count > 1) {
+    hipLaunchKernelGGL(stab_path_delta_kernel, dim3(blocks_for(count - 1)), dim3(kThreads), 0, st, count - 1, first, D.gyro_t.p, D.rates.p, D.frame_t.p,
+                       d_interval, J.P.time_offset, J.P.reference_row * J.P.line_delay, d_delta);
+    OICC_HIP_TRY(hipGetLastError());
+  }
+  const int run = std::max(kMinRun, (count + kScanLanes - 1) / kScanLanes);
+  hipLaunchKernelGGL(stab_path_scan_kernel, dim3(1), dim3(kScanLanes), 0, st, count, run, d_delta, d_path + 4 * size_t(first));
+  OICC_HIP_TRY(hipGetLastError());
+  return OICC_OK;
+}
+
+bool level_ok(const oicc_stab_level* l) {
+  if (!l || l->num_accl < 1 || !l->accl_t || !l->accl || !all_finite(l->accl_t, l->num_accl) || !all_finite(l->accl, 3 * l->num_accl)) return false;
+  for (int64_t j = 1; j < l->num_accl; ++j) if (!(l->accl_t[j] > l->accl_t[j - 1])) return false;
+  return std::isfinite(l->gravity_sigma_s) && l->gravity_sigma_s > 0.0 && std::isfinite(l->gravity_const) && l->gravity_const > 0.0 &&
+         std::isfinite(l->accl_gate) && l->accl_gate >= 0.0 && l->lock >= 0.0 && l->lock <= 1.0 && std::isfinite(l->roll_rad);
+}
+
+// What the host decides for the horizon lock, by time comparisons only: s_jk = ((accl_t[j] - frame_t[k]) + offset) - reference delay
+struct LevelHost {
+  std::vector<int32_t> frame_of;            // [na] the last on-path frame with s_jk >= 0; -1 before the first reference time or behind the last
+  std::vector<int64_t> sample_interval;     // [na] the last gyro interval i <= n - 2 with tau_i(k) <= s_jk
+  std::vector<int64_t> win_lo, win_hi;      // [frames] the used samples with |s_jk| <= 3 sigma_g, both ends included; hi < lo: none
+  Rotation Ric;                             // R(q_i_c), the quaternion normalised first
+};
+
+void level_host(const oicc_rs_scene* scene, const Judged& J, const oicc_stab_level* l, int first, int count, LevelHost* H) {
+  const int64_t na = l->num_accl, n = J.num_gyro;
+  const int F = J.num_frames;
+  const double off = J.P.time_offset, refd = J.P.reference_row * J.P.line_delay, reach = 3.0 * l->gravity_sigma_s;
+  auto s = [&](int64_t j, int k) { return ((l->accl_t[j] - scene->frame_t[k]) + off) - refd; };
+  H->frame_of.assign(size_t(na), -1); H->sample_interval.assign(size_t(na), 0);
+  H->win_lo.assign(size_t(F), 0); H->win_hi.assign(size_t(F), -1);
+  {
+    const double* qi = scene->q_i_c;
+    const double norm = std::sqrt(((qi[0] * qi[0] + qi[1] * qi[1]) + qi[2] * qi[2]) + qi[3] * qi[3]);
+    const double w = qi[0] / norm, x = qi[1] / norm, y = qi[2] / norm, z = qi[3] / norm;
+    H->Ric = Rotation{{1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
+                       2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
+                       2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)}};
+  }
+  if (count < 1) return;
+  const int last = first + count - 1;
+  int64_t used_lo = na, used_hi = -1;
+  for (int64_t j = 0; j < na; ++j) {
+    if (!(s(j, first) >= 0.0) || s(j, last) > 0.0) continue;
+    int b = first, e = last + 1;                                 // number of on-path frames with s_jk >= 0, from `first`
+    while (b < e) { const int m = (b + e) / 2; if (s(j, m) >= 0.0) b = m + 1; else e = m; }
+    const int k = b - 1;
+    const double sj = s(j, k);
+    auto tau = [&](int64_t i) { return ((scene->gyro_t[i] - scene->frame_t[k]) + off) - refd; };
+    int64_t gb = 0, ge = n;                                      // number of gyro samples with tau_i <= s_jk
+    while (gb < ge) { const int64_t m = (gb + ge) / 2; if (tau(m) <= sj) gb = m + 1; else ge = m; }
+    H->frame_of[size_t(j)] = k;
+    H->sample_interval[size_t(j)] = std::max<int64_t>(std::min(gb - 1, n - 2), 0);
+    used_lo = std::min(used_lo, j); used_hi = j;
+  }
+  for (int k = first; k <= last && used_hi >= used_lo; ++k) {
+    int64_t b = used_lo, e = used_hi + 1;                        // the first used sample with s_jk >= -reach
+    while (b < e) { const int64_t m = (b + e) / 2; if (s(m, k) < -reach) b = m + 1; else e = m; }
+    const int64_t lo = b;
+    b = used_lo; e = used_hi + 1;                                // the number of used samples with s_jk <= reach, from used_lo
+    while (b < e) { const int64_t m = (b + e) / 2; if (s(m, k) <= reach) b = m + 1; else e = m; }
+    H->win_lo[size_t(k)] = lo; H->win_hi[size_t(k)] = b - 1;
+  }
+}
+
+// The device side of the horizon lock: the samples, what the host decided, the world vectors and the gate.
+struct LevelDevice {
+  oicc::DevBuf<double> accl_t, accl, world;
+  oicc::DevBuf<int32_t> frame_of;
+  oicc::DevBuf<int64_t> sample_interval, win_lo, win_hi;
+  oicc::DevBuf<uint8_t> gate;
+};
+
+// uploads and G1: the path must be on the stream already
+int launch_accl_world(const Judged& J, const oicc_stab_level* l, const LevelHost& H, hipStream_t st, const Prepared& D, const int64_t* d_interval,
+                      const double* d_path, LevelDevice* V) {
+  const size_t na = size_t(l->num_accl), f = size_t(J.num_frames);
+  OICC_HIP_TRY(V->accl_t.resize(na)); OICC_HIP_TRY(V->accl.resize(3 * na)); OICC_HIP_TRY(V->world.resize(3 * na)); OICC_HIP_TRY(V->gate.resize(na));
+  OICC_HIP_TRY(V->frame_of.resize(na)); OICC_HIP_TRY(V->sample_interval.resize(na)); OICC_HIP_TRY(V->win_lo.resize(f)); OICC_HIP_TRY(V->win_hi.resize(f));
+  OICC_HIP_TRY(hipMemcpyAsync(V->accl_t.p, l->accl_t, sizeof(double) * na, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(V->accl.p, l->accl, sizeof(double) * 3 * na, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(V->frame_of.p, H.frame_of.data(), sizeof(int32_t) * na, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(V->sample_interval.p, H.sample_interval.data(), sizeof(int64_t) * na, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(V->win_lo.p, H.win_lo.data(), sizeof(int64_t) * f, hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(V->win_hi.p, H.win_hi.data(), sizeof(int64_t) * f, hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(stab_accl_world_kernel, dim3(blocks_for(int64_t(na))), dim3(kThreads), 0, st, int64_t(na), V->accl_t.p, V->accl.p, V->frame_of.p,
+                     V->sample_interval.p, D.gyro_t.p, D.rates.p, D.frame_t.p, d_interval, d_path, H.Ric, J.P.time_offset,
+                     J.P.reference_row * J.P.line_delay, l->gravity_const, l->accl_gate, V->world.p, V->gate.p);
+  OICC_HIP_TRY(hipGetLastError());
+  return OICC_OK;
+}
+
+// What oicc_stab_plan_level returns on top of oicc_stab_plan
+struct LevelOut {
+  double *level_q, *up, *roll, *level_angle;
+  int32_t *gravity_samples, *level_status;
+};
+
+// oicc_stab_plan (level and out null) and oicc_stab_plan_level; device_ms [3] or [5]
+int plan_impl(int32_t device_ordinal, const oicc_rs_scene* scene, const oicc_stab_options* options, const oicc_stab_level* level, double* path_q,
+              double* smooth_q, double* correction_q, double* required_zoom, double* zoom, int32_t* iterations, int32_t* frame_status,
+              uint8_t* zoom_clamped, const LevelOut* out, double* device_ms) {
+  Judged J;
+  if (int rc = judge_scene(scene, &J)) return rc;
+  if (!options_ok(options) || !path_q || !smooth_q || !correction_q || !required_zoom || !zoom || !iterations || !frame_status || !zoom_clamped)
+    return OICC_ERR_INVALID_ARG;
+  if (out && (!out->level_q || !out->up || !out->roll || !out->level_angle || !out->gravity_samples || !out->level_status)) return OICC_ERR_INVALID_ARG;
+  if (level && !level_ok(level)) return OICC_ERR_INVALID_ARG;
+  const int F = J.num_frames;
+  const double sigma = options->smoothing_sigma_s;
+  std::vector<int64_t> interval;
+  int first = 0, count = 0;
+  if (int rc = find_path(scene, J, &interval, &first, &count)) return rc;
+  LevelHost H;
+  if (level) level_host(scene, J, level, first, count, &H);
   // the smoothing windows, frame indices with both ends included: t_ref,m - t_ref,k = frame_t[m] - frame_t[k]
   std::vector<int32_t> win_lo(size_t(F), 0), win_hi(size_t(F), 0);
   {
@@ -508,16 +765,25 @@ extern "C" int oicc_stab_plan(int32_t device_ordinal, const oicc_rs_scene* scene
   for (int k = 0; k < F; ++k) h_corr[size_t(4 * k)] = 1.0;
   const int points = border_points(J.P.dst_w, J.P.dst_h);
   const int waves = int(blocks_for(points)) * kWaves;
-  float ms[3] = {0.0f, 0.0f, 0.0f};
+  // the horizon lock's outputs as they are without a level: level_q = smooth_q (copied below), no up, no roll, angle 0
+  std::vector<double> h_level, h_up(size_t(3 * F), qnan), h_roll(size_t(F), qnan), h_angle(size_t(F), 0.0);
+  std::vector<int32_t> h_samples(size_t(F), 0), h_lstatus(size_t(F), level ? 2 : 0);
+  float ms[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   {
     Prepared D;
+    LevelDevice V;
     oicc::DevBuf<int64_t> d_interval;
-    oicc::DevBuf<int32_t> d_lo, d_hi, d_iter;
-    oicc::DevBuf<double> d_delta, d_path, d_smooth, d_wave, d_req;
-    oicc::Event e1, e2, e3;
+    oicc::DevBuf<int32_t> d_lo, d_hi, d_iter, d_samples, d_lstatus;
+    oicc::DevBuf<double> d_delta, d_path, d_smooth, d_wave, d_req, d_level, d_up, d_roll, d_angle;
+    oicc::Event e1, e2, e3, g1, g2, g3;
     oicc::Stream st;
     OICC_HIP_TRY(st.create());
     OICC_HIP_TRY(e1.create()); OICC_HIP_TRY(e2.create()); OICC_HIP_TRY(e3.create());
+    if (level) {
+      OICC_HIP_TRY(g1.create()); OICC_HIP_TRY(g2.create()); OICC_HIP_TRY(g3.create());
+      OICC_HIP_TRY(d_level.resize(size_t(4 * F))); OICC_HIP_TRY(d_up.resize(size_t(3 * F))); OICC_HIP_TRY(d_roll.resize(size_t(F)));
+      OICC_HIP_TRY(d_angle.resize(size_t(F))); OICC_HIP_TRY(d_samples.resize(size_t(F))); OICC_HIP_TRY(d_lstatus.resize(size_t(F)));
+    }
     OICC_HIP_TRY(d_interval.resize(size_t(F))); OICC_HIP_TRY(d_lo.resize(size_t(F))); OICC_HIP_TRY(d_hi.resize(size_t(F)));
     OICC_HIP_TRY(d_iter.resize(size_t(F))); OICC_HIP_TRY(d_delta.resize(size_t(4 * std::max(count - 1, 1))));
     OICC_HIP_TRY(d_path.resize(size_t(4 * F))); OICC_HIP_TRY(d_smooth.resize(size_t(4 * F)));
@@ -532,16 +798,7 @@ extern "C" int oicc_stab_plan(int32_t device_ordinal, const oicc_rs_scene* scene
     OICC_HIP_TRY(hipMemcpyAsync(D.correction.p, h_corr.data(), sizeof(double) * size_t(4 * F), hipMemcpyHostToDevice, st));
     OICC_HIP_TRY(hipMemcpyAsync(D.zoom.p, h_zoom.data(), sizeof(double) * size_t(F), hipMemcpyHostToDevice, st));
     if (int rc = launch_tables(J, st, &D)) return rc;          // ev[1]: the path starts here
-    if (count > 0) {
-      if (count > 1) {
-        hipLaunchKernelGGL(stab_path_delta_kernel, dim3(blocks_for(count - 1)), dim3(kThreads), 0, st, count - 1, first, D.gyro_t.p, D.rates.p, D.frame_t.p,
-                           d_interval.p, off, refd, d_delta.p);
-        OICC_HIP_TRY(hipGetLastError());
-      }
-      const int run = std::max(kMinRun, (count + kScanLanes - 1) / kScanLanes);
-      hipLaunchKernelGGL(stab_path_scan_kernel, dim3(1), dim3(kScanLanes), 0, st, count, run, d_delta.p, d_path.p + 4 * size_t(first));
-      OICC_HIP_TRY(hipGetLastError());
-    }
+    if (int rc = launch_path(J, st, D, d_interval.p, first, count, d_delta.p, d_path.p)) return rc;
     OICC_HIP_TRY(hipEventRecord(e1, st));
     if (count > 0) {
       hipLaunchKernelGGL(stab_smooth_kernel, dim3(unsigned((count + kWaves - 1) / kWaves)), dim3(kThreads), 0, st, count, first, D.frame_t.p, d_path.p, d_lo.p,
@@ -549,6 +806,26 @@ extern "C" int oicc_stab_plan(int32_t device_ordinal, const oicc_rs_scene* scene
       OICC_HIP_TRY(hipGetLastError());
     }
     OICC_HIP_TRY(hipEventRecord(e2, st));
+    if (level) {                                               // between the smoothing and the zoom: device_ms [3] and [4]
+      // level_q starts as smooth_q (NaN off the path), the rest as without gravity
+      OICC_HIP_TRY(hipMemcpyAsync(d_level.p, d_smooth.p, sizeof(double) * size_t(4 * F), hipMemcpyDeviceToDevice, st));
+      OICC_HIP_TRY(hipMemcpyAsync(d_up.p, h_up.data(), sizeof(double) * size_t(3 * F), hipMemcpyHostToDevice, st));
+      OICC_HIP_TRY(hipMemcpyAsync(d_roll.p, h_roll.data(), sizeof(double) * size_t(F), hipMemcpyHostToDevice, st));
+      OICC_HIP_TRY(hipMemcpyAsync(d_angle.p, h_angle.data(), sizeof(double) * size_t(F), hipMemcpyHostToDevice, st));
+      OICC_HIP_TRY(hipMemcpyAsync(d_samples.p, h_samples.data(), sizeof(int32_t) * size_t(F), hipMemcpyHostToDevice, st));
+      OICC_HIP_TRY(hipMemcpyAsync(d_lstatus.p, h_lstatus.data(), sizeof(int32_t) * size_t(F), hipMemcpyHostToDevice, st));
+      OICC_HIP_TRY(hipEventRecord(g1, st));
+      if (int rc = launch_accl_world(J, level, H, st, D, d_interval.p, d_path.p, &V)) return rc;
+      OICC_HIP_TRY(hipEventRecord(g2, st));
+      if (count > 0) {
+        hipLaunchKernelGGL(stab_level_kernel, dim3(unsigned((count + kWaves - 1) / kWaves)), dim3(kThreads), 0, st, count, first, D.frame_t.p, V.accl_t.p,
+                           V.world.p, V.gate.p, V.win_lo.p, V.win_hi.p, d_path.p, d_smooth.p, J.P.time_offset, J.P.reference_row * J.P.line_delay,
+                           level->gravity_sigma_s, level->gravity_const, level->lock, std::remainder(level->roll_rad, kTwoPi),
+                           options->max_correction_rad, d_level.p, D.correction.p, d_up.p, d_roll.p, d_angle.p, d_samples.p, d_lstatus.p);
+        OICC_HIP_TRY(hipGetLastError());
+      }
+      OICC_HIP_TRY(hipEventRecord(g3, st));                    // the zoom starts here
+    }
     if (int rc = launch_records(J, st, &D)) return rc;         // at zoom 1
     for (int f0 = 0; f0 < F; f0 += kFrameChunk) {
       const int m = std::min(kFrameChunk, F - f0);
@@ -564,10 +841,23 @@ extern "C" int oicc_stab_plan(int32_t device_ordinal, const oicc_rs_scene* scene
     OICC_HIP_TRY(hipMemcpyAsync(h_corr.data(), D.correction.p, sizeof(double) * size_t(4 * F), hipMemcpyDeviceToHost, st));
     OICC_HIP_TRY(hipMemcpyAsync(h_iter.data(), d_iter.p, sizeof(int32_t) * size_t(F), hipMemcpyDeviceToHost, st));
     OICC_HIP_TRY(hipMemcpyAsync(h_req.data(), d_req.p, sizeof(double) * size_t(F), hipMemcpyDeviceToHost, st));
+    if (level) {
+      OICC_HIP_TRY(hipMemcpyAsync(h_up.data(), d_up.p, sizeof(double) * size_t(3 * F), hipMemcpyDeviceToHost, st));
+      OICC_HIP_TRY(hipMemcpyAsync(h_roll.data(), d_roll.p, sizeof(double) * size_t(F), hipMemcpyDeviceToHost, st));
+      OICC_HIP_TRY(hipMemcpyAsync(h_angle.data(), d_angle.p, sizeof(double) * size_t(F), hipMemcpyDeviceToHost, st));
+      OICC_HIP_TRY(hipMemcpyAsync(h_samples.data(), d_samples.p, sizeof(int32_t) * size_t(F), hipMemcpyDeviceToHost, st));
+      OICC_HIP_TRY(hipMemcpyAsync(h_lstatus.data(), d_lstatus.p, sizeof(int32_t) * size_t(F), hipMemcpyDeviceToHost, st));
+      h_level.resize(size_t(4 * F));
+      OICC_HIP_TRY(hipMemcpyAsync(h_level.data(), d_level.p, sizeof(double) * size_t(4 * F), hipMemcpyDeviceToHost, st));
+    }
     OICC_HIP_TRY(hipStreamSynchronize(st));
     OICC_HIP_TRY(hipEventElapsedTime(&ms[0], D.ev[1], e1));
     OICC_HIP_TRY(hipEventElapsedTime(&ms[1], e1, e2));
-    OICC_HIP_TRY(hipEventElapsedTime(&ms[2], e2, e3));
+    OICC_HIP_TRY(hipEventElapsedTime(&ms[2], level ? g3 : e2, e3));
+    if (level) {
+      OICC_HIP_TRY(hipEventElapsedTime(&ms[3], g1, g2));
+      OICC_HIP_TRY(hipEventElapsedTime(&ms[4], g2, g3));
+    }
   }
   std::memcpy(path_q, h_path.data(), sizeof(double) * size_t(4 * F));
   std::memcpy(smooth_q, h_smooth.data(), sizeof(double) * size_t(4 * F));
@@ -576,7 +866,66 @@ extern "C" int oicc_stab_plan(int32_t device_ordinal, const oicc_rs_scene* scene
   std::memcpy(required_zoom, h_req.data(), sizeof(double) * size_t(F));
   copy_status(J, frame_status);
   applied_zoom(F, scene->frame_t, required_zoom, frame_status, *options, zoom, zoom_clamped);
-  if (device_ms) for (int k = 0; k < 3; ++k) device_ms[k] = double(ms[k]);
+  if (device_ms) for (int k = 0; k < (out ? 5 : 3); ++k) device_ms[k] = double(ms[k]);
+  if (out) {
+    std::memcpy(out->level_q, level ? h_level.data() : h_smooth.data(), sizeof(double) * size_t(4 * F));
+    std::memcpy(out->up, h_up.data(), sizeof(double) * size_t(3 * F));
+    std::memcpy(out->roll, h_roll.data(), sizeof(double) * size_t(F));
+    std::memcpy(out->level_angle, h_angle.data(), sizeof(double) * size_t(F));
+    std::memcpy(out->gravity_samples, h_samples.data(), sizeof(int32_t) * size_t(F));
+    std::memcpy(out->level_status, h_lstatus.data(), sizeof(int32_t) * size_t(F));
+  }
+  return OICC_OK;
+}
+
+}  // namespace
+
+extern "C" int oicc_stab_plan(int32_t device_ordinal, const oicc_rs_scene* scene, const oicc_stab_options* options, double* path_q, double* smooth_q,
+                              double* correction_q, double* required_zoom, double* zoom, int32_t* iterations, int32_t* frame_status,
+                              uint8_t* zoom_clamped, double* device_ms) {
+  return plan_impl(device_ordinal, scene, options, nullptr, path_q, smooth_q, correction_q, required_zoom, zoom, iterations, frame_status, zoom_clamped,
+                   nullptr, device_ms);
+}
+
+extern "C" int oicc_stab_plan_level(int32_t device_ordinal, const oicc_rs_scene* scene, const oicc_stab_options* options, const oicc_stab_level* level,
+                                    double* path_q, double* smooth_q, double* correction_q, double* required_zoom, double* zoom, int32_t* iterations,
+                                    int32_t* frame_status, uint8_t* zoom_clamped, double* level_q, double* up, double* roll, double* level_angle,
+                                    int32_t* gravity_samples, int32_t* level_status, double* device_ms) {
+  const LevelOut out = {level_q, up, roll, level_angle, gravity_samples, level_status};
+  return plan_impl(device_ordinal, scene, options, level, path_q, smooth_q, correction_q, required_zoom, zoom, iterations, frame_status, zoom_clamped,
+                   &out, device_ms);
+}
+
+// G1 of the horizon lock alone: the path, then every accelerometer sample in the path's frame
+extern "C" int oicc_debug_stab_accl_world(int32_t device_ordinal, const oicc_rs_scene* scene, const oicc_stab_level* level, double* world,
+                                          int32_t* frame_of) {
+  Judged J;
+  if (int rc = judge_scene(scene, &J)) return rc;
+  if (!level_ok(level) || !world || !frame_of) return OICC_ERR_INVALID_ARG;
+  const int F = J.num_frames;
+  std::vector<int64_t> interval;
+  int first = 0, count = 0;
+  if (int rc = find_path(scene, J, &interval, &first, &count)) return rc;
+  LevelHost H;
+  level_host(scene, J, level, first, count, &H);
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
+  const size_t na = size_t(level->num_accl);
+  const std::vector<double> h_path(size_t(4 * F), std::nan(""));
+  Prepared D;
+  LevelDevice V;
+  oicc::DevBuf<int64_t> d_interval;
+  oicc::DevBuf<double> d_delta, d_path;
+  oicc::Stream st;
+  OICC_HIP_TRY(st.create());
+  OICC_HIP_TRY(d_interval.resize(size_t(F))); OICC_HIP_TRY(d_delta.resize(size_t(4 * std::max(count - 1, 1)))); OICC_HIP_TRY(d_path.resize(size_t(4 * F)));
+  if (int rc = upload_scene(scene, J, st, &D)) return rc;
+  OICC_HIP_TRY(hipMemcpyAsync(d_interval.p, interval.data(), sizeof(int64_t) * size_t(F), hipMemcpyHostToDevice, st));
+  OICC_HIP_TRY(hipMemcpyAsync(d_path.p, h_path.data(), sizeof(double) * size_t(4 * F), hipMemcpyHostToDevice, st));
+  if (int rc = launch_path(J, st, D, d_interval.p, first, count, d_delta.p, d_path.p)) return rc;
+  if (int rc = launch_accl_world(J, level, H, st, D, d_interval.p, d_path.p, &V)) return rc;
+  OICC_HIP_TRY(hipMemcpyAsync(world, V.world.p, sizeof(double) * 3 * na, hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(hipStreamSynchronize(st));
+  std::memcpy(frame_of, H.frame_of.data(), sizeof(int32_t) * na);
   return OICC_OK;
 }
 

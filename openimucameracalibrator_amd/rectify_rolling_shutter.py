@@ -56,6 +56,23 @@ def read_gyro_intrinsics(path_intr, path_bias):
     return intr, bias
 
 
+def read_accl_intrinsics(path_intr, path_bias):
+    """(accelerometer intrinsics [6]: the three misalignments of the upper triangle and three scales, accl bias [3]) of the same two
+    files; identity and zero without a file."""
+    intr = np.array([0.0, 0.0, 0.0, 1.0, 1.0, 1.0]); bias = np.zeros(3)
+    if path_bias:
+        try:
+            b = json.load(open(path_bias))["accl_bias"]
+            bias = np.array([float(b[k]) for k in "xyz"])
+        except (OSError, ValueError):
+            print("Error loading IMU bias file: %s" % path_bias, file=sys.stderr)
+    if path_intr:
+        a = json.load(open(path_intr))["accelerometer"]
+        M, Sc = a["misalignment_matrix"], a["scale_matrix"]
+        intr = np.array([-M[0][1], M[0][2], -M[1][2], Sc[0][0], Sc[1][1], Sc[2][2]], dtype=np.float64)
+    return intr, bias
+
+
 def frame_time_from_name(name, t_offset_cam_s):
     """<timestamp_ns>.png -> timestamp_ns 1e-9 + t_offset_cam_s, the rule the calibration program applies to view keys; None for
     another name."""

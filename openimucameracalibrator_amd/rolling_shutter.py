@@ -55,6 +55,29 @@ def corrected_gyro(telemetry, gyro_intrinsics=None, gyro_bias=None):
     return t, np.stack([(MS[r, 0] * d[:, 0] + MS[r, 1] * d[:, 1]) + MS[r, 2] * d[:, 2] for r in range(3)], -1)
 
 
+def accl_ms_matrix(accl_intrinsics):
+    """MS_a of the six accelerometer intrinsics (three misalignments: the upper triangle, three scales), as the device's
+    imu_ms_matrix with the lower misalignments 0."""
+    a = np.asarray(accl_intrinsics, dtype=np.float64).ravel()
+    if len(a) != 6:
+        raise ValueError("accl_intrinsics holds 6 values (3 misalignments, 3 scales)")
+    return gyro_ms_matrix(np.concatenate([a[:3], np.zeros(3), a[3:]]))
+
+
+def corrected_accl(telemetry, accl_intrinsics=None, accl_bias=None):
+    """(t [n] seconds in the IMU clock, accl [n, 3] = MS_a (a_m - b_a) in the IMU frame, m/s^2: up at rest) of a telemetry dict
+    (timestamps_ns, accelerometer), the correction of the accelerometer residual, in corrected_gyro's order.  None: identity
+    intrinsics, zero bias."""
+    t = np.asarray(telemetry["timestamps_ns"], dtype=np.float64) * 1e-9
+    a = np.asarray(telemetry["accelerometer"], dtype=np.float64).reshape(-1, 3)
+    if len(t) != len(a):
+        raise ValueError("telemetry: %d timestamps for %d accelerometer samples" % (len(t), len(a)))
+    b = np.zeros(3) if accl_bias is None else np.asarray(accl_bias, dtype=np.float64).reshape(3)
+    MS = np.eye(3) if accl_intrinsics is None else accl_ms_matrix(accl_intrinsics)
+    d = a - b
+    return t, np.stack([(MS[r, 0] * d[:, 0] + MS[r, 1] * d[:, 1]) + MS[r, 2] * d[:, 2] for r in range(3)], -1)
+
+
 class Scene:
     """Everything the entries share: source and destination camera (model, intrinsics, w, h), R (row-major 3 x 3, destination
     camera -> source camera), gyro times [n] (IMU clock) and corrected rates [n, 3] (IMU frame), q_i_c (w, x, y, z),

@@ -3,7 +3,8 @@
 
 On top of the rolling-shutter rectification: stab_plan integrates the orientation path of a whole clip, smooths it on SO(3) and
 finds the zoom that keeps every stabilised frame inside its source image; stab_map and stab_frames then warp chunks of frames with
-the plan's per-frame correction and zoom, the rolling shutter taken out in the same pass.  The scene is rolling_shutter.Scene with
+the plan's per-frame correction and zoom, the rolling shutter taken out in the same pass.  With a LevelOptions the plan also levels
+the smooth camera by gravity from the accelerometer (horizon lock).  The scene is rolling_shutter.Scene with
 strictly increasing frame times and a plain PINHOLE destination.  Rotation only; there is no CPU path: every function raises
 without the HIP library or a device."""
 import ctypes as C
@@ -11,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import _abi
-from .rolling_shutter import DEFAULT_BATCH, Scene, _check, _dp, _is_cuda_tensor      # noqa: F401  (Scene: part of this interface)
+from .rolling_shutter import DEFAULT_BATCH, Scene, _check, _dp, _is_cuda_tensor, corrected_accl      # noqa: F401  (Scene, corrected_accl: part of this interface)
 
 ZOOM_MODES = {"none": 0, "fixed": 1, "dynamic": 2}
 
@@ -35,27 +36,69 @@ class StabOptions:
         return _abi.StabOptions(self.smoothing_sigma_s, self.max_correction_rad, self.zoom_mode, 0, self.zoom_window_s, self.max_zoom)
 
 
+class LevelOptions:
+    """The horizon lock (oicc_stab_level): accl_t [na] seconds in the IMU clock, strictly increasing, and accl [na, 3], the corrected
+    specific force in the IMU frame in m/s^2 (corrected_accl: up at rest); gravity_sigma_s: sigma of the Gaussian window of the
+    gravity mean; gravity_const; accl_gate: samples whose norm is further from gravity_const are left out (0: no gate); lock in
+    [0, 1]: the part of the roll that is taken out; roll_rad: the roll that is wanted."""
+
+    def __init__(self, accl_t, accl, gravity_sigma_s=1.0, gravity_const=9.811104, accl_gate=0.0, lock=1.0, roll_rad=0.0):
+        self.accl_t = np.ascontiguousarray(accl_t, dtype=np.float64).ravel()
+        self.accl = np.ascontiguousarray(accl, dtype=np.float64).reshape(-1, 3)
+        if len(self.accl_t) != len(self.accl):
+            raise ValueError("%d accelerometer times for %d samples" % (len(self.accl_t), len(self.accl)))
+        self.gravity_sigma_s, self.gravity_const, self.accl_gate = float(gravity_sigma_s), float(gravity_const), float(accl_gate)
+        self.lock, self.roll_rad = float(lock), float(roll_rad)
+
+    def c(self):
+        """The struct; this object keeps its arrays alive."""
+        return _abi.StabLevel(len(self.accl_t), _dp(self.accl_t), _dp(self.accl), self.gravity_sigma_s, self.gravity_const, self.accl_gate, self.lock,
+                              self.roll_rad)
+
+
 class StabPlan:
     """What stab_plan returns, arrays over the scene's frames: path_q, smooth_q, correction_q [frames, 4] (w, x, y, z; NaN path and
     smooth off the path), required_zoom, zoom [frames], iterations, frame_status [frames] int32, zoom_clamped [frames] uint8,
-    device_ms [3] (path, smoothing, zoom kernels)."""
+    device_ms [3] (path, smoothing, zoom kernels).  With a level also level_q [frames, 4], up [frames, 3] (up in the smooth camera),
+    roll, level_angle [frames], gravity_samples, level_status [frames] int32 (0 levelled, 1 the camera looks along gravity, 2 no
+    gravity), and device_ms [5] (then the two kernels of the horizon lock)."""
 
-    def __init__(self, n):
+    def __init__(self, n, level=False):
         self.path_q, self.smooth_q, self.correction_q = np.zeros((n, 4)), np.zeros((n, 4)), np.zeros((n, 4))
         self.required_zoom, self.zoom = np.zeros(n), np.zeros(n)
         self.iterations, self.frame_status = np.zeros(n, np.int32), np.zeros(n, np.int32)
         self.zoom_clamped = np.zeros(n, np.uint8)
-        self.device_ms = np.zeros(3)
+        self.device_ms = np.zeros(5 if level else 3)
+        if level:
+            self.level_q, self.up, self.roll, self.level_angle = np.zeros((n, 4)), np.zeros((n, 3)), np.zeros(n), np.zeros(n)
+            self.gravity_samples, self.level_status = np.zeros(n, np.int32), np.zeros(n, np.int32)
 
 
-def stab_plan(scene, options=None, device=0):
-    """The plan of a clip: scene.frame_t holds every frame's time."""
+def stab_plan(scene, options=None, device=0, level=None):
+    """The plan of a clip: scene.frame_t holds every frame's time.  level: LevelOptions, the horizon lock."""
     o = (StabOptions() if options is None else options).c()
-    p = StabPlan(max(scene.num_frames, 1))
-    _check(_bound().plan(int(device), scene.ref(), C.byref(o), _dp(p.path_q), _dp(p.smooth_q), _dp(p.correction_q), _dp(p.required_zoom), _dp(p.zoom),
-                         p.iterations.ctypes.data_as(_abi.c_i32p), p.frame_status.ctypes.data_as(_abi.c_i32p),
-                         p.zoom_clamped.ctypes.data_as(_abi.c_u8p), _dp(p.device_ms)), "oicc_stab_plan")
+    p = StabPlan(max(scene.num_frames, 1), level is not None)
+    i32 = lambda a: a.ctypes.data_as(_abi.c_i32p)
+    if level is None:
+        _check(_bound().plan(int(device), scene.ref(), C.byref(o), _dp(p.path_q), _dp(p.smooth_q), _dp(p.correction_q), _dp(p.required_zoom), _dp(p.zoom),
+                             i32(p.iterations), i32(p.frame_status), p.zoom_clamped.ctypes.data_as(_abi.c_u8p), _dp(p.device_ms)), "oicc_stab_plan")
+        return p
+    lv = level.c()
+    _check(_bound().plan_level(int(device), scene.ref(), C.byref(o), C.byref(lv), _dp(p.path_q), _dp(p.smooth_q), _dp(p.correction_q), _dp(p.required_zoom),
+                               _dp(p.zoom), i32(p.iterations), i32(p.frame_status), p.zoom_clamped.ctypes.data_as(_abi.c_u8p), _dp(p.level_q), _dp(p.up),
+                               _dp(p.roll), _dp(p.level_angle), i32(p.gravity_samples), i32(p.level_status), _dp(p.device_ms)), "oicc_stab_plan_level")
     return p
+
+
+def accl_world(scene, level, device=0):
+    """Step G1 of the horizon lock alone: (world [na, 3], every accelerometer sample in the frame of the path, NaN for the samples
+    before the first on-path frame's reference time or behind the last one's; frame_of [na] int32, the sample's frame or -1)."""
+    lv = level.c()
+    na = max(len(level.accl_t), 1)
+    world = np.zeros((na, 3)); frame_of = np.zeros(na, np.int32)
+    _check(_bound().debug_accl_world(int(device), scene.ref(), C.byref(lv), _dp(world), frame_of.ctypes.data_as(_abi.c_i32p)),
+           "oicc_debug_stab_accl_world")
+    return world, frame_of
 
 
 def applied_zoom(frame_t, required_zoom, frame_status, options):

@@ -6,12 +6,18 @@ rolling-shutter PNG frames, from the gyroscope.
   [--undistort] [--balance 0] [--output_camera_json F] [--device 0]
   [--smoothing_s 0.5] [--max_correction_deg 0] [--zoom_mode none|fixed|dynamic] [--zoom_window_s 1] [--max_zoom 4]
   [--output_plan_json F]
+  [--horizon_lock 0] [--horizon_roll_deg 0] [--gravity_window_s 1] [--gravity_const 9.811104] [--accl_gate 0]
 
 The flags and files of rectify_rolling_shutter.  The destination is always the rectified pinhole of --balance (--undistort is
 accepted and changes nothing).  stabilization.stab_plan sees the times of every <timestamp_ns>.png of the folder, in the order of
 their times: the orientation path, the smooth camera (--smoothing_s: sigma of the Gaussian window; --max_correction_deg: 0 = no
 bound) and the zoom.  Then the frames are read in chunks and stabilization.stab_frames warps each chunk with its part of the plan
-(rotation only).  --output_plan_json receives, per frame, name, status, correction quaternion, required and applied zoom.  Frames
+(rotation only).  --output_plan_json receives, per frame, name, status, correction quaternion, required and applied zoom.
+--horizon_lock X in (0, 1] turns the horizon lock on: the accelerometer of the telemetry, corrected by the accelerometer part of
+--imu_intrinsics and --imu_bias_file, gives gravity over a Gaussian window of sigma --gravity_window_s, and the part X of the
+smooth camera's roll against --horizon_roll_deg is taken out (--accl_gate G: samples whose norm is further than G from
+--gravity_const are left out; 0 = no gate); the plan file then also holds level_q, up, roll, level_angle, gravity_samples and
+level_status per frame.  With --horizon_lock 0 the PNGs and the plan file are what they are without these flags.  Frames
 without gyro coverage are not written: they are listed on stderr with the reason.  The twin of csrc/host/stabilize_frames.cpp: the
 same PNGs, the same plan file.  No reference counterpart."""
 import argparse
@@ -27,7 +33,7 @@ from . import io_files
 from . import rolling_shutter as rs
 from . import stabilization as stab
 from . import synthetic as S
-from .rectify_rolling_shutter import frame_time_from_name, read_gyro_intrinsics, read_imu_camera_result
+from .rectify_rolling_shutter import frame_time_from_name, read_accl_intrinsics, read_gyro_intrinsics, read_imu_camera_result
 from .undistort_images import read_frame
 
 BATCH = 16
@@ -43,14 +49,21 @@ def json_number(v):
     return "%.17g" % v if math.isfinite(v) else "null"
 
 
-def plan_json(names, status, correction_q, required_zoom, zoom, zoom_clamped):
-    """The plan file's text, one line per frame; byte for byte what csrc/host/stabilization.hpp writes."""
+def plan_json(names, status, correction_q, required_zoom, zoom, zoom_clamped, level=None):
+    """The plan file's text, one line per frame; byte for byte what csrc/host/stabilization.hpp writes.  level: the plan itself or a
+    dict with level_q, up, roll, level_angle, gravity_samples and level_status (the horizon lock is on), or None."""
+    get = (lambda key: level[key]) if isinstance(level, dict) else (lambda key: getattr(level, key))
     s = "{\"frames\": ["
     for k, name in enumerate(names):
         s += ",\n" if k else "\n"
-        s += " {\"name\": \"%s\", \"status\": %d, \"correction_q\": [%s], \"required_zoom\": %s, \"zoom\": %s, \"zoom_clamped\": %d}" % (
+        s += " {\"name\": \"%s\", \"status\": %d, \"correction_q\": [%s], \"required_zoom\": %s, \"zoom\": %s, \"zoom_clamped\": %d" % (
             name, int(status[k]), ", ".join(json_number(float(c)) for c in correction_q[k]), json_number(float(required_zoom[k])),
             json_number(float(zoom[k])), int(zoom_clamped[k]))
+        if level is not None:
+            s += ", \"level_q\": [%s], \"up\": [%s], \"roll\": %s, \"level_angle\": %s, \"gravity_samples\": %d, \"level_status\": %d" % (
+                ", ".join(json_number(float(c)) for c in get("level_q")[k]), ", ".join(json_number(float(c)) for c in get("up")[k]),
+                json_number(float(get("roll")[k])), json_number(float(get("level_angle")[k])), int(get("gravity_samples")[k]), int(get("level_status")[k]))
+        s += "}"
     return s + "\n]}\n"
 
 
@@ -77,6 +90,11 @@ def main(argv=None):
     ap.add_argument("--zoom_window_s", type=float, default=1.0)
     ap.add_argument("--max_zoom", type=float, default=4.0)
     ap.add_argument("--output_plan_json", default="")
+    ap.add_argument("--horizon_lock", type=float, default=0.0)
+    ap.add_argument("--horizon_roll_deg", type=float, default=0.0)
+    ap.add_argument("--gravity_window_s", type=float, default=1.0)
+    ap.add_argument("--gravity_const", type=float, default=9.811104)
+    ap.add_argument("--accl_gate", type=float, default=0.0)
     args = io_files.parse_reference_flags(ap, argv)
     if args.zoom_mode not in stab.ZOOM_MODES:
         print("--zoom_mode is none, fixed or dynamic", file=sys.stderr)
@@ -116,10 +134,16 @@ def main(argv=None):
     def scene_of(t):
         return rs.Scene((model, intr, w, h), dst, gyro_t, rates, t, line_delay, q_i_c=q_i_c, time_offset_imu_to_cam=time_offset, reference_row=reference_row)
 
-    plan = stab.stab_plan(scene_of(times), options, device=args.device)          # over the whole clip
+    level = None
+    if args.horizon_lock != 0.0:               # off: the plan and its file as without the horizon lock
+        accl_t, accl = rs.corrected_accl(telemetry, *read_accl_intrinsics(args.imu_intrinsics, args.imu_bias_file))
+        level = stab.LevelOptions(accl_t, accl, args.gravity_window_s, args.gravity_const, args.accl_gate, args.horizon_lock,
+                                  args.horizon_roll_deg * math.pi / 180.0)
+    plan = stab.stab_plan(scene_of(times), options, device=args.device, level=level)          # over the whole clip
     if args.output_plan_json:
         with open(args.output_plan_json, "w", newline="") as f:
-            f.write(plan_json(names, plan.frame_status, plan.correction_q, plan.required_zoom, plan.zoom, plan.zoom_clamped))
+            f.write(plan_json(names, plan.frame_status, plan.correction_q, plan.required_zoom, plan.zoom, plan.zoom_clamped,
+                              None if level is None else plan))
     os.makedirs(args.output_path, exist_ok=True)
     k = written = 0
     while k < len(names):                      # runs of frames with the same colour layout travel as one call
