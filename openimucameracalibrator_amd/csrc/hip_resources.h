@@ -78,6 +78,10 @@ struct DevBuf {
     return hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, st) == hipSuccess;
   }
   bool upload(const std::vector<T>& h, hipStream_t st) { return upload(h.data(), h.size(), st); }
+  // copies only, for an entry that has made every allocation ahead of its first copy: count <= n
+  bool copy_from(const T* h, size_t count, hipStream_t st) { return hipMemcpyAsync(p, h, count * sizeof(T), hipMemcpyHostToDevice, st) == hipSuccess; }
+  bool copy_from(const std::vector<T>& h, hipStream_t st) { return copy_from(h.data(), h.size(), st); }
+  bool download(T* h, size_t count, hipStream_t st) const { return hipMemcpyAsync(h, p, count * sizeof(T), hipMemcpyDeviceToHost, st) == hipSuccess; }
   void attach(T* ptr, size_t count) { release(); p = ptr; n = count; owned = false; }
 };
 

@@ -17,12 +17,8 @@
 // tests/rolling_shutter_restatement.py restates every step in numpy.  Compiled with -ffp-contract=off like camera_maps.o: with
 // all rates zero the map is bit-equal to camera_map_kernel's, and the fused frames are byte-equal to remapping through the map.
 #include <hip/hip_runtime.h>
-#include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
-#include <cstring>
-#include <vector>
 #include "rolling_shutter_device.h"
 
 namespace {
@@ -157,75 +153,42 @@ __global__ __launch_bounds__(kThreads) void rs_rotation_kernel(RsParams P, const
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 
 // The device side of a scene: the per-frame tables and, where wanted, the destination rays.
+// The third stage is the ray kernel; the output drivers of rolling_shutter_device.h launch through map_chunk and frames_chunk.
 struct Prepared {
-  oicc::DevBuf<double> gyro_t, rates, frame_t, table;
-  oicc::DevBuf<int64_t> first;
-  oicc::DevBuf<int32_t> count;
+  SceneStage scene;
   oicc::DevBuf<double2> rays;
   oicc::DevBuf<uint8_t> ray_status;
-  oicc::Event ev[3];     // before the table kernel, behind it, behind the ray kernel
-};
 
-// Enqueues the uploads, the table kernel and (with_rays) the ray kernel on st; J and the scene arrays must outlive the stream's work.
-int prepare(const oicc_rs_scene* s, const Judged& J, bool with_rays, hipStream_t st, Prepared* D) {
-  const size_t n = size_t(J.num_gyro), f = size_t(J.num_frames);
-  const int64_t pixels = int64_t(J.P.dst_w) * J.P.dst_h;
-  for (auto& e : D->ev) OICC_HIP_TRY(e.create());
-  OICC_HIP_TRY(D->gyro_t.resize(n));
-  OICC_HIP_TRY(D->rates.resize(3 * n));
-  OICC_HIP_TRY(D->frame_t.resize(f));
-  OICC_HIP_TRY(D->first.resize(f));
-  OICC_HIP_TRY(D->count.resize(f));
-  OICC_HIP_TRY(D->table.resize(size_t(kMaxWindow) * kEntry * f));
-  if (with_rays) {                          // every allocation before the first event: none sits inside a timed span
-    OICC_HIP_TRY(D->rays.resize(size_t(pixels)));
-    OICC_HIP_TRY(D->ray_status.resize(size_t(pixels)));
+  // Enqueues the uploads, the table kernel and (with_rays) the ray kernel on st; J and the scene arrays must outlive the stream's work.
+  int prepare(const oicc_rs_scene* s, const Judged& J, bool with_rays, hipStream_t st) {
+    const int64_t pixels = J.pixels();
+    if (int rc = scene.allocate(J)) return rc;
+    // every allocation before the first copy and event: none sits inside a timed span
+    if (with_rays) { OICC_HIP_TRY(rays.resize(size_t(pixels))); OICC_HIP_TRY(ray_status.resize(size_t(pixels))); }
+    if (int rc = scene.upload(s, J, st)) return rc;
+    if (int rc = scene.launch_tables(J, st)) return rc;
+    if (with_rays) {
+      hipLaunchKernelGGL(rs_ray_kernel, dim3(blocks_for(pixels)), dim3(kThreads), 0, st, J.P.dst, J.P.dst_closed_form, J.P.dst_w, pixels, rays.p, ray_status.p);
+      OICC_HIP_TRY(hipGetLastError());
+    }
+    OICC_HIP_TRY(hipEventRecord(scene.ev[2], st));
+    return OICC_OK;
   }
-  OICC_HIP_TRY(hipMemcpyAsync(D->gyro_t.p, s->gyro_t, sizeof(double) * n, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(D->rates.p, J.rates_cam.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(D->frame_t.p, s->frame_t, sizeof(double) * f, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(D->first.p, J.first.data(), sizeof(int64_t) * f, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(D->count.p, J.count.data(), sizeof(int32_t) * f, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipEventRecord(D->ev[0], st));
-  hipLaunchKernelGGL(rs_frame_table_kernel, dim3(unsigned((J.num_frames + 63) / 64)), dim3(64), 0, st, J.num_frames, D->gyro_t.p, D->rates.p,
-                     D->frame_t.p, D->first.p, D->count.p, J.P.time_offset, J.P.reference_row * J.P.line_delay, D->table.p);
-  OICC_HIP_TRY(hipGetLastError());
-  OICC_HIP_TRY(hipEventRecord(D->ev[1], st));
-  if (with_rays) {
-    hipLaunchKernelGGL(rs_ray_kernel, dim3(blocks_for(pixels)), dim3(kThreads), 0, st, J.P.dst, J.P.dst_closed_form, J.P.dst_w, pixels, D->rays.p,
-                       D->ray_status.p);
-    OICC_HIP_TRY(hipGetLastError());
-  }
-  OICC_HIP_TRY(hipEventRecord(D->ev[2], st));
-  return OICC_OK;
-}
 
-// frames [first, first + num) of the scene; frames_dev / out_dev start at frame `first`
-int launch_rectify(hipStream_t st, const Judged& J, const Prepared& D, int first, int num, int channels, const uint8_t* frames_dev, int border,
-                   uint8_t* out_dev) {
-  const int64_t pixels = int64_t(J.P.dst_w) * J.P.dst_h;
-  const int64_t in_frame = int64_t(J.P.src_w) * J.P.src_h * channels, out_frame = pixels * channels;
-  for (int done = 0; done < num; done += kFrameChunk) {
-    const int m = std::min(kFrameChunk, num - done);
+  void map_chunk(hipStream_t st, const Judged& J, int first, int m, float2* map, uint8_t* valid, uint8_t* evaluations) const {
+    hipLaunchKernelGGL(rs_map_kernel, dim3(blocks_for(J.pixels()), unsigned(m)), dim3(kThreads), 0, st, J.P, first, scene.table.p, scene.count.p, rays.p,
+                       ray_status.p, J.pixels(), map, valid, evaluations);
+  }
+
+  void frames_chunk(hipStream_t st, const Judged& J, int first, int m, int channels, const uint8_t* in, int border, uint8_t* out) const {
+    const int64_t pixels = J.pixels();
     const dim3 grid(blocks_for(pixels), unsigned(m));
     if (channels == 1)
-      hipLaunchKernelGGL(rs_rectify_kernel<1>, grid, dim3(kThreads), 0, st, J.P, first + done, D.table.p, D.count.p, D.rays.p, D.ray_status.p, pixels,
-                         frames_dev + done * in_frame, border, out_dev + done * out_frame);
+      hipLaunchKernelGGL(rs_rectify_kernel<1>, grid, dim3(kThreads), 0, st, J.P, first, scene.table.p, scene.count.p, rays.p, ray_status.p, pixels, in, border, out);
     else
-      hipLaunchKernelGGL(rs_rectify_kernel<3>, grid, dim3(kThreads), 0, st, J.P, first + done, D.table.p, D.count.p, D.rays.p, D.ray_status.p, pixels,
-                         frames_dev + done * in_frame, border, out_dev + done * out_frame);
-    if (hipGetLastError() != hipSuccess) return OICC_ERR_HIP;
+      hipLaunchKernelGGL(rs_rectify_kernel<3>, grid, dim3(kThreads), 0, st, J.P, first, scene.table.p, scene.count.p, rays.p, ray_status.p, pixels, in, border, out);
   }
-  return OICC_OK;
-}
-
-void copy_status(const Judged& J, int32_t* frame_status) {
-  if (frame_status) std::memcpy(frame_status, J.status.data(), sizeof(int32_t) * J.status.size());
-}
-
-bool frames_args_ok(int32_t channels, int32_t border_value) {
-  return (channels == 1 || channels == 3) && border_value >= 0 && border_value <= 255;
-}
+};
 
 }  // namespace
 
@@ -234,43 +197,9 @@ extern "C" int oicc_rs_rectify_map(int32_t device_ordinal, const oicc_rs_scene* 
   Judged J;
   if (int rc = judge(scene, &J)) return rc;
   if (!map || !valid || !frame_status) return OICC_ERR_INVALID_ARG;
-  if (int rc = oicc::select_device(device_ordinal)) return rc;
-  const int64_t pixels = int64_t(J.P.dst_w) * J.P.dst_h;
-  const size_t total = size_t(pixels) * size_t(J.num_frames);
   Prepared D;
-  oicc::DevBuf<float2> d_map; oicc::DevBuf<uint8_t> d_valid, d_evals;
-  oicc::Event e1;
-  oicc::Stream st;
-  float ms[3] = {0.0f, 0.0f, 0.0f};
-  OICC_HIP_TRY(st.create());
-  OICC_HIP_TRY(e1.create());
-  OICC_HIP_TRY(d_map.resize(total));
-  OICC_HIP_TRY(d_valid.resize(total));
-  if (evaluations) OICC_HIP_TRY(d_evals.resize(total));
-  if (int rc = prepare(scene, J, true, st, &D)) return rc;
-  for (int first = 0; first < J.num_frames; first += kFrameChunk) {
-    const int m = std::min(kFrameChunk, J.num_frames - first);
-    hipLaunchKernelGGL(rs_map_kernel, dim3(blocks_for(pixels), unsigned(m)), dim3(kThreads), 0, st, J.P, first, D.table.p, D.count.p, D.rays.p,
-                       D.ray_status.p, pixels, d_map.p, d_valid.p, d_evals.p);
-    OICC_HIP_TRY(hipGetLastError());
-  }
-  OICC_HIP_TRY(hipEventRecord(e1, st));
-  OICC_HIP_TRY(hipMemcpyAsync(map, d_map.p, sizeof(float2) * total, hipMemcpyDeviceToHost, st));
-  OICC_HIP_TRY(hipMemcpyAsync(valid, d_valid.p, total, hipMemcpyDeviceToHost, st));
-  if (evaluations) OICC_HIP_TRY(hipMemcpyAsync(evaluations, d_evals.p, total, hipMemcpyDeviceToHost, st));
-  OICC_HIP_TRY(hipStreamSynchronize(st));
-  OICC_HIP_TRY(hipEventElapsedTime(&ms[0], D.ev[0], D.ev[1]));
-  OICC_HIP_TRY(hipEventElapsedTime(&ms[1], D.ev[1], D.ev[2]));
-  OICC_HIP_TRY(hipEventElapsedTime(&ms[2], D.ev[2], e1));
-  if (device_ms) for (int k = 0; k < 3; ++k) device_ms[k] = double(ms[k]);
-  copy_status(J, frame_status);
-  if (num_valid)
-    for (int k = 0; k < J.num_frames; ++k) {
-      int64_t c = 0;
-      for (int64_t i = 0; i < pixels; ++i) c += valid[int64_t(k) * pixels + i];
-      num_valid[k] = c;
-    }
-  return OICC_OK;
+  return run_map(device_ordinal, J, D, [&](hipStream_t st) { return D.prepare(scene, J, true, st); }, map, valid, evaluations, frame_status, num_valid,
+                 device_ms);
 }
 
 extern "C" int oicc_rs_rectify_frames_device(void* hip_stream, const oicc_rs_scene* scene, int32_t channels, const uint8_t* frames_dev,
@@ -278,15 +207,9 @@ extern "C" int oicc_rs_rectify_frames_device(void* hip_stream, const oicc_rs_sce
   Judged J;
   if (int rc = judge(scene, &J)) return rc;
   if (!frames_args_ok(channels, border_value) || !frames_dev || !out_dev || !frame_status) return OICC_ERR_INVALID_ARG;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (int rc = oicc::on_current_device(stream, {frames_dev, out_dev})) return rc;
   Prepared D;
-  int rc = prepare(scene, J, true, stream, &D);
-  if (rc == OICC_OK) rc = launch_rectify(stream, J, D, 0, J.num_frames, channels, frames_dev, border_value, out_dev);
-  // the tables are this call's own: it returns once the stream has run the work, and frees them
-  if (hipStreamSynchronize(stream) != hipSuccess && rc == OICC_OK) rc = OICC_ERR_HIP;
-  if (rc == OICC_OK) copy_status(J, frame_status);
-  return rc;
+  return run_frames_device(static_cast<hipStream_t>(hip_stream), J, D, [&](hipStream_t st) { return D.prepare(scene, J, true, st); }, channels, frames_dev,
+                           border_value, out_dev, frame_status);
 }
 
 extern "C" int oicc_rs_rectify_frames(int32_t device_ordinal, const oicc_rs_scene* scene, int32_t channels, const uint8_t* frames,
@@ -294,26 +217,9 @@ extern "C" int oicc_rs_rectify_frames(int32_t device_ordinal, const oicc_rs_scen
   Judged J;
   if (int rc = judge(scene, &J)) return rc;
   if (!frames_args_ok(channels, border_value) || batch < 1 || !frames || !out || !frame_status) return OICC_ERR_INVALID_ARG;
-  if (int rc = oicc::select_device(device_ordinal)) return rc;
-  const auto t_start = std::chrono::steady_clock::now();
-  oicc_rs_frames_report rep = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   Prepared D;
-  FramePipeline pipe;      // behind the tables: its streams are drained before the tables go
-  if (int rc = pipe.open(J.num_frames, batch, int64_t(J.P.src_w) * J.P.src_h * channels, int64_t(J.P.dst_w) * J.P.dst_h * channels)) return rc;
-  if (int rc = prepare(scene, J, true, pipe.slot[0].st, &D)) return rc;
-  OICC_HIP_TRY(hipStreamSynchronize(pipe.slot[0].st));      // both streams read the tables
-  float ms = 0.0f;
-  OICC_HIP_TRY(hipEventElapsedTime(&ms, D.ev[0], D.ev[1])); rep.ms_table = ms;
-  OICC_HIP_TRY(hipEventElapsedTime(&ms, D.ev[1], D.ev[2])); rep.ms_rays = ms;
-  const int rc = pipe.run(frames, out, [&](hipStream_t st, int first, int num, const uint8_t* d_in, uint8_t* d_out) {
-    return launch_rectify(st, J, D, first, num, channels, d_in, border_value, d_out);
-  });
-  if (rc != OICC_OK) return rc;
-  copy_status(J, frame_status);
-  rep.ms_upload = pipe.ms_upload; rep.ms_kernel = pipe.ms_kernel; rep.ms_download = pipe.ms_download;
-  rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-  if (report) *report = rep;
-  return OICC_OK;
+  return run_frames(device_ordinal, J, D, [&](hipStream_t st) { return D.prepare(scene, J, true, st); }, channels, frames, border_value, batch, out,
+                    frame_status, report);
 }
 
 namespace {
@@ -336,7 +242,7 @@ int run_queries(int32_t device_ordinal, const oicc_rs_scene* scene, int64_t n, c
   float ms = 0.0f;
   OICC_HIP_TRY(st.create());
   OICC_HIP_TRY(e0.create()); OICC_HIP_TRY(e1.create());
-  if (int rc = prepare(scene, J, false, st, &D)) return rc;
+  if (int rc = D.prepare(scene, J, false, st)) return rc;
   OICC_HIP_TRY(d_frame.resize(size_t(n)));
   OICC_HIP_TRY(d_in.resize(kIn * size_t(n)));
   OICC_HIP_TRY(d_out.resize(kOut * size_t(n)));
@@ -345,9 +251,9 @@ int run_queries(int32_t device_ordinal, const oicc_rs_scene* scene, int64_t n, c
   OICC_HIP_TRY(hipMemcpyAsync(d_in.p, in, sizeof(double) * kIn * size_t(n), hipMemcpyHostToDevice, st));
   OICC_HIP_TRY(hipEventRecord(e0, st));
   if (QUERY == 0)
-    hipLaunchKernelGGL(rs_points_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, J.P, D.table.p, D.count.p, n, d_frame.p, d_in.p, d_out.p, d_st.p);
+    hipLaunchKernelGGL(rs_points_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, J.P, D.scene.table.p, D.scene.count.p, n, d_frame.p, d_in.p, d_out.p, d_st.p);
   else
-    hipLaunchKernelGGL(rs_rotation_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, J.P, D.table.p, D.count.p, n, d_frame.p, d_in.p, d_out.p, d_st.p);
+    hipLaunchKernelGGL(rs_rotation_kernel, dim3(blocks_for(n)), dim3(kThreads), 0, st, J.P, D.scene.table.p, D.scene.count.p, n, d_frame.p, d_in.p, d_out.p, d_st.p);
   OICC_HIP_TRY(hipGetLastError());
   OICC_HIP_TRY(hipEventRecord(e1, st));
   OICC_HIP_TRY(hipMemcpyAsync(out, d_out.p, sizeof(double) * kOut * size_t(n), hipMemcpyDeviceToHost, st));

@@ -1,21 +1,25 @@
 // What the rolling-shutter rectification (rolling_shutter.hip) and the stabilisation (stabilization.hip) share: quaternions, the
 // exponential of a gyro interval with a linear rate, the per-frame table of relative rotations and its kernel, R_rel at a row, the
-// fixed point on the source row, and the host's judgement of an oicc_rs_scene with the frame windows.  Both units are compiled with
-// -ffp-contract=off (csrc/Makefile): every sum here rounds as tests/rolling_shutter_restatement.py does.  The kernel is static and
-// the host functions inline: each unit has its own copy.
+// fixed point on the source row, and on the host the judgement of an oicc_rs_scene (its rules by time comparisons live in
+// gyro_scene_host.h, which needs no HIP), the scene stage that puts the tables on the device, and the drivers of the three output
+// entries each unit has (map, frames on the caller's stream, batched frames).  Both units are compiled with -ffp-contract=off
+// (csrc/Makefile): every sum here rounds as tests/rolling_shutter_restatement.py does.  The kernel is static and the host functions
+// inline: each unit has its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 #include "camera_device.h"
+#include "gyro_scene_host.h"
 
 namespace oicc_rs {
 
 using namespace oicc_camera;
 
-constexpr int kMaxWindow = 256;          // gyro samples per frame window
 constexpr int kEntry = 8;                // doubles per table entry: tau, Q' (w x y z), omega (x y z)
 constexpr int kMaxEvaluations = 24;
 constexpr double kRowTol = 1e-10;
@@ -150,13 +154,12 @@ struct Judged {
   std::vector<double> rates_cam;       // [n][3]
   std::vector<int64_t> first;          // [frames] first window sample
   std::vector<int32_t> count, status;  // [frames] window samples (0 where status != 0), oicc frame status
+  int64_t pixels() const { return int64_t(P.dst_w) * P.dst_h; }      // of the destination
 };
 
-inline bool all_finite(const double* a, int64_t n) {
-  for (int64_t i = 0; i < n; ++i) if (!std::isfinite(a[i])) return false;
-  return true;
-}
+inline double reference_delay(const RsParams& P) { return reference_delay(P.reference_row, P.line_delay); }
 
+// the camera construction and the argument checks here; the rates and the windows by gyro_scene_host.h
 inline int judge(const oicc_rs_scene* s, Judged* J) {
   if (!s) return OICC_ERR_INVALID_ARG;
   RsParams& P = J->P;
@@ -172,43 +175,147 @@ inline int judge(const oicc_rs_scene* s, Judged* J) {
       !all_finite(s->q_i_c, 4) || !std::isfinite(s->time_offset_imu_to_cam) || !std::isfinite(s->line_delay_s) ||
       !std::isfinite(s->reference_row)) return OICC_ERR_INVALID_ARG;
   for (int64_t j = 1; j < s->num_gyro; ++j) if (!(s->gyro_t[j] > s->gyro_t[j - 1])) return OICC_ERR_INVALID_ARG;
-  const double* qi = s->q_i_c;
-  const double norm = std::sqrt(((qi[0] * qi[0] + qi[1] * qi[1]) + qi[2] * qi[2]) + qi[3] * qi[3]);
-  if (!(std::fabs(norm - 1.0) <= 1e-6)) return OICC_ERR_INVALID_ARG;
+  if (!(std::fabs(quaternion_norm(s->q_i_c) - 1.0) <= 1e-6)) return OICC_ERR_INVALID_ARG;
   P.src_w = s->src_w; P.src_h = s->src_h; P.dst_w = s->dst_w; P.dst_h = s->dst_h;
   P.src_closed_form = is_plain_pinhole(P.src); P.dst_closed_form = is_plain_pinhole(P.dst);
   P.line_delay = s->line_delay_s; P.reference_row = s->reference_row; P.time_offset = s->time_offset_imu_to_cam;
   J->num_frames = s->num_frames; J->num_gyro = s->num_gyro;
-  // rates into the camera frame, once: T_i_c takes camera coordinates to IMU coordinates, so omega_c = R(q_i_c)^T omega_i
-  {
-    const double w = qi[0] / norm, x = qi[1] / norm, y = qi[2] / norm, z = qi[3] / norm;
-    const double M[9] = {1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
-                         2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
-                         2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)};
-    J->rates_cam.resize(size_t(3 * s->num_gyro));
-    for (int64_t j = 0; j < s->num_gyro; ++j) {
-      const double* o = s->gyro_rates + 3 * j;
-      for (int c = 0; c < 3; ++c) J->rates_cam[size_t(3 * j + c)] = (M[c] * o[0] + M[3 + c] * o[1]) + M[6 + c] * o[2];
+  const size_t f = size_t(s->num_frames);
+  J->rates_cam.resize(size_t(3 * s->num_gyro)); J->first.resize(f); J->count.resize(f); J->status.resize(f);
+  rates_cam(s->num_gyro, s->gyro_rates, s->q_i_c, J->rates_cam.data());
+  frame_windows(s->num_gyro, s->gyro_t, s->num_frames, s->frame_t, s->time_offset_imu_to_cam, s->line_delay_s, s->reference_row, s->src_h,
+                J->first.data(), J->count.data(), J->status.data());
+  return OICC_OK;
+}
+
+inline void copy_status(const Judged& J, int32_t* frame_status) { std::memcpy(frame_status, J.status.data(), sizeof(int32_t) * J.status.size()); }
+
+inline bool frames_args_ok(int32_t channels, int32_t border_value) { return (channels == 1 || channels == 3) && border_value >= 0 && border_value <= 255; }
+
+// The device side of a scene that both units share: the gyro samples, the frame windows and the per-frame tables.  allocate() makes
+// every allocation; upload() and launch_tables() only queue work.  A unit allocates its own third-stage buffers (rays, or correction,
+// zoom and records) between allocate() and upload(): no allocation follows the first asynchronous copy or sits inside a timed span.
+struct SceneStage {
+  oicc::DevBuf<double> gyro_t, rates, frame_t, table;
+  oicc::DevBuf<int64_t> first;
+  oicc::DevBuf<int32_t> count;
+  oicc::Event ev[3];     // before the table kernel, behind it, behind the unit's third stage (the unit records that one)
+
+  int allocate(const Judged& J) {
+    const size_t n = size_t(J.num_gyro), f = size_t(J.num_frames);
+    for (auto& e : ev) OICC_HIP_TRY(e.create());
+    OICC_HIP_TRY(gyro_t.resize(n)); OICC_HIP_TRY(rates.resize(3 * n)); OICC_HIP_TRY(frame_t.resize(f));
+    OICC_HIP_TRY(first.resize(f)); OICC_HIP_TRY(count.resize(f)); OICC_HIP_TRY(table.resize(size_t(kMaxWindow) * kEntry * f));
+    return OICC_OK;
+  }
+  // J and the scene arrays must outlive the stream's work
+  int upload(const oicc_rs_scene* s, const Judged& J, hipStream_t st) {
+    OICC_HIP_TRY(gyro_t.copy_from(s->gyro_t, size_t(J.num_gyro), st)); OICC_HIP_TRY(rates.copy_from(J.rates_cam, st));
+    OICC_HIP_TRY(frame_t.copy_from(s->frame_t, size_t(J.num_frames), st)); OICC_HIP_TRY(first.copy_from(J.first, st)); OICC_HIP_TRY(count.copy_from(J.count, st));
+    return OICC_OK;
+  }
+  int launch_tables(const Judged& J, hipStream_t st) {
+    OICC_HIP_TRY(hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(rs_frame_table_kernel, dim3(unsigned((J.num_frames + 63) / 64)), dim3(64), 0, st, J.num_frames, gyro_t.p, rates.p, frame_t.p,
+                       first.p, count.p, J.P.time_offset, reference_delay(J.P), table.p);
+    OICC_HIP_TRY(hipGetLastError());
+    OICC_HIP_TRY(hipEventRecord(ev[1], st));
+    return OICC_OK;
+  }
+};
+
+// ---- the three output entries of a unit, written once ------------------------------------------------------------------------------
+// D is the unit's Prepared: a SceneStage `scene`, the unit's third stage, and one launch each for a chunk of frames [first, first + m),
+// m <= kFrameChunk: D.map_chunk(st, J, first, m, map, valid, evaluations) on whole-scene arrays [frames][pixels] (evaluations or null) and
+// D.frames_chunk(st, J, first, m, channels, in, border, out), in / out starting at frame `first`.  prepare(st) fills D on a stream: the
+// unit's allocations, then the uploads, the table kernel and the third stage, scene.ev[0..2] around them.
+
+// frames [first, first + num) of the scene; frames_dev / out_dev start at frame `first`
+template <class Prepared>
+int launch_frames(hipStream_t st, const Judged& J, const Prepared& D, int first, int num, int channels, const uint8_t* frames_dev, int border,
+                  uint8_t* out_dev) {
+  const int64_t in_frame = int64_t(J.P.src_w) * J.P.src_h * channels, out_frame = int64_t(J.P.dst_w) * J.P.dst_h * channels;
+  for (int done = 0; done < num; done += kFrameChunk) {
+    D.frames_chunk(st, J, first + done, std::min(kFrameChunk, num - done), channels, frames_dev + done * in_frame, border, out_dev + done * out_frame);
+    if (hipGetLastError() != hipSuccess) return OICC_ERR_HIP;
+  }
+  return OICC_OK;
+}
+
+// the map entry: a stream of its own, declared behind D (the caller's) and the map buffers
+template <class Prepared, class Prepare>
+int run_map(int32_t device_ordinal, const Judged& J, Prepared& D, Prepare&& prepare, float* map, uint8_t* valid, uint8_t* evaluations,
+            int32_t* frame_status, int64_t* num_valid, double* device_ms) {
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
+  const int64_t pixels = J.pixels();
+  const size_t total = size_t(pixels) * size_t(J.num_frames);
+  oicc::DevBuf<float2> d_map; oicc::DevBuf<uint8_t> d_valid, d_evals;
+  oicc::Event e1;
+  oicc::Stream st;
+  float ms[3] = {0.0f, 0.0f, 0.0f};
+  OICC_HIP_TRY(st.create());
+  OICC_HIP_TRY(e1.create());
+  OICC_HIP_TRY(d_map.resize(total));
+  OICC_HIP_TRY(d_valid.resize(total));
+  if (evaluations) OICC_HIP_TRY(d_evals.resize(total));
+  if (int rc = prepare(st.s)) return rc;
+  for (int first = 0; first < J.num_frames; first += kFrameChunk) {
+    D.map_chunk(st, J, first, std::min(kFrameChunk, J.num_frames - first), d_map.p, d_valid.p, d_evals.p);
+    OICC_HIP_TRY(hipGetLastError());
+  }
+  OICC_HIP_TRY(hipEventRecord(e1, st));
+  OICC_HIP_TRY(hipMemcpyAsync(map, d_map.p, sizeof(float2) * total, hipMemcpyDeviceToHost, st));
+  OICC_HIP_TRY(d_valid.download(valid, total, st));
+  if (evaluations) OICC_HIP_TRY(d_evals.download(evaluations, total, st));
+  OICC_HIP_TRY(hipStreamSynchronize(st));
+  OICC_HIP_TRY(hipEventElapsedTime(&ms[0], D.scene.ev[0], D.scene.ev[1]));
+  OICC_HIP_TRY(hipEventElapsedTime(&ms[1], D.scene.ev[1], D.scene.ev[2]));
+  OICC_HIP_TRY(hipEventElapsedTime(&ms[2], D.scene.ev[2], e1));
+  if (device_ms) for (int k = 0; k < 3; ++k) device_ms[k] = double(ms[k]);
+  copy_status(J, frame_status);
+  if (num_valid)
+    for (int k = 0; k < J.num_frames; ++k) {
+      int64_t c = 0;
+      for (int64_t i = 0; i < pixels; ++i) c += valid[int64_t(k) * pixels + i];
+      num_valid[k] = c;
     }
-  }
-  // windows: the row times of y in [0, src_h - 1] together with t_ref, relative to the frame time, against a_j = (t_j - t_k) + offset
-  const double last = double(s->src_h - 1) * s->line_delay_s, ref = s->reference_row * s->line_delay_s;
-  const double lo = std::min(std::min(0.0, last), ref), hi = std::max(std::max(0.0, last), ref);
-  const int64_t n = s->num_gyro;
-  J->first.assign(size_t(s->num_frames), 0); J->count.assign(size_t(s->num_frames), 0); J->status.assign(size_t(s->num_frames), 0);
-  for (int k = 0; k < s->num_frames; ++k) {
-    const double tk = s->frame_t[k], off = s->time_offset_imu_to_cam;
-    auto a = [&](int64_t j) { return (s->gyro_t[j] - tk) + off; };
-    if (lo < a(0) || hi > a(n - 1)) { J->status[size_t(k)] = 1; continue; }
-    int64_t b = 0, e = n;                       // number of samples with a_j <= lo
-    while (b < e) { const int64_t m = (b + e) / 2; if (a(m) <= lo) b = m + 1; else e = m; }
-    const int64_t j0 = std::min(b - 1, n - 2);
-    b = 0; e = n;                               // number of samples with a_j < hi
-    while (b < e) { const int64_t m = (b + e) / 2; if (a(m) < hi) b = m + 1; else e = m; }
-    const int64_t j1 = std::max(b, j0 + 1);
-    if (j1 - j0 + 1 > kMaxWindow) { J->status[size_t(k)] = 2; continue; }
-    J->first[size_t(k)] = j0; J->count[size_t(k)] = int32_t(j1 - j0 + 1);
-  }
+  return OICC_OK;
+}
+
+// the frames entry on the caller's stream: D is this call's own, so it returns once the stream has run the work, and the caller frees D
+template <class Prepared, class Prepare>
+int run_frames_device(hipStream_t stream, const Judged& J, Prepared& D, Prepare&& prepare, int32_t channels, const uint8_t* frames_dev,
+                      int32_t border_value, uint8_t* out_dev, int32_t* frame_status) {
+  if (int rc = oicc::on_current_device(stream, {frames_dev, out_dev})) return rc;
+  int rc = prepare(stream);
+  if (rc == OICC_OK) rc = launch_frames(stream, J, D, 0, J.num_frames, channels, frames_dev, border_value, out_dev);
+  if (hipStreamSynchronize(stream) != hipSuccess && rc == OICC_OK) rc = OICC_ERR_HIP;
+  if (rc == OICC_OK) copy_status(J, frame_status);
+  return rc;
+}
+
+// the batched frames entry; report.ms_rays is the unit's third stage
+template <class Prepared, class Prepare>
+int run_frames(int32_t device_ordinal, const Judged& J, Prepared& D, Prepare&& prepare, int32_t channels, const uint8_t* frames, int32_t border_value,
+               int32_t batch, uint8_t* out, int32_t* frame_status, oicc_rs_frames_report* report) {
+  if (int rc = oicc::select_device(device_ordinal)) return rc;
+  const auto t_start = std::chrono::steady_clock::now();
+  oicc_rs_frames_report rep = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+  FramePipeline pipe;      // behind D (the caller's): its streams are drained before the tables go
+  if (int rc = pipe.open(J.num_frames, batch, int64_t(J.P.src_w) * J.P.src_h * channels, int64_t(J.P.dst_w) * J.P.dst_h * channels)) return rc;
+  if (int rc = prepare(pipe.slot[0].st.s)) return rc;
+  OICC_HIP_TRY(hipStreamSynchronize(pipe.slot[0].st));      // both streams read what D holds
+  float ms = 0.0f;
+  OICC_HIP_TRY(hipEventElapsedTime(&ms, D.scene.ev[0], D.scene.ev[1])); rep.ms_table = ms;
+  OICC_HIP_TRY(hipEventElapsedTime(&ms, D.scene.ev[1], D.scene.ev[2])); rep.ms_rays = ms;
+  const int rc = pipe.run(frames, out, [&](hipStream_t st, int first, int num, const uint8_t* d_in, uint8_t* d_out) {
+    return launch_frames(st, J, D, first, num, channels, d_in, border_value, d_out);
+  });
+  if (rc != OICC_OK) return rc;
+  copy_status(J, frame_status);
+  rep.ms_upload = pipe.ms_upload; rep.ms_kernel = pipe.ms_kernel; rep.ms_download = pipe.ms_download;
+  rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+  if (report) *report = rep;
   return OICC_OK;
 }
 

@@ -21,13 +21,8 @@
 // tests/stabilization_restatement.py restates every step in numpy.  Compiled with -ffp-contract=off like rolling_shutter.o:
 // oicc_stab_map is bit-equal to oicc_rs_rectify_map called with R9 = M_k and the scaled destination intrinsics.
 #include <hip/hip_runtime.h>
-#include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdint>
-#include <cstring>
-#include <limits>
-#include <vector>
 #include "rolling_shutter_device.h"
 
 namespace {
@@ -455,6 +450,8 @@ __global__ __launch_bounds__(kThreads) void stab_frames_kernel(RsParams P, int f
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
+// What the host decides by time comparisons (the path, the smoothing and gravity windows), the applied zoom and the argument checks
+// are gyro_scene_host.h's; the scene stage and the drivers of the three output entries are rolling_shutter_device.h's.
 
 // the rolling-shutter judgement and the two further requirements of the stabilisation
 int judge_scene(const oicc_rs_scene* s, Judged* J) {
@@ -464,265 +461,68 @@ int judge_scene(const oicc_rs_scene* s, Judged* J) {
   return OICC_OK;
 }
 
-bool options_ok(const oicc_stab_options* o) {
-  return o && std::isfinite(o->smoothing_sigma_s) && o->smoothing_sigma_s >= 0.0 && std::isfinite(o->max_correction_rad) && o->max_correction_rad >= 0.0 &&
-         o->zoom_mode >= 0 && o->zoom_mode <= 2 && std::isfinite(o->zoom_window_s) && o->zoom_window_s >= 0.0 && std::isfinite(o->max_zoom) &&
-         o->max_zoom >= 1.0;
-}
-
-// correction_q [frames][4] unit within 1e-6 (used as given), zoom [frames] finite and positive
-bool plan_arrays_ok(const double* correction_q, const double* zoom, int frames) {
-  if (!correction_q || !zoom || !all_finite(correction_q, 4 * int64_t(frames)) || !all_finite(zoom, frames)) return false;
-  for (int k = 0; k < frames; ++k) {
-    const double* q = correction_q + 4 * k;
-    if (!(std::fabs(std::sqrt(((q[0] * q[0] + q[1] * q[1]) + q[2] * q[2]) + q[3] * q[3]) - 1.0) <= 1e-6) || !(zoom[k] > 0.0)) return false;
-  }
-  return true;
-}
-
-// The device side of a scene with its plan: the per-frame tables and records.
-struct Prepared {
-  oicc::DevBuf<double> gyro_t, rates, frame_t, table, correction, zoom;
-  oicc::DevBuf<int64_t> first;
-  oicc::DevBuf<int32_t> count;
-  oicc::DevBuf<StabRecord> record;
-  oicc::Event ev[3];     // before the table kernel, behind it, behind the record kernel
-};
-
-int upload_scene(const oicc_rs_scene* s, const Judged& J, hipStream_t st, Prepared* D) {
-  const size_t n = size_t(J.num_gyro), f = size_t(J.num_frames);
-  for (auto& e : D->ev) OICC_HIP_TRY(e.create());
-  OICC_HIP_TRY(D->gyro_t.resize(n));
-  OICC_HIP_TRY(D->rates.resize(3 * n));
-  OICC_HIP_TRY(D->frame_t.resize(f));
-  OICC_HIP_TRY(D->first.resize(f));
-  OICC_HIP_TRY(D->count.resize(f));
-  OICC_HIP_TRY(D->table.resize(size_t(kMaxWindow) * kEntry * f));
-  OICC_HIP_TRY(D->correction.resize(4 * f));
-  OICC_HIP_TRY(D->zoom.resize(f));
-  OICC_HIP_TRY(D->record.resize(f));
-  OICC_HIP_TRY(hipMemcpyAsync(D->gyro_t.p, s->gyro_t, sizeof(double) * n, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(D->rates.p, J.rates_cam.data(), sizeof(double) * 3 * n, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(D->frame_t.p, s->frame_t, sizeof(double) * f, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(D->first.p, J.first.data(), sizeof(int64_t) * f, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(D->count.p, J.count.data(), sizeof(int32_t) * f, hipMemcpyHostToDevice, st));
-  return OICC_OK;
-}
-
-int launch_tables(const Judged& J, hipStream_t st, Prepared* D) {
-  OICC_HIP_TRY(hipEventRecord(D->ev[0], st));
-  hipLaunchKernelGGL(rs_frame_table_kernel, dim3(unsigned((J.num_frames + 63) / 64)), dim3(64), 0, st, J.num_frames, D->gyro_t.p, D->rates.p,
-                     D->frame_t.p, D->first.p, D->count.p, J.P.time_offset, J.P.reference_row * J.P.line_delay, D->table.p);
-  OICC_HIP_TRY(hipGetLastError());
-  OICC_HIP_TRY(hipEventRecord(D->ev[1], st));
-  return OICC_OK;
-}
-
-// the records from D->correction and D->zoom, which the stream has been given before
-int launch_records(const Judged& J, hipStream_t st, Prepared* D) {
-  hipLaunchKernelGGL(stab_record_kernel, dim3(unsigned((J.num_frames + 63) / 64)), dim3(64), 0, st, J.num_frames, J.P.R, J.P.dst.in[0], J.P.dst.in[2],
-                     D->correction.p, D->zoom.p, D->record.p);
-  OICC_HIP_TRY(hipGetLastError());
-  return OICC_OK;
-}
-
-// Enqueues the uploads, the table kernel and the record kernel on st; J, the scene arrays and the plan arrays must outlive the work.
-int prepare(const oicc_rs_scene* s, const Judged& J, const double* correction_q, const double* zoom, hipStream_t st, Prepared* D) {
-  const size_t f = size_t(J.num_frames);
-  if (int rc = upload_scene(s, J, st, D)) return rc;
-  OICC_HIP_TRY(hipMemcpyAsync(D->correction.p, correction_q, sizeof(double) * 4 * f, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(D->zoom.p, zoom, sizeof(double) * f, hipMemcpyHostToDevice, st));
-  if (int rc = launch_tables(J, st, D)) return rc;
-  if (int rc = launch_records(J, st, D)) return rc;
-  OICC_HIP_TRY(hipEventRecord(D->ev[2], st));
-  return OICC_OK;
-}
-
-// frames [first, first + num) of the scene; frames_dev / out_dev start at frame `first`
-int launch_frames(hipStream_t st, const Judged& J, const Prepared& D, int first, int num, int channels, const uint8_t* frames_dev, int border,
-                  uint8_t* out_dev) {
-  const int64_t pixels = int64_t(J.P.dst_w) * J.P.dst_h;
-  const int64_t in_frame = int64_t(J.P.src_w) * J.P.src_h * channels, out_frame = pixels * channels;
-  for (int done = 0; done < num; done += kFrameChunk) {
-    const int m = std::min(kFrameChunk, num - done);
-    const dim3 grid(blocks_for(pixels), unsigned(m));
-    if (channels == 1)
-      hipLaunchKernelGGL(stab_frames_kernel<1>, grid, dim3(kThreads), 0, st, J.P, first + done, D.table.p, D.count.p, D.record.p, pixels,
-                         frames_dev + done * in_frame, border, out_dev + done * out_frame);
-    else
-      hipLaunchKernelGGL(stab_frames_kernel<3>, grid, dim3(kThreads), 0, st, J.P, first + done, D.table.p, D.count.p, D.record.p, pixels,
-                         frames_dev + done * in_frame, border, out_dev + done * out_frame);
-    if (hipGetLastError() != hipSuccess) return OICC_ERR_HIP;
-  }
-  return OICC_OK;
-}
-
-void copy_status(const Judged& J, int32_t* frame_status) { std::memcpy(frame_status, J.status.data(), sizeof(int32_t) * J.status.size()); }
-
-bool frames_args_ok(int32_t channels, int32_t border_value) { return (channels == 1 || channels == 3) && border_value >= 0 && border_value <= 255; }
-
 int border_points(int w, int h) { return (w == 1 || h == 1) ? w * h : 2 * (w + h) - 4; }
 
-// The applied zoom from the required one, on the host: O(frames x window).  t [frames] strictly increasing, z [frames] (used where
-// status is 0).  mode 0: 1; 1: the maximum; 2: the running maximum over |dt| <= T, then its Gaussian mean (sigma T / 2) over the same
-// window, held inside the window's own range, so that Z_k >= z_k survives the rounding of the mean.
-void applied_zoom(int frames, const double* t, const double* z, const int32_t* status, const oicc_stab_options& o, double* Z, uint8_t* clamped) {
-  std::vector<double> Y(size_t(frames), 1.0);
-  if (o.zoom_mode == 1) {
-    double m = -std::numeric_limits<double>::infinity();
-    for (int k = 0; k < frames; ++k) if (status[k] == 0) m = std::max(m, z[k]);
-    for (int k = 0; k < frames; ++k) Z[k] = m == -std::numeric_limits<double>::infinity() ? 1.0 : m;
-  } else if (o.zoom_mode == 2) {
-    const double T = o.zoom_window_s, sg = T / 2.0;
-    int lo = 0, hi = 0;                       // the window [lo, hi) of frame k
-    std::vector<int> wlo(size_t(frames), 0), whi(size_t(frames), 0);
-    for (int k = 0; k < frames; ++k) {
-      while (t[k] - t[lo] > T) ++lo;
-      if (hi < k + 1) hi = k + 1;
-      while (hi < frames && t[hi] - t[k] <= T) ++hi;
-      wlo[size_t(k)] = lo; whi[size_t(k)] = hi;
-      double m = -std::numeric_limits<double>::infinity();
-      for (int j = lo; j < hi; ++j) if (status[j] == 0) m = std::max(m, z[j]);
-      Y[size_t(k)] = m == -std::numeric_limits<double>::infinity() ? 1.0 : m;
-    }
-    for (int k = 0; k < frames; ++k) {
-      double num = 0.0, den = 0.0, ymin = Y[size_t(k)], ymax = Y[size_t(k)];
-      for (int j = wlo[size_t(k)]; j < whi[size_t(k)]; ++j) {
-        const double dt = t[j] - t[k];
-        const double g = sg > 0.0 ? std::exp(-(dt * dt) / (2.0 * (sg * sg))) : 1.0;
-        num += g * Y[size_t(j)]; den += g;
-        ymin = std::min(ymin, Y[size_t(j)]); ymax = std::max(ymax, Y[size_t(j)]);
-      }
-      const double mean = ymax == ymin ? ymin : num / den;         // inf among the Y: inf, not NaN
-      Z[k] = std::isnan(mean) ? ymax : std::min(std::max(mean, ymin), ymax);
-    }
-  } else {
-    for (int k = 0; k < frames; ++k) Z[k] = 1.0;
-  }
-  for (int k = 0; k < frames; ++k) {
-    clamped[k] = Z[k] > o.max_zoom ? 1 : 0;
-    if (clamped[k]) Z[k] = o.max_zoom;
-  }
-}
+// The device side of a scene with its plan: the per-frame tables and records.  The third stage is the record kernel from correction
+// and zoom; the output drivers launch through map_chunk and frames_chunk.
+struct Prepared {
+  SceneStage scene;
+  oicc::DevBuf<double> correction, zoom;
+  oicc::DevBuf<StabRecord> record;
 
-// the path by time comparisons: tau_j = ((t_j - t_k) + offset) - reference delay, on the path when tau_0 <= 0 <= tau_{n-1};
-// interval [frames]: the gyro interval of t_ref
-int find_path(const oicc_rs_scene* scene, const Judged& J, std::vector<int64_t>* interval, int* first_out, int* count_out) {
-  const int F = J.num_frames;
-  const int64_t n = J.num_gyro;
-  const double off = J.P.time_offset, refd = J.P.reference_row * J.P.line_delay;
-  interval->assign(size_t(F), 0);
-  int first = 0, count = 0;
-  for (int k = 0; k < F; ++k) {
-    auto tau = [&](int64_t j) { return ((scene->gyro_t[j] - scene->frame_t[k]) + off) - refd; };
-    if (tau(0) > 0.0 || tau(n - 1) < 0.0) continue;
-    if (count == 0) first = k;
-    if (first + count != k) return OICC_ERR_INVALID_ARG;      // contiguous by the order of the times; anything else is not a clip
-    ++count;
-    int64_t b = 0, e = n;                                       // number of samples with tau_j <= 0
-    while (b < e) { const int64_t m = (b + e) / 2; if (tau(m) <= 0.0) b = m + 1; else e = m; }
-    (*interval)[size_t(k)] = std::min(b - 1, n - 2);
+  int allocate(const Judged& J) {
+    const size_t f = size_t(J.num_frames);
+    if (int rc = scene.allocate(J)) return rc;
+    OICC_HIP_TRY(correction.resize(4 * f)); OICC_HIP_TRY(zoom.resize(f)); OICC_HIP_TRY(record.resize(f));
+    return OICC_OK;
   }
-  *first_out = first; *count_out = count;
-  return OICC_OK;
-}
 
-// the delta and the scan kernel: d_path [frames][4] gets the on-path frames
-int launch_path(const Judged& J, hipStream_t st, const Prepared& D, const int64_t* d_interval, int first, int count, double* d_delta, double* d_path) {
-  if (count < 1) return OICC_OK;
-  if (count > 1) {
-    hipLaunchKernelGGL(stab_path_delta_kernel, dim3(blocks_for(count - 1)), dim3(kThreads), 0, st, count - 1, first, D.gyro_t.p, D.rates.p, D.frame_t.p,
-                       d_interval, J.P.time_offset, J.P.reference_row * J.P.line_delay, d_delta);
+  // the records from correction and zoom, which the stream has been given before
+  int launch_records(const Judged& J, hipStream_t st) {
+    hipLaunchKernelGGL(stab_record_kernel, dim3(unsigned((J.num_frames + 63) / 64)), dim3(64), 0, st, J.num_frames, J.P.R, J.P.dst.in[0], J.P.dst.in[2],
+                       correction.p, zoom.p, record.p);
     OICC_HIP_TRY(hipGetLastError());
+    return OICC_OK;
   }
-  const int run = std::max(kMinRun, (count + kScanLanes - 1) / kScanLanes);
-  hipLaunchKernelGGL(stab_path_scan_kernel, dim3(1), dim3(kScanLanes), 0, st, count, run, d_delta, d_path + 4 * size_t(first));
-  OICC_HIP_TRY(hipGetLastError());
-  return OICC_OK;
-}
 
-bool level_ok(const oicc_stab_level* l) {
-  if (!l || l->num_accl < 1 || !l->accl_t || !l->accl || !all_finite(l->accl_t, l->num_accl) || !all_finite(l->accl, 3 * l->num_accl)) return false;
-  for (int64_t j = 1; j < l->num_accl; ++j) if (!(l->accl_t[j] > l->accl_t[j - 1])) return false;
-  return std::isfinite(l->gravity_sigma_s) && l->gravity_sigma_s > 0.0 && std::isfinite(l->gravity_const) && l->gravity_const > 0.0 &&
-         std::isfinite(l->accl_gate) && l->accl_gate >= 0.0 && l->lock >= 0.0 && l->lock <= 1.0 && std::isfinite(l->roll_rad);
-}
+  // Enqueues the uploads, the table kernel and the record kernel on st; J, the scene arrays and the plan arrays must outlive the work.
+  int prepare(const oicc_rs_scene* s, const Judged& J, const double* correction_q, const double* zoom_in, hipStream_t st) {
+    const size_t f = size_t(J.num_frames);
+    if (int rc = allocate(J)) return rc;
+    if (int rc = scene.upload(s, J, st)) return rc;
+    OICC_HIP_TRY(correction.copy_from(correction_q, 4 * f, st));
+    OICC_HIP_TRY(zoom.copy_from(zoom_in, f, st));
+    if (int rc = scene.launch_tables(J, st)) return rc;
+    if (int rc = launch_records(J, st)) return rc;
+    OICC_HIP_TRY(hipEventRecord(scene.ev[2], st));
+    return OICC_OK;
+  }
 
-// What the host decides for the horizon lock, by time comparisons only: s_jk = ((accl_t[j] - frame_t[k]) + offset) - reference delay
-struct LevelHost {
-  std::vector<int32_t> frame_of;            // [na] the last on-path frame with s_jk >= 0; -1 before the first reference time or behind the last
-  std::vector<int64_t> sample_interval;     // [na] the last gyro interval i <= n - 2 with tau_i(k) <= s_jk
-  std::vector<int64_t> win_lo, win_hi;      // [frames] the used samples with |s_jk| <= 3 sigma_g, both ends included; hi < lo: none
-  Rotation Ric;                             // R(q_i_c), the quaternion normalised first
+  void map_chunk(hipStream_t st, const Judged& J, int first, int m, float2* map, uint8_t* valid, uint8_t* evaluations) const {
+    hipLaunchKernelGGL(stab_map_kernel, dim3(blocks_for(J.pixels()), unsigned(m)), dim3(kThreads), 0, st, J.P, first, scene.table.p, scene.count.p, record.p,
+                       J.pixels(), map, valid, evaluations);
+  }
+
+  void frames_chunk(hipStream_t st, const Judged& J, int first, int m, int channels, const uint8_t* in, int border, uint8_t* out) const {
+    const int64_t pixels = J.pixels();
+    const dim3 grid(blocks_for(pixels), unsigned(m));
+    if (channels == 1)
+      hipLaunchKernelGGL(stab_frames_kernel<1>, grid, dim3(kThreads), 0, st, J.P, first, scene.table.p, scene.count.p, record.p, pixels, in, border, out);
+    else
+      hipLaunchKernelGGL(stab_frames_kernel<3>, grid, dim3(kThreads), 0, st, J.P, first, scene.table.p, scene.count.p, record.p, pixels, in, border, out);
+  }
 };
 
-void level_host(const oicc_rs_scene* scene, const Judged& J, const oicc_stab_level* l, int first, int count, LevelHost* H) {
-  const int64_t na = l->num_accl, n = J.num_gyro;
-  const int F = J.num_frames;
-  const double off = J.P.time_offset, refd = J.P.reference_row * J.P.line_delay, reach = 3.0 * l->gravity_sigma_s;
-  auto s = [&](int64_t j, int k) { return ((l->accl_t[j] - scene->frame_t[k]) + off) - refd; };
-  H->frame_of.assign(size_t(na), -1); H->sample_interval.assign(size_t(na), 0);
-  H->win_lo.assign(size_t(F), 0); H->win_hi.assign(size_t(F), -1);
-  {
-    const double* qi = scene->q_i_c;
-    const double norm = std::sqrt(((qi[0] * qi[0] + qi[1] * qi[1]) + qi[2] * qi[2]) + qi[3] * qi[3]);
-    const double w = qi[0] / norm, x = qi[1] / norm, y = qi[2] / norm, z = qi[3] / norm;
-    H->Ric = Rotation{{1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - w * z), 2.0 * (x * z + w * y),
-                       2.0 * (x * y + w * z), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - w * x),
-                       2.0 * (x * z - w * y), 2.0 * (y * z + w * x), 1.0 - 2.0 * (x * x + y * y)}};
-  }
-  if (count < 1) return;
-  const int last = first + count - 1;
-  int64_t used_lo = na, used_hi = -1;
-  for (int64_t j = 0; j < na; ++j) {
-    if (!(s(j, first) >= 0.0) || s(j, last) > 0.0) continue;
-    int b = first, e = last + 1;                                 // number of on-path frames with s_jk >= 0, from `first`
-    while (b < e) { const int m = (b + e) / 2; if (s(j, m) >= 0.0) b = m + 1; else e = m; }
-    const int k = b - 1;
-    const double sj = s(j, k);
-    auto tau = [&](int64_t i) { return ((scene->gyro_t[i] - scene->frame_t[k]) + off) - refd; };
-    int64_t gb = 0, ge = n;                                      // number of gyro samples with tau_i <= s_jk
-    while (gb < ge) { const int64_t m = (gb + ge) / 2; if (tau(m) <= sj) gb = m + 1; else ge = m; }
-    H->frame_of[size_t(j)] = k;
-    H->sample_interval[size_t(j)] = std::max<int64_t>(std::min(gb - 1, n - 2), 0);
-    used_lo = std::min(used_lo, j); used_hi = j;
-  }
-  for (int k = first; k <= last && used_hi >= used_lo; ++k) {
-    int64_t b = used_lo, e = used_hi + 1;                        // the first used sample with s_jk >= -reach
-    while (b < e) { const int64_t m = (b + e) / 2; if (s(m, k) < -reach) b = m + 1; else e = m; }
-    const int64_t lo = b;
-    b = used_lo; e = used_hi + 1;                                // the number of used samples with s_jk <= reach, from used_lo
-    while (b < e) { const int64_t m = (b + e) / 2; if (s(m, k) <= reach) b = m + 1; else e = m; }
-    H->win_lo[size_t(k)] = lo; H->win_hi[size_t(k)] = b - 1;
-  }
-}
-
-// The device side of the horizon lock: the samples, what the host decided, the world vectors and the gate.
-struct LevelDevice {
-  oicc::DevBuf<double> accl_t, accl, world;
-  oicc::DevBuf<int32_t> frame_of;
-  oicc::DevBuf<int64_t> sample_interval, win_lo, win_hi;
-  oicc::DevBuf<uint8_t> gate;
+// A host array and its device twin of the same size: the array as it is before a kernel writes it goes up, the result comes down.
+// An empty one (a stage that does not run) allocates and copies nothing.
+template <class T>
+struct Twin {
+  std::vector<T> h;
+  oicc::DevBuf<T> d;
+  bool alloc() { return d.resize(h.size()); }
+  bool up(hipStream_t st) { return h.empty() || d.copy_from(h, st); }
+  bool down(hipStream_t st) { return h.empty() || d.download(h.data(), h.size(), st); }
 };
-
-// uploads and G1: the path must be on the stream already
-int launch_accl_world(const Judged& J, const oicc_stab_level* l, const LevelHost& H, hipStream_t st, const Prepared& D, const int64_t* d_interval,
-                      const double* d_path, LevelDevice* V) {
-  const size_t na = size_t(l->num_accl), f = size_t(J.num_frames);
-  OICC_HIP_TRY(V->accl_t.resize(na)); OICC_HIP_TRY(V->accl.resize(3 * na)); OICC_HIP_TRY(V->world.resize(3 * na)); OICC_HIP_TRY(V->gate.resize(na));
-  OICC_HIP_TRY(V->frame_of.resize(na)); OICC_HIP_TRY(V->sample_interval.resize(na)); OICC_HIP_TRY(V->win_lo.resize(f)); OICC_HIP_TRY(V->win_hi.resize(f));
-  OICC_HIP_TRY(hipMemcpyAsync(V->accl_t.p, l->accl_t, sizeof(double) * na, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(V->accl.p, l->accl, sizeof(double) * 3 * na, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(V->frame_of.p, H.frame_of.data(), sizeof(int32_t) * na, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(V->sample_interval.p, H.sample_interval.data(), sizeof(int64_t) * na, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(V->win_lo.p, H.win_lo.data(), sizeof(int64_t) * f, hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(V->win_hi.p, H.win_hi.data(), sizeof(int64_t) * f, hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(stab_accl_world_kernel, dim3(blocks_for(int64_t(na))), dim3(kThreads), 0, st, int64_t(na), V->accl_t.p, V->accl.p, V->frame_of.p,
-                     V->sample_interval.p, D.gyro_t.p, D.rates.p, D.frame_t.p, d_interval, d_path, H.Ric, J.P.time_offset,
-                     J.P.reference_row * J.P.line_delay, l->gravity_const, l->accl_gate, V->world.p, V->gate.p);
-  OICC_HIP_TRY(hipGetLastError());
-  return OICC_OK;
-}
 
 // What oicc_stab_plan_level returns on top of oicc_stab_plan
 struct LevelOut {
@@ -730,7 +530,168 @@ struct LevelOut {
   int32_t *gravity_samples, *level_status;
 };
 
-// oicc_stab_plan (level and out null) and oicc_stab_plan_level; device_ms [3] or [5]
+// One plan: what the host decided, the host arrays that asynchronous copies read or write, the device buffers, the events, and the
+// stream LAST, so that every way out drains it before anything declared above it goes (hip_resources.h, the order rule).  open()
+// makes every allocation; the stages behind it only queue work on st.
+struct Plan {
+  int F = 0, first = 0, count = 0;                 // frames; the on-path frames [first, first + count)
+  int points = 0, waves = 0;                       // border points of the destination and the waves that march them
+  Twin<int64_t> interval;                          // [frames] the gyro interval of t_ref
+  Twin<int32_t> lo, hi, iter;                      // [frames] the smoothing windows, the iterations of the mean
+  Twin<double> path, smooth, req;                  // [frames][4], [frames][4], [frames]
+  std::vector<double> h_corr, h_zoom;              // [frames][4], [frames]: their device twins are D's
+  Twin<int32_t> frame_of;                          // the horizon lock, as level_windows decides: [na]
+  Twin<int64_t> sample_interval, g_lo, g_hi;       // [na], [frames], [frames]
+  Rotation Ric;                                    // R(q_i_c)
+  Twin<double> level, up, roll, angle;             // its outputs: [frames][4], [frames][3], [frames], [frames]
+  Twin<int32_t> samples, lstatus;
+  Prepared D;
+  oicc::DevBuf<double> delta, wave, accl_t, accl, world;
+  oicc::DevBuf<uint8_t> gate;
+  oicc::Event e1, e2, e3, g1, g2, g3;              // behind the path, the smoothing and the zoom; before G1, behind it, behind G2
+  float ms[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  oicc::Stream st;
+
+  // The path and, with a level, each sample's frame and interval and the gravity windows: host only, before a device is looked for.
+  int decide_path(const oicc_rs_scene* scene, const Judged& J, const oicc_stab_level* l) {
+    F = J.num_frames;
+    interval.h.resize(size_t(F));
+    if (int rc = find_path(J.num_gyro, scene->gyro_t, F, scene->frame_t, J.P.time_offset, reference_delay(J.P), interval.h.data(), &first, &count)) return rc;
+    path.h.assign(size_t(4 * F), std::nan(""));
+    if (!l) return OICC_OK;
+    frame_of.h.resize(size_t(l->num_accl)); sample_interval.h.resize(size_t(l->num_accl)); g_lo.h.resize(size_t(F)); g_hi.h.resize(size_t(F));
+    unit_rotation(scene->q_i_c, Ric.r);
+    level_windows(J.num_gyro, scene->gyro_t, F, scene->frame_t, J.P.time_offset, reference_delay(J.P), l->num_accl, l->accl_t, l->gravity_sigma_s, first, count,
+                  frame_of.h.data(), sample_interval.h.data(), g_lo.h.data(), g_hi.h.data());
+    return OICC_OK;
+  }
+
+  // The smoothing windows and every array as it is before a kernel writes it: NaN smooth camera and required zoom, the identity as
+  // correction, zoom 1, and the horizon lock's outputs as they are without gravity (no up, no roll, angle 0; status 2 with a level).
+  void decide_fills(const oicc_rs_scene* scene, const Judged& J, double sigma, bool with_level) {
+    const size_t f = size_t(F);
+    const double qnan = std::nan("");
+    lo.h.resize(f); hi.h.resize(f);
+    smoothing_windows(F, scene->frame_t, first, count, sigma, lo.h.data(), hi.h.data());
+    smooth.h.assign(4 * f, qnan); h_corr.assign(4 * f, 0.0); h_zoom.assign(f, 1.0); req.h.assign(f, qnan); iter.h.assign(f, 0);
+    for (size_t k = 0; k < f; ++k) h_corr[4 * k] = 1.0;
+    up.h.assign(3 * f, qnan); roll.h.assign(f, qnan); angle.h.assign(f, 0.0); samples.h.assign(f, 0); lstatus.h.assign(f, with_level ? 2 : 0);
+    if (with_level) level.h.resize(4 * f);
+    points = border_points(J.P.dst_w, J.P.dst_h);
+    waves = int(blocks_for(points)) * kWaves;
+  }
+
+  // The stream and every allocation; whole: with the events of oicc_stab_plan's spans.  What decide_fills has not sized stays empty.
+  int open(const Judged& J, const oicc_stab_level* l, bool whole) {
+    OICC_HIP_TRY(st.create());
+    if (whole) for (oicc::Event* e : {&e1, &e2, &e3}) OICC_HIP_TRY(e->create());
+    if (whole && l) for (oicc::Event* e : {&g1, &g2, &g3}) OICC_HIP_TRY(e->create());
+    if (l) for (Twin<double>* t : {&level, &up, &roll, &angle}) OICC_HIP_TRY(t->alloc());
+    if (l) for (Twin<int32_t>* t : {&samples, &lstatus, &frame_of}) OICC_HIP_TRY(t->alloc());
+    for (Twin<int32_t>* t : {&lo, &hi, &iter}) OICC_HIP_TRY(t->alloc());
+    for (Twin<int64_t>* t : {&interval, &sample_interval, &g_lo, &g_hi}) OICC_HIP_TRY(t->alloc());
+    for (Twin<double>* t : {&path, &smooth, &req}) OICC_HIP_TRY(t->alloc());
+    OICC_HIP_TRY(delta.resize(size_t(4 * std::max(count - 1, 1)))); OICC_HIP_TRY(wave.resize(size_t(F) * size_t(waves)));
+    if (int rc = D.allocate(J)) return rc;
+    if (!l) return OICC_OK;
+    const size_t na = size_t(l->num_accl);
+    OICC_HIP_TRY(accl_t.resize(na)); OICC_HIP_TRY(accl.resize(3 * na)); OICC_HIP_TRY(world.resize(3 * na)); OICC_HIP_TRY(gate.resize(na));
+    return OICC_OK;
+  }
+
+  // the scene and the initial fills; the debug entry has the path's alone
+  int upload(const oicc_rs_scene* scene, const Judged& J) {
+    if (int rc = D.scene.upload(scene, J, st)) return rc;
+    OICC_HIP_TRY(interval.up(st)); OICC_HIP_TRY(lo.up(st)); OICC_HIP_TRY(hi.up(st)); OICC_HIP_TRY(iter.up(st)); OICC_HIP_TRY(path.up(st)); OICC_HIP_TRY(smooth.up(st));
+    if (!h_corr.empty()) { OICC_HIP_TRY(D.correction.copy_from(h_corr, st)); OICC_HIP_TRY(D.zoom.copy_from(h_zoom, st)); }
+    return OICC_OK;
+  }
+
+  // the delta and the scan kernel: path.d [frames][4] gets the on-path frames
+  int path_stage(const Judged& J) {
+    if (count < 1) return OICC_OK;
+    if (count > 1) {
+      hipLaunchKernelGGL(stab_path_delta_kernel, dim3(blocks_for(count - 1)), dim3(kThreads), 0, st, count - 1, first, D.scene.gyro_t.p, D.scene.rates.p,
+                         D.scene.frame_t.p, interval.d.p, J.P.time_offset, reference_delay(J.P), delta.p);
+      OICC_HIP_TRY(hipGetLastError());
+    }
+    const int run = std::max(kMinRun, (count + kScanLanes - 1) / kScanLanes);
+    hipLaunchKernelGGL(stab_path_scan_kernel, dim3(1), dim3(kScanLanes), 0, st, count, run, delta.p, path.d.p + 4 * size_t(first));
+    OICC_HIP_TRY(hipGetLastError());
+    return OICC_OK;
+  }
+
+  int smooth_stage(const oicc_stab_options* o) {
+    if (count < 1) return OICC_OK;
+    hipLaunchKernelGGL(stab_smooth_kernel, dim3(unsigned((count + kWaves - 1) / kWaves)), dim3(kThreads), 0, st, count, first, D.scene.frame_t.p, path.d.p,
+                       lo.d.p, hi.d.p, o->smoothing_sigma_s, o->max_correction_rad, smooth.d.p, D.correction.p, iter.d.p);
+    OICC_HIP_TRY(hipGetLastError());
+    return OICC_OK;
+  }
+
+  // the samples and what the host decided for them go up, then G1: the path must be on the stream already
+  int accl_world_stage(const Judged& J, const oicc_stab_level* l) {
+    const size_t na = size_t(l->num_accl);
+    OICC_HIP_TRY(accl_t.copy_from(l->accl_t, na, st)); OICC_HIP_TRY(accl.copy_from(l->accl, 3 * na, st));
+    OICC_HIP_TRY(frame_of.up(st)); OICC_HIP_TRY(sample_interval.up(st)); OICC_HIP_TRY(g_lo.up(st)); OICC_HIP_TRY(g_hi.up(st));
+    hipLaunchKernelGGL(stab_accl_world_kernel, dim3(blocks_for(int64_t(na))), dim3(kThreads), 0, st, int64_t(na), accl_t.p, accl.p, frame_of.d.p,
+                       sample_interval.d.p, D.scene.gyro_t.p, D.scene.rates.p, D.scene.frame_t.p, interval.d.p, path.d.p, Ric, J.P.time_offset,
+                       reference_delay(J.P), l->gravity_const, l->accl_gate, world.p, gate.p);
+    OICC_HIP_TRY(hipGetLastError());
+    return OICC_OK;
+  }
+
+  // between the smoothing and the zoom.  level_q starts as smooth_q (NaN off the path), the rest as without gravity; then G1 and G2
+  int level_stage(const Judged& J, const oicc_stab_options* o, const oicc_stab_level* l) {
+    OICC_HIP_TRY(hipMemcpyAsync(level.d.p, smooth.d.p, sizeof(double) * size_t(4 * F), hipMemcpyDeviceToDevice, st));
+    OICC_HIP_TRY(up.up(st)); OICC_HIP_TRY(roll.up(st)); OICC_HIP_TRY(angle.up(st)); OICC_HIP_TRY(samples.up(st)); OICC_HIP_TRY(lstatus.up(st));
+    OICC_HIP_TRY(hipEventRecord(g1, st));
+    if (int rc = accl_world_stage(J, l)) return rc;
+    OICC_HIP_TRY(hipEventRecord(g2, st));
+    if (count > 0) {
+      hipLaunchKernelGGL(stab_level_kernel, dim3(unsigned((count + kWaves - 1) / kWaves)), dim3(kThreads), 0, st, count, first, D.scene.frame_t.p, accl_t.p,
+                         world.p, gate.p, g_lo.d.p, g_hi.d.p, path.d.p, smooth.d.p, J.P.time_offset, reference_delay(J.P), l->gravity_sigma_s,
+                         l->gravity_const, l->lock, std::remainder(l->roll_rad, kTwoPi), o->max_correction_rad, level.d.p, D.correction.p, up.d.p,
+                         roll.d.p, angle.d.p, samples.d.p, lstatus.d.p);
+      OICC_HIP_TRY(hipGetLastError());
+    }
+    OICC_HIP_TRY(hipEventRecord(g3, st));                      // the zoom starts here
+    return OICC_OK;
+  }
+
+  // the records at zoom 1, the march of every border point, the minimum per frame
+  int zoom_stage(const Judged& J) {
+    if (int rc = D.launch_records(J, st)) return rc;
+    for (int f0 = 0; f0 < F; f0 += kFrameChunk) {
+      const int m = std::min(kFrameChunk, F - f0);
+      hipLaunchKernelGGL(stab_zoom_kernel, dim3(blocks_for(points), unsigned(m)), dim3(kThreads), 0, st, J.P, f0, D.scene.table.p, D.scene.count.p, D.record.p,
+                         points, waves, wave.p);
+      OICC_HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(stab_zoom_min_kernel, dim3(unsigned((F + 63) / 64)), dim3(64), 0, st, F, waves, wave.p, req.d.p);
+    OICC_HIP_TRY(hipGetLastError());
+    return OICC_OK;
+  }
+
+  // the results into the host arrays, the wait, and the spans: path, smoothing, zoom, and with a level G1 and G2
+  int download_stage(bool with_level) {
+    OICC_HIP_TRY(path.down(st)); OICC_HIP_TRY(smooth.down(st)); OICC_HIP_TRY(D.correction.download(h_corr.data(), h_corr.size(), st));
+    OICC_HIP_TRY(iter.down(st)); OICC_HIP_TRY(req.down(st));
+    if (with_level) for (Twin<double>* t : {&up, &roll, &angle, &level}) OICC_HIP_TRY(t->down(st));
+    if (with_level) for (Twin<int32_t>* t : {&samples, &lstatus}) OICC_HIP_TRY(t->down(st));
+    OICC_HIP_TRY(hipStreamSynchronize(st));
+    OICC_HIP_TRY(hipEventElapsedTime(&ms[0], D.scene.ev[1], e1));
+    OICC_HIP_TRY(hipEventElapsedTime(&ms[1], e1, e2));
+    OICC_HIP_TRY(hipEventElapsedTime(&ms[2], with_level ? g3 : e2, e3));
+    if (with_level) { OICC_HIP_TRY(hipEventElapsedTime(&ms[3], g1, g2)); OICC_HIP_TRY(hipEventElapsedTime(&ms[4], g2, g3)); }
+    return OICC_OK;
+  }
+};
+
+template <class T>
+void copy_out(T* to, const std::vector<T>& from) { std::memcpy(to, from.data(), sizeof(T) * from.size()); }
+
+// oicc_stab_plan (level and out null) and oicc_stab_plan_level; device_ms [3] or [5].  Only an OK return touches the caller's arrays.
 int plan_impl(int32_t device_ordinal, const oicc_rs_scene* scene, const oicc_stab_options* options, const oicc_stab_level* level, double* path_q,
               double* smooth_q, double* correction_q, double* required_zoom, double* zoom, int32_t* iterations, int32_t* frame_status,
               uint8_t* zoom_clamped, const LevelOut* out, double* device_ms) {
@@ -740,140 +701,28 @@ int plan_impl(int32_t device_ordinal, const oicc_rs_scene* scene, const oicc_sta
     return OICC_ERR_INVALID_ARG;
   if (out && (!out->level_q || !out->up || !out->roll || !out->level_angle || !out->gravity_samples || !out->level_status)) return OICC_ERR_INVALID_ARG;
   if (level && !level_ok(level)) return OICC_ERR_INVALID_ARG;
-  const int F = J.num_frames;
-  const double sigma = options->smoothing_sigma_s;
-  std::vector<int64_t> interval;
-  int first = 0, count = 0;
-  if (int rc = find_path(scene, J, &interval, &first, &count)) return rc;
-  LevelHost H;
-  if (level) level_host(scene, J, level, first, count, &H);
-  // the smoothing windows, frame indices with both ends included: t_ref,m - t_ref,k = frame_t[m] - frame_t[k]
-  std::vector<int32_t> win_lo(size_t(F), 0), win_hi(size_t(F), 0);
-  {
-    int lo = first, hi = first;
-    for (int k = first; k < first + count; ++k) {
-      while (scene->frame_t[k] - scene->frame_t[lo] > 3.0 * sigma) ++lo;
-      if (hi < k) hi = k;
-      while (hi + 1 < first + count && scene->frame_t[hi + 1] - scene->frame_t[k] <= 3.0 * sigma) ++hi;
-      win_lo[size_t(k)] = lo; win_hi[size_t(k)] = hi;
-    }
-  }
+  Plan p;
+  if (int rc = p.decide_path(scene, J, level)) return rc;
+  p.decide_fills(scene, J, options->smoothing_sigma_s, level != nullptr);
   if (int rc = oicc::select_device(device_ordinal)) return rc;
-  const double qnan = std::nan("");
-  std::vector<double> h_path(size_t(4 * F), qnan), h_smooth(size_t(4 * F), qnan), h_corr(size_t(4 * F), 0.0), h_zoom(size_t(F), 1.0), h_req(size_t(F), qnan);
-  std::vector<int32_t> h_iter(size_t(F), 0);
-  for (int k = 0; k < F; ++k) h_corr[size_t(4 * k)] = 1.0;
-  const int points = border_points(J.P.dst_w, J.P.dst_h);
-  const int waves = int(blocks_for(points)) * kWaves;
-  // the horizon lock's outputs as they are without a level: level_q = smooth_q (copied below), no up, no roll, angle 0
-  std::vector<double> h_level, h_up(size_t(3 * F), qnan), h_roll(size_t(F), qnan), h_angle(size_t(F), 0.0);
-  std::vector<int32_t> h_samples(size_t(F), 0), h_lstatus(size_t(F), level ? 2 : 0);
-  float ms[5] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-  {
-    Prepared D;
-    LevelDevice V;
-    oicc::DevBuf<int64_t> d_interval;
-    oicc::DevBuf<int32_t> d_lo, d_hi, d_iter, d_samples, d_lstatus;
-    oicc::DevBuf<double> d_delta, d_path, d_smooth, d_wave, d_req, d_level, d_up, d_roll, d_angle;
-    oicc::Event e1, e2, e3, g1, g2, g3;
-    oicc::Stream st;
-    OICC_HIP_TRY(st.create());
-    OICC_HIP_TRY(e1.create()); OICC_HIP_TRY(e2.create()); OICC_HIP_TRY(e3.create());
-    if (level) {
-      OICC_HIP_TRY(g1.create()); OICC_HIP_TRY(g2.create()); OICC_HIP_TRY(g3.create());
-      OICC_HIP_TRY(d_level.resize(size_t(4 * F))); OICC_HIP_TRY(d_up.resize(size_t(3 * F))); OICC_HIP_TRY(d_roll.resize(size_t(F)));
-      OICC_HIP_TRY(d_angle.resize(size_t(F))); OICC_HIP_TRY(d_samples.resize(size_t(F))); OICC_HIP_TRY(d_lstatus.resize(size_t(F)));
-    }
-    OICC_HIP_TRY(d_interval.resize(size_t(F))); OICC_HIP_TRY(d_lo.resize(size_t(F))); OICC_HIP_TRY(d_hi.resize(size_t(F)));
-    OICC_HIP_TRY(d_iter.resize(size_t(F))); OICC_HIP_TRY(d_delta.resize(size_t(4 * std::max(count - 1, 1))));
-    OICC_HIP_TRY(d_path.resize(size_t(4 * F))); OICC_HIP_TRY(d_smooth.resize(size_t(4 * F)));
-    OICC_HIP_TRY(d_wave.resize(size_t(F) * size_t(waves))); OICC_HIP_TRY(d_req.resize(size_t(F)));
-    if (int rc = upload_scene(scene, J, st, &D)) return rc;
-    OICC_HIP_TRY(hipMemcpyAsync(d_interval.p, interval.data(), sizeof(int64_t) * size_t(F), hipMemcpyHostToDevice, st));
-    OICC_HIP_TRY(hipMemcpyAsync(d_lo.p, win_lo.data(), sizeof(int32_t) * size_t(F), hipMemcpyHostToDevice, st));
-    OICC_HIP_TRY(hipMemcpyAsync(d_hi.p, win_hi.data(), sizeof(int32_t) * size_t(F), hipMemcpyHostToDevice, st));
-    OICC_HIP_TRY(hipMemcpyAsync(d_iter.p, h_iter.data(), sizeof(int32_t) * size_t(F), hipMemcpyHostToDevice, st));
-    OICC_HIP_TRY(hipMemcpyAsync(d_path.p, h_path.data(), sizeof(double) * size_t(4 * F), hipMemcpyHostToDevice, st));
-    OICC_HIP_TRY(hipMemcpyAsync(d_smooth.p, h_smooth.data(), sizeof(double) * size_t(4 * F), hipMemcpyHostToDevice, st));
-    OICC_HIP_TRY(hipMemcpyAsync(D.correction.p, h_corr.data(), sizeof(double) * size_t(4 * F), hipMemcpyHostToDevice, st));
-    OICC_HIP_TRY(hipMemcpyAsync(D.zoom.p, h_zoom.data(), sizeof(double) * size_t(F), hipMemcpyHostToDevice, st));
-    if (int rc = launch_tables(J, st, &D)) return rc;          // ev[1]: the path starts here
-    if (int rc = launch_path(J, st, D, d_interval.p, first, count, d_delta.p, d_path.p)) return rc;
-    OICC_HIP_TRY(hipEventRecord(e1, st));
-    if (count > 0) {
-      hipLaunchKernelGGL(stab_smooth_kernel, dim3(unsigned((count + kWaves - 1) / kWaves)), dim3(kThreads), 0, st, count, first, D.frame_t.p, d_path.p, d_lo.p,
-                         d_hi.p, sigma, options->max_correction_rad, d_smooth.p, D.correction.p, d_iter.p);
-      OICC_HIP_TRY(hipGetLastError());
-    }
-    OICC_HIP_TRY(hipEventRecord(e2, st));
-    if (level) {                                               // between the smoothing and the zoom: device_ms [3] and [4]
-      // level_q starts as smooth_q (NaN off the path), the rest as without gravity
-      OICC_HIP_TRY(hipMemcpyAsync(d_level.p, d_smooth.p, sizeof(double) * size_t(4 * F), hipMemcpyDeviceToDevice, st));
-      OICC_HIP_TRY(hipMemcpyAsync(d_up.p, h_up.data(), sizeof(double) * size_t(3 * F), hipMemcpyHostToDevice, st));
-      OICC_HIP_TRY(hipMemcpyAsync(d_roll.p, h_roll.data(), sizeof(double) * size_t(F), hipMemcpyHostToDevice, st));
-      OICC_HIP_TRY(hipMemcpyAsync(d_angle.p, h_angle.data(), sizeof(double) * size_t(F), hipMemcpyHostToDevice, st));
-      OICC_HIP_TRY(hipMemcpyAsync(d_samples.p, h_samples.data(), sizeof(int32_t) * size_t(F), hipMemcpyHostToDevice, st));
-      OICC_HIP_TRY(hipMemcpyAsync(d_lstatus.p, h_lstatus.data(), sizeof(int32_t) * size_t(F), hipMemcpyHostToDevice, st));
-      OICC_HIP_TRY(hipEventRecord(g1, st));
-      if (int rc = launch_accl_world(J, level, H, st, D, d_interval.p, d_path.p, &V)) return rc;
-      OICC_HIP_TRY(hipEventRecord(g2, st));
-      if (count > 0) {
-        hipLaunchKernelGGL(stab_level_kernel, dim3(unsigned((count + kWaves - 1) / kWaves)), dim3(kThreads), 0, st, count, first, D.frame_t.p, V.accl_t.p,
-                           V.world.p, V.gate.p, V.win_lo.p, V.win_hi.p, d_path.p, d_smooth.p, J.P.time_offset, J.P.reference_row * J.P.line_delay,
-                           level->gravity_sigma_s, level->gravity_const, level->lock, std::remainder(level->roll_rad, kTwoPi),
-                           options->max_correction_rad, d_level.p, D.correction.p, d_up.p, d_roll.p, d_angle.p, d_samples.p, d_lstatus.p);
-        OICC_HIP_TRY(hipGetLastError());
-      }
-      OICC_HIP_TRY(hipEventRecord(g3, st));                    // the zoom starts here
-    }
-    if (int rc = launch_records(J, st, &D)) return rc;         // at zoom 1
-    for (int f0 = 0; f0 < F; f0 += kFrameChunk) {
-      const int m = std::min(kFrameChunk, F - f0);
-      hipLaunchKernelGGL(stab_zoom_kernel, dim3(blocks_for(points), unsigned(m)), dim3(kThreads), 0, st, J.P, f0, D.table.p, D.count.p, D.record.p, points,
-                         waves, d_wave.p);
-      OICC_HIP_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(stab_zoom_min_kernel, dim3(unsigned((F + 63) / 64)), dim3(64), 0, st, F, waves, d_wave.p, d_req.p);
-    OICC_HIP_TRY(hipGetLastError());
-    OICC_HIP_TRY(hipEventRecord(e3, st));
-    OICC_HIP_TRY(hipMemcpyAsync(h_path.data(), d_path.p, sizeof(double) * size_t(4 * F), hipMemcpyDeviceToHost, st));
-    OICC_HIP_TRY(hipMemcpyAsync(h_smooth.data(), d_smooth.p, sizeof(double) * size_t(4 * F), hipMemcpyDeviceToHost, st));
-    OICC_HIP_TRY(hipMemcpyAsync(h_corr.data(), D.correction.p, sizeof(double) * size_t(4 * F), hipMemcpyDeviceToHost, st));
-    OICC_HIP_TRY(hipMemcpyAsync(h_iter.data(), d_iter.p, sizeof(int32_t) * size_t(F), hipMemcpyDeviceToHost, st));
-    OICC_HIP_TRY(hipMemcpyAsync(h_req.data(), d_req.p, sizeof(double) * size_t(F), hipMemcpyDeviceToHost, st));
-    if (level) {
-      OICC_HIP_TRY(hipMemcpyAsync(h_up.data(), d_up.p, sizeof(double) * size_t(3 * F), hipMemcpyDeviceToHost, st));
-      OICC_HIP_TRY(hipMemcpyAsync(h_roll.data(), d_roll.p, sizeof(double) * size_t(F), hipMemcpyDeviceToHost, st));
-      OICC_HIP_TRY(hipMemcpyAsync(h_angle.data(), d_angle.p, sizeof(double) * size_t(F), hipMemcpyDeviceToHost, st));
-      OICC_HIP_TRY(hipMemcpyAsync(h_samples.data(), d_samples.p, sizeof(int32_t) * size_t(F), hipMemcpyDeviceToHost, st));
-      OICC_HIP_TRY(hipMemcpyAsync(h_lstatus.data(), d_lstatus.p, sizeof(int32_t) * size_t(F), hipMemcpyDeviceToHost, st));
-      h_level.resize(size_t(4 * F));
-      OICC_HIP_TRY(hipMemcpyAsync(h_level.data(), d_level.p, sizeof(double) * size_t(4 * F), hipMemcpyDeviceToHost, st));
-    }
-    OICC_HIP_TRY(hipStreamSynchronize(st));
-    OICC_HIP_TRY(hipEventElapsedTime(&ms[0], D.ev[1], e1));
-    OICC_HIP_TRY(hipEventElapsedTime(&ms[1], e1, e2));
-    OICC_HIP_TRY(hipEventElapsedTime(&ms[2], level ? g3 : e2, e3));
-    if (level) {
-      OICC_HIP_TRY(hipEventElapsedTime(&ms[3], g1, g2));
-      OICC_HIP_TRY(hipEventElapsedTime(&ms[4], g2, g3));
-    }
-  }
-  std::memcpy(path_q, h_path.data(), sizeof(double) * size_t(4 * F));
-  std::memcpy(smooth_q, h_smooth.data(), sizeof(double) * size_t(4 * F));
-  std::memcpy(correction_q, h_corr.data(), sizeof(double) * size_t(4 * F));
-  std::memcpy(iterations, h_iter.data(), sizeof(int32_t) * size_t(F));
-  std::memcpy(required_zoom, h_req.data(), sizeof(double) * size_t(F));
+  if (int rc = p.open(J, level, true)) return rc;
+  if (int rc = p.upload(scene, J)) return rc;
+  if (int rc = p.D.scene.launch_tables(J, p.st)) return rc;          // ev[1]: the path starts here
+  if (int rc = p.path_stage(J)) return rc;
+  OICC_HIP_TRY(hipEventRecord(p.e1, p.st));
+  if (int rc = p.smooth_stage(options)) return rc;
+  OICC_HIP_TRY(hipEventRecord(p.e2, p.st));
+  if (level) if (int rc = p.level_stage(J, options, level)) return rc;          // device_ms [3] and [4]
+  if (int rc = p.zoom_stage(J)) return rc;
+  OICC_HIP_TRY(hipEventRecord(p.e3, p.st));
+  if (int rc = p.download_stage(level != nullptr)) return rc;
+  copy_out(path_q, p.path.h); copy_out(smooth_q, p.smooth.h); copy_out(correction_q, p.h_corr); copy_out(iterations, p.iter.h); copy_out(required_zoom, p.req.h);
   copy_status(J, frame_status);
-  applied_zoom(F, scene->frame_t, required_zoom, frame_status, *options, zoom, zoom_clamped);
-  if (device_ms) for (int k = 0; k < (out ? 5 : 3); ++k) device_ms[k] = double(ms[k]);
+  applied_zoom(p.F, scene->frame_t, required_zoom, frame_status, *options, zoom, zoom_clamped);
+  if (device_ms) for (int k = 0; k < (out ? 5 : 3); ++k) device_ms[k] = double(p.ms[k]);
   if (out) {
-    std::memcpy(out->level_q, level ? h_level.data() : h_smooth.data(), sizeof(double) * size_t(4 * F));
-    std::memcpy(out->up, h_up.data(), sizeof(double) * size_t(3 * F));
-    std::memcpy(out->roll, h_roll.data(), sizeof(double) * size_t(F));
-    std::memcpy(out->level_angle, h_angle.data(), sizeof(double) * size_t(F));
-    std::memcpy(out->gravity_samples, h_samples.data(), sizeof(int32_t) * size_t(F));
-    std::memcpy(out->level_status, h_lstatus.data(), sizeof(int32_t) * size_t(F));
+    copy_out(out->level_q, level ? p.level.h : p.smooth.h); copy_out(out->up, p.up.h); copy_out(out->roll, p.roll.h);
+    copy_out(out->level_angle, p.angle.h); copy_out(out->gravity_samples, p.samples.h); copy_out(out->level_status, p.lstatus.h);
   }
   return OICC_OK;
 }
@@ -896,36 +745,22 @@ extern "C" int oicc_stab_plan_level(int32_t device_ordinal, const oicc_rs_scene*
                    &out, device_ms);
 }
 
-// G1 of the horizon lock alone: the path, then every accelerometer sample in the path's frame
+// G1 of the horizon lock alone: the plan's own path stage and G1 stage, then every accelerometer sample in the path's frame
 extern "C" int oicc_debug_stab_accl_world(int32_t device_ordinal, const oicc_rs_scene* scene, const oicc_stab_level* level, double* world,
                                           int32_t* frame_of) {
   Judged J;
   if (int rc = judge_scene(scene, &J)) return rc;
   if (!level_ok(level) || !world || !frame_of) return OICC_ERR_INVALID_ARG;
-  const int F = J.num_frames;
-  std::vector<int64_t> interval;
-  int first = 0, count = 0;
-  if (int rc = find_path(scene, J, &interval, &first, &count)) return rc;
-  LevelHost H;
-  level_host(scene, J, level, first, count, &H);
+  Plan p;
+  if (int rc = p.decide_path(scene, J, level)) return rc;
   if (int rc = oicc::select_device(device_ordinal)) return rc;
-  const size_t na = size_t(level->num_accl);
-  const std::vector<double> h_path(size_t(4 * F), std::nan(""));
-  Prepared D;
-  LevelDevice V;
-  oicc::DevBuf<int64_t> d_interval;
-  oicc::DevBuf<double> d_delta, d_path;
-  oicc::Stream st;
-  OICC_HIP_TRY(st.create());
-  OICC_HIP_TRY(d_interval.resize(size_t(F))); OICC_HIP_TRY(d_delta.resize(size_t(4 * std::max(count - 1, 1)))); OICC_HIP_TRY(d_path.resize(size_t(4 * F)));
-  if (int rc = upload_scene(scene, J, st, &D)) return rc;
-  OICC_HIP_TRY(hipMemcpyAsync(d_interval.p, interval.data(), sizeof(int64_t) * size_t(F), hipMemcpyHostToDevice, st));
-  OICC_HIP_TRY(hipMemcpyAsync(d_path.p, h_path.data(), sizeof(double) * size_t(4 * F), hipMemcpyHostToDevice, st));
-  if (int rc = launch_path(J, st, D, d_interval.p, first, count, d_delta.p, d_path.p)) return rc;
-  if (int rc = launch_accl_world(J, level, H, st, D, d_interval.p, d_path.p, &V)) return rc;
-  OICC_HIP_TRY(hipMemcpyAsync(world, V.world.p, sizeof(double) * 3 * na, hipMemcpyDeviceToHost, st));
-  OICC_HIP_TRY(hipStreamSynchronize(st));
-  std::memcpy(frame_of, H.frame_of.data(), sizeof(int32_t) * na);
+  if (int rc = p.open(J, level, false)) return rc;
+  if (int rc = p.upload(scene, J)) return rc;
+  if (int rc = p.path_stage(J)) return rc;
+  if (int rc = p.accl_world_stage(J, level)) return rc;
+  OICC_HIP_TRY(p.world.download(world, 3 * size_t(level->num_accl), p.st));
+  OICC_HIP_TRY(hipStreamSynchronize(p.st));
+  copy_out(frame_of, p.frame_of.h);
   return OICC_OK;
 }
 
@@ -945,43 +780,9 @@ extern "C" int oicc_stab_map(int32_t device_ordinal, const oicc_rs_scene* scene,
   Judged J;
   if (int rc = judge_scene(scene, &J)) return rc;
   if (!plan_arrays_ok(correction_q, zoom, J.num_frames) || !map || !valid || !frame_status) return OICC_ERR_INVALID_ARG;
-  if (int rc = oicc::select_device(device_ordinal)) return rc;
-  const int64_t pixels = int64_t(J.P.dst_w) * J.P.dst_h;
-  const size_t total = size_t(pixels) * size_t(J.num_frames);
   Prepared D;
-  oicc::DevBuf<float2> d_map; oicc::DevBuf<uint8_t> d_valid, d_evals;
-  oicc::Event e1;
-  oicc::Stream st;
-  float ms[3] = {0.0f, 0.0f, 0.0f};
-  OICC_HIP_TRY(st.create());
-  OICC_HIP_TRY(e1.create());
-  OICC_HIP_TRY(d_map.resize(total));
-  OICC_HIP_TRY(d_valid.resize(total));
-  if (evaluations) OICC_HIP_TRY(d_evals.resize(total));
-  if (int rc = prepare(scene, J, correction_q, zoom, st, &D)) return rc;
-  for (int first = 0; first < J.num_frames; first += kFrameChunk) {
-    const int m = std::min(kFrameChunk, J.num_frames - first);
-    hipLaunchKernelGGL(stab_map_kernel, dim3(blocks_for(pixels), unsigned(m)), dim3(kThreads), 0, st, J.P, first, D.table.p, D.count.p, D.record.p, pixels,
-                       d_map.p, d_valid.p, d_evals.p);
-    OICC_HIP_TRY(hipGetLastError());
-  }
-  OICC_HIP_TRY(hipEventRecord(e1, st));
-  OICC_HIP_TRY(hipMemcpyAsync(map, d_map.p, sizeof(float2) * total, hipMemcpyDeviceToHost, st));
-  OICC_HIP_TRY(hipMemcpyAsync(valid, d_valid.p, total, hipMemcpyDeviceToHost, st));
-  if (evaluations) OICC_HIP_TRY(hipMemcpyAsync(evaluations, d_evals.p, total, hipMemcpyDeviceToHost, st));
-  OICC_HIP_TRY(hipStreamSynchronize(st));
-  OICC_HIP_TRY(hipEventElapsedTime(&ms[0], D.ev[0], D.ev[1]));
-  OICC_HIP_TRY(hipEventElapsedTime(&ms[1], D.ev[1], D.ev[2]));
-  OICC_HIP_TRY(hipEventElapsedTime(&ms[2], D.ev[2], e1));
-  if (device_ms) for (int k = 0; k < 3; ++k) device_ms[k] = double(ms[k]);
-  copy_status(J, frame_status);
-  if (num_valid)
-    for (int k = 0; k < J.num_frames; ++k) {
-      int64_t c = 0;
-      for (int64_t i = 0; i < pixels; ++i) c += valid[int64_t(k) * pixels + i];
-      num_valid[k] = c;
-    }
-  return OICC_OK;
+  return run_map(device_ordinal, J, D, [&](hipStream_t st) { return D.prepare(scene, J, correction_q, zoom, st); }, map, valid, evaluations, frame_status,
+                 num_valid, device_ms);
 }
 
 extern "C" int oicc_stab_frames_device(void* hip_stream, const oicc_rs_scene* scene, const double* correction_q, const double* zoom, int32_t channels,
@@ -990,17 +791,12 @@ extern "C" int oicc_stab_frames_device(void* hip_stream, const oicc_rs_scene* sc
   if (int rc = judge_scene(scene, &J)) return rc;
   if (!plan_arrays_ok(correction_q, zoom, J.num_frames) || !frames_args_ok(channels, border_value) || !frames_dev || !out_dev || !frame_status)
     return OICC_ERR_INVALID_ARG;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  if (int rc = oicc::on_current_device(stream, {frames_dev, out_dev})) return rc;
   Prepared D;
-  int rc = prepare(scene, J, correction_q, zoom, stream, &D);
-  if (rc == OICC_OK) rc = launch_frames(stream, J, D, 0, J.num_frames, channels, frames_dev, border_value, out_dev);
-  // the tables and records are this call's own: it returns once the stream has run the work, and frees them
-  if (hipStreamSynchronize(stream) != hipSuccess && rc == OICC_OK) rc = OICC_ERR_HIP;
-  if (rc == OICC_OK) copy_status(J, frame_status);
-  return rc;
+  return run_frames_device(static_cast<hipStream_t>(hip_stream), J, D, [&](hipStream_t st) { return D.prepare(scene, J, correction_q, zoom, st); }, channels,
+                           frames_dev, border_value, out_dev, frame_status);
 }
 
+// the report's ms_rays is here the record kernel
 extern "C" int oicc_stab_frames(int32_t device_ordinal, const oicc_rs_scene* scene, const double* correction_q, const double* zoom, int32_t channels,
                                 const uint8_t* frames, int32_t border_value, int32_t batch, uint8_t* out, int32_t* frame_status,
                                 oicc_rs_frames_report* report) {
@@ -1008,24 +804,7 @@ extern "C" int oicc_stab_frames(int32_t device_ordinal, const oicc_rs_scene* sce
   if (int rc = judge_scene(scene, &J)) return rc;
   if (!plan_arrays_ok(correction_q, zoom, J.num_frames) || !frames_args_ok(channels, border_value) || batch < 1 || !frames || !out || !frame_status)
     return OICC_ERR_INVALID_ARG;
-  if (int rc = oicc::select_device(device_ordinal)) return rc;
-  const auto t_start = std::chrono::steady_clock::now();
-  oicc_rs_frames_report rep = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   Prepared D;
-  FramePipeline pipe;      // behind the tables: its streams are drained before the tables go
-  if (int rc = pipe.open(J.num_frames, batch, int64_t(J.P.src_w) * J.P.src_h * channels, int64_t(J.P.dst_w) * J.P.dst_h * channels)) return rc;
-  if (int rc = prepare(scene, J, correction_q, zoom, pipe.slot[0].st, &D)) return rc;
-  OICC_HIP_TRY(hipStreamSynchronize(pipe.slot[0].st));      // both streams read the tables and records
-  float ms = 0.0f;
-  OICC_HIP_TRY(hipEventElapsedTime(&ms, D.ev[0], D.ev[1])); rep.ms_table = ms;
-  OICC_HIP_TRY(hipEventElapsedTime(&ms, D.ev[1], D.ev[2])); rep.ms_rays = ms;      // here: the record kernel
-  const int rc = pipe.run(frames, out, [&](hipStream_t st, int first, int num, const uint8_t* d_in, uint8_t* d_out) {
-    return launch_frames(st, J, D, first, num, channels, d_in, border_value, d_out);
-  });
-  if (rc != OICC_OK) return rc;
-  copy_status(J, frame_status);
-  rep.ms_upload = pipe.ms_upload; rep.ms_kernel = pipe.ms_kernel; rep.ms_download = pipe.ms_download;
-  rep.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-  if (report) *report = rep;
-  return OICC_OK;
+  return run_frames(device_ordinal, J, D, [&](hipStream_t st) { return D.prepare(scene, J, correction_q, zoom, st); }, channels, frames, border_value, batch,
+                    out, frame_status, report);
 }
